@@ -2,7 +2,15 @@
 """
 bench.py -- energy-points/sec of the NEGF hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (the headline with the roofline of the timed
+steps).  --full adds everything else the benchmark measures or checks: the CPU baselines (with their device-vs-oracle
+parity check), the warm (g(E) cache on) steps, the secondary lines under "extra" and, for N > 1, the strong-scaling
+blocks; --no-cpu / --no-warm / --no-extra / --no-whole-host leave single legs of --full out.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64; a complex result as
+<name>_real.npy and <name>_imag.npy; at most 64 MB in all, a fixed seeded sample of the elements above that).  The inputs
+are seeded: the same arguments give the same inputs in every run.
 
 N = 1 runs in this process.  N > 1: when launched by torch.distributed.run (RANK/WORLD_SIZE in the
 environment) every rank runs the worker below; launched plainly, this process starts N workers
@@ -27,7 +35,7 @@ per-energy scalars), STRONG scaling (the grid is fixed, the ranks divide it):
       486-point ANT contour + GrInt over the 256-point real-axis grid (the density-matrix build of SURVEY 8d C4);
   c5: 2 x 1000 spin-block F / S, qV = 0.5 V window at 300 K, 512 Legendre points; one step = GrLessInt(ind=-1)
       + calculate_transmission(spin='u') on that grid.
-The default (c3) is the headline and the only configuration with CPU / secondary legs.
+The default (c3) is the headline and the only configuration with CPU / secondary legs (--full).
 
 The JSON line carries
   roofline     : the kernel that dominates the step (the chain fixed point, > 90 % of it) against the
@@ -43,9 +51,10 @@ The JSON line carries
                      frac <= 1 is asserted; only this one is a matrix-core utilisation.
                  mfma_busy_frac is the PMC counter SQ_VALU_MFMA_BUSY_CYCLES of the committed profile of the same
                  kernel source / (launch duration x 2.4 GHz x 1024 SIMDs).
-  cpu_baseline : the numpy oracle (the reference's CPU restatement) timed on this host on a bounded
+  cpu_baseline : (--full) the numpy oracle (the reference's CPU restatement) timed on this host on a bounded
                  sample of the same energies.
-  extra        : the north-star target case (N_orb = 500, constant Sigma, 1000 energies: GPU time and
+  warm         : (--full) the same step with the g(E) cache on.
+  extra        : (--full) the north-star target case (N_orb = 500, constant Sigma, 1000 energies: GPU time and
                  CPU sample) and BASELINE config C2 (N_orb = 200, constant Sigma, 1000 energies) with the
                  roofline of the dense inverse kernels.
 """
@@ -319,6 +328,29 @@ def pmc_counter(kernel_substr, counter, source_file="k_chain1d_rs.hip"):
     return None
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: every array of ``arrays`` (name -> array) as DIR/<name>.npy in float64, a complex one as
+    <name>_real.npy / <name>_imag.npy.  Above DUMP_BYTES_MAX in all, every array is cut to the same fraction of its
+    elements: a sample at flat indices drawn with a fixed seed (sorted), so that two runs write the same elements."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    total = sum(a.size * (16 if np.iscomplexobj(a) else 8) for a in arrays.values())
+    budget = DUMP_BYTES_MAX - 2 * 4096 * len(arrays)              # (room for the .npy headers)
+    frac = min(1.0, budget / total) if total else 1.0
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if frac < 1.0:
+            k = max(1, int(a.size * frac))
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        if np.iscomplexobj(a):
+            np.save(os.path.join(dirname, name + "_real.npy"), np.ascontiguousarray(a.real, dtype=np.float64))
+            np.save(os.path.join(dirname, name + "_imag.npy"), np.ascontiguousarray(a.imag, dtype=np.float64))
+        else:
+            np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 # ---------------------------------------------------------------------------------- the worker
 def _init_ranks():
     """(torch, dist, world, rank, local_rank, rehearsal) with the process group initialised for world > 1."""
@@ -425,10 +457,12 @@ def worker_c3(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     res_cold = out.cpu().numpy()
-    # warm steps: the same integral with the g(E) cache on -- one step fills it, the next ones only form
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, {"gr_int": res_cold})     # the integral GrInt hands its caller
+    # (--full) warm steps: the same integral with the g(E) cache on -- one step fills it, the next ones only form
     # Sigma = t g t^H; bit-identical result (asserted); NOT the headline
     warm = None
-    if world == 1 and not args.no_warm:
+    if world == 1 and args.full and not args.no_warm:
         eng.set_chain_cache(512)
         step(); fence()
         eng.profile(True); eng.profile_reset()
@@ -515,7 +549,7 @@ def worker_c3(args):
             line["warm"] = warm
         if world > 1:
             line["comm_ms"] = comm_ms        # the sum all-reduce of the N_orb x N_orb result, per step (events on the stream)
-        if not args.no_cpu and world == 1:           # the CPU leg is an N=1 figure (rank 0 only)
+        if args.full and not args.no_cpu and world == 1:           # the CPU leg is an N=1 figure (rank 0 only)
             import oracle
             ref = oracle.Chain1DSigma(F, S, inds, kw["taus"], kw["staus"], kw["alphas"], kw["aOverlaps"],
                                       kw["betas"], kw["bOverlaps"], eta=ETA)
@@ -544,16 +578,16 @@ def worker_c3(args):
                 wh.pop("_sum"); wh.pop("_idx")
                 wh["gpu_over_whole_host"] = line["value"] / wh["value"]
                 line["cpu_baseline"]["whole_host"] = wh
-        if not args.no_extra and world == 1:
+        if args.full and not args.no_extra and world == 1:
             line["extra"] = {"north_star_N500_x_1000": extra_const(eng, 500, 50, 1000, 3, reps=3, cpu_budget=6.0,
                                                                    no_cpu=args.no_cpu, whole_host=not args.no_whole_host),
                              "C2_N200_x_1000": extra_const(eng, 200, 20, 1000, 2, reps=10, cpu_budget=4.0,
                                                            no_cpu=args.no_cpu),
                              # BASELINE configs[0]-sized: 60 basis functions (the ethane demo), 100 real-axis points
                              "C1_N60_x_100": extra_const(eng, 60, 6, 100, 1, reps=20, cpu_budget=2.0, no_cpu=args.no_cpu)}
-    if world > 1 and not args.no_extra:
+    if world > 1 and args.full and not args.no_extra:
         # what BASELINE calls multi-GPU: the FIXED C4 / C5 steps through the product's own sharding over these ranks
-        # (strong scaling), beside the weak C3 line -- the driver's command only passes --gpus N
+        # (strong scaling), beside the weak C3 line (--full: a plain --gpus N run times the C3 steps only)
         strong = {}
         for cfg, nsteps in (("c4", 5), ("c5", 2)):
             l = run_api(cfg, nsteps, 1, 1, torch, dist, world, rank, local_rank, rehearsal,
@@ -595,7 +629,8 @@ def one_gpu_ms_per_step(config):
 def worker_api(args):
     """BASELINE configs C4 / C5 through the drop-in API with the product's own energy sharding (strong scaling)."""
     torch, dist, world, rank, local_rank, rehearsal = _init_ranks()
-    line = run_api(args.config, args.steps, args.warmup, args.emulate_share, torch, dist, world, rank, local_rank, rehearsal)
+    line = run_api(args.config, args.steps, args.warmup, args.emulate_share, torch, dist, world, rank, local_rank, rehearsal,
+                   dump_dir=args.dump_outputs)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -603,10 +638,12 @@ def worker_api(args):
         dist.destroy_process_group()
 
 
-def run_api(config, steps, warmup, emulate_share, torch, dist, world, rank, local_rank, rehearsal, check_local=False):
+def run_api(config, steps, warmup, emulate_share, torch, dist, world, rank, local_rank, rehearsal, check_local=False,
+            dump_dir=None):
     """One strong-scaling measurement of C4 / C5 in an initialised process group: the bench line (rank 0; None elsewhere).
     ``check_local``: rank 0 also evaluates the step WITHOUT sharding and the line carries the largest relative deviation
-    of the sharded result from it (``sharded_vs_local_rel``)."""
+    of the sharded result from it (``sharded_vs_local_rel``).  ``dump_dir``: rank 0 writes the last timed step's results
+    there (write_outputs)."""
     import types
     args = types.SimpleNamespace(config=config, steps=steps, warmup=warmup, emulate_share=emulate_share)
     from gaunegf_amd import distributed as D
@@ -692,6 +729,9 @@ def run_api(config, steps, warmup, emulate_share, torch, dist, world, rank, loca
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert all(np.all(np.isfinite(np.asarray(r if not isinstance(r, tuple) else r[0]))) for r in res)
+    if dump_dir and rank == 0:
+        names = ("gr_int_contour", "gr_int_real_axis") if args.config == "c4" else ("gless_int", "transmission_u")
+        write_outputs(dump_dir, {n: (r if not isinstance(r, tuple) else r[0]) for n, r in zip(names, res)})
     cm_calls = D.comm_ms_total() if world > 1 else (0.0, 0)
     D.comm_ms_stop()
     local_dev = None
@@ -818,6 +858,7 @@ def worker_scf(args):
     eng = get_engine()
     names = [x for x in args.scf_systems.split(",") if x]
     out_sys = []
+    dumped = {}
     # host numpy of the step (eigenvalues of S^-1 F, Lowdin occupations: the reference's own host work, scfE.py:460-468,
     # density.py:822): BLAS threads limited to this process's CPU share -- the box reports 256 CPUs to OpenBLAS but
     # schedules one GPU's share of them, and 256 BLAS threads on that turn a 200 x 200 solve into 90 ms
@@ -879,6 +920,9 @@ def worker_scf(args):
                    "profiled_kernel_groups_per_step": sum(v[1] for v in fam.values()) / args.steps,
                    "family_ms_per_step": {k: v[0] / args.steps for k, v in fam.items() if v[1]},
                    "fermi": float(steps[-1].fermi), "electrons": float(np.real(np.trace(steps[-1].P @ S)))}
+            tag = rec["system"].replace("/", "_")
+            dumped[tag + "_P"] = steps[-1].P                    # what FockToP leaves its caller: P and the Fermi level
+            dumped[tag + "_fermi"] = np.array([steps[-1].fermi], dtype=np.float64)
             if "cache" in opt:
                 rec["chain_cache"] = eng.chain_cache_stats()
             # parity: the same step replayed with the numpy oracle serving every integral (bounded: small systems)
@@ -897,6 +941,8 @@ def worker_scf(args):
                 assert rec["parity_rel_fro_P_vs_oracle_replay"] < 1e-8, rec
             out_sys.append(rec)
     eng.set_chain_cache(0); eng.set_chain_cache(512)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, dumped)
     head = out_sys[0]
     line = {"metric": "density-matrix wall time, one NEGFE.FockToP step (adaptive contour + real axis + Muller Fermi search + bias window)",
             "value": head["wall_ms_per_step"], "unit": "ms", "n_gpus": 1, "steps": args.steps, "warmup": max(args.warmup, 1),
@@ -980,13 +1026,20 @@ def main():
     ap.add_argument("--energies", type=int, default=2000, help="energy points per GPU (c3)")
     ap.add_argument("--emulate-share", type=int, default=1,
                     help="c4 / c5 on one GPU: run only rank 0's share of a K-way energy-cyclic sharding (the small per-GPU batches)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines and their parity check, the warm "
+                         "steps, the secondary lines (extra), for --gpus N > 1 the strong-scaling blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
-    ap.add_argument("--no-extra", action="store_true", help="skip the N_orb=500 x 1000 and C2 secondary lines")
-    ap.add_argument("--no-warm", action="store_true", help="skip the warm (g(E) cache on) steps after the timed cold ones: "
-                    "profiler runs, whose per-kernel averages should hold the cold launches only")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the N_orb=500 x 1000 and C2 secondary lines")
+    ap.add_argument("--no-warm", action="store_true", help="with --full: skip the warm (g(E) cache on) steps after the timed "
+                    "cold ones: profiler runs, whose per-kernel averages should hold the cold launches only")
     ap.add_argument("--no-whole-host", action="store_true", help="skip the CPU pools over ALL usable CPUs (keep the 16-process ones)")
     ap.add_argument("--cpu-budget", type=float, default=18.0, help="seconds of CPU work for the headline baseline")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:

@@ -3,9 +3,10 @@
 # N_orb=500 x 1000 and C2 secondary lines), of the C5 configuration, and separate PMC passes (FETCH_SIZE,
 # WRITE_SIZE, SQ groups) on the headline alone.  Outputs under gpurun_out/prof_r2/.
 mkdir -p gpurun_out/prof_r2
+P=$PWD/$_      # (the output folder just made)
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_r2/bench -- python $R/bench.py --steps 2 --warmup 1 --no-cpu > $R/gpurun_out/prof_r2/bench.json 2> $R/gpurun_out/prof_r2/bench.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench -- python $R/bench.py --steps 2 --warmup 1 --full --no-cpu > $P/bench.json 2> $P/bench.err
 rc=$?; echo "bench trace exit=$rc"; if [ $rc -ne 0 ]; then tail -5 $R/gpurun_out/prof_r2/bench.err; exit $rc; fi
 if [ -z "$SKIP_C5" ]; then
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_r2/c5 -- python $R/scripts/bench_configs.py c5 > $R/gpurun_out/prof_r2/c5.json 2> $R/gpurun_out/prof_r2/c5.err

@@ -11,7 +11,7 @@ P=$R/gpurun_out/prof_r5
 cd /tmp && export TMPDIR=/tmp
 step() { echo "== $1"; }
 step "bench trace"
-timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench -- python $R/bench.py --steps 2 --warmup 1 --no-cpu --no-warm > $P/bench.json 2> $P/bench.err
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench -- python $R/bench.py --steps 2 --warmup 1 --full --no-cpu --no-warm > $P/bench.json 2> $P/bench.err
 rc=$?; echo "bench trace exit=$rc"; [ $rc -ne 0 ] && { tail -5 $P/bench.err; exit $rc; }
 run() { # dir name, counters, program...
   local name=$1 ctr=$2; shift 2

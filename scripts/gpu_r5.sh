@@ -3,6 +3,7 @@
 # steps: inv_tests | inv_time | inv_ab | small | fuzz | tests | bench | c4 | c5 | share | scf | kstats | pmc
 set -o pipefail
 mkdir -p gpurun_out
+OUT=$_      # (the output folder just made)
 export TMPDIR=/tmp
 for step in "$@"; do
   echo "=== $step"
@@ -13,7 +14,7 @@ for step in "$@"; do
     small) for v in ${SMALL_STRIP:-1}; do echo "NEGF_GJ_STRIP=$v"; NEGF_GJ_STRIP=$v timeout -k 10 600 python scripts/time_smallbatch.py ${SMALL_CASES:-800x12 800x61 800x93 800x486 1000x64 1000x128 500x64 500x250} || exit 1; done > gpurun_out/r5_small.log 2>&1; grep -E "^n=|STRIP" gpurun_out/r5_small.log ;;
     fuzz) timeout -k 10 900 python scripts/fuzz_inverse.py > gpurun_out/r5_fuzz.log 2>&1; rc=$?; tail -8 gpurun_out/r5_fuzz.log; [ $rc -eq 0 ] || exit $rc ;;
     tests) timeout -k 10 1100 python -m pytest tests -x -q -m gpu > gpurun_out/r5_tests.log 2>&1; rc=$?; tail -5 gpurun_out/r5_tests.log; [ $rc -eq 0 ] || exit $rc ;;
-    bench) timeout -k 10 600 python bench.py > gpurun_out/r5_bench.json 2> gpurun_out/r5_bench.err || exit 1; cat gpurun_out/r5_bench.json ;;
+    bench) timeout -k 10 600 python bench.py --full > $OUT/r5_bench.json 2> $OUT/r5_bench.err || exit 1; cat $OUT/r5_bench.json ;;
     c4) timeout -k 10 600 python bench.py --config c4 --no-cpu > gpurun_out/r5_c4.json 2> gpurun_out/r5_c4.err || exit 1; cat gpurun_out/r5_c4.json ;;
     c5) timeout -k 10 600 python bench.py --config c5 --no-cpu > gpurun_out/r5_c5.json 2> gpurun_out/r5_c5.err || exit 1; cat gpurun_out/r5_c5.json ;;
     share) for c in c4 c5; do timeout -k 10 600 python bench.py --config $c --emulate-share 8 --no-cpu > gpurun_out/r5_${c}_share8.json 2> gpurun_out/r5_${c}_share8.err || exit 1; cat gpurun_out/r5_${c}_share8.json; done ;;

@@ -241,6 +241,28 @@ def test_bench_flop_accounting():
         bench.hbm_fraction(9e12, 1.0)
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 arrays, a complex one as _real / _imag; above the size bound a sample of the
+    elements drawn with a fixed seed -- the same elements in every run, within the bound."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    z = rng.standard_normal((30, 40)) + 1j * rng.standard_normal((30, 40))
+    t = rng.standard_normal(7)
+    bench.write_outputs(str(tmp_path / "all"), {"z": z, "t": t})
+    assert sorted(os.listdir(tmp_path / "all")) == ["t.npy", "z_imag.npy", "z_real.npy"]
+    zr, zi, tt = (np.load(tmp_path / "all" / f) for f in ("z_real.npy", "z_imag.npy", "t.npy"))
+    assert zr.dtype == zi.dtype == tt.dtype == np.float64
+    assert np.array_equal(zr + 1j * zi, z) and np.array_equal(tt, t)
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 2 * 4096 * 2 + 16 * 300 + 8 * 7)
+    runs = []
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"z": z, "t": t})
+        runs.append([np.load(tmp_path / d / f) for f in ("z_real.npy", "z_imag.npy", "t.npy")])
+        assert sum(a.nbytes for a in runs[-1]) <= 16 * 300 + 8 * 7
+    assert all(np.array_equal(a, b) for a, b in zip(*runs))
+    assert 0 < runs[0][0].size < z.size and np.all(np.isin(runs[0][0], z.real))
+
 def test_host_blas_thread_limit_is_scoped(monkeypatch):
     """The density step limits the threads of its host BLAS / LAPACK calls (_hostblas.py) and gives the setting back:
     inside ``limited()`` every BLAS pool runs at most host_threads() threads, afterwards what it had before."""
@@ -295,8 +317,11 @@ def test_calc_emin_reference_route_is_bit_identical(monkeypatch):
     value, while the default route differs in the last bits (same grids to 1e-12)."""
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from helpers import random_system
+    from gaunegf_amd import _hostblas
     F, S = random_system(300, 11)
-    ref_start = min(np.sort(np.real(np.linalg.eigvals(np.linalg.solve(S, F)))))
+    # with the host BLAS thread count calcEmin runs its algebra with (_hostblas.limited_call): LAPACK's last bits depend on it
+    with _hostblas.limited():
+        ref_start = min(np.sort(np.real(np.linalg.eigvals(np.linalg.solve(S, F)))))
 
     class Flat:                                     # DOS below tol everywhere: calcEmin returns its start value - 5
         def sigmaTot(self, E): return -1e3j * np.eye(300)
@@ -315,7 +340,8 @@ def test_calc_emin_reference_route_is_bit_identical(monkeypatch):
 
     monkeypatch.setattr(D, "_compute_dos_at_energy", lambda E, F_, S_, sig: 0.0)      # (the product's serves it from the GPU)
     monkeypatch.setenv("NEGF_CALC_EMIN_ROUTE", "reference")
-    assert D._lowest_orbital_energy(F, S) == ref_start
+    with _hostblas.limited():
+        assert D._lowest_orbital_energy(F, S) == ref_start
     emin_ref = D.calcEmin(F, S, Flat(), tol=1e-3)
     assert emin_ref == ref_start - 5
     g_ref, g_direct = grids(emin_ref), grids(ref_start - 5)

@@ -119,7 +119,7 @@ def test_rccl_legs_on_one_gpu(engine):
 
 
 def test_bench_gpus_2_rehearsal_carries_the_strong_scaling_blocks():
-    """``bench.py --gpus N`` (the driver's multi-GPU command) keeps the weak C3 line and adds ``extra.c4_strong`` /
+    """``bench.py --gpus N --full`` (the multi-GPU command) keeps the weak C3 line and adds ``extra.c4_strong`` /
     ``extra.c5_strong``: BASELINE's multi-GPU configurations as FIXED steps through the product's own sharding
     (distributed.enable, one all-reduce / all-gather per pass of the engine).  Rehearsed here with two ranks on the one GPU over
     gloo (NEGF_BENCH_REHEARSAL=1): both blocks are present with their timing, communication and roofline fields, and the
@@ -131,7 +131,7 @@ def test_bench_gpus_2_rehearsal_carries_the_strong_scaling_blocks():
     env = dict(os.environ, NEGF_BENCH_REHEARSAL="1", NEGF_BENCH_CHECK_LOCAL="1")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--energies", "24", "--no-cpu", "--no-warm"], env=env, capture_output=True, text=True, timeout=900)
+                        "--energies", "24", "--full", "--no-cpu", "--no-warm"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -1443,3 +1443,32 @@ def test_imaginary_part_of_the_real_axis_integral(engine, N):
     for k in range(3):
         r = oracle.gr_point(g_ref.sigmaTot(E[k]), E[k], F, S)
         assert rel_fro(G[k].imag, r.imag) < TOL, k
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """``bench.py --steps K --warmup W --dump-outputs DIR`` without --full: the headline line alone (no CPU, warm or secondary
+    legs), K timed steps, and DIR holding the integral the last timed step computed -- the product's GrInt of the same
+    seeded workload -- as float64 real / imaginary parts."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--energies", "16", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "energy-points/s"
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 16) < 1e-6 * 16
+    assert not {"cpu_baseline", "warm", "extra"} & set(line)
+    got = np.load(out / "gr_int_real.npy") + 1j * np.load(out / "gr_int_imag.npy")
+    sys.path.insert(0, root)
+    import bench
+    from gaunegf_amd.integrate import GrInt
+    from gaunegf_amd.surfG1D import surfG
+    F, S, inds, kw = bench.c3_system()
+    E, w = bench.legendre_grid(16, -2.0, 2.0)
+    ref = GrInt(F, S, surfG(F, S, inds, **kw), E.astype(complex), w.astype(complex))
+    assert got.shape == ref.shape and rel_fro(got, ref) < 1e-10, rel_fro(got, ref)
