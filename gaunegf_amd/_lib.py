@@ -62,6 +62,10 @@ SIGNATURES = {
     "negf_gr_int_seg_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     "negf_gless_int_seg_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     "negf_transmission_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "negf_eigvalsh_batched": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "negf_channel_count": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip]),
+    "negf_transmission_channels": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "negf_transmission_channels_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "negf_sync": (C.c_int, [_vp]),
     "negf_last_info": (C.c_int, [_vp, C.c_int, _vp]),
     "negf_last_iters": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
@@ -70,6 +74,7 @@ SIGNATURES = {
     "negf_chain_cache_clear": (C.c_int, [_vp]),
     "negf_chain_cache_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                          C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "negf_workspace_bytes": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "negf_profile_enable": (C.c_int, [_vp, C.c_int]),
     "negf_profile_reset": (C.c_int, [_vp]),
     "negf_profile_read": (C.c_int, [_vp, C.c_char_p, _dp, _ip]),

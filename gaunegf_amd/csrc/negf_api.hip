@@ -783,6 +783,7 @@ void negf_destroy(negf_ctx* c)
     for (auto& sl : c->sys) { dev_free(sl.dF); dev_free(sl.dS); }
     c->d_F = c->d_S = nullptr;
     dev_free(c->d_acc); dev_free(c->d_seg_out); dev_free(c->d_ref_P); dev_free(c->d_ref_meta);
+    dev_free(c->d_chan); dev_free(c->d_chan_rank); dev_free(c->d_chan_T);
     prof_resolve(c);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     delete c;
@@ -1042,9 +1043,12 @@ int negf_sigma_const(negf_ctx* c, int n_contacts, const double* sigma, int* hand
             for (int i = 0; i < n; ++i) if (used[i]) { inds.push_back(i); ++cnt; }
             ks[k] = cnt;
         }
-        bool ok = 2 * (int)inds.size() <= n;
-        for (int k : ks) ok = ok && k > 0;
-        if (ok) {
+        // the contact blocks are set up whenever every contact has a support (has_blocks: the eigenchannels read
+        // them); the compact products of GrLessInt / negf_transmission keep their own condition (compact_ok)
+        bool has = true;
+        for (int k : ks) has = has && k > 0;
+        const bool ok = has && 2 * (int)inds.size() <= n;
+        if (has) {
             if ((rc = setup_blocks(c, p, n_contacts, ks.data(), inds.data()))) { free_provider(p); return rc; }
             std::vector<cplx> blk((size_t)p->blk_stride);
             for (int k = 0; k < n_contacts; ++k) {
@@ -1057,7 +1061,15 @@ int negf_sigma_const(negf_ctx* c, int n_contacts, const double* sigma, int* hand
             if ((rc = dev_alloc(&p->d_const_blk, blk.size())) || (rc = upload(c, p->d_const_blk, blk.data(), blk.size()))) {
                 free_provider(p); return rc;
             }
-            p->compact_ok = true;
+            p->has_blocks = true;
+            p->compact_ok = ok;
+            if (!ok) {
+                // blocks for the eigenchannels only: the provider keeps blk_stride = 0 (and no d_pos), as before they
+                // existed -- the workspace sizes its Sigma block staging d_blk by blk_stride, and no CONST path reads
+                // d_blk (formSigma's -1e-9 i S background makes every orbital part of the support: 2 n^2 per energy)
+                p->blk_stride = 0;
+                dev_free(p->d_pos);
+            }
         }
     }
     *handle = add_provider(c, p);
@@ -2012,6 +2024,167 @@ done:
     return rc;
 }
 
+// ---------------------------------------------------------------- eigenchannels
+// T(E) = sum_n T_n(E), T_n the eigenvalues of t^H t, t = Gamma_R^{1/2} G_RL Gamma_L^{1/2}.  On the contact with the
+// smaller orbital list s (L unless K_R < K_L; o the other one): Gamma_s = L L^H by pivoted Cholesky, and the T_n are
+// the eigenvalues of H = L^H B L, B = G_LR Gamma_R G_LR^H (s = L) or G_LR^H Gamma_L G_LR (s = R), G_LR = G[I_L, I_R].
+// Per energy: Z = L^H op(G_LR) (K_s x K_o), W = Z Gamma_o, H = W Z^H -- three small batched products -- and the
+// Jacobi eigenvalues of H's leading rank x rank block.
+namespace {
+
+struct ChanPlan { int cL, cR, KL, KR, Ks, Ko; bool mirror; };
+
+int chan_plan(negf_ctx* c, SigmaProvider* p, int contact_L, int contact_R, ChanPlan* pl)
+{
+    if (!c || c->n <= 0) return NEGF_ESTATE;
+    if (!p) return NEGF_EINVAL;
+    // providers whose Gamma_c is confined to a known orbital list
+    const bool ok = (p->kind == SK_CONST && p->has_blocks) ||
+                    ((p->kind == SK_CHAIN1D || p->kind == SK_BETHE) && !p->d_xi);
+    if (!ok) return NEGF_EINVAL;
+    const int cL = norm_contact(p, contact_L), cR = norm_contact(p, contact_R);
+    if (cL < 0 || cR < 0) return NEGF_EINVAL;                   // (the total self-energy is not a contact)
+    pl->cL = cL; pl->cR = cR; pl->KL = p->nc[cL]; pl->KR = p->nc[cR];
+    pl->mirror = pl->KR < pl->KL;
+    pl->Ks = std::min(pl->KL, pl->KR); pl->Ko = std::max(pl->KL, pl->KR);
+    if (pl->Ks > channels_kmax()) return NEGF_EINVAL;
+    return NEGF_OK;
+}
+
+}  // namespace
+
+int negf_channel_count(negf_ctx* c, int handle, int contact_L, int contact_R, int* nchan)
+{
+    if (!nchan) return NEGF_EINVAL;
+    ChanPlan pl;
+    const int rc = chan_plan(c, get_provider(c, handle), contact_L, contact_R, &pl);
+    if (rc) return rc;
+    *nchan = pl.Ks;
+    return NEGF_OK;
+}
+
+int negf_transmission_channels_dev(negf_ctx* c, int handle, int contact_L, int contact_R, int m, const double* E_dev,
+                                   int nchan, double* T_dev)
+{
+    SigmaProvider* p = get_provider(c, handle);
+    int rc = check_ready(c, p, m);
+    if (rc) return rc;
+    ChanPlan pl;
+    if ((rc = chan_plan(c, p, contact_L, contact_R, &pl))) return rc;
+    if (nchan < 1 || !T_dev || (m > 0 && !E_dev)) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    const int n = c->n;
+    const size_t n2 = (size_t)n * n;
+    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
+    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
+    const bool constant = p->kind == SK_CONST;
+    const int Ks = pl.Ks, Ko = pl.Ko, batch = c->batch;
+    // work area per energy: G_LR | Z | W (K_s K_o each) | H (K_s^2), then L^H: one matrix (CONST: Gamma does not
+    // depend on E, factored once per call) or one per energy -- sized here, not carved out of the n x n workspace
+    // (contact lists may cover more than half of the orbitals)
+    const size_t kk = (size_t)Ks * Ko, ks2 = (size_t)Ks * Ks, per = 3 * kk + ks2;
+    const size_t need = per * batch + ks2 * (constant ? 1 : batch);
+    const size_t need_r = constant ? 1 : (size_t)batch;      // pivoted Cholesky ranks
+    if (need > c->chan_cap || need_r > c->chan_rank_cap) {
+        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
+        dev_free(c->d_chan); dev_free(c->d_chan_rank); c->chan_cap = 0; c->chan_rank_cap = 0;
+        if ((rc = dev_alloc(&c->d_chan, need)) || (rc = dev_alloc(&c->d_chan_rank, need_r))) return rc;
+        c->chan_cap = need; c->chan_rank_cap = need_r;
+    }
+    cplx* Glr = c->d_chan;
+    cplx* Z = Glr + kk * batch;
+    cplx* W = Z + kk * batch;
+    cplx* H = W + kk * batch;
+    cplx* Lh = H + ks2 * batch;
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    for (int m0 = 0; m0 < m; m0 += batch) {
+        const int nb = std::min(batch, m - m0);
+        if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
+        GammaSmall gL, gR;
+        {
+            ProfScope ps(c, "gamma");
+            if ((rc = run_gamma_small(c, p, pl.cL, nb, 0, &gL))) return rc;
+            if ((rc = run_gamma_small(c, p, pl.cR, nb, 1, &gR))) return rc;
+        }
+        const GammaSmall& gs = pl.mirror ? gR : gL;
+        const GammaSmall& go = pl.mirror ? gL : gR;
+        const size_t lstride = constant ? 0 : ks2;
+        if (!constant || m0 == 0) {
+            ProfScope ps(c, "eig");
+            if (!launch_pivoted_cholesky(c->stream, Ks, constant ? 1 : nb, gs.mat, gs.stride, Lh, ks2, c->d_chan_rank))
+                return NEGF_EINVAL;
+        }
+        {
+            ProfScope ps(c, "zgemm");
+            launch_gather_block(c->stream, n, pl.KL, pl.KR, nb, c->G, n2, gL.idx, gR.idx, Glr, kk);
+            // Z = L^H op(G_LR): G_LR (K_L x K_R) as it is, or its conjugate transpose (stored N x K, opB = 1) in the mirror form
+            launch_zgemm(c->stream, Ks, Ko, Ks, nb, Lh, Ks, lstride, Glr, pl.mirror ? Ks : Ko, kk, pl.mirror ? 1 : 0, Z, Ko, kk);
+            launch_zgemm(c->stream, Ks, Ko, Ko, nb, Z, Ko, kk, go.mat, Ko, go.stride, 0, W, Ko, kk);
+            launch_zgemm(c->stream, Ks, Ks, Ko, nb, W, Ko, kk, Z, Ko, kk, 1, H, Ks, ks2);
+        }
+        ProfScope ps(c, "eig");
+        // (the rank of a CONST factor serves every energy: rank stride 0.  All nchan columns are written: values,
+        //  zeros beyond the rank or K_s, or a whole NaN row for a singular energy)
+        if (!launch_eigvalsh_batched(c->stream, Ks, nb, H, Ks, ks2, c->d_chan_rank, constant ? 0 : 1, T_dev + (size_t)m0 * nchan, nchan,
+                                     nchan, true, c->d_info + m0, true, -1)) return NEGF_EINVAL;
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_transmission_channels(negf_ctx* c, int handle, int contact_L, int contact_R, int m, const double* E,
+                               int nchan, double* T_chan, int* info)
+{
+    SigmaProvider* p = get_provider(c, handle);
+    int rc = check_ready(c, p, m);
+    if (rc) return rc;
+    if (nchan < 1 || (m > 0 && (!E || !T_chan))) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    const size_t cnt = (size_t)m * nchan;
+    if (cnt > c->chan_T_cap) {
+        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
+        dev_free(c->d_chan_T); c->chan_T_cap = 0;
+        if ((rc = dev_alloc(&c->d_chan_T, cnt))) return rc;
+        c->chan_T_cap = cnt;
+    }
+    if ((rc = negf_transmission_channels_dev(c, handle, contact_L, contact_R, m, reinterpret_cast<double*>(c->d_E), nchan,
+                                             c->d_chan_T))) return rc;
+    if ((rc = download(c, T_chan, c->d_chan_T, cnt))) return rc;
+    return reduce_info(c, m, info);
+}
+
+int negf_eigvalsh_batched(negf_ctx* c, int K, int m, const double* A, double* w, int* info)
+{
+    if (!c) return NEGF_EINVAL;
+    if (K < 1 || K > channels_kmax() || m < 0 || (m > 0 && (!A || !w))) return NEGF_EINVAL;
+    if (m == 0) return NEGF_OK;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    const size_t k2 = (size_t)K * K;
+    cplx* dA = nullptr; double* dw = nullptr; int* di = nullptr;
+    int rc;
+    if ((rc = dev_alloc(&dA, k2 * m)) || (rc = dev_alloc(&dw, (size_t)K * m)) || (rc = dev_alloc(&di, (size_t)m))) {
+        dev_free(dA); dev_free(dw); return rc;
+    }
+    std::vector<int> hi((size_t)m);
+    rc = upload(c, dA, reinterpret_cast<const cplx*>(A), k2 * m);
+    if (!rc) {
+        ProfScope ps(c, "eig");
+        if (!launch_eigvalsh_batched(c->stream, K, m, dA, K, k2, nullptr, 0, dw, K, K, false, di, false, 1)) rc = NEGF_EINVAL;
+    }
+    if (!rc && hipGetLastError() != hipSuccess) rc = NEGF_EHIP;
+    if (!rc) rc = download(c, w, dw, (size_t)K * m);
+    if (!rc) rc = download(c, hi.data(), di, (size_t)m);
+    dev_free(dA); dev_free(dw); dev_free(di);
+    if (rc) return rc;
+    for (int i = 0; i < m; ++i) {
+        if (info) info[i] = hi[i];
+        if (hi[i] != 0) rc = NEGF_ESINGULAR;
+    }
+    return rc;
+}
+
 // ------------------------------------------------------------ g(E) cache knob
 int negf_set_chain_cache(negf_ctx* c, int max_grids)
 {
@@ -2055,6 +2228,14 @@ int negf_chain_cache_stats(negf_ctx* c, long long* hits, long long* misses, long
 }
 
 // ------------------------------------------------------------------ diagnostics
+int negf_workspace_bytes(negf_ctx* c, long long* work, long long* blocks)
+{
+    if (!c) return NEGF_EINVAL;
+    if (work) *work = c->batch > 0 ? 3LL * ((long long)c->n * c->n * c->batch + 64) * (long long)sizeof(cplx) : 0;
+    if (blocks) *blocks = (long long)c->blk_cap * (long long)sizeof(cplx);
+    return NEGF_OK;
+}
+
 int negf_profile_enable(negf_ctx* c, int on) { if (!c) return NEGF_EINVAL; c->profiling = on != 0; return NEGF_OK; }
 int negf_profile_reset(negf_ctx* c) { if (!c) return NEGF_EINVAL; prof_resolve(c); c->prof.clear(); return NEGF_OK; }
 int negf_profile_read(negf_ctx* c, const char* family, double* total_ms, int* launches)

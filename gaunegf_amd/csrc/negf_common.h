@@ -115,6 +115,11 @@ struct SigmaProvider {
     // (block providers without Xi; CONST providers whose matrices vanish outside a small support)
     bool compact_ok = false;
     cplx* d_const_blk = nullptr;   // CONST: Sigma_c restricted to its support, [blk_stride]
+    // CONST: every contact's Sigma has a nonzero support and the block fields above describe it (set whenever that
+    // holds, also when the supports cover more than half of the orbitals and compact_ok is false): the eigenchannel
+    // path (negf_transmission_channels) reads Gamma_c on its orbital list from d_const_blk.  Without compact_ok the
+    // provider keeps blk_stride = 0: it sizes the context's Sigma block staging (d_blk), which no CONST path reads
+    bool has_blocks = false;
     // PRECOMPUTED
     int m_pre = 0;
     int pre_nc = 0;
@@ -225,6 +230,12 @@ struct negf_ctx {
     unsigned char* d_ref_meta = nullptr;   // its level table: ratio | maxdp | maxbits [REF_MAX_LEVELS each] | first[REF_MAX_INTS + 1] | level[REF_MAX_INTS] | nanflag[REF_MAX_LEVELS]
     cplx* d_small_part = nullptr;  // per-workgroup partial sums of the small fused kernel
     size_t small_part_cap = 0;
+    cplx* d_chan = nullptr;        // eigenchannel work area: G[I_L, I_R], the products and H per energy, and L^H (negf_transmission_channels)
+    size_t chan_cap = 0;
+    int* d_chan_rank = nullptr;    // rank of the pivoted Cholesky factor per energy
+    size_t chan_rank_cap = 0;
+    double* d_chan_T = nullptr;    // [m][nchan] staging of the host-pointer entry point
+    size_t chan_T_cap = 0;
     GjSideStreams gj_side;
     int chain_rr_quantum = -1, chain_rr_slots = 0;   // negf_set_chain_round_robin
     int small_algo = 0;            // 0: n <= 96 takes the fused single-kernel path, 1: never (negf_set_small_algo)
@@ -382,6 +393,18 @@ struct SmallFusedArgs {
     int nseg = 0;                     // > 0: the energies are nseg consecutive segments ending at seg_end[s] (HOST array);
     const int* seg_end = nullptr;     //      out holds one n x n sum per segment
 };
+// Eigenchannels (k_channels.hip): one workgroup per matrix, K <= channels_kmax().
+// Eigenvalues of the Hermitian matrices in the lower triangles of A[b] (their leading rank[b] x rank[b] blocks when
+// rank is non-null; rank[b * rank_stride], 0 = one rank for all), sorted ascending or descending into w[b * ldw + 0 .. nout), exact zeros at positions >= rank[b].
+// info[b]: chk_in -> a nonzero info[b] on entry yields a NaN row and is kept; else flag_sign * (0 converged,
+// 1 non-finite input -> NaN row, 2 not converged within the sweep limit).  false: K out of range (nothing launched).
+int channels_kmax();
+bool launch_eigvalsh_batched(hipStream_t st, int K, int nb, const cplx* A, int lda, size_t strideA, const int* rank,
+                             int rank_stride, double* w, int ldw, int nout, bool descending, int* info, bool chk_in, int flag_sign);
+// Pivoted Cholesky of the Hermitian PSD K x K matrices G[b]: Lh[b] = L^H (K x K, rows >= rank[b] zero), G ~ L L^H
+bool launch_pivoted_cholesky(hipStream_t st, int K, int nb, const cplx* G, size_t strideG, cplx* Lh, size_t strideL,
+                             int* rank);
+
 bool small_fused_supported(int n);
 int small_fused_grid(int n, int m);
 void launch_small_fused(hipStream_t st, SmallFusedArgs a);

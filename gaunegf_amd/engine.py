@@ -404,6 +404,82 @@ class Engine:
         self._numerical(rc, info[:E.size], "transmission")
         return (T, Ts) if spin_block else T
 
+    # ------------------------------------------------------ eigenchannels
+    EIG_KMAX = 96
+
+    def eigvalsh(self, A):
+        """Ascending eigenvalues [m, K] of the Hermitian matrices A [m, K, K] (or one [K, K] -> [K]), K <= 96, read from
+        their lower triangles like numpy.linalg.eigvalsh: batched complex Jacobi on the GPU (negf_eigvalsh_batched).
+        A row whose input is not finite is NaN; ``last_info`` holds the per-matrix flags (1 non-finite, 2 not converged)."""
+        A = np.asarray(A)
+        single = A.ndim == 2
+        A = _c128(A[None] if single else A)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise ValueError(f"eigvalsh: expected [m, K, K] Hermitian matrices, got shape {A.shape}")
+        m, K = A.shape[0], A.shape[1]
+        if not 1 <= K <= self.EIG_KMAX:
+            raise ValueError(f"eigvalsh: K = {K} outside 1 .. {self.EIG_KMAX} (the matrix is held in one compute unit's LDS)")
+        w = np.zeros((m, K), dtype=np.float64)
+        info = np.zeros(max(m, 1), dtype=np.int32)
+        rc = check(self._lib.negf_eigvalsh_batched(self._ctx, K, m, _ptr(A), _ptr(w), _ptr(info)), "negf_eigvalsh_batched")
+        self.last_info = info[:m]
+        if rc == _lib.NEGF_ESINGULAR:
+            bad = np.nonzero(info[:m])[0]
+            warnings.warn(f"eigvalsh: non-finite input or no convergence for matrices {bad[:8].tolist()}"
+                          f"{'...' if bad.size > 8 else ''}", RuntimeWarning)
+        return w[0] if single else w
+
+    def channel_count(self, handle, contact_L, contact_R):
+        """min(K_L, K_R): the number of transmission eigenchannels of (contact_L, contact_R).  NotImplementedError for
+        providers whose couplings are not confined to an orbital list, and for more than 96 channels."""
+        nc = C.c_int(0)
+        rc = self._lib.negf_channel_count(self._ctx, int(handle), int(contact_L), int(contact_R), C.byref(nc))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(
+                "transmission eigenchannels need a self-energy provider whose couplings live on known contact orbital "
+                "lists (constant Sigma with a nonzero support per contact, 1-D chain leads, Bethe leads without the "
+                f"Xi Sigma Xi transform) and at most {self.EIG_KMAX} channels; this provider / contact pair is not served")
+        check(rc, "negf_channel_count")
+        return nc.value
+
+    def transmission_channels(self, handle, contact_L, contact_R, E, nchan=None):
+        """Transmission eigenchannels T_n(E) [m, nchan], descending per energy (negf_transmission_channels); nchan
+        defaults to channel_count().  Rows of singular energies are NaN (with a warning, as transmission)."""
+        count = self.channel_count(handle, contact_L, contact_R)
+        nchan = count if nchan is None else int(nchan)
+        if nchan < 1:
+            raise ValueError("nchan must be at least 1")
+        E, _ = self._grid(E)
+        T = np.zeros((E.size, nchan), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = check(self._lib.negf_transmission_channels(self._ctx, int(handle), int(contact_L), int(contact_R), E.size,
+                                                        _ptr(E), nchan, _ptr(T), _ptr(info)), "negf_transmission_channels")
+        info = info[:E.size]
+        # info > 0: singular E S - F - Sigma (LAPACK pivot column); < 0: the eigensolver's flags on H (-1 non-finite,
+        # -2 not converged) -- reported apart
+        self._numerical(_lib.NEGF_ESINGULAR if np.any(info > 0) else 0, np.where(info > 0, info, 0), "transmission_channels")
+        self.last_info = info
+        bad = np.nonzero(info < 0)[0]
+        if bad.size:
+            what = {-1: "non-finite H", -2: "Jacobi not converged within its sweep limit"}
+            kinds = sorted({what.get(int(v), str(int(v))) for v in info[bad]})
+            warnings.warn(f"transmission_channels: eigensolver flags ({', '.join(kinds)}) at energy indices "
+                          f"{bad[:8].tolist()}{'...' if bad.size > 8 else ''}", RuntimeWarning)
+        return T
+
+    def workspace_bytes(self):
+        """(work, blocks): device bytes of the three n x n work areas per energy in flight and of the Sigma block staging
+        of chain / Bethe providers (negf_workspace_bytes)."""
+        w = C.c_longlong(0); b = C.c_longlong(0)
+        check(self._lib.negf_workspace_bytes(self._ctx, C.byref(w), C.byref(b)), "negf_workspace_bytes")
+        return w.value, b.value
+
+    def transmission_channels_dev(self, handle, contact_L, contact_R, m, E_ptr, nchan, T_ptr):
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        check(self._lib.negf_transmission_channels_dev(self._ctx, int(handle), int(contact_L), int(contact_R), int(m),
+                                                       C.c_void_p(E_ptr), int(nchan), C.c_void_p(T_ptr)),
+              "negf_transmission_channels_dev")
+
     def dos(self, handle, E, per_site=True):
         E, _ = self._grid(E)
         tot = np.zeros(E.size, dtype=np.float64)

@@ -251,6 +251,69 @@ def _transmission_batch(F, S, sigma_calc, energies, spin):
             eng.sigma_free(h)
 
 
+def _channels_batch(F, S, sigma_calc, energies, spin, nchan):
+    """Transmission eigenchannels [m, nchan] ('r') or (up, down) for all ``energies`` on the GPU."""
+    if spin not in ('r', 'u', 'ro', 'g'):
+        raise ValueError(f"Unknown spin configuration '{spin}'. Use 'r', 'u', 'ro', or 'g'")
+    energies = np.asarray(energies)
+    F = np.asarray(F)
+    S = np.asarray(S)
+    size = F.shape[0]
+    if spin == 'g':
+        raise NotImplementedError("transmission eigenchannels: the spinor ('g') layout mixes spins inside each contact "
+                                  "block; channels are served for 'r' and for spin-diagonal 'u' / 'ro' systems only")
+    if spin in ('u', 'ro'):
+        blocks = _spin_diagonal_blocks(F, S) if _sigma_is_spin_expanded(sigma_calc, size) else None
+        if blocks is None:
+            raise NotImplementedError("transmission eigenchannels with spin 'u' / 'ro' need an exactly block-diagonal "
+                                      "(spin-diagonal) F, S and a spin-expanded N x N self-energy; spin mixing is not served")
+        return (_channels_batch(blocks[0], blocks[1], sigma_calc, energies, 'r', nchan),
+                _channels_batch(blocks[2], blocks[3], sigma_calc, energies, 'r', nchan))
+    eng = get_engine()
+    eng.set_system(F, S)
+    if sigma_calc.energy_dependent and not hasattr(sigma_calc.sig1, "_negf_lower"):
+        raise NotImplementedError("transmission eigenchannels need a provider the engine lowers itself (surfGTest, "
+                                  "surfG, surfGB or static matrices); this self-energy object is evaluated on the host")
+    h, temp = sigma_calc._lower(eng, energies, spin, size)
+    try:
+        if temp:
+            raise NotImplementedError("transmission eigenchannels: this self-energy is staged per energy (no contact "
+                                      "orbital lists); use static matrices or a native surfG / surfGB / surfGTest object")
+        return eng.transmission_channels(h, 0, -1, energies, nchan)
+    finally:
+        if temp:
+            eng.sigma_free(h)
+
+
+def _channel_count(F, S, sigma_calc, spin):
+    """Number of channels calculate_transmission_channels reports by default (min(K_L, K_R) of the lowered provider)."""
+    F = np.asarray(F)
+    S = np.asarray(S)
+    if spin in ('u', 'ro'):
+        blocks = _spin_diagonal_blocks(F, S) if _sigma_is_spin_expanded(sigma_calc, F.shape[0]) else None
+        if blocks is None:
+            raise NotImplementedError("transmission eigenchannels with spin 'u' / 'ro' need an exactly block-diagonal "
+                                      "(spin-diagonal) F, S and a spin-expanded N x N self-energy; spin mixing is not served")
+        F, S = blocks[0], blocks[1]
+    elif spin == 'g':
+        raise NotImplementedError("transmission eigenchannels: the spinor ('g') layout mixes spins inside each contact "
+                                  "block; channels are served for 'r' and for spin-diagonal 'u' / 'ro' systems only")
+    if sigma_calc.energy_dependent and not hasattr(sigma_calc.sig1, "_negf_lower"):
+        raise NotImplementedError("transmission eigenchannels need a provider the engine lowers itself (surfGTest, "
+                                  "surfG, surfGB or static matrices); this self-energy object is evaluated on the host")
+    eng = get_engine()
+    eng.set_system(F, S)
+    h, temp = sigma_calc._lower(eng, np.zeros(0), 'r', F.shape[0])
+    try:
+        if temp:
+            raise NotImplementedError("transmission eigenchannels: this self-energy is staged per energy (no contact "
+                                      "orbital lists)")
+        return eng.channel_count(h, 0, -1)
+    finally:
+        if temp:
+            eng.sigma_free(h)
+
+
 def _dos_batch(F, S, sigma_calc, energies, spin):
     F = np.asarray(F)
     S = np.asarray(S)
@@ -379,6 +442,37 @@ def calculate_transmission(F, S, sigma_calculator, energy_list, spin=None, check
     if spin_trans is not None:
         return transmission, spin_trans
     return transmission
+
+
+def calculate_transmission_channels(F, S, sigma_calculator, energy_list, spin=None, nchan=None):
+    """Transmission eigenchannels: T(E) = sum_n T_n(E), T_n the eigenvalues of t^H t with t = Gamma_R^{1/2} G_RL
+    Gamma_L^{1/2} -- how many channels conduct and how much each carries.  Returns [m, nchan] for spin 'r', and
+    (up, down) for 'u' / 'ro' on a spin-diagonal system with a spin-expanded self-energy.  Each row is descending,
+    exact zeros beyond the numerical rank of the smaller contact's coupling; sum_n T_n(E) equals
+    calculate_transmission.  ``nchan`` defaults to min(K_L, K_R), the contacts' orbital counts (at most 96).
+    Served for self-energies confined to contact orbital lists (static matrices, surfGTest, surfG, surfGB without
+    the Xi Sigma Xi transform); others, 'g' and spin mixing raise NotImplementedError.  A contact's orbital list is the
+    support of its Sigma: formSigma (and so surfGTest) adds -1e-9 i S on every orbital, which makes K_L = K_R = N --
+    N channels, most of them the ~1e-9 background (it is above the 1e-14 relative rank cut), and NotImplementedError
+    for N > 96.  Static matrices that vanish outside the contact orbitals give K_c = the contact's orbital count."""
+    energy_list = np.asarray(energy_list)
+    if spin is None:
+        spin = 'r'
+    if spin not in ('r', 'u', 'ro', 'g'):
+        raise ValueError(f"Unknown spin configuration '{spin}'. Use 'r', 'u', 'ro', or 'g'")
+    if nchan is None:
+        nchan = _channel_count(F, S, sigma_calculator, spin)
+    nchan = int(nchan)
+    m = len(energy_list)
+    if spin == 'r':
+        return _dist.sharded_map(lambda idx: _channels_batch(F, S, sigma_calculator, energy_list[idx], spin, nchan),
+                                 m, (nchan,))
+
+    def both(idx):
+        up, down = _channels_batch(F, S, sigma_calculator, energy_list[idx], spin, nchan)
+        return np.concatenate([up, down], axis=1)
+    res = _dist.sharded_map(both, m, (2 * nchan,))
+    return res[:, :nchan], res[:, nchan:]
 
 
 def calculate_dos(F, S, sigma_calculator, energy_list, spin=None, checkpoint_file=None,
@@ -548,6 +642,17 @@ def cohTrans(Elist, F, S, sig1, sig2):
     T_ = calculate_transmission(F, S, _static_calc(sig1, sig2), Elist, spin='r')
     _report(Elist, T_, "Transmission")
     return T_.tolist()
+
+
+def cohTransChannels(Elist, F, S, sig1, sig2, nchan=None):
+    """Transmission eigenchannels [M, nchan] with energy-independent self-energies (next to cohTrans); each row sums
+    to cohTrans's T(E)."""
+    return calculate_transmission_channels(F, S, _static_calc(sig1, sig2), Elist, spin='r', nchan=nchan)
+
+
+def cohTransChannelsE(Elist, F, S, g, nchan=None):
+    """Transmission eigenchannels [M, nchan] with an energy-dependent provider ``g`` (next to cohTransE)."""
+    return calculate_transmission_channels(F, S, _dynamic_calc(g), Elist, spin='r', nchan=nchan)
 
 
 def _spin_trans(Elist, F, S, calc, spin):

@@ -253,9 +253,43 @@ int negf_chain_cache_clear(negf_ctx* ctx);
 /* counters since negf_create; entries / bytes currently held (any pointer may be NULL) */
 int negf_chain_cache_stats(negf_ctx* ctx, long long* hits, long long* misses, long long* entries, long long* bytes);
 
+/* ------------------------------------------------------ transmission eigenchannels
+ * T(E) = sum_n T_n(E), T_n the eigenvalues of t^H t, t = Gamma_R^{1/2} G_RL Gamma_L^{1/2} (the reference has no such
+ * function; it is the decomposition of its _transmission_kernel_restricted, transport.py:150-157).  For contacts L, R with
+ * orbital lists I_L, I_R (|I_L| = K_L, |I_R| = K_R):
+ *   Gamma_c = i (Sigma_c - Sigma_c^H) on I_c,  B = G[I_L,I_R] Gamma_R G[I_L,I_R]^H  (K_L x K_L, Hermitian PSD),
+ *   Gamma_L = L L^H by PIVOTED Cholesky, truncated where the largest remaining diagonal is <= 1e-14 max diag Gamma_L
+ *   (Gamma is PSD and often rank-deficient; L has r_L <= K_L columns),
+ *   T_n = eigenvalues of H = L^H B L (r_L x r_L): the nonzero spectrum of t^H t.
+ * When K_R < K_L the mirror form (L and R swapped, B = G[I_L,I_R]^H Gamma_L G[I_L,I_R]) puts the eigenproblem on the
+ * smaller contact.  Output: nchan = min(K_L, K_R) values per energy in DESCENDING order, exact zeros beyond the
+ * numerical rank, not clamped (a channel of -1e-17 is reported as such).  Sum rule: sum_n T_n = Re Tr[Gamma_L G
+ * Gamma_R G^H], what negf_transmission returns, up to rounding and the truncation above.
+ * Providers: those whose Gamma_c is confined to a known orbital list -- CONST when every contact's Sigma has a nonzero
+ * support, CHAIN1D, BETHE without Xi; any other provider, the total self-energy as a contact, or min(K_L, K_R) > 96
+ * return NEGF_EINVAL. */
+
+/* ascending eigenvalues of m Hermitian K x K matrices (K <= 96), read from their lower triangles (imaginary parts of
+ * the diagonal ignored) -- the reference's utils.eigh (utils.py:61-63) / numpy.linalg.eigvalsh, values only.  Parallel
+ * cyclic complex Jacobi, one workgroup per matrix.  A_c128 [m][K][K], w [m][K]; info [m] or NULL: 0, 1 = non-finite
+ * input (NaN row), 2 = not converged within the sweep limit; NEGF_ESINGULAR when any info is nonzero. */
+int negf_eigvalsh_batched(negf_ctx* ctx, int K, int m, const double* A_c128, double* w, int* info);
+/* min(K_L, K_R): the number of channels of (contact_L, contact_R); NEGF_EINVAL where the channels are not served */
+int negf_channel_count(negf_ctx* ctx, int handle, int contact_L, int contact_R, int* nchan);
+/* T_chan [m][nchan]: the min(nchan, count) largest channels, zeros in columns >= count.  info [m] or NULL as in
+ * negf_transmission (a singular energy gives a NaN row, every one of its nchan columns); additionally -1 / -2 where the eigensolver met a non-finite
+ * H / did not converge (NEGF_ESINGULAR then as well). */
+int negf_transmission_channels(negf_ctx* ctx, int handle, int contact_L, int contact_R, int m, const double* E_c128,
+                               int nchan, double* T_chan, int* info);
+int negf_transmission_channels_dev(negf_ctx* ctx, int handle, int contact_L, int contact_R, int m, const double* E_dev,
+                                   int nchan, double* T_chan_dev);
+
 /* ------------------------------------------------------------- diagnostics */
 /* hipEvent timing of the library's own kernels, per kernel family
- * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe"). */
+ * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig"). */
+/* device bytes held by the context's energy workspace: the three n x n work areas per energy in flight (work) and the
+ * staging of the self-energy blocks of CHAIN1D / BETHE providers (blocks); either pointer may be NULL */
+int negf_workspace_bytes(negf_ctx* ctx, long long* work, long long* blocks);
 int negf_profile_enable(negf_ctx* ctx, int on);
 int negf_profile_reset(negf_ctx* ctx);
 int negf_profile_read(negf_ctx* ctx, const char* family, double* total_ms, int* launches);
