@@ -302,6 +302,18 @@ __device__ __forceinline__ double sf_readlane_f64(double v, int lane)       // (
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
 }
 
+// the multiplier product and the update of the columns-per-wave layout with their fused multiply-adds spelled out: both
+// forms below (per step, per panel) then round identically whatever the compiler would contract at each site
+__device__ __forceinline__ cplx sf_mul(cplx a, cplx b)
+{
+    return cmake(fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x));
+}
+
+__device__ __forceinline__ cplx sf_fnma(cplx a, cplx b, cplx c)          // a - b c
+{
+    return cmake(fma(b.y, c.y, fma(-b.x, c.x, a.x)), fma(-b.y, c.x, fma(-b.x, c.y, a.y)));
+}
+
 // ---- second layout (round 4, later; the default): COLUMNS PER WAVE, ROWS PER LANE.  Wave w owns the columns
 // [w CPW, (w+1) CPW), lane l the rows l and l + 64 (RPL = 1 for n <= 64): the tile W[RPL][CPW] is again in registers
 // with static indices, because the pivot steps run as  for (owner wave) for (c = 0 .. CPW-1, unrolled)  -- step
@@ -311,9 +323,12 @@ __device__ __forceinline__ double sf_readlane_f64(double v, int lane)       // (
 //     needs two: there column and row are both spread over all waves);
 //   * the pivot row's entries in a wave's own columns are in that wave's lane p: a wave-local LDS line (written by one
 //     lane, read by all, no barrier -- a wave's LDS operations execute in order), as in the chain kernel's rs_factor;
-//   * the update is select-free: multipliers f_i = c_i / pivot for i != p and f_p = 1 - 1 / pivot (row p then becomes
-//     row_p / pivot by the same formula), column k reset to the unit vector e_p beforehand, so every lane runs
-//     RPL x CPW complex FMAs on the RAW pivot row: ~150 vector instructions per step and wave against ~350.
+//   * the update is select-free: multipliers f_i = c_i / pivot for i != p and f_p = -1 / pivot, with row p (in lane p)
+//     and column k (in the owner wave) reset to zero beforehand, so row p becomes 0 - (-1 / pivot) row_p = row_p / pivot
+//     by the same formula and every lane runs RPL x CPW complex FMAs on the RAW pivot row: ~150 vector instructions per
+//     step and wave against ~350.  (Not f_p = 1 - 1 / pivot on the row itself: 1 - 1 / pivot is rounded to an ABSOLUTE
+//     u, which costs the pivot row log2 |pivot| bits and erases it for |pivot| >= 2^53 -- core levels, or E, F, Sigma in
+//     other units -- while every other operation here is exact under a power-of-two scale.)
 // The matrix is assembled into LDS with coalesced reads first (same operation order as the tile layout), the
 // un-permuted inverse goes back to LDS, and the accumulate / store phases are those of the tile layout.
 template <int RPL, int CPW, bool PANEL>
@@ -403,33 +418,36 @@ __global__ __launch_bounds__(SF_THREADS, RPL == 1 ? 4 : 2) void small_cw_kernel(
 #pragma unroll
                             for (int r = 0; r < RPL; ++r) {
                                 const int i = lane + 64 * r;
-                                const cplx m_ = cmul(W[r][c], ip);
+                                const cplx m_ = sf_mul(W[r][c], ip);
                                 const bool isp = i == p;
-                                f[r] = cmake(isp ? 1.0 - ip.x : m_.x, isp ? -ip.y : m_.y);
+                                f[r] = cmake(isp ? -ip.x : m_.x, isp ? -ip.y : m_.y);
                                 used[r] = used[r] || isp;
                                 Fq[c * ROWS + i] = f[r];
                             }
                             if (lane == 0) { pivrow_s[k] = p; colof_s[p] = k; }
                             __builtin_amdgcn_wave_barrier();
-                            if (lane == pl) {                     // (column k becomes e_p: its entry in row p is 1)
+                            if (lane == pl) {                     // (column k becomes e_p: its entry in row p is 1); row p restarts from 0
                                 if (RPL == 2 && pr) {             // (a uniform branch, not a select between the register rows)
 #pragma unroll
-                                    for (int cc = 0; cc < CPW; ++cc) rowl[wave][cc] = cc == c ? cmake(1.0, 0.0) : W[RPL - 1][cc];
+                                    for (int cc = 0; cc < CPW; ++cc) { rowl[wave][cc] = cc == c ? cmake(1.0, 0.0) : W[RPL - 1][cc]; W[RPL - 1][cc] = cmake(0.0, 0.0); }
                                 } else {
 #pragma unroll
-                                    for (int cc = 0; cc < CPW; ++cc) rowl[wave][cc] = cc == c ? cmake(1.0, 0.0) : W[0][cc];
+                                    for (int cc = 0; cc < CPW; ++cc) { rowl[wave][cc] = cc == c ? cmake(1.0, 0.0) : W[0][cc]; W[0][cc] = cmake(0.0, 0.0); }
                                 }
                             }
                             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                             __builtin_amdgcn_wave_barrier();
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                            // (an opaque zero, as in the per-step form: a literal one lets the compiler fold the update of column k
+                            // and contract it differently -- the two forms would no longer be bitwise equal)
+                            const double z0 = sf_opaque(0.0);
 #pragma unroll
-                            for (int r = 0; r < RPL; ++r) W[r][c] = cmake(lane + 64 * r == p ? 1.0 : 0.0, 0.0);
+                            for (int r = 0; r < RPL; ++r) W[r][c] = cmake(z0, z0);
 #pragma unroll
                             for (int cc = 0; cc < CPW; ++cc) {
                                 const cplx rb = rowl[wave][cc];
 #pragma unroll
-                                for (int r = 0; r < RPL; ++r) W[r][cc] = cfnma(W[r][cc], f[r], rb);
+                                for (int r = 0; r < RPL; ++r) W[r][cc] = sf_fnma(W[r][cc], f[r], rb);
                             }
                         }
                     }
@@ -455,13 +473,13 @@ __global__ __launch_bounds__(SF_THREADS, RPL == 1 ? 4 : 2) void small_cw_kernel(
                                 pn = pivrow_s[k + 1];
                             }
                             __builtin_amdgcn_wave_barrier();
-                            if (lane == pl) {
+                            if (lane == pl) {                     // (row p restarts from 0)
                                 if (RPL == 2 && pr) {
 #pragma unroll
-                                    for (int cc = 0; cc < CPW; ++cc) rowl[wave][cc] = W[RPL - 1][cc];
+                                    for (int cc = 0; cc < CPW; ++cc) { rowl[wave][cc] = W[RPL - 1][cc]; W[RPL - 1][cc] = cmake(0.0, 0.0); }
                                 } else {
 #pragma unroll
-                                    for (int cc = 0; cc < CPW; ++cc) rowl[wave][cc] = W[0][cc];
+                                    for (int cc = 0; cc < CPW; ++cc) { rowl[wave][cc] = W[0][cc]; W[0][cc] = cmake(0.0, 0.0); }
                                 }
                             }
                             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -471,7 +489,7 @@ __global__ __launch_bounds__(SF_THREADS, RPL == 1 ? 4 : 2) void small_cw_kernel(
                             for (int cc = 0; cc < CPW; ++cc) {
                                 const cplx rb = rowl[wave][cc];
 #pragma unroll
-                                for (int r = 0; r < RPL; ++r) W[r][cc] = cfnma(W[r][cc], f[r], rb);
+                                for (int r = 0; r < RPL; ++r) W[r][cc] = sf_fnma(W[r][cc], f[r], rb);
                             }
                         }
                     }
@@ -515,6 +533,14 @@ __global__ __launch_bounds__(SF_THREADS, RPL == 1 ? 4 : 2) void small_cw_kernel(
                             // (in the owner wave column k is about to become the unit vector e_p: its entry in row p is 1)
                             rowl[wave][cc] = (wave == ow && cc == c) ? cmake(1.0, 0.0) : v;
                         }
+                        // row p restarts from 0: the update below leaves 0 - (-1 / pivot) row_p in it
+                        if (RPL == 2 && pr) {
+#pragma unroll
+                            for (int cc = 0; cc < CPW; ++cc) W[RPL - 1][cc] = cmake(0.0, 0.0);
+                        } else {
+#pragma unroll
+                            for (int cc = 0; cc < CPW; ++cc) W[0][cc] = cmake(0.0, 0.0);
+                        }
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
@@ -524,20 +550,21 @@ __global__ __launch_bounds__(SF_THREADS, RPL == 1 ? 4 : 2) void small_cw_kernel(
                     for (int r = 0; r < RPL; ++r) {
                         const int i = lane + 64 * r;
                         const cplx cv = colb[buf][i];             // (rows >= n hold zeros: published by the owner)
-                        const cplx m_ = cmul(cv, ip);
+                        const cplx m_ = sf_mul(cv, ip);
                         const bool isp = i == p;
-                        f[r] = cmake(isp ? 1.0 - ip.x : m_.x, isp ? -ip.y : m_.y);
+                        f[r] = cmake(isp ? -ip.x : m_.x, isp ? -ip.y : m_.y);
                         used[r] = used[r] || isp;
                     }
                     if (wave == ow) {
+                        const double z0 = sf_opaque(0.0);
 #pragma unroll
-                        for (int r = 0; r < RPL; ++r) W[r][c] = cmake(lane + 64 * r == p ? 1.0 : 0.0, 0.0);
+                        for (int r = 0; r < RPL; ++r) W[r][c] = cmake(z0, z0);
                     }
 #pragma unroll
                     for (int cc = 0; cc < CPW; ++cc) {
                         const cplx rb = rowl[wave][cc];
 #pragma unroll
-                        for (int r = 0; r < RPL; ++r) W[r][cc] = cfnma(W[r][cc], f[r], rb);
+                        for (int r = 0; r < RPL; ++r) W[r][cc] = sf_fnma(W[r][cc], f[r], rb);
                     }
                 }
             }
