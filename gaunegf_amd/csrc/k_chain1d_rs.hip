@@ -64,13 +64,13 @@ constexpr int RS_NB = RS_PANEL;           // panel width of the small inverse: h
 #ifndef RS_RR
 #define RS_RR 1
 #endif
-#ifndef RS_PHAT
-#define RS_PHAT 1                     // 1: the factoring wave stores P - E (E: a one at every (pivot row, its column) of the panel), so that the
-#endif                                //    updates are PURE accumulations W += (P - E) Q -- the pivot rows' old content cancels in the
-                                      //    product instead of being masked per tile (8 compares + 16 selects of the 42 vector
-                                      //    instructions a rank-8 tile update carried beside its 6 matrix instructions); the ones ride
-                                      //    along as constants (every later update is additive, and neither a Q row nor a P operand of a
-                                      //    later panel contains such an element) and are added back where the inverse is read (gather_mix)
+// The pivot rows of a panel are replaced, not updated: W[pivot row][col] = 0 + P[pivot row][:] Q[:][col].  The trailing
+// update needs no per-tile mask for that: the owner of a column tile has the panel's pivot rows of its columns (the Q
+// fragment) in registers before it writes, so it zeroes them in LDS first and every tile is then a pure accumulation
+// W += P Q (rs_update_col).  Only the look-ahead tile, whose Q fragment every wave reads, masks its seed
+// (rs_update_tile<.., true>).  Storing P - E instead (a one short at every (pivot row, its column), added back where
+// the inverse is read) saves the zeroing but forms the pivot row as q + (1/p - 1) q: 1/p - 1 is rounded to an
+// absolute u, so the row loses log2 |p| bits, all of them for |p| >= 2^53, and the read-back (x - 1) + 1 loses u / |x|.
 #ifndef RS_UPD_3M
 #define RS_UPD_3M 1                   // trailing / look-ahead updates (K = 8): 1 = three real products per tile and k-step (3M: operand
 #endif                                //    sums and a 12-instruction recombination per tile), 0 = four (no vector work per tile at all)
@@ -268,7 +268,6 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
     cplx a[RS_NB];                                      //  hoisted out of the fixed-point loop and kept alive)
     bool avail = r < n && colof[r] < 0;
     cplx myip = cmake(1.0, 0.0);
-    int mycol = -1;                                     // the panel column this lane's row is the pivot row of
     cplx* wrow = W + r * P + p0;                        // rows >= n are zero padding
 #pragma unroll
     for (int s = 0; s < RS_NB; ++s) {
@@ -350,7 +349,6 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             }
             a[j] = is_piv ? cmake(1.0, 0.0) : coef;
             myip = cmake(is_piv ? ip.x : myip.x, is_piv ? ip.y : myip.y);
-            mycol = is_piv ? j : mycol;
             avail = avail && !is_piv;
         }
     }
@@ -358,15 +356,14 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
 #pragma unroll
         for (int s = 0; s < RS_NB; ++s)
             if (s < pw) {
-                cplx v = cmul(a[s], myip);                  // the deferred pivot-row scaling
-                if (RS_PHAT && s == mycol) v.x -= 1.0;      // P - E (see RS_PHAT)
-                wrow[s] = v;
+                wrow[s] = cmul(a[s], myip);                 // the deferred pivot-row scaling
             }
     }
 }
 
 // ---- trailing update with panel [p0, p0+pw), in place:
 //        W[i][col] = (i pivot row of the panel ? 0 : W[i][col]) + P[i][:] Q[:][col]
+// (the 0 by a mask of the seed, MASK, or because the pivot rows were zeroed after Q was read: rs_zero_pivot_rows)
 // A Q fragment holds the panel's pivot rows in the columns of one column tile (B operand); for the
 // column-strip tile TR every 4-column block holds the same columns TR*16 + (l&3) (see mfma3s).
 template <int P, int NKS, int TR /* last tile when it is a remainder strip, else -1 */>
@@ -390,7 +387,24 @@ __device__ __forceinline__ void rs_wait_count(const unsigned* cnt, unsigned targ
     while (*reinterpret_cast<const volatile unsigned*>(cnt) < target) __builtin_amdgcn_s_sleep(1);
 }
 
+// the panel's pivot rows in the columns of this lane's Q fragment (rs_load_qf) that are to be updated, [clo, chi) inside
+// the matrix, are set to zero: the owner of those columns calls it after its Q fragment is loaded (a wave's LDS
+// operations execute in order, and the stores may alias the loads, so neither the compiler nor the LDS reorders them)
 template <int P, int NKS, int TR>
+__device__ __forceinline__ void rs_zero_pivot_rows(int n, cplx* W, const int* pivrow, int tj, int p0, int pw, int fi, int fk,
+                                                   int clo, int chi)
+{
+    const int col = (TR >= 0 && tj == TR) ? TR * 16 + (fi & 3) : tj * 16 + fi;
+    if (col >= clo && col < chi && col < n) {
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const int k = ks * 4 + fk;
+            if (k < pw) W[pivrow[p0 + k] * P + col] = cmake(0.0, 0.0);
+        }
+    }
+}
+
+template <int P, int NKS, int TR, bool MASK /* seed the pivot rows of the panel with 0 (else they already are 0) */>
 __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof, int ti, int tj, int p0, int pw,
                                                int fi, int fk, const cplx (&qf)[NKS], int clo, int chi /* columns [clo, chi) are stored */,
                                                const unsigned* wait_cnt = nullptr, unsigned wait_target = 0 /* stores wait for *wait_cnt >= wait_target */)
@@ -402,14 +416,14 @@ __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof,
         cplx cv[4], pa[NKS];
         int cf[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { if (!RS_PHAT) cf[r] = colof[ti * 16 + fk + 4 * r]; cv[r] = cbase[4 * r * P]; }
+        for (int r = 0; r < 4; ++r) { if (MASK) cf[r] = colof[ti * 16 + fk + 4 * r]; cv[r] = cbase[4 * r * P]; }
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) pa[ks] = pbase[ks * 4];
         constexpr bool M3 = RS_UPD_3M && P > 35;            // 3M (mfma3) in the 168-VGPR kernels
         d4 ua, ub = {0, 0, 0, 0}, uc;                       // accumulators, seeded with the old tile
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const bool keep = RS_PHAT || !(cf[r] >= p0 && cf[r] < p0 + pw);
+            const bool keep = !MASK || !(cf[r] >= p0 && cf[r] < p0 + pw);
             ua[r] = keep ? cv[r].x : 0.0; uc[r] = keep ? (M3 ? cv[r].x + cv[r].y : cv[r].y) : 0.0;
         }
 #pragma unroll
@@ -430,12 +444,12 @@ __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof,
         const bool mine = !(rowstrip && colstrip) || (fi >> 2) == 0;      // the corner block exists four times
         const cplx* prow = W + (rowstrip ? TR * 16 + (fi & 3) : ti * 16 + fi) * P + p0 + fk;
         cplx* cptr = W + row * P + col;
-        const int cf = RS_PHAT ? -1 : colof[row];
+        const int cf = MASK ? colof[row] : -1;
         const cplx cv = *cptr;
         cplx pa[NKS];
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) pa[ks] = prow[ks * 4];
-        const bool keep = RS_PHAT || !(cf >= p0 && cf < p0 + pw);
+        const bool keep = !MASK || !(cf >= p0 && cf < p0 + pw);
         double ua = keep ? cv.x : 0.0, ub = 0.0, uc = keep ? cv.x + cv.y : 0.0;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks)
@@ -446,7 +460,8 @@ __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof,
 }
 
 // column tile tj, all row tiles, by the wave that owns the column tile in this stage.  The Q fragment is read
-// into registers before the first store, so the owner needs no snapshot of the pivot rows.
+// into registers before the first store, so the owner needs no snapshot of the pivot rows; it then zeroes them, so
+// that every tile of the column is a pure accumulation.
 template <int T16, int P, int NKS, int TR>
 __device__ __forceinline__ void rs_update_col(int n, cplx* W, const int* pivrow, const int* colof,
                                               int tj, int p0, int pw, int lane, int clo, int chi)
@@ -455,10 +470,11 @@ __device__ __forceinline__ void rs_update_col(int n, cplx* W, const int* pivrow,
     const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
     cplx qf[NKS];
     rs_load_qf<P, NKS, TR>(W, pivrow, tj, p0, pw, fi, fk, qf);
+    rs_zero_pivot_rows<P, NKS, TR>(n, W, pivrow, tj, p0, pw, fi, fk, clo, chi);
     if (TR >= 0 && tj == TR) {                               // the column strip: every tile on the 4x4x4 instruction
 #pragma unroll
         for (int ti = 0; ti < T16; ++ti) {
-            rs_update_tile<P, NKS, TR>(n, W, colof, ti, tj, p0, pw, fi, fk, qf, clo, chi);
+            rs_update_tile<P, NKS, TR, false>(n, W, colof, ti, tj, p0, pw, fi, fk, qf, clo, chi);
             __builtin_amdgcn_sched_barrier(0);
         }
         return;
@@ -471,14 +487,12 @@ __device__ __forceinline__ void rs_update_col(int n, cplx* W, const int* pivrow,
     for (int ks = 0; ks < NKS; ++ks) qs[ks] = qf[ks].x + qf[ks].y;
     cplx* cbase = W + fk * P + col;                          // C tile element (ti*16 + fk + 4r, col)
     const cplx* pbase = W + fi * P + p0 + fk;                // P operand element (ti*16 + fi, p0 + ks*4 + fk)
-    const int* cfb = colof + fk;
     // the operands of row tile ti+1 are requested before tile ti is stored (LDS operations of a wave
     // execute in order, and tile ti+1 shares no element with tile ti), so that the loads overlap the MFMAs
     cplx cv[2][4], pa[2][NKS];
-    int cf[2][4];
     auto fetch = [&](int ti, int s) __attribute__((always_inline)) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { if (!RS_PHAT) cf[s][r] = cfb[ti * 16 + 4 * r]; cv[s][r] = cbase[(ti * 16 + 4 * r) * P]; }
+        for (int r = 0; r < 4; ++r) cv[s][r] = cbase[(ti * 16 + 4 * r) * P];
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) pa[s][ks] = pbase[ti * 16 * P + ks * 4];   // k >= pw pairs with qf == 0 (finite element)
     };
@@ -489,10 +503,7 @@ __device__ __forceinline__ void rs_update_col(int n, cplx* W, const int* pivrow,
         if (ti + 1 < FT) fetch(ti + 1, s ^ 1);
         d4 ua, ub = {0, 0, 0, 0}, uc;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const bool keep = RS_PHAT || !(cf[s][r] >= p0 && cf[s][r] < p0 + pw);
-            ua[r] = keep ? cv[s][r].x : 0.0; uc[r] = keep ? (M3 ? cv[s][r].x + cv[s][r].y : cv[s][r].y) : 0.0;
-        }
+        for (int r = 0; r < 4; ++r) { ua[r] = cv[s][r].x; uc[r] = M3 ? cv[s][r].x + cv[s][r].y : cv[s][r].y; }
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             if (M3) mfma3(ua, ub, uc, pa[s][ks].x, pa[s][ks].y, pa[s][ks].x + pa[s][ks].y, qf[ks].x, qf[ks].y, qs[ks]);
@@ -506,7 +517,7 @@ __device__ __forceinline__ void rs_update_col(int n, cplx* W, const int* pivrow,
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (TR >= 0) rs_update_tile<P, NKS, TR>(n, W, colof, TR, tj, p0, pw, fi, fk, qf, clo, chi);    // the row strip
+    if (TR >= 0) rs_update_tile<P, NKS, TR, false>(n, W, colof, TR, tj, p0, pw, fi, fk, qf, clo, chi);    // the row strip
 }
 
 // In-place blocked Gauss-Jordan reduction of the n x n matrix W (LDS, pitch P) with implicit
@@ -547,12 +558,12 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
             // on to the trailing update, which touches neither the next panel's columns nor anybody else's pivot rows.
             la_epoch += RS_WAVES;
             if (lane == 0) atomicAdd(&la_cnt[0], 1u);
-            if (wave < T16 && wave * 16 < n) rs_update_tile<P, RS_NB / 4, TR>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB, &la_cnt[0], la_epoch);
+            if (wave < T16 && wave * 16 < n) rs_update_tile<P, RS_NB / 4, TR, true>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB, &la_cnt[0], la_epoch);
             if (lane == 0) atomicAdd(&la_cnt[1], 1u);
             if (wave == fw) rs_wait_count(&la_cnt[1], la_epoch);
 #else
             __syncthreads();
-            if (!(RS_ABLATE & 2) && wave < T16 && wave * 16 < n) rs_update_tile<P, RS_NB / 4, TR>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB);
+            if (!(RS_ABLATE & 2) && wave < T16 && wave * 16 < n) rs_update_tile<P, RS_NB / 4, TR, true>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB);
             __syncthreads();
 #endif
         }
@@ -859,12 +870,6 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
         }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) gm[ks] = ks < ksteps ? gsrc[pr[ks] * P] : cmake(0.0, 0.0);
-        if (RS_PHAT) {
-            // the work matrix holds  (reduced M) - E : element (pivrow[c], c) is one short for every column c.  g_new[k][col]
-            // = W[pivrow[k]][colof[col]] is such an element exactly when colof[col] == k
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) gm[ks].x += (cfc == ks * 4 + fk) ? 1.0 : 0.0;
-        }
         if (st && tid == 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st[5] = __builtin_amdgcn_s_memrealtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st[6] = __builtin_amdgcn_s_memrealtime(); }
         bool lane_over = false, lane_ok = true;
         if (!first) {
