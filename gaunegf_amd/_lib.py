@@ -42,6 +42,8 @@ SIGNATURES = {
     "negf_sigma_const": (C.c_int, [_vp, C.c_int, _vp, _ip]),
     "negf_sigma_chain1d": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _ip]),
+    "negf_sigma_chain1d_rd": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        C.c_double, C.c_double, C.c_int, C.c_int, _ip]),
     "negf_sigma_bethe": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _ip]),
     "negf_bethe_raw": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,

@@ -14,6 +14,13 @@ FERMI_CALCULATION_TOL = 1e-3
 FERMI_SEARCH_CYCLES = 10
 SURFACE_GREEN_CONVERGENCE = 1e-5
 SURFACE_RELAXATION_FACTOR = 0.1
+# Solver of the 1-D chain surface Green's function (not in the reference): 'fixed-point' is the reference's relaxed loop
+# (surfG1D.py:223-295), 'doubling' the renormalisation-decimation recursion, stopped when the correction of a step is
+# at most SURFACE_DOUBLING_TOL times the renormalised surface block (2**-52: it no longer reaches it) or after
+# SURFACE_DOUBLING_MAX_STEPS steps
+SURFACE_GREEN_SOLVER = 'fixed-point'
+SURFACE_DOUBLING_TOL = 2**-52
+SURFACE_DOUBLING_MAX_STEPS = 64
 
 # Integration parameters
 ADAPTIVE_INTEGRATION_TOL = 1e-4

@@ -36,51 +36,10 @@
 // Every job stops on ITS OWN convergence (the reference's vmap runs all energies until the
 // slowest lane converges; results are identical because a converged lane is frozen there).
 #include "negf_common.h"
-#include "wave_utils.h"
+#include "chain_rs_inverse.h"       // the small inverse (rs_factor ... rs_inverse) and the 3M helpers, shared with k_chain1d_rd.hip
 #include <algorithm>
 
 namespace {
-
-constexpr int RS_THREADS = 256;
-constexpr int RS_WAVES = 4;
-#ifndef RS_PANEL
-#define RS_PANEL 8
-#endif
-constexpr int RS_NB = RS_PANEL;           // panel width of the small inverse: half a column tile (8) or a whole one (16)
-#ifndef RS_PRIO
-#define RS_PRIO 1
-#endif
-#ifndef RS_REMAINDER
-#define RS_REMAINDER 1
-#endif
-#ifndef RS_ROW_MODE
-#define RS_ROW_MODE 0                 // pivot row of the factoring wave: 0 LDS line (round 2), 1 v_readlane, 2 ds_bpermute
-#endif
-#ifndef RS_LA_FLAGS
-#define RS_LA_FLAGS 0                 // look-ahead of the small inverse synchronised by two workgroup barriers (0) or by LDS counters
-                                      // (1: built and measured in round 4 -- parity green, the C3 launch 666 ms against 668: with
-                                      // three workgroups per CU a barrier's wait is another workgroup's issue slot, not idle time)
-#endif
-#ifndef RS_RR
-#define RS_RR 1
-#endif
-// The pivot rows of a panel are replaced, not updated: W[pivot row][col] = 0 + P[pivot row][:] Q[:][col].  The trailing
-// update needs no per-tile mask for that: the owner of a column tile has the panel's pivot rows of its columns (the Q
-// fragment) in registers before it writes, so it zeroes them in LDS first and every tile is then a pure accumulation
-// W += P Q (rs_update_col).  Only the look-ahead tile, whose Q fragment every wave reads, masks its seed
-// (rs_update_tile<.., true>).  Storing P - E instead (a one short at every (pivot row, its column), added back where
-// the inverse is read) saves the zeroing but forms the pivot row as q + (1/p - 1) q: 1/p - 1 is rounded to an
-// absolute u, so the row loses log2 |p| bits, all of them for |p| >= 2^53, and the read-back (x - 1) + 1 loses u / |x|.
-#ifndef RS_UPD_3M
-#define RS_UPD_3M 1                   // trailing / look-ahead updates (K = 8): 1 = three real products per tile and k-step (3M: operand
-#endif                                //    sums and a 12-instruction recombination per tile), 0 = four (no vector work per tile at all)
-#ifndef RS_ABLATE
-#define RS_ABLATE 0                   // diagnostic builds only (wrong results; timing with force_iters): 1 = no panel factoring (the chain
-#endif                                //    wave's pivot steps), 2 = no trailing / look-ahead updates, 4 = no products, 8 = no mixing phase
-#ifndef RS_STAMPS
-#define RS_STAMPS 0                   // 1: diagnostic build -- the phase / cycle stamps of NEGF_CHAIN_STAMPS=1 are compiled in
-#endif                                //    (NEGF_EXTRA_HIPCC_FLAGS=-DRS_STAMPS=1 python -m gaunegf_amd.build --force); the production
-                                      //    kernel carries none of their branches
 
 struct ChainRsArgs {
     const cplx *alpha, *Salpha, *beta, *Sbeta, *tau, *Stau;   // concatenated per contact
@@ -152,463 +111,6 @@ __global__ void rs_rr_init_kernel(RsQueue* q, unsigned cap, unsigned jobs)
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < cap) q->ring[i] = ~0ull;
     if (i == 0) { q->head = 0u; q->tail = jobs; q->jobs = jobs; q->cap = cap; }
-}
-
-// maximum of a 32-bit key over the wave (all lanes active), wave-uniform result.  Four DPP steps inside the rows
-// of 16 lanes leave the row maximum in every lane of a row; row_bcast:15 / row_bcast:31 (the GFX9 wave-reduction
-// steps) then carry it across the rows into lane 63: seven vector instructions and one v_readlane.  With
-// bound_ctrl and a zero "old" value the compiler folds each lane move into its v_max_u32 (v_max_u32_dpp);
-// zero is the identity of the maximum, and the row steps read no invalid lane.
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ unsigned rs_dpp_max_u32(unsigned k)
-{
-    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)k, CTRL, ROW_MASK, 0xF, true);
-    return o > k ? o : k;
-}
-
-__device__ __forceinline__ unsigned rs_wave_max_u32(unsigned k)
-{
-    k = rs_dpp_max_u32<0xB1>(k);            // quad_perm [1,0,3,2]
-    k = rs_dpp_max_u32<0x4E>(k);            // quad_perm [2,3,0,1]
-    k = rs_dpp_max_u32<0x141>(k);           // row_half_mirror
-    k = rs_dpp_max_u32<0x140>(k);           // row_mirror: every lane of a row holds the row maximum
-    k = rs_dpp_max_u32<0x142, 0xA>(k);      // row_bcast:15 into rows 1 and 3
-    k = rs_dpp_max_u32<0x143, 0xC>(k);      // row_bcast:31 into rows 2 and 3: lane 63 holds the maximum
-    return (unsigned)__builtin_amdgcn_readlane((int)k, 63);
-}
-
-// ---- remainder tiles.  n_c = 50 is three tiles of 16 and two more rows / columns; a fourth 16 x 16 tile for
-// them costs as much as a full one.  v_mfma_f64_4x4x4_4b_f64 has the operand maps of the 16x16x4 instruction
-// (A: lane l holds A[l&15][l>>4], B: B[l>>4][l&15]) and computes the four DIAGONAL 4 x 4 blocks of the
-// 16 x 16 product, D_b[i][j] at lane 16 i + 4 b + j, in a quarter of the time (probed on MI355X,
-// scripts/probe/mfma4x4_probe.hip).  Used in two ways when the last tile holds <= 4 rows / columns:
-//   row strip  (last ROW tile):    every 4-row block of the A operand is loaded with the SAME rows
-//              (row R0 + (l&3)); the B operand is the normal 16-column fragment.  D lane l holds element
-//              (R0 + (l>>4), C0 + (l&15)) -- exactly component r = 0 of the 16 x 16 C layout.
-//   column strip (last COLUMN tile): every 4-column block of the B operand holds the SAME columns
-//              (column C0 + (l&3)); the A operand is the normal 16-row fragment.  D lane l holds element
-//              (R0 + 4 ((l>>2)&3) + (l>>4), C0 + (l&3)).
-// Both leave their result in component 0 of the tile's accumulator.
-__device__ __forceinline__ void zmfma4(double& ar, double& ai, cplx pa, cplx qb)
-{
-    ar = __builtin_amdgcn_mfma_f64_4x4x4f64(pa.x, qb.x, ar, 0, 0, 0);
-    ar = __builtin_amdgcn_mfma_f64_4x4x4f64(pa.y, -qb.y, ar, 0, 0, 0);
-    ai = __builtin_amdgcn_mfma_f64_4x4x4f64(pa.x, qb.y, ai, 0, 0, 0);
-    ai = __builtin_amdgcn_mfma_f64_4x4x4f64(pa.y, qb.x, ai, 0, 0, 0);
-}
-// pa * conj(b)
-__device__ __forceinline__ void zmfma4_conjb(double& ar, double& ai, cplx pa, cplx b)
-{
-    ar = __builtin_amdgcn_mfma_f64_4x4x4f64(pa.x, b.x, ar, 0, 0, 0);
-    ar = __builtin_amdgcn_mfma_f64_4x4x4f64(pa.y, b.y, ar, 0, 0, 0);
-    ai = __builtin_amdgcn_mfma_f64_4x4x4f64(pa.y, b.x, ai, 0, 0, 0);
-    ai = __builtin_amdgcn_mfma_f64_4x4x4f64(-pa.x, b.y, ai, 0, 0, 0);
-}
-#define RS_M3S(A, B, C, PR, PI, PS, QR, QI, QS) do { double a_ = (A)[0], b_ = (B)[0], c_ = (C)[0]; mfma3s(a_, b_, c_, PR, PI, PS, QR, QI, QS); (A)[0] = a_; (B)[0] = b_; (C)[0] = c_; } while (0)
-#define RS_ZMFMA4(ACCR, ACCI, PA, QB) do { double r_ = (ACCR)[0], i_ = (ACCI)[0]; zmfma4(r_, i_, PA, QB); (ACCR)[0] = r_; (ACCI)[0] = i_; } while (0)
-#define RS_ZMFMA4C(ACCR, ACCI, PA, QB) do { double r_ = (ACCR)[0], i_ = (ACCI)[0]; zmfma4_conjb(r_, i_, PA, QB); (ACCR)[0] = r_; (ACCI)[0] = i_; } while (0)
-
-// ---- complex products by three real ones ("3M"): with p = pr + i pi, q = qr + i qi
-//        a = sum pr qr,   b = sum pi qi,   c = sum (pr + pi)(qr + qi)     =>  p q       = (a - b) + i (c - a - b)
-//        a, b as above,                    c = sum (pr + pi)(qr - qi)     =>  p conj(q) = (a + b) + i (c - a + b)
-// i.e. 3 matrix instructions per tile and k-step instead of 4: a quarter of the matrix-pipe time of every product
-// and update, for one or two additions per operand fragment.  The FP64 matrix instruction holds its SIMD's vector
-// issue for most of its 64 cycles (rs_wave_role below), so matrix-pipe time is what the sweep is made of.
-__device__ __forceinline__ void mfma3(d4& a, d4& b, d4& c, double pr, double pi, double ps, double qr, double qi, double qs)
-{
-    a = __builtin_amdgcn_mfma_f64_16x16x4f64(pr, qr, a, 0, 0, 0);
-    b = __builtin_amdgcn_mfma_f64_16x16x4f64(pi, qi, b, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f64_16x16x4f64(ps, qs, c, 0, 0, 0);
-}
-#ifndef RS_3M_GEMM
-#define RS_3M_GEMM 1
-#endif
-// the same on the 4x4x4 instruction (remainder strips, one value per lane)
-__device__ __forceinline__ void mfma3s(double& a, double& b, double& c, double pr, double pi, double ps, double qr, double qi, double qs)
-{
-    a = __builtin_amdgcn_mfma_f64_4x4x4f64(pr, qr, a, 0, 0, 0);
-    b = __builtin_amdgcn_mfma_f64_4x4x4f64(pi, qi, b, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f64_4x4x4f64(ps, qs, c, 0, 0, 0);
-}
-
-// Hide a loop-invariant value from the optimiser: without this LLVM hoists every (tile, k-step)
-// LDS address of the sweep out of the fixed-point loop -- hundreds of live address registers that
-// are then spilled to scratch and reloaded inside the MFMA loops.
-template <class T>
-__device__ __forceinline__ T rs_opaque(T v)
-{
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-__device__ __forceinline__ double rs_readlane_f64(double v, int srclane)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), srclane),
-                            __builtin_amdgcn_readlane(__double2loint(v), srclane));
-}
-
-// ---- panel [p0, p0+pw) factored by ONE wave: lane = row, 16 complex per lane, no barrier inside.  A wave
-// alone issues one instruction per ~4 cycles whatever its kind, and the vector ALU of its SIMD is what
-// the co-resident workgroups compete for, so the column step is written for instruction count:
-//   * pivot search: |re|+|im| (izamax metric) compared on the HIGH WORD of the double -- sign 0, exponent,
-//     20 mantissa bits -- with one v_max_u32 per DPP step; the pivot is the lowest row whose high word
-//     equals the maximum (ballot + find-first): the LAPACK choice up to ties within 2^-20 relative, which
-//     go to the lower row as LAPACK's exact ties do;
-//   * the pivot row reaches the other lanes through a 256-byte LDS line (the pivot lane writes its 16
-//     values, every lane reads them back: 32 LDS instructions instead of 68 v_readlane, and off the VALU);
-//   * 1/|pivot|^2 by v_rcp_f64 and two Newton steps (the pivots of these matrices are far from the
-//     overflow / denormal range the IEEE division sequence guards).
-// A pivot row is not scaled at its column step (multiplier 0, a one in the pivot column) but once at
-// the end of the panel: the later steps act linearly on it, and every lane runs the same select-free update.
-template <int P>
-__device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colof, cplx* rowline /*[16] LDS*/,
-                                          int p0, int pw, int lane, unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */)
-{
-    const int r = rs_opaque(lane);                      // (see rs_opaque: nothing derived from the lane index is
-    cplx a[RS_NB];                                      //  hoisted out of the fixed-point loop and kept alive)
-    bool avail = r < n && colof[r] < 0;
-    cplx myip = cmake(1.0, 0.0);
-    cplx* wrow = W + r * P + p0;                        // rows >= n are zero padding
-#pragma unroll
-    for (int s = 0; s < RS_NB; ++s) {
-        const cplx v = wrow[s];
-        const bool ok = (r < n) & (s < pw);
-        a[s] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
-    }
-#pragma unroll
-    for (int j = 0; j < RS_NB; ++j) {
-        if (j < pw) {
-            const bool stamp_here = fst && j == 4;
-            unsigned long long tq0 = 0, tq1 = 0, tq2 = 0, tq3 = 0, tq4 = 0;
-            if (stamp_here) tq0 = __builtin_amdgcn_s_memtime();
-            const double v = cabs1(a[j]);
-            const unsigned hi = (avail && v == v) ? (unsigned)__double2hiint(v) : 0u;
-            const unsigned m = rs_wave_max_u32(hi);
-            int pphys;
-            if (m != 0) {
-                pphys = (int)__ffsll((unsigned long long)__ballot(hi == m)) - 1;
-            } else {                                    // no usable candidate (zero / NaN column): lowest available row
-                const unsigned long long av = __ballot(avail);
-                pphys = av ? (int)__ffsll(av) - 1 : 0x7fffffff;
-            }
-            pphys = __builtin_amdgcn_readfirstlane(pphys);
-            if (stamp_here) tq1 = __builtin_amdgcn_s_memtime();
-            const bool is_piv = r == pphys;
-            cplx rb[RS_NB];
-#if RS_ROW_MODE == 0
-            // through a 256-byte LDS line: one lane writes its 16 values, all lanes read them back.  The wave-level
-            // barriers keep the compiler from ordering the two sides of the divergent branch the other way round
-            // (it does, without them), the LDS then executes the wave's instructions in order
-            __builtin_amdgcn_wave_barrier();            // the reads of the previous column step are issued
-            if (is_piv) {
-                pivrow[p0 + j] = pphys; colof[pphys] = p0 + j;
-#pragma unroll
-                for (int s = 0; s < RS_NB; ++s) rowline[s] = a[s];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int s = 0; s < RS_NB; ++s) rb[s] = rowline[s];
-#elif RS_ROW_MODE == 1
-            // through v_readlane (wave-uniform results, scalar operands of the FMAs): measured 10 cycles each
-            if (is_piv) { pivrow[p0 + j] = pphys; colof[pphys] = p0 + j; }
-#pragma unroll
-            for (int s = 0; s < RS_NB; ++s)
-                rb[s] = cmake(rs_readlane_f64(a[s].x, pphys), rs_readlane_f64(a[s].y, pphys));
-#else
-            // through ds_bpermute_b32: every lane reads the pivot lane's register over the LDS crossbar -- no memory,
-            // no write -> wait -> read round trip, no wave barriers: one pass of 64 pipelined LDS instructions
-            if (is_piv) { pivrow[p0 + j] = pphys; colof[pphys] = p0 + j; }
-            const int baddr = pphys << 2;
-#pragma unroll
-            for (int s = 0; s < RS_NB; ++s) {
-                rb[s].x = __hiloint2double(__builtin_amdgcn_ds_bpermute(baddr, __double2hiint(a[s].x)),
-                                           __builtin_amdgcn_ds_bpermute(baddr, __double2loint(a[s].x)));
-                rb[s].y = __hiloint2double(__builtin_amdgcn_ds_bpermute(baddr, __double2hiint(a[s].y)),
-                                           __builtin_amdgcn_ds_bpermute(baddr, __double2loint(a[s].y)));
-            }
-#endif
-            if (stamp_here) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tq2 = __builtin_amdgcn_s_memtime(); }
-            const cplx pv = rb[j];
-            const double d = pv.x * pv.x + pv.y * pv.y;
-            double sc = __builtin_amdgcn_rcp(d);
-            sc = fma(sc, fma(-d, sc, 1.0), sc);
-            sc = fma(sc, fma(-d, sc, 1.0), sc);
-            const cplx ip = cmake(pv.x * sc, -pv.y * sc);
-            const cplx mf = cneg(cmul(a[j], ip));
-            const cplx coef = cmake(is_piv ? 0.0 : mf.x, is_piv ? 0.0 : mf.y);
-            if (stamp_here) { asm volatile("" :: "v"(coef.x), "v"(coef.y)); tq3 = __builtin_amdgcn_s_memtime(); }
-#pragma unroll
-            for (int s = 0; s < RS_NB; ++s) a[s] = cfma(a[s], coef, rb[s]);
-            if (stamp_here) {
-#pragma unroll
-                for (int s = 0; s < RS_NB; ++s) asm volatile("" :: "v"(a[s].x), "v"(a[s].y));
-                tq4 = __builtin_amdgcn_s_memtime();
-                if (lane == 0) { fst[0] = tq0; fst[1] = tq1; fst[2] = tq2; fst[3] = tq3; fst[4] = tq4; }
-            }
-            a[j] = is_piv ? cmake(1.0, 0.0) : coef;
-            myip = cmake(is_piv ? ip.x : myip.x, is_piv ? ip.y : myip.y);
-            avail = avail && !is_piv;
-        }
-    }
-    if (r < n) {
-#pragma unroll
-        for (int s = 0; s < RS_NB; ++s)
-            if (s < pw) {
-                wrow[s] = cmul(a[s], myip);                 // the deferred pivot-row scaling
-            }
-    }
-}
-
-// ---- trailing update with panel [p0, p0+pw), in place:
-//        W[i][col] = (i pivot row of the panel ? 0 : W[i][col]) + P[i][:] Q[:][col]
-// (the 0 by a mask of the seed, MASK, or because the pivot rows were zeroed after Q was read: rs_zero_pivot_rows)
-// A Q fragment holds the panel's pivot rows in the columns of one column tile (B operand); for the
-// column-strip tile TR every 4-column block holds the same columns TR*16 + (l&3) (see mfma3s).
-template <int P, int NKS, int TR /* last tile when it is a remainder strip, else -1 */>
-__device__ __forceinline__ void rs_load_qf(const cplx* W, const int* pivrow, int tj, int p0, int pw, int fi, int fk,
-                                           cplx (&qf)[NKS])
-{
-    const int col = (TR >= 0 && tj == TR) ? TR * 16 + (fi & 3) : tj * 16 + fi;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-        const int k = ks * 4 + fk;
-        const cplx v = W[pivrow[p0 + k] * P + col];          // k >= pw: some valid row, zeroed below
-        const bool ok = k < pw;
-        qf[ks] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
-    }
-}
-
-// one tile (ti, tj): a full 16 x 16 tile, or a row / column strip (one value per lane, corner: one block)
-__device__ __forceinline__ void rs_wait_count(const unsigned* cnt, unsigned target)
-{
-    // (LDS counter of the look-ahead, see rs_inverse: spins only while another wave of the workgroup is behind)
-    while (*reinterpret_cast<const volatile unsigned*>(cnt) < target) __builtin_amdgcn_s_sleep(1);
-}
-
-// the panel's pivot rows in the columns of this lane's Q fragment (rs_load_qf) that are to be updated, [clo, chi) inside
-// the matrix, are set to zero: the owner of those columns calls it after its Q fragment is loaded (a wave's LDS
-// operations execute in order, and the stores may alias the loads, so neither the compiler nor the LDS reorders them)
-template <int P, int NKS, int TR>
-__device__ __forceinline__ void rs_zero_pivot_rows(int n, cplx* W, const int* pivrow, int tj, int p0, int pw, int fi, int fk,
-                                                   int clo, int chi)
-{
-    const int col = (TR >= 0 && tj == TR) ? TR * 16 + (fi & 3) : tj * 16 + fi;
-    if (col >= clo && col < chi && col < n) {
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const int k = ks * 4 + fk;
-            if (k < pw) W[pivrow[p0 + k] * P + col] = cmake(0.0, 0.0);
-        }
-    }
-}
-
-template <int P, int NKS, int TR, bool MASK /* seed the pivot rows of the panel with 0 (else they already are 0) */>
-__device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof, int ti, int tj, int p0, int pw,
-                                               int fi, int fk, const cplx (&qf)[NKS], int clo, int chi /* columns [clo, chi) are stored */,
-                                               const unsigned* wait_cnt = nullptr, unsigned wait_target = 0 /* stores wait for *wait_cnt >= wait_target */)
-{
-    const bool rowstrip = TR >= 0 && ti == TR, colstrip = TR >= 0 && tj == TR;
-    if (!rowstrip && !colstrip) {
-        cplx* cbase = W + (ti * 16 + fk) * P + tj * 16 + fi;
-        const cplx* pbase = W + (ti * 16 + fi) * P + p0 + fk;
-        cplx cv[4], pa[NKS];
-        int cf[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { if (MASK) cf[r] = colof[ti * 16 + fk + 4 * r]; cv[r] = cbase[4 * r * P]; }
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) pa[ks] = pbase[ks * 4];
-        constexpr bool M3 = RS_UPD_3M && P > 35;            // 3M (mfma3) in the 168-VGPR kernels
-        d4 ua, ub = {0, 0, 0, 0}, uc;                       // accumulators, seeded with the old tile
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const bool keep = !MASK || !(cf[r] >= p0 && cf[r] < p0 + pw);
-            ua[r] = keep ? cv[r].x : 0.0; uc[r] = keep ? (M3 ? cv[r].x + cv[r].y : cv[r].y) : 0.0;
-        }
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            if (M3) mfma3(ua, ub, uc, pa[ks].x, pa[ks].y, pa[ks].x + pa[ks].y, qf[ks].x, qf[ks].y, qf[ks].x + qf[ks].y);
-            else zmfma(ua, uc, pa[ks], qf[ks]);
-        }
-        if (wait_cnt) rs_wait_count(wait_cnt, wait_target);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = ti * 16 + fk + 4 * r;
-            const int cj = tj * 16 + fi;
-            if (i < n && cj < n && cj >= clo && cj < chi) cbase[4 * r * P] = M3 ? cmake(ua[r] - ub[r], uc[r] - ua[r] - ub[r]) : cmake(ua[r], uc[r]);
-        }
-    } else {
-        const int row = rowstrip ? TR * 16 + fk : ti * 16 + 4 * (fi >> 2) + fk;
-        const int col = colstrip ? TR * 16 + (fi & 3) : tj * 16 + fi;
-        const bool mine = !(rowstrip && colstrip) || (fi >> 2) == 0;      // the corner block exists four times
-        const cplx* prow = W + (rowstrip ? TR * 16 + (fi & 3) : ti * 16 + fi) * P + p0 + fk;
-        cplx* cptr = W + row * P + col;
-        const int cf = MASK ? colof[row] : -1;
-        const cplx cv = *cptr;
-        cplx pa[NKS];
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) pa[ks] = prow[ks * 4];
-        const bool keep = !MASK || !(cf >= p0 && cf < p0 + pw);
-        double ua = keep ? cv.x : 0.0, ub = 0.0, uc = keep ? cv.x + cv.y : 0.0;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks)
-            mfma3s(ua, ub, uc, pa[ks].x, pa[ks].y, pa[ks].x + pa[ks].y, qf[ks].x, qf[ks].y, qf[ks].x + qf[ks].y);
-        if (wait_cnt) rs_wait_count(wait_cnt, wait_target);
-        if (mine && row < n && col < n && col >= clo && col < chi) *cptr = cmake(ua - ub, uc - ua - ub);
-    }
-}
-
-// column tile tj, all row tiles, by the wave that owns the column tile in this stage.  The Q fragment is read
-// into registers before the first store, so the owner needs no snapshot of the pivot rows; it then zeroes them, so
-// that every tile of the column is a pure accumulation.
-template <int T16, int P, int NKS, int TR>
-__device__ __forceinline__ void rs_update_col(int n, cplx* W, const int* pivrow, const int* colof,
-                                              int tj, int p0, int pw, int lane, int clo, int chi)
-{
-    constexpr int FT = TR >= 0 ? TR : T16;                   // full row tiles
-    const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
-    cplx qf[NKS];
-    rs_load_qf<P, NKS, TR>(W, pivrow, tj, p0, pw, fi, fk, qf);
-    rs_zero_pivot_rows<P, NKS, TR>(n, W, pivrow, tj, p0, pw, fi, fk, clo, chi);
-    if (TR >= 0 && tj == TR) {                               // the column strip: every tile on the 4x4x4 instruction
-#pragma unroll
-        for (int ti = 0; ti < T16; ++ti) {
-            rs_update_tile<P, NKS, TR, false>(n, W, colof, ti, tj, p0, pw, fi, fk, qf, clo, chi);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        return;
-    }
-    const int col = tj * 16 + fi;
-    const bool colin = col >= clo && col < chi;             // this lane's column is one of those to be updated
-    constexpr bool M3 = RS_UPD_3M && P > 35;                 // 3M (mfma3) in the 168-VGPR kernels
-    double qs[NKS];                                          // 3M: re + im of the Q fragment, once per column tile
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) qs[ks] = qf[ks].x + qf[ks].y;
-    cplx* cbase = W + fk * P + col;                          // C tile element (ti*16 + fk + 4r, col)
-    const cplx* pbase = W + fi * P + p0 + fk;                // P operand element (ti*16 + fi, p0 + ks*4 + fk)
-    // the operands of row tile ti+1 are requested before tile ti is stored (LDS operations of a wave
-    // execute in order, and tile ti+1 shares no element with tile ti), so that the loads overlap the MFMAs
-    cplx cv[2][4], pa[2][NKS];
-    auto fetch = [&](int ti, int s) __attribute__((always_inline)) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) cv[s][r] = cbase[(ti * 16 + 4 * r) * P];
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) pa[s][ks] = pbase[ti * 16 * P + ks * 4];   // k >= pw pairs with qf == 0 (finite element)
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int ti = 0; ti < FT; ++ti) {
-        const int s = ti & 1;
-        if (ti + 1 < FT) fetch(ti + 1, s ^ 1);
-        d4 ua, ub = {0, 0, 0, 0}, uc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { ua[r] = cv[s][r].x; uc[r] = M3 ? cv[s][r].x + cv[s][r].y : cv[s][r].y; }
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            if (M3) mfma3(ua, ub, uc, pa[s][ks].x, pa[s][ks].y, pa[s][ks].x + pa[s][ks].y, qf[ks].x, qf[ks].y, qs[ks]);
-            else zmfma(ua, uc, pa[s][ks], qf[ks]);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = ti * 16 + fk + 4 * r;
-            // with a remainder strip (TR >= 0) the full tiles lie inside the matrix: rows, columns < 16 TR < n
-            if (colin && (TR >= 0 || (i < n && col < n))) cbase[(ti * 16 + 4 * r) * P] = M3 ? cmake(ua[r] - ub[r], uc[r] - ua[r] - ub[r]) : cmake(ua[r], uc[r]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (TR >= 0) rs_update_tile<P, NKS, TR, false>(n, W, colof, TR, tj, p0, pw, fi, fk, qf, clo, chi);    // the row strip
-}
-
-// In-place blocked Gauss-Jordan reduction of the n x n matrix W (LDS, pitch P) with implicit
-// pivoting.  On return  inv[i][j] = W[pivrow[i]][colof[j]].  All 256 threads call it; colof[] must be
-// -1 and visible (a barrier since it was reset).  Stage s: all waves apply panel s to the column tile of
-// panel s+1 (one row tile each, two barriers), then one wave factors panel s+1 while the other waves apply
-// panel s to the remaining column tiles (one owner per column tile, no barrier), one barrier at the end.
-template <int T16, int P, int TR>
-__device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* colof, cplx* rowline, int tid,
-                                           int wave /* role number of this wave, see rs_wave_role */, bool fixed_fw,
-                                           unsigned* la_cnt /* [2] LDS */, unsigned& la_epoch,
-                                           unsigned long long* st = nullptr)
-{
-    const int lane = tid & 63;
-    int sti = 0;
-    auto stamp = [&]() __attribute__((always_inline)) { if (st && tid == 0) st[sti] = __builtin_amdgcn_s_memrealtime(); ++sti; };
-    const int npanels = (n + RS_NB - 1) / RS_NB;
-    const int ntiles = (n + 15) >> 4;
-    for (int sgi = -1; sgi < npanels; ++sgi) {
-        const bool has_cur = sgi >= 0, has_next = sgi + 1 < npanels;
-        const int p0 = has_cur ? sgi * RS_NB : 0, pw = has_cur ? min(RS_NB, n - p0) : 0;
-        const int n0 = (sgi + 1) * RS_NB, nw = has_next ? min(RS_NB, n - n0) : 0;
-        const int tp = p0 >> 4, tl = n0 >> 4;                   // column tiles of the panel and of the next one
-        // the wave that factors panel sgi+1: the chain wave (role RS_WAVES-1), or -- roles by wave number -- each in turn
-        const int fw = fixed_fw ? RS_WAVES - 1 : (sgi + 1) & (RS_WAVES - 1);
-        if (has_cur && has_next) {
-            // look-ahead: the columns of panel sgi+1 (a whole column tile, or one half of one), one row tile per wave
-            // (T16 <= 4 = number of waves)
-            const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
-            cplx qf[RS_NB / 4];
-            rs_load_qf<P, RS_NB / 4, TR>(W, pivrow, tl, p0, pw, fi, fk, qf);
-#if RS_LA_FLAGS
-            // No workgroup barrier in the look-ahead (there were two, seven times a sweep): two LDS counters instead.
-            // la_cnt[0] counts the waves whose Q fragment -- the panel's pivot rows in the next panel's columns, rows that
-            // other waves are about to overwrite -- is on its way (a wave's LDS operations execute in order, so its
-            // counter increment is behind its reads); a wave stores its look-ahead tile only when all four are.
-            // la_cnt[1] counts the waves that have stored; only the FACTORING wave waits for it -- the others go straight
-            // on to the trailing update, which touches neither the next panel's columns nor anybody else's pivot rows.
-            la_epoch += RS_WAVES;
-            if (lane == 0) atomicAdd(&la_cnt[0], 1u);
-            if (wave < T16 && wave * 16 < n) rs_update_tile<P, RS_NB / 4, TR, true>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB, &la_cnt[0], la_epoch);
-            if (lane == 0) atomicAdd(&la_cnt[1], 1u);
-            if (wave == fw) rs_wait_count(&la_cnt[1], la_epoch);
-#else
-            __syncthreads();
-            if (!(RS_ABLATE & 2) && wave < T16 && wave * 16 < n) rs_update_tile<P, RS_NB / 4, TR, true>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB);
-            __syncthreads();
-#endif
-        }
-        if (has_cur) {
-            // the other columns, tile by tile, one owner per tile (the owner reads its Q fragment before it writes):
-            // dealt to the three waves that do not factor, to all four after the last panel.  A tile's columns minus
-            // the panel's own and minus the look-ahead columns (panels of 8: one half of the panel's tile remains when
-            // the panel is its upper half, one half of the next tile when the look-ahead took its lower half).
-            const int team = has_next ? RS_WAVES - 1 : RS_WAVES;
-            const int me = has_next ? ((wave - fw - 1) & (RS_WAVES - 1)) : wave;
-            int cnt = 0;
-#pragma unroll 1
-            for (int tj = 0; tj < ntiles; ++tj) {
-                int clo = tj * 16, chi = tj * 16 + 16;
-                if (tj == tp) {
-                    if (RS_NB == 16) continue;
-                    if (p0 & 8) chi = p0; else clo = p0 + RS_NB;
-                }
-                if (has_next && tj == tl) {
-                    if (RS_NB == 16) continue;
-                    if (n0 & 8) chi = min(chi, n0); else clo = max(clo, n0 + RS_NB);
-                }
-                if (clo >= chi || clo >= n) continue;
-                const bool mine = (!has_next || wave != fw) && (cnt % team == me);
-                ++cnt;
-                if (mine && !(RS_ABLATE & 2)) {
-                    // a narrow last panel (<= 4 columns) runs one k-step
-                    if (pw <= 4) rs_update_col<T16, P, 1, TR>(n, W, pivrow, colof, tj, p0, pw, lane, clo, chi);
-                    else rs_update_col<T16, P, RS_NB / 4, TR>(n, W, pivrow, colof, tj, p0, pw, lane, clo, chi);
-                }
-            }
-        }
-        if (has_next && wave == fw) {
-            if (st && lane == 0) st[16 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
-            // the factoring wave is its workgroup's critical path (the others wait for it at the barrier):
-            // it goes first when it shares its SIMD's issue slots with waves of the other workgroups
-            if (RS_PRIO) __builtin_amdgcn_s_setprio(3);
-            if (!(RS_ABLATE & 1)) rs_factor<P>(n, W, pivrow, colof, rowline, n0, nw, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
-            else if (lane < nw) { pivrow[n0 + lane] = n0 + lane; colof[n0 + lane] = n0 + lane; }
-            if (RS_PRIO) __builtin_amdgcn_s_setprio(0);
-            if (st && lane == 0) st[17 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
-        }
-        stamp();
-        __syncthreads();                 // panel sgi+1 (columns of W, pivrow/colof) and the update complete
-    }
 }
 
 // P: compile-time pitch of the work matrix (odd, >= n): every tile / k-step offset is an immediate of the

@@ -172,7 +172,7 @@ ChainGEntry* gcache_lookup(negf_ctx* c, const SigmaProvider* p, const cplx* Eh, 
     for (auto& e : c->gcache) {
         if (!e.valid || e.E_hash != eh || e.lead_hash != p->lead_hash || (int)e.E.size() != nb) continue;
         if (e.eta != p->eta || e.conv != p->conv || e.relFactor != p->relFactor || e.max_iter != p->max_iter ||
-            e.force_iters != p->force_iters || e.nc != p->nc) continue;
+            e.force_iters != p->force_iters || e.solver != p->solver || e.nc != p->nc) continue;
         if (std::memcmp(e.E.data(), Eh, (size_t)nb * sizeof(cplx)) != 0) continue;
         if (e.lead != p->h_lead && (e.lead->size() != p->h_lead->size() ||
                                     std::memcmp(e.lead->data(), p->h_lead->data(), e.lead->size() * sizeof(cplx)) != 0)) continue;
@@ -218,6 +218,7 @@ ChainGEntry* gcache_lookup(negf_ctx* c, const SigmaProvider* p, const cplx* Eh, 
     }
     v->nc = p->nc; v->lead = p->h_lead; v->lead_hash = p->lead_hash; v->E_hash = eh;
     v->eta = p->eta; v->conv = p->conv; v->relFactor = p->relFactor; v->max_iter = p->max_iter; v->force_iters = p->force_iters;
+    v->solver = p->solver;
     v->E.assign(Eh, Eh + nb);
     v->used = ++c->gcache_clock;
     return v;
@@ -426,7 +427,7 @@ int run_sigma_blocks(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, int* 
     if (p->kind == SK_CHAIN1D) {
         static int force_v1 = -1;
         if (force_v1 < 0) { const char* e = getenv("NEGF_CHAIN1D_ALGO"); force_v1 = (e && strcmp(e, "global") == 0) ? 1 : 0; }
-        const bool lds_path = chain1d_lds_supported(p->nc_max) && !force_v1;
+        const bool lds_path = chain1d_lds_supported(p->nc_max) && (!force_v1 || p->solver == 1);
         // the g(E) cache (ChainGEntry): a launch whose lead and energies were evaluated before only forms Sigma = t g t^H
         ChainGEntry* ent = nullptr;
         bool hit = false;
@@ -436,7 +437,34 @@ int run_sigma_blocks(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, int* 
             std::vector<cplx> tmp;
             ent = gcache_lookup(c, p, host_energies(c, E, nb, tmp), nb, &hit);
         }
-        ProfScope ps(c, hit ? "chain1d_hit" : "chain1d");
+        ProfScope ps(c, p->solver == 1 ? (hit ? "chain1d_rd_hit" : "chain1d_rd") : (hit ? "chain1d_hit" : "chain1d"));
+        if (p->solver == 1) {
+            // renormalisation-decimation: one launch, no job order (units differ by at most a factor two in length)
+            const size_t need = chain1d_rd_scratch_elems(p->nc_max, p->n_contacts, nb);
+            if (need > c->scratch_cap) {
+                NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
+                dev_free(c->d_scratch); c->scratch_cap = 0;
+                int rc = dev_alloc(&c->d_scratch, need);
+                if (rc) return rc;
+                c->scratch_cap = need;
+            }
+            const int jobs = nb * p->n_contacts;
+            if (hit) {
+                launch_chain1d_rd(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, ent->d_g, 2);
+                if (iters) NEGF_HIP_CHECK(hipMemcpyAsync(iters, ent->d_it, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+                if (conv) NEGF_HIP_CHECK(hipMemcpyAsync(conv, ent->d_cv, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+                return NEGF_OK;
+            }
+            if (ent && (!iters || !conv)) ent = nullptr;
+            launch_chain1d_rd(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, ent ? ent->d_g : nullptr, 1);
+            if (ent) {
+                NEGF_HIP_CHECK(hipMemcpyAsync(ent->d_it, iters, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+                NEGF_HIP_CHECK(hipMemcpyAsync(ent->d_cv, conv, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+                NEGF_HIP_CHECK(hipGetLastError());
+                ent->valid = true;
+            }
+            return NEGF_OK;
+        }
         if (lds_path) {
             const size_t need = chain1d_lds_scratch_elems(p->nc_max, p->n_contacts, nb, std::max(p->max_iter, p->force_iters), c->chain_rr_quantum);
             if (need > c->scratch_cap) {
@@ -1149,6 +1177,19 @@ int negf_sigma_chain1d(negf_ctx* c, int n_contacts, const int* nc, const int* in
     p->eta = eta; p->conv = conv; p->relFactor = relFactor; p->max_iter = max_iter;
     p->force_iters = force_iters;
     *handle = add_provider(c, p);
+    return NEGF_OK;
+}
+
+int negf_sigma_chain1d_rd(negf_ctx* c, int n_contacts, const int* nc, const int* inds,
+                          const double* alpha, const double* Salpha, const double* beta,
+                          const double* Sbeta, const double* tau, const double* Stau,
+                          double eta, double tol, int max_steps, int force_steps, int* handle)
+{
+    if (!(tol >= 0.0) || max_steps < 0) return NEGF_EINVAL;
+    int rc = negf_sigma_chain1d(c, n_contacts, nc, inds, alpha, Salpha, beta, Sbeta, tau, Stau, eta, tol, 1.0, max_steps,
+                                force_steps, handle);
+    if (rc) return rc;
+    c->providers[*handle]->solver = 1;
     return NEGF_OK;
 }
 

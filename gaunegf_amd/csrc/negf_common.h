@@ -92,6 +92,10 @@ struct SigmaProvider {
     unsigned long long lead_hash = 0;
     double eta = 0, conv = 0, relFactor = 0, mix = 0;
     int max_iter = 0, force_iters = -1;
+    // CHAIN1D: how the surface Green's function is found.  0 = the reference's relaxed fixed point (conv, relFactor,
+    // max_iter as above), 1 = renormalisation-decimation (k_chain1d_rd.hip): conv holds its tol, max_iter its max_steps,
+    // force_iters its force_steps, relFactor is unused (1)
+    int solver = 0;
     // job order of the next chain launch (predicted on the device)
     int* d_order = nullptr;
     int order_cap = 0;
@@ -141,6 +145,7 @@ struct ChainGEntry {
     unsigned long long lead_hash = 0, E_hash = 0;
     double eta = 0, conv = 0, relFactor = 0;
     int max_iter = 0, force_iters = -1;
+    int solver = 0;                                // (SigmaProvider::solver: an entry serves the solver that filled it only)
     std::vector<cplx> E;
     cplx* d_g = nullptr;    size_t g_cap = 0;      // [energies][blk_stride]
     int* d_it = nullptr;    int* d_cv = nullptr;   size_t it_cap = 0;   // [energies][n_contacts]
@@ -356,6 +361,11 @@ void launch_chain1d_lds(hipStream_t st, const SigmaProvider& p, const int* d_nc,
                         const cplx* E, cplx* blk, int* iters, int* conv, cplx* gold_scratch, const int* order,
                         cplx* gcache = nullptr, int gc_mode = 0, int rr_quantum = -1, int rr_slots = 0,
                         bool order_trusted = true);
+// renormalisation-decimation solver (k_chain1d_rd.hip; p.conv = tol, p.max_iter = max_steps, p.force_iters = force_steps).
+// scratch: chain1d_rd_scratch_elems() complex values; gcache / gc_mode as in launch_chain1d_lds (n_c <= 64 only)
+size_t chain1d_rd_scratch_elems(int nc_max, int n_contacts, int nb);
+void launch_chain1d_rd(hipStream_t st, const SigmaProvider& p, const int* d_nc, const int* d_blk_off, int nb,
+                       const cplx* E, cplx* blk, int* iters, int* conv, cplx* scratch, cplx* gcache, int gc_mode);
 // order[0..count) = jobs by decreasing sweep count predicted from the previous evaluation (k_chain1d_order.hip)
 bool chain1d_order_supported(int count);
 void launch_chain1d_predict_order(hipStream_t st, const cplx* prevE, const int* prev_iters, int prev_n, int n_contacts,

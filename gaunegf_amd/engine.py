@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import NEGF_IND_TOTAL, NEGF_SPIN_BLOCK, NEGF_SPIN_RESTRICTED, check
+from .config import SURFACE_DOUBLING_MAX_STEPS, SURFACE_DOUBLING_TOL
 
 _engines = {}
 
@@ -190,7 +191,13 @@ class Engine:
         return h.value
 
     def sigma_chain1d(self, inds_list, alphas, Salphas, betas, Sbetas, taus, Staus,
-                      eta, conv, relFactor, max_iter=2000, force_iters=-1):
+                      eta, conv, relFactor, max_iter=2000, force_iters=-1, solver='fixed-point',
+                      tol=SURFACE_DOUBLING_TOL, max_steps=SURFACE_DOUBLING_MAX_STEPS):
+        """CHAIN1D provider.  solver='fixed-point': the reference's relaxed loop (conv, relFactor, max_iter);
+        solver='doubling': renormalisation-decimation (tol, max_steps; conv / relFactor / max_iter are ignored and
+        force_iters counts doubling steps)."""
+        if solver not in ('fixed-point', 'doubling'):
+            raise ValueError(f"solver must be 'fixed-point' or 'doubling', got {solver!r}")
         nc = np.array([len(i) for i in inds_list], dtype=np.int32)
         inds = np.ascontiguousarray(np.concatenate([np.asarray(i).ravel() for i in inds_list]), dtype=np.int32)
 
@@ -204,6 +211,12 @@ class Engine:
             return np.ascontiguousarray(np.concatenate(out))
         a, Sa, b, Sb, t, St = (cat(x) for x in (alphas, Salphas, betas, Sbetas, taus, Staus))
         h = C.c_int(-1)
+        if solver == 'doubling':
+            check(self._lib.negf_sigma_chain1d_rd(self._ctx, len(nc), _ptr(nc), _ptr(inds), _ptr(a), _ptr(Sa),
+                                                  _ptr(b), _ptr(Sb), _ptr(t), _ptr(St), float(eta), float(tol),
+                                                  int(max_steps), int(force_iters), C.byref(h)),
+                  "negf_sigma_chain1d_rd")
+            return h.value
         check(self._lib.negf_sigma_chain1d(self._ctx, len(nc), _ptr(nc), _ptr(inds), _ptr(a), _ptr(Sa),
                                            _ptr(b), _ptr(Sb), _ptr(t), _ptr(St), float(eta), float(conv),
                                            float(relFactor), int(max_iter), int(force_iters), C.byref(h)),

@@ -12,7 +12,10 @@ device, one workgroup per (energy, contact), and Sigma never visits the host.
 """
 import numpy as np
 
+from . import config
 from .config import ETA, SURFACE_GREEN_CONVERGENCE, SURFACE_RELAXATION_FACTOR, SURFACE_GREEN_MAX_ITER
+
+SOLVERS = ('fixed-point', 'doubling')
 
 
 def fractional_matrix_power(S, power):
@@ -24,8 +27,25 @@ def fractional_matrix_power(S, power):
 
 
 class surfG:
+    @property
+    def solver(self):
+        return self._solver
+
+    @solver.setter
+    def solver(self, value):
+        if value not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {value!r}")
+        self._solver = value
+
     def __init__(self, Fock, Overlap, indsList, taus=None, staus=None, alphas=None, aOverlaps=None,
-                 betas=None, bOverlaps=None, eta=ETA):
+                 betas=None, bOverlaps=None, eta=ETA, solver=None):
+        # solver: how g is found.  'fixed-point' = the reference's relaxed loop (the default, config.SURFACE_GREEN_SOLVER),
+        # 'doubling' = renormalisation-decimation: the converged fixed point in 10-25 steps.  Under 'doubling' the
+        # conv / relFactor arguments of g / sigma / sigmaTot / sigma_batch are ignored (the stop rule is doubling_tol,
+        # doubling_max_steps) and force_iters counts doubling steps.  May be changed later: g.solver = 'doubling'.
+        self.solver = config.SURFACE_GREEN_SOLVER if solver is None else solver
+        self.doubling_tol = config.SURFACE_DOUBLING_TOL
+        self.doubling_max_steps = config.SURFACE_DOUBLING_MAX_STEPS
         self.F = np.array(Fock)
         self.S = np.array(Overlap)
         self.X = np.array(fractional_matrix_power(Overlap, -0.5))
@@ -118,8 +138,12 @@ class surfG:
         """CHAIN1D provider handle for (conv, relFactor); cached until setF/setContacts.
         ``identity_tau`` builds the variant with t = I (tau = -I, Stau = 0), whose
         'self-energy' is the surface Green's function g itself."""
+        doubling = self.solver == 'doubling'
+        if doubling:
+            conv, relFactor = 0.0, 1.0         # ignored by the solver: one provider whatever the caller passed
         key = (id(engine), getattr(engine, "generation", 0), self._version, float(conv), float(relFactor),
-               bool(identity_tau), float(self.eta), int(self.force_iters))
+               bool(identity_tau), float(self.eta), int(self.force_iters), self.solver,
+               float(self.doubling_tol) if doubling else 0.0, int(self.doubling_max_steps) if doubling else 0)
         if key in self._lowered:
             return self._lowered[key][1]
         if len(self._lowered) > 8:
@@ -140,7 +164,8 @@ class surfG:
                                  [self.aList[i] for i in ids], [self.aSList[i] for i in ids],
                                  [self.bList[i] for i in ids], [self.bSList[i] for i in ids],
                                  taus, staus, self.eta, conv, relFactor,
-                                 max_iter=SURFACE_GREEN_MAX_ITER, force_iters=self.force_iters)
+                                 max_iter=SURFACE_GREEN_MAX_ITER, force_iters=self.force_iters, solver=self.solver,
+                                 tol=self.doubling_tol, max_steps=self.doubling_max_steps)
         self._lowered[key] = (engine, h)
         return h
 
@@ -158,7 +183,8 @@ class surfG:
 
     # ---- reference protocol ------------------------------------------------
     def g(self, E, i, conv=SURFACE_GREEN_CONVERGENCE, relFactor=SURFACE_RELAXATION_FACTOR):
-        """Surface Green's function of contact i at E (surfG1D.py:223-295)."""
+        """Surface Green's function of contact i at E (surfG1D.py:223-295).  conv and relFactor belong to the
+        'fixed-point' solver; 'doubling' ignores them (here and in sigma / sigmaTot / sigma_batch)."""
         eng = self._engine()
         h = self._negf_lower(eng, conv, relFactor, identity_tau=True)
         full = eng.sigma_eval(h, i, [E], self.num_contacts)[0]

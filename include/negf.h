@@ -112,6 +112,30 @@ int negf_sigma_chain1d(negf_ctx* ctx, int n_contacts, const int* nc, const int* 
                        double eta, double conv, double relFactor, int max_iter,
                        int force_iters, int* handle);
 
+/* 1-D chain provider with the renormalisation-decimation ("doubling", Lopez Sancho - Rubio) solver: a CHAIN1D provider
+ * like negf_sigma_chain1d's -- same arguments, same kind, served by every entry point that serves that one -- whose
+ * surface Green's function is NOT found by the reference's relaxed loop (surfG1D.py:223-295:
+ * g <- 0.1 inv(A - B g B^H) + 0.9 g until the relative change is <= 1e-5 or 2000 sweeps have run) but by
+ *     es = e = A,  a = B,  b = B^H          (A = (E + i eta) Salpha - alpha, B = (E + i eta) Sbeta - beta; b is taken as a
+ *                                            matrix, so it conjugates the complex energy as surfG1D.py:262 does)
+ *     step:  G = inv(e);  P = a G;  Q = b G;  D = P b
+ *            es <- es - D;   e <- e - D - Q a;   a <- P a;   b <- Q b;   steps += 1
+ *     g = inv(es);   Sigma = t g t^H,  t = E Stau - tau
+ * Stop rule: after the step in which  max |D_ij| <= tol * max |es_ij|  (es already updated; |x| = |re| + |im|, the
+ * izamax metric: a relative test, exact under power-of-two scaling), or at max_steps.  tol = 2^-52 means "the
+ * correction no longer reaches es"; the Python layer's defaults are tol = 2^-52, max_steps = 64.
+ * Step k of the recursion IS iterate 2^k - 1 of the unrelaxed loop g <- inv(A - B g B^H) started from inv(A): the same
+ * semi-infinite chain, doubled in length at every step instead of grown by one cell.
+ * force_steps >= 0 runs exactly that many steps (0: g = inv(A)); -1 the stop rule.  negf_last_iters reports the steps
+ * and converged = 0 for a unit that reached max_steps (it returns what it has) or met a zero pivot / non-finite input
+ * (a NaN block).  Inverses for n_c <= 64 use the pivoting rule described at negf_sigma_chain1d.  The g(E) cache keys
+ * on the solver and on tol / max_steps / force_steps: the two solvers never serve each other's entries. */
+int negf_sigma_chain1d_rd(negf_ctx* ctx, int n_contacts, const int* nc, const int* inds,
+                          const double* alpha, const double* Salpha,
+                          const double* beta, const double* Sbeta,
+                          const double* tau, const double* Stau,
+                          double eta, double tol, int max_steps, int force_steps, int* handle);
+
 /* Bethe-lattice provider: surfGBethe.py:479-575, 958-1108.  Per contact: onsite
  * H [9][9] and the 12 direction matrices S,V [12][9][9] (all float64), the list
  * of contact atoms (orbital indices [n_atoms][9], concatenated over contacts) and
@@ -286,7 +310,8 @@ int negf_transmission_channels_dev(negf_ctx* ctx, int handle, int contact_L, int
 
 /* ------------------------------------------------------------- diagnostics */
 /* hipEvent timing of the library's own kernels, per kernel family
- * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig"). */
+ * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig";
+ * "chain1d_rd": the renormalisation-decimation solver's launches, "chain1d_hit" / "chain1d_rd_hit": g(E) cache hits). */
 /* device bytes held by the context's energy workspace: the three n x n work areas per energy in flight (work) and the
  * staging of the self-energy blocks of CHAIN1D / BETHE providers (blocks); either pointer may be NULL */
 int negf_workspace_bytes(negf_ctx* ctx, long long* work, long long* blocks);
