@@ -812,6 +812,7 @@ void negf_destroy(negf_ctx* c)
     c->d_F = c->d_S = nullptr;
     dev_free(c->d_acc); dev_free(c->d_seg_out); dev_free(c->d_ref_P); dev_free(c->d_ref_meta);
     dev_free(c->d_chan); dev_free(c->d_chan_rank); dev_free(c->d_chan_T);
+    dev_free(c->d_bond_map); dev_free(c->d_bond_carry); dev_free(c->d_bond_T);
     prof_resolve(c);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     delete c;
@@ -1349,6 +1350,50 @@ int negf_gr_int_dev(negf_ctx* c, int handle, int m, const double* E_dev, const d
     return NEGF_OK;
 }
 
+// A_c = G Gamma_c G^H for the batch [m0, m0 + nb) -> c->W1 (Hermitian unless the caller handed in its own coupling
+// matrices); c->W2 is free again on return.  Shared by GrLessInt and the local transmission.
+static int run_gless_products(negf_ctx* c, SigmaProvider* p, int contact, int m0, int nb, const cplx* E)
+{
+    int rc;
+    const size_t n2 = (size_t)c->n * c->n;
+    const int n = c->n;
+    if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
+    if (compact_available(c, p)) {
+        // G Gamma G^H = (G[:, I] Gamma_II) G[:, I]^H : Gc and X live in the free buffer W2
+        GammaSmall g;
+        { ProfScope ps(c, "gamma"); if ((rc = run_gamma_small(c, p, contact, nb, 0, &g))) return rc; }
+        cplx* Gc = c->W2;                              // [nb][n x K]
+        cplx* X = c->W2 + (size_t)n * g.K;             // [nb][n x K]   (2 n K <= n^2)
+        ProfScope ps(c, "zgemm");
+        launch_gather_block(c->stream, n, n, g.K, nb, c->G, n2, nullptr, g.idx, Gc, n2);
+        // X = (Gc Gamma)^H, K x n, stored conjugate-transposed by the first product; W1 = Gc X: the second operand
+        // in the plain form (see the dense products below)
+        launch_zgemm(c->stream, n, g.K, g.K, nb, Gc, g.K, n2, g.mat, g.K, g.stride, 4, X, n, n2);
+        launch_zgemm(c->stream, n, n, g.K, nb, Gc, g.K, n2, X, n, n2, 2, c->W1, n, n2);     // Hermitian result
+        return NEGF_OK;
+    }
+    size_t gs = 0;
+    const cplx* gam = nullptr;
+    { ProfScope ps(c, "gamma"); if ((rc = run_gamma(c, p, contact, m0, nb, c->W1, c->W2, &gam, &gs))) return rc; }
+    ProfScope ps(c, "zgemm");
+    // G Gamma G^H (integrate.py:81).  Gamma = i (Sigma - Sigma^H) is Hermitian, element by element, and so is the
+    // result: W2 = (G Gamma)^H -- the first product stores its result conjugate-transposed -- and W1 = G W2
+    // ( = G Gamma^H G^H), upper block tiles computed, lower ones mirrored.  Both products read their second
+    // operand in the plain form (k_zgemm.hip: the operand conjugate-transposed on the fly costs the L2 twice
+    // the requests).
+    // (coupling matrices handed in by the caller -- pre_is_gamma -- need not be Hermitian: X = G Gamma, then
+    //  the full product X G^H)
+    const bool full = p->kind == SK_PRECOMPUTED && p->pre_is_gamma;
+    if (!full) {
+        launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, gam, n, gs, 4, c->W2, n, n2);
+        launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, c->W2, n, n2, 2, c->W1, n, n2);
+    } else {
+        launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, gam, n, gs, 0, c->W2, n, n2);
+        launch_zgemm(c->stream, n, n, n, nb, c->W2, n, n2, c->G, n, n2, 1, c->W1, n, n2);
+    }
+    return NEGF_OK;
+}
+
 // sum_m w_m G Gamma_c G^H over the energies E[0..m) (device pointers).  nseg == 0: one sum into out [n*n]; nseg > 0: the
 // energies are nseg consecutive segments ending at seg_end[s] (host array) and out [nseg][n*n] receives one sum each.
 static int gless_core(negf_ctx* c, SigmaProvider* p, int contact, int m, const cplx* E, const cplx* w, cplx* out,
@@ -1356,7 +1401,6 @@ static int gless_core(negf_ctx* c, SigmaProvider* p, int contact, int m, const c
 {
     int rc;
     const size_t n2 = (size_t)c->n * c->n;
-    const int n = c->n;
     if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
     if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
     NEGF_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)std::max(nseg, 1) * n2 * sizeof(cplx), c->stream));
@@ -1370,45 +1414,7 @@ static int gless_core(negf_ctx* c, SigmaProvider* p, int contact, int m, const c
     };
     for (int m0 = 0; m0 < m; m0 += c->batch) {
         const int nb = std::min(c->batch, m - m0);
-        if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
-        if (compact_available(c, p)) {
-            // G Gamma G^H = (G[:, I] Gamma_II) G[:, I]^H : Gc and X live in the free buffer W2
-            GammaSmall g;
-            { ProfScope ps(c, "gamma"); if ((rc = run_gamma_small(c, p, contact, nb, 0, &g))) return rc; }
-            cplx* Gc = c->W2;                              // [nb][n x K]
-            cplx* X = c->W2 + (size_t)n * g.K;             // [nb][n x K]   (2 n K <= n^2)
-            {
-                ProfScope ps(c, "zgemm");
-                launch_gather_block(c->stream, n, n, g.K, nb, c->G, n2, nullptr, g.idx, Gc, n2);
-                // X = (Gc Gamma)^H, K x n, stored conjugate-transposed by the first product; W1 = Gc X: the second operand
-                // in the plain form (see the dense products below)
-                launch_zgemm(c->stream, n, g.K, g.K, nb, Gc, g.K, n2, g.mat, g.K, g.stride, 4, X, n, n2);
-                launch_zgemm(c->stream, n, n, g.K, nb, Gc, g.K, n2, X, n, n2, 2, c->W1, n, n2);     // Hermitian result
-            }
-            accumulate(c->W1, m0, nb);
-            continue;
-        }
-        size_t gs = 0;
-        const cplx* gam = nullptr;
-        { ProfScope ps(c, "gamma"); if ((rc = run_gamma(c, p, contact, m0, nb, c->W1, c->W2, &gam, &gs))) return rc; }
-        {
-            ProfScope ps(c, "zgemm");
-            // G Gamma G^H (integrate.py:81).  Gamma = i (Sigma - Sigma^H) is Hermitian, element by element, and so is the
-            // result: W2 = (G Gamma)^H -- the first product stores its result conjugate-transposed -- and W1 = G W2
-            // ( = G Gamma^H G^H), upper block tiles computed, lower ones mirrored.  Both products read their second
-            // operand in the plain form (k_zgemm.hip: the operand conjugate-transposed on the fly costs the L2 twice
-            // the requests).
-            // (coupling matrices handed in by the caller -- pre_is_gamma -- need not be Hermitian: X = G Gamma, then
-            //  the full product X G^H)
-            const bool full = p->kind == SK_PRECOMPUTED && p->pre_is_gamma;
-            if (!full) {
-                launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, gam, n, gs, 4, c->W2, n, n2);
-                launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, c->W2, n, n2, 2, c->W1, n, n2);
-            } else {
-                launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, gam, n, gs, 0, c->W2, n, n2);
-                launch_zgemm(c->stream, n, n, n, nb, c->W2, n, n2, c->G, n, n2, 1, c->W1, n, n2);
-            }
-        }
+        if ((rc = run_gless_products(c, p, contact, m0, nb, E))) return rc;
         accumulate(c->W1, m0, nb);
     }
     c->last_m = m;
@@ -2223,6 +2229,169 @@ int negf_eigvalsh_batched(negf_ctx* c, int K, int m, const double* A, double* w,
         if (info) info[i] = hi[i];
         if (hi[i] != 0) rc = NEGF_ESINGULAR;
     }
+    return rc;
+}
+
+// ------------------------------------------------------- local (bond) transmission
+// flow[i][j](E) = 2 Im[(E S - F)_ij A_c,ji],  A_c = G Gamma_c G^H: the GrLessInt sequence up to A_c (run_gless_products),
+// then one pass of k_bond.hip over A_c where GrLessInt runs launch_accumulate.  The reference has no such function.
+namespace {
+
+// a context-owned device buffer that only grows
+extern "C++" template <typename T>
+int ensure_cap(negf_ctx* c, T** p, size_t* cap, size_t need)
+{
+    if (need <= *cap) return NEGF_OK;
+    NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
+    dev_free(*p); *cap = 0;
+    int rc = dev_alloc(p, need);
+    if (rc) return rc;
+    *cap = need;
+    return NEGF_OK;
+}
+
+// providers served: all that negf_gless_int serves, except coupling matrices handed in by the caller (they need not
+// be Hermitian, and the kernels read A_ji as conj(A_ij))
+int bond_check(negf_ctx* c, SigmaProvider* p, int m, int ind, int* contact)
+{
+    int rc = check_ready(c, p, m);
+    if (rc) return rc;
+    if (p->kind == SK_PRECOMPUTED && p->pre_is_gamma) return NEGF_EINVAL;
+    if (c->n > bond_max_n()) return NEGF_EINVAL;
+    *contact = norm_contact(p, ind);
+    return *contact == -2 ? NEGF_EINVAL : NEGF_OK;
+}
+
+// The orbital -> group map sorted once per call: perm = the orbitals by group, ascending inside a group; goff = the
+// groups' offsets in perm.  *identity: every orbital is its own group, in order (the elementwise kernel serves it).
+int bond_stage_groups(negf_ctx* c, int n_groups, const int* group_of, bool* identity)
+{
+    const int n = c->n;
+    *identity = true;
+    if (!group_of) return n_groups == n ? NEGF_OK : NEGF_EINVAL;
+    if (n_groups < 1 || n_groups > n) return NEGF_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        if (group_of[i] < 0 || group_of[i] >= n_groups) return NEGF_EINVAL;
+        if (group_of[i] != i) *identity = false;
+    }
+    if (*identity && n_groups == n) return NEGF_OK;
+    *identity = false;
+    std::vector<int> map((size_t)n + n_groups + 1, 0);
+    int* perm = map.data();
+    int* goff = map.data() + n;
+    for (int i = 0; i < n; ++i) ++goff[group_of[i] + 1];
+    for (int g = 0; g < n_groups; ++g) goff[g + 1] += goff[g];
+    std::vector<int> next(goff, goff + n_groups);
+    for (int i = 0; i < n; ++i) perm[next[group_of[i]]++] = i;
+    int rc = ensure_cap(c, &c->d_bond_map, &c->bond_map_cap, map.size());
+    if (rc) return rc;
+    return upload(c, c->d_bond_map, map.data(), map.size());
+}
+
+}  // namespace
+
+int negf_local_transmission_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev, int n_groups,
+                                const int* group_of, double* out_dev)
+{
+    SigmaProvider* p = get_provider(c, handle);
+    int contact = -2;
+    int rc = bond_check(c, p, m, ind, &contact);
+    if (rc) return rc;
+    if (m > 0 && (!E_dev || !out_dev)) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    bool identity = true;
+    if ((rc = bond_stage_groups(c, n_groups, group_of, &identity))) return rc;
+    const int n = c->n;
+    const int* perm = identity ? nullptr : c->d_bond_map;
+    const int* goff = identity ? nullptr : c->d_bond_map + n;
+    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
+    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    const size_t tab = (size_t)n_groups * n_groups;
+    for (int m0 = 0; m0 < m; m0 += c->batch) {
+        const int nb = std::min(c->batch, m - m0);
+        if ((rc = run_gless_products(c, p, contact, m0, nb, E))) return rc;
+        ProfScope ps(c, "bond");
+        if (!launch_bond_tables(c->stream, n, nb, E + m0, c->d_S, c->d_F, c->W1, c->d_info + m0, n_groups, perm, goff,
+                                out_dev + tab * m0)) return NEGF_EINVAL;
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_local_transmission(negf_ctx* c, int handle, int ind, int m, const double* E, int n_groups, const int* group_of,
+                            double* out, int* info)
+{
+    SigmaProvider* p = get_provider(c, handle);
+    int contact = -2;
+    int rc = bond_check(c, p, m, ind, &contact);
+    if (rc) return rc;
+    if (n_groups < 1 || (m > 0 && (!E || !out))) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    const size_t cnt = (size_t)m * n_groups * n_groups;
+    if ((rc = ensure_cap(c, &c->d_bond_T, &c->bond_T_cap, cnt))) return rc;
+    if ((rc = negf_local_transmission_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), n_groups, group_of,
+                                          c->d_bond_T))) return rc;
+    if ((rc = download(c, out, c->d_bond_T, cnt))) return rc;
+    return reduce_info(c, m, info);
+}
+
+int negf_bond_int_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    SigmaProvider* p = get_provider(c, handle);
+    int contact = -2;
+    int rc = bond_check(c, p, m, ind, &contact);
+    if (rc) return rc;
+    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    const size_t n2 = (size_t)c->n * c->n;
+    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
+    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
+    if ((rc = ensure_cap(c, &c->d_bond_carry, &c->bond_carry_cap, n2))) return rc;
+    NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, n2 * sizeof(double), c->stream));
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    for (int m0 = 0; m0 < m; m0 += c->batch) {
+        const int nb = std::min(c->batch, m - m0);
+        if ((rc = run_gless_products(c, p, contact, m0, nb, E))) return rc;
+        ProfScope ps(c, "bond");
+        // (the chunk records go where the products' temporaries were: (nb / 32 + 2) n^2 doubles of W2's 2 nb n^2)
+        launch_bond_int(c->stream, (int)n2, m, m0, nb, E + m0, w_dev + m0, c->d_S, c->d_F, c->W1, c->d_bond_carry,
+                        reinterpret_cast<double*>(c->W2), out_dev);
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_bond_int(negf_ctx* c, int handle, int ind, int m, const double* E, const double* w, double* out, int* info)
+{
+    SigmaProvider* p = get_provider(c, handle);
+    int contact = -2;
+    int rc = bond_check(c, p, m, ind, &contact);
+    if (rc) return rc;
+    if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    // the real weights ride in the [w] part of the pinned buffer and of d_w (m doubles of their m complex values)
+    const size_t gb = (size_t)m * sizeof(cplx);
+    double* dw = reinterpret_cast<double*>(c->d_w);
+    if (m > 0) {
+        std::memcpy(c->h_pin + gb, w, (size_t)m * sizeof(double));
+        NEGF_HIP_CHECK(hipMemcpyAsync(dw, c->h_pin + gb, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    double* dout = reinterpret_cast<double*>(c->d_acc);          // n^2 doubles of its n^2 complex values
+    if ((rc = negf_bond_int_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), dw, dout))) return rc;
+    const size_t ob = (size_t)c->n * c->n * sizeof(double);
+    unsigned char* pout = c->h_pin + 2 * gb;
+    int* pinfo = reinterpret_cast<int*>(pout + ob);
+    NEGF_HIP_CHECK(hipMemcpyAsync(pout, dout, ob, hipMemcpyDeviceToHost, c->stream));
+    if (m > 0) NEGF_HIP_CHECK(hipMemcpyAsync(pinfo, c->d_info, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    { const int wrc = wait_stream(c); if (wrc) return wrc; }
+    copy_bytes(out, pout, ob);
+    rc = NEGF_OK;
+    for (int i = 0; i < m; ++i) { if (info) info[i] = pinfo[i]; if (pinfo[i] != 0) rc = NEGF_ESINGULAR; }
     return rc;
 }
 

@@ -241,6 +241,12 @@ struct negf_ctx {
     size_t chan_rank_cap = 0;
     double* d_chan_T = nullptr;    // [m][nchan] staging of the host-pointer entry point
     size_t chan_T_cap = 0;
+    int* d_bond_map = nullptr;     // local transmission: perm [n] | goff [ng + 1] of the call's orbital -> group map
+    size_t bond_map_cap = 0;
+    double* d_bond_carry = nullptr; // [n*n] running sum of the 32-energy chunk a batch boundary cuts (negf_bond_int)
+    size_t bond_carry_cap = 0;
+    double* d_bond_T = nullptr;    // [m][ng][ng] staging of the host-pointer entry point
+    size_t bond_T_cap = 0;
     GjSideStreams gj_side;
     int chain_rr_quantum = -1, chain_rr_slots = 0;   // negf_set_chain_round_robin
     int small_algo = 0;            // 0: n <= 96 takes the fused single-kernel path, 1: never (negf_set_small_algo)
@@ -414,6 +420,20 @@ bool launch_eigvalsh_batched(hipStream_t st, int K, int nb, const cplx* A, int l
 // Pivoted Cholesky of the Hermitian PSD K x K matrices G[b]: Lh[b] = L^H (K x K, rows >= rank[b] zero), G ~ L L^H
 bool launch_pivoted_cholesky(hipStream_t st, int K, int nb, const cplx* G, size_t strideG, cplx* Lh, size_t strideL,
                              int* rank);
+
+// Local (bond) transmission (k_bond.hip): flow[i][j] = 2 Im[(E S - F)_ij conj(A_ij)] from the Hermitian A = G Gamma_c G^H.
+// launch_bond_tables: per-energy tables out [nb][ng][ng]; perm / goff (device, [n] / [ng + 1]) = the orbitals sorted by
+// group and the groups' offsets, perm == null: every orbital its own group (ng = n).  info[b] != 0 -> a NaN table.
+// false: n exceeds bond_max_n() (nothing launched).
+int bond_max_n();
+bool launch_bond_tables(hipStream_t st, int n, int nb, const cplx* E, const cplx* S, const cplx* F, const cplx* A,
+                        const int* info, int ng, const int* perm, const int* goff, double* out);
+// out [n2] += sum_b w[b] flow_b for the batch [m0, m0 + nb) of a grid of m energies (E, w, A indexed from the batch's
+// first energy), bitwise independent of the batch cut; carry [n2] lives across the batches of one grid, part is
+// scratch of bond_int_scratch_doubles(n2, nb) doubles (<= 2 nb n2)
+size_t bond_int_scratch_doubles(int n2, int nb);
+void launch_bond_int(hipStream_t st, int n2, int m, int m0, int nb, const cplx* E, const double* w, const cplx* S,
+                     const cplx* F, const cplx* A, double* carry, double* part, double* out);
 
 bool small_fused_supported(int n);
 int small_fused_grid(int n, int m);

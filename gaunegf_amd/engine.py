@@ -493,6 +493,82 @@ class Engine:
                                                        C.c_void_p(E_ptr), int(nchan), C.c_void_p(T_ptr)),
               "negf_transmission_channels_dev")
 
+    # ------------------------------------------- local (bond) transmission
+    BOND_MAX_N = 8192
+
+    _BOND_REFUSED = ("local transmission reads A_ji as conj(A_ij), A = G Gamma_c G^H: coupling matrices handed in by the "
+                     "caller (sigma_precomputed(gammas=...)) need not be Hermitian and are not served, nor are systems of "
+                     "more than 8192 orbitals; an invalid contact index is refused the same way")
+
+    def _groups(self, groups, n_groups=None):
+        """(n_groups, int32 map or None) of an orbital -> group map of length n (None: every orbital its own group)."""
+        if groups is None:
+            if n_groups not in (None, self.n):
+                raise ValueError(f"without a group map there are n = {self.n} groups, not {n_groups}")
+            return self.n, None
+        g = np.asarray(groups).ravel()
+        if g.size != self.n:
+            raise ValueError(f"groups must map each of the {self.n} orbitals to a group, got {g.size} entries")
+        if not np.issubdtype(g.dtype, np.integer):
+            raise ValueError("groups must be integers")
+        ng = int(g.max()) + 1 if n_groups is None else int(n_groups)
+        if g.min() < 0 or g.max() >= ng or ng > self.n:
+            raise ValueError(f"group labels must lie in [0, n_groups) with n_groups <= n; got {int(g.min())} .. {int(g.max())}, n_groups = {ng}")
+        return ng, np.ascontiguousarray(g, dtype=np.int32)
+
+    def local_transmission(self, handle, ind, E, groups=None, n_groups=None):
+        """Local (bond) transmission tables [m, n_g, n_g] of the current injected by contact ``ind``
+        (negf_local_transmission): entry [k, a, b] = sum_{i in a, j in b} 2 Im[(E_k S - F)_ij (G Gamma G^H)_ji].
+        ``groups``: orbital -> group labels (length n), None = per orbital pair.  Tables of singular energies are NaN
+        (with a warning, as transmission)."""
+        ng, g = self._groups(groups, n_groups)
+        E, _ = self._grid(E)
+        out = np.zeros((E.size, ng, ng), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lib.negf_local_transmission(self._ctx, int(handle), _ind(ind), E.size, _ptr(E), ng, _ptr(g), _ptr(out),
+                                               _ptr(info))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._BOND_REFUSED)
+        self._numerical(check(rc, "negf_local_transmission"), info[:E.size], "local_transmission")
+        return out
+
+    def local_transmission_dev(self, handle, ind, m, E_ptr, groups, out_ptr, n_groups=None):
+        """negf_local_transmission_dev: grid and the [m, n_g, n_g] result in HBM; ``groups`` stays a host array (or None)."""
+        ng, g = self._groups(groups, n_groups)
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        rc = self._lib.negf_local_transmission_dev(self._ctx, int(handle), _ind(ind), int(m), C.c_void_p(E_ptr), ng, _ptr(g),
+                                                   C.c_void_p(out_ptr))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._BOND_REFUSED)
+        check(rc, "negf_local_transmission_dev")
+
+    def bond_int(self, handle, ind, E, w):
+        """sum_k w_k flow(E_k) [n, n] float64 with REAL weights, one pass (negf_bond_int)."""
+        w = np.asarray(w).ravel()
+        if np.iscomplexobj(w):
+            if np.any(w.imag != 0):
+                raise ValueError("bond_int takes real weights")
+            w = w.real
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        E, _ = self._grid(E)
+        assert E.size == w.size, "Elist and weights must have the same length"
+        out = np.zeros((self.n, self.n), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lib.negf_bond_int(self._ctx, int(handle), _ind(ind), E.size, _ptr(E), _ptr(w), _ptr(out), _ptr(info))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._BOND_REFUSED)
+        self._numerical(check(rc, "negf_bond_int"), info[:E.size], "bond_int")
+        return out
+
+    def bond_int_dev(self, handle, ind, m, E_ptr, w_ptr, out_ptr):
+        """negf_bond_int_dev: E complex128 [m], w float64 [m] and out float64 [n, n] in HBM."""
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        rc = self._lib.negf_bond_int_dev(self._ctx, int(handle), _ind(ind), int(m), C.c_void_p(E_ptr), C.c_void_p(w_ptr),
+                                         C.c_void_p(out_ptr))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._BOND_REFUSED)
+        check(rc, "negf_bond_int_dev")
+
     def dos(self, handle, E, per_site=True):
         E, _ = self._grid(E)
         tot = np.zeros(E.size, dtype=np.float64)

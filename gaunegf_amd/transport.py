@@ -314,6 +314,101 @@ def _channel_count(F, S, sigma_calc, spin):
             eng.sigma_free(h)
 
 
+def _bond_layout(F, S, sigma_calc, spin):
+    """How the local transmission of (F, S, spin) is evaluated: [(F, S, perm)] -- one system for 'r' (perm None), the two
+    N x N spin blocks for a spin-diagonal 'u' / 'ro' system with a spin-expanded self-energy, and otherwise the whole
+    2N x 2N system: as it is for 'u' / 'ro' with spin mixing, shuffled to block form (perm) for 'g'."""
+    if spin not in ('r', 'u', 'ro', 'g'):
+        raise ValueError(f"Unknown spin configuration '{spin}'. Use 'r', 'u', 'ro', or 'g'")
+    F = np.asarray(F)
+    S = np.asarray(S)
+    size = F.shape[0]
+    if spin in ('u', 'ro') and SPIN_BLOCK_SPLIT and _sigma_is_spin_expanded(sigma_calc, size):
+        blocks = _spin_diagonal_blocks(F, S)
+        if blocks is not None:
+            return [(blocks[0], blocks[1], None), (blocks[2], blocks[3], None)]
+    if spin == 'g':
+        return [(F, S, _spinor_perm(size // 2))]
+    return [(F, S, None)]
+
+
+def _bond_handle(eng, F, S, perm, sigma_calc, energies, spin):
+    """Make (F, S) the resident system and lower the self-energy the way _transmission_batch does; (handle, temporary)."""
+    size = F.shape[0]
+    if perm is not None:
+        ix = np.ix_(perm, perm)
+        tot = np.stack([np.asarray(sigma_calc.get_sigma_total(E, spin, size))[ix] for E in energies])
+        sL = np.stack([np.asarray(sigma_calc.get_sigma(E, 0, spin, size))[ix] for E in energies])
+        sR = np.stack([np.asarray(sigma_calc.get_sigma(E, -1, spin, size))[ix] for E in energies])
+        eng.set_system(F[ix], S[ix])
+        return eng.sigma_precomputed(tot, np.stack([sL, sR], axis=1)), True
+    eng.set_system(F, S)
+    # (a spin block of a 'u' / 'ro' system sees the N x N self-energy: lowered as a restricted system)
+    return sigma_calc._lower(eng, energies, spin if size != _sigma_size(sigma_calc) else 'r', size)
+
+
+def _sigma_size(sigma_calc):
+    if sigma_calc.energy_dependent:
+        f = getattr(sigma_calc.sig1, "F", None)
+        return None if f is None else np.asarray(f).shape[0]
+    return SigmaCalculator._static(sigma_calc.sig1).shape[0]
+
+
+def _check_contact(contact):
+    if contact not in (0, 1, -1):
+        raise ValueError(f"contact must be 0 (the first contact) or 1 / -1 (the second), got {contact!r}")
+    return int(contact)
+
+
+def _local_batch(layout, sigma_calc, energies, spin, groups, n_groups, contact):
+    """Local transmission tables of all ``energies``: [len(layout), m, n_g, n_g]."""
+    energies = np.asarray(energies)
+    eng = get_engine()
+    out = []
+    for F, S, perm in layout:
+        g = groups
+        if perm is not None:                       # block form: position q holds the caller's orbital perm[q]
+            g = (np.arange(F.shape[0]) if groups is None else np.asarray(groups))[perm]
+        h, temp = _bond_handle(eng, F, S, perm, sigma_calc, energies, spin)
+        try:
+            out.append(eng.local_transmission(h, contact, energies, g, n_groups))
+        finally:
+            if temp:
+                eng.sigma_free(h)
+    return np.stack(out)
+
+
+def _bond_int_batch(layout, sigma_calc, energies, weights, spin, contact):
+    """sum_k w_k flow(E_k) per system of the layout, in the caller's orbital order: [len(layout), n, n]."""
+    energies = np.asarray(energies)
+    eng = get_engine()
+    out = []
+    for F, S, perm in layout:
+        h, temp = _bond_handle(eng, F, S, perm, sigma_calc, energies, spin)
+        try:
+            flow = eng.bond_int(h, contact, energies, weights)
+        finally:
+            if temp:
+                eng.sigma_free(h)
+        if perm is not None:
+            back = np.empty_like(flow)
+            back[np.ix_(perm, perm)] = flow
+            flow = back
+        out.append(flow)
+    return np.stack(out)
+
+
+def _group_count(groups, n):
+    if groups is None:
+        return n
+    g = np.asarray(groups).ravel()
+    if g.size != n:
+        raise ValueError(f"groups must map each of the {n} orbitals to a group, got {g.size} entries")
+    if not np.issubdtype(g.dtype, np.integer) or g.min() < 0:
+        raise ValueError("groups must be non-negative integers")
+    return int(g.max()) + 1
+
+
 def _dos_batch(F, S, sigma_calc, energies, spin):
     F = np.asarray(F)
     S = np.asarray(S)
@@ -473,6 +568,73 @@ def calculate_transmission_channels(F, S, sigma_calculator, energy_list, spin=No
         return np.concatenate([up, down], axis=1)
     res = _dist.sharded_map(both, m, (2 * nchan,))
     return res[:, :nchan], res[:, nchan:]
+
+
+def calculate_local_transmission(F, S, sigma_calculator, energy_list, groups=None, contact=0, spin=None):
+    """Local (bond) transmission: WHERE the transmission injected by ``contact`` flows.  Per energy, with K = E S - F
+    (no self-energies) and A = G Gamma_c G^H, flow[i, j] = 2 Im[K_ij A_ji] is the transmission flowing from orbital i to
+    orbital j; with ``groups`` (orbital -> atom / fragment labels, one per orbital) the table is summed over the orbital
+    pairs of each pair of groups.  Returns [m, n_g, n_g] (n_g = N without groups): real, antisymmetric, and for every split
+    of the groups into a side holding the injecting contact and a side holding the other one the entries across the cut
+    sum to calculate_transmission's T(E); rows of groups outside all contacts sum to zero.
+    spin 'r': as is.  'u' / 'ro' on a spin-diagonal system with a spin-expanded N x N self-energy: (up, down), ``groups``
+    of length N.  'g', and 'u' / 'ro' with spin mixing: the total over the 2N x 2N system, ``groups`` of length 2N in the
+    caller's orbital order; its cuts sum to the full trace Tr[Gamma_L G Gamma_R G^H] of the 2N system, which the
+    spin-block sum of calculate_transmission (the reference's pairing of G_ud with (G^H)_ud) equals only without spin
+    mixing.  Explicit coupling matrices (non-Hermitian in general) are not served."""
+    energy_list = np.asarray(energy_list)
+    if spin is None:
+        spin = 'r'
+    contact = _check_contact(contact)
+    layout = _bond_layout(F, S, sigma_calculator, spin)
+    n_g = _group_count(groups, layout[0][0].shape[0])
+    k = len(layout)
+    res = _dist.sharded_map(
+        lambda idx: np.moveaxis(_local_batch(layout, sigma_calculator, energy_list[idx], spin, groups, n_g, contact), 0, 1)
+        .reshape(-1, k * n_g, n_g), len(energy_list), (k * n_g, n_g))
+    res = np.asarray(res).reshape(len(energy_list), k, n_g, n_g)
+    return res[:, 0] if k == 1 else (res[:, 0], res[:, 1])
+
+
+def calculate_bond_currents(F, S, sigma_calculator, fermi, qV, T=TEMPERATURE, groups=None, spin=None, dE=ENERGY_STEP):
+    """Bond currents in amperes [n_g, n_g]: the local transmission integrated over calculate_current's grid with its
+    occupation factor, trapezoid weights (signed step for qV < 0), e/h and the factor 2 of spin 'r' -- in ONE pass over
+    the grid (Engine.bond_int) --, so that every cut separating the first contact from the second sums to
+    calculate_current of the same arguments, sign included.  ``groups`` and spin as calculate_local_transmission
+    ((up, down) for a spin-diagonal 'u' / 'ro' system: the cuts equal the uu and dd entries of calculate_current's
+    spin list).  qV ~ 0 returns zeros."""
+    if fermi is None or qV is None:
+        raise ValueError("fermi and qV must be provided for current calculations")
+    if spin is None:
+        spin = 'r'
+    layout = _bond_layout(F, S, sigma_calculator, spin)
+    n = layout[0][0].shape[0]
+    n_g = _group_count(groups, n)
+    k = len(layout)
+    if np.allclose(0, qV):
+        z = np.zeros((n_g, n_g))
+        return z if k == 1 else (z, z.copy())
+    energies, muL, muR = current_grid(fermi, qV, T, dE)
+    if len(energies) == 0:
+        raise ValueError("No energies in integration window. Check fermi, qV, and dE.")
+    # trapezoid(y * occupation, energies) = sum_k w_k y_k
+    w = np.zeros(len(energies))
+    if len(energies) > 1:
+        d = np.diff(energies)
+        w[:-1] += d / 2
+        w[1:] += d / 2
+    if T != 0:
+        w = w * np.abs(1 / (np.exp((energies - muR) / (kB * T)) + 1) - 1 / (np.exp((energies - muL) / (kB * T)) + 1))
+    flow = _dist.sharded_sum(lambda idx: _bond_int_batch(layout, sigma_calculator, energies[idx], w[idx], spin, 0),
+                             len(energies))
+    flow = eoverh * np.asarray(flow)
+    if spin == 'r':
+        flow = flow * 2
+    if groups is not None:
+        onehot = np.zeros((n, n_g))
+        onehot[np.arange(n), np.asarray(groups).ravel()] = 1.0
+        flow = np.stack([onehot.T @ f @ onehot for f in flow])
+    return flow[0] if k == 1 else (flow[0], flow[1])
 
 
 def calculate_dos(F, S, sigma_calculator, energy_list, spin=None, checkpoint_file=None,
@@ -653,6 +815,17 @@ def cohTransChannels(Elist, F, S, sig1, sig2, nchan=None):
 def cohTransChannelsE(Elist, F, S, g, nchan=None):
     """Transmission eigenchannels [M, nchan] with an energy-dependent provider ``g`` (next to cohTransE)."""
     return calculate_transmission_channels(F, S, _dynamic_calc(g), Elist, spin='r', nchan=nchan)
+
+
+def localTrans(Elist, F, S, sig1, sig2, groups=None):
+    """Local (bond) transmission tables [M, n_g, n_g] with energy-independent self-energies (next to cohTrans); every cut
+    between the contacts sums to cohTrans's T(E)."""
+    return calculate_local_transmission(F, S, _static_calc(sig1, sig2), Elist, groups=groups, spin='r')
+
+
+def localTransE(Elist, F, S, g, groups=None):
+    """Local (bond) transmission tables [M, n_g, n_g] with an energy-dependent provider ``g`` (next to cohTransE)."""
+    return calculate_local_transmission(F, S, _dynamic_calc(g), Elist, groups=groups, spin='r')
 
 
 def _spin_trans(Elist, F, S, calc, spin):

@@ -308,9 +308,40 @@ int negf_transmission_channels(negf_ctx* ctx, int handle, int contact_L, int con
 int negf_transmission_channels_dev(negf_ctx* ctx, int handle, int contact_L, int contact_R, int m, const double* E_dev,
                                    int nchan, double* T_chan_dev);
 
+/* ------------------------------------------------------ local (bond) transmission
+ * Where in the junction the current injected by contact `ind` flows (the reference has no such function; it is the
+ * orbital-resolved form of its transmission, transport.py:150-157, built on the products of GrLessInt,
+ * integrate.py:74-82).  Per energy, with K = E S - F (the assembled matrix WITHOUT the self-energies) and
+ * A_c = G Gamma_c G^H, Gamma_c = i (Sigma_c - Sigma_c^H):
+ *     flow[i][j] = 2 Im[K_ij A_c,ji]          -- transmission flowing from orbital i to orbital j.
+ * For Hermitian F, S and real E it is real antisymmetric and conserves: for every split of the orbitals into
+ * P (holding contact c's orbitals) and Q (holding every other contact's), sum_{i in P, j in Q} flow[i][j] is the total
+ * transmission out of c -- Tr[Gamma_L G Gamma_R G^H] for two contacts --, and the row of an orbital outside all
+ * contacts sums to zero.  Complex E and non-Hermitian F are not rejected: the formula is applied literally (the
+ * conservation law then does not hold).  A_c,ji is read as conj(A_c,ij): providers whose coupling matrices were
+ * handed in by the caller (negf_sigma_precomputed with gammas; they need not be Hermitian) return NEGF_EINVAL, and so
+ * does n > 8192.  Every other provider negf_gless_int serves is served, ind as there.
+ * group_of: host int[n], orbital -> group in [0, n_groups) (atoms, fragments, spin-resolved atoms; empty groups
+ * allowed), or NULL with n_groups = n for every orbital its own group.  out [m][n_groups][n_groups]:
+ *     out[k][a][b] = sum_{i in a, j in b} flow[i][j](E_k);
+ * a singular energy gives a NaN table and its info, as negf_transmission.  All sums have a fixed order (no atomics):
+ * results are bitwise equal from run to run, do not depend on negf_set_batch, and relabelling the groups permutes the
+ * table bit for bit. */
+int negf_local_transmission(negf_ctx* ctx, int handle, int ind, int m, const double* E_c128, int n_groups,
+                            const int* group_of, double* out, int* info);
+int negf_local_transmission_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, int n_groups,
+                                const int* group_of, double* out_dev);
+/* sum_k w_k flow(E_k) with REAL weights w [m], in one pass: out [n][n] float64.  Chunks of 32 consecutive energies of
+ * the grid are added in order and the chunk sums in order, whatever the workspace batch.  A singular energy enters
+ * as negf_gless_int's does (its info is set, NEGF_ESINGULAR returned). */
+int negf_bond_int(negf_ctx* ctx, int handle, int ind, int m, const double* E_c128, const double* w,
+                  double* out, int* info);
+int negf_bond_int_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, const double* w_dev,
+                      double* out_dev);
+
 /* ------------------------------------------------------------- diagnostics */
 /* hipEvent timing of the library's own kernels, per kernel family
- * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig";
+ * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig", "bond";
  * "chain1d_rd": the renormalisation-decimation solver's launches, "chain1d_hit" / "chain1d_rd_hit": g(E) cache hits). */
 /* device bytes held by the context's energy workspace: the three n x n work areas per energy in flight (work) and the
  * staging of the self-energy blocks of CHAIN1D / BETHE providers (blocks); either pointer may be NULL */

@@ -1,0 +1,560 @@
+"""Local (bond) transmission on the GPU (negf_local_transmission, negf_bond_int and their front ends) against the numpy
+restatement and the extended-precision truth of tests/bond_ref.py.
+
+Bars (none of them taken from what the device returns):
+  * parity with bond_ref.flow on the Sigma(E) the device itself evaluated (negf_sigma_eval): 1e-8 relative Frobenius per
+    energy, the project's bar for G(E)-derived quantities;
+  * the calibrated bar on the CONST inputs of bond_ref.const_cases(): error against the clongdouble truth at most
+    bond_ref.C_BOND (= 4, test_bond_host.test_calibration) times the larger error of the two float64 forms;
+  * conservation against the device's own transmission: |sum_cut flowG - T| <= 1e-8 max(|T|, sum_cut |flow|) for the cut
+    at every group boundary between the contacts and one random split; interior rows, flowG + flowG^T and diag flowG
+    under the same bar (scale: the table's absolute sum).  The numpy restatement is asserted to stay a factor 100
+    inside these bars on every input first (here for the providers whose Sigma comes from the device, in
+    test_bond_host.py for the CONST inputs).  surfGTest / formSigma contacts put -1e-9 i S on EVERY orbital, so no split
+    separates those contacts exactly: that provider is held to parity only.
+  * permuted group labels: the permuted table BITWISE -- the library sorts the orbitals by group, ascending orbital index
+    inside a group, and every partial sum is indexed by positions inside the groups only, so relabelling moves whole
+    sums and changes none.
+"""
+import os
+import socket
+import warnings
+
+import numpy as np
+import pytest
+import scipy.linalg as sla
+
+import bond_ref as br
+from helpers import chain_lead, random_system
+
+pytestmark = pytest.mark.gpu
+
+BAR = br.PROJECT_BAR
+
+
+def _rel(a, b):
+    return np.linalg.norm(a - b) / np.linalg.norm(b)
+
+
+def _near_eigenvalue(F, S, target=0.6):
+    ev = sla.eigh(F, S, eigvals_only=True)
+    return float(ev[np.argmin(np.abs(ev - target))]) + 5e-4
+
+
+def _check_parity(tables, F, S, sig_at, E, what):
+    worst = 0.0
+    for k, e in enumerate(E):
+        ref = br.flow(F, S, sig_at(k), e)
+        err = _rel(tables[k], ref)
+        worst = max(worst, err)
+        print(f"{what}: E={e:.6g} parity {err:.3g} (bar {BAR:g})")
+        assert err <= BAR, (what, k, err)
+    return worst
+
+
+def _check_conservation(tab, T, case_nc, groups, cuts, what, restated=None):
+    """tab [n_g, n_g] of one energy against the transmission T; `restated`: the numpy table of the same input, which must
+    sit a factor 100 inside every bar before the device is judged."""
+    for name, t, bar in (("numpy", restated, BAR / 100), ("device", tab, BAR)):
+        if t is None:
+            continue
+        tot = np.abs(t).sum()
+        for P in cuts:
+            blockPQ = t[np.ix_(P, ~P)]
+            d, scale = abs(blockPQ.sum() - T), max(abs(T), np.abs(blockPQ).sum())
+            assert d <= bar * scale, (what, name, "cut", d, scale)
+        g_lo, g_hi = int(groups[case_nc[0] - 1]) + 1, int(groups[len(groups) - case_nc[1]])
+        assert np.all(np.abs(t[g_lo:g_hi].sum(axis=1)) <= bar * tot), (what, name, "interior rows")
+        assert np.abs(t + t.T).max() <= bar * tot, (what, name, "antisymmetry")
+        assert np.abs(np.diag(t)).max() <= bar * tot, (what, name, "diagonal")
+
+
+# --------------------------------------------------------------------------- CONST: parity, calibrated bar, conservation
+@pytest.mark.parametrize("idx", [0, 1, 2])
+def test_const_parity_truth_and_conservation(engine, idx):
+    c = br.const_cases()[idx]
+    groups = c.atom_groups()
+    E = c.energies
+    engine.set_system(c.F, c.S)
+    h = engine.sigma_const(c.sigmas)
+    try:
+        orb = engine.local_transmission(h, 0, E)
+        grp = engine.local_transmission(h, 0, E, groups)
+        T = engine.transmission(h, 0, 1, E)
+    finally:
+        engine.sigma_free(h)
+    assert orb.shape == (E.size, c.n, c.n) and grp.shape == (E.size, groups.max() + 1, groups.max() + 1)
+    _check_parity(orb, c.F, c.S, lambda k: c.sigmas, E, f"CONST n={c.n}")
+    worst = 0.0
+    for k, e in enumerate(E):
+        truth = br.flow_truth(c.F, c.S, c.sigmas, e)
+        e64 = max(br.rel_err(br.flow(c.F, c.S, c.sigmas, e), truth), br.rel_err(br.flow_alt(c.F, c.S, c.sigmas, e), truth))
+        err = br.rel_err(orb[k], truth)
+        worst = max(worst, err / e64)
+        print(f"CONST n={c.n} E={e:.6g}: device error vs truth {err:.3g}, float64 forms {e64:.3g}, ratio {err / e64:.3g} "
+              f"(allowed {br.C_BOND:g})")
+        assert err <= br.C_BOND * e64, (c.n, e, err, e64)
+        assert _rel(grp[k], br.group_table(br.flow(c.F, c.S, c.sigmas, e), groups)) <= BAR
+        _check_conservation(grp[k], T[k], c.nc, groups, c.group_cuts(groups), f"CONST n={c.n} E={e:.6g}")
+        for P in c.cuts():                                               # orbital table, orbital cuts
+            d, scale = br.cut_defect(orb[k], T[k], P)
+            assert d <= BAR * scale
+    print(f"CONST n={c.n}: worst device error / float64 error {worst:.3g}")
+
+
+def test_const_windowed_n300(engine):
+    """n = 300: the windowed inverse; contacts of 50 and 40 orbitals; parity and conservation."""
+    c = br.BondCase(300, (50, 40), 4)
+    groups = c.atom_groups(10)
+    E = c.energies
+    engine.set_system(c.F, c.S)
+    h = engine.sigma_const(c.sigmas)
+    try:
+        orb = engine.local_transmission(h, 0, E)
+        grp = engine.local_transmission(h, 0, E, groups)
+        T = engine.transmission(h, 0, 1, E)
+    finally:
+        engine.sigma_free(h)
+    _check_parity(orb, c.F, c.S, lambda k: c.sigmas, E, "CONST n=300")
+    for k, e in enumerate(E):
+        ref = br.group_table(br.flow(c.F, c.S, c.sigmas, e), groups)
+        assert _rel(grp[k], ref) <= BAR
+        _check_conservation(grp[k], T[k], c.nc, groups, c.group_cuts(groups), f"CONST n=300 E={e:.6g}", restated=ref)
+
+
+def test_second_contact_and_total(engine):
+    """ind = 1 / -1: the flow injected by the other contact; its cuts carry -T towards contact 0's side."""
+    c = br.const_cases()[0]
+    E = c.energies
+    engine.set_system(c.F, c.S)
+    h = engine.sigma_const(c.sigmas)
+    try:
+        one = engine.local_transmission(h, 1, E)
+        last = engine.local_transmission(h, -1, E)
+        T = engine.transmission(h, 0, 1, E)
+    finally:
+        engine.sigma_free(h)
+    assert np.array_equal(one, last)
+    for k, e in enumerate(E):
+        assert _rel(one[k], br.flow(c.F, c.S, c.sigmas, e, 1)) <= BAR
+        for P in c.cuts():
+            blockQP = one[k][np.ix_(~P, P)]
+            assert abs(blockQP.sum() - T[k]) <= BAR * max(abs(T[k]), np.abs(blockQP).sum())
+
+
+# --------------------------------------------------------------------------- other providers
+def test_surfgtest_dense_path_parity(engine):
+    """formSigma-style contacts: full support -> the dense G Gamma G^H products.  Parity only (the -1e-9 i S background on
+    every orbital leaves no split that separates the contacts exactly)."""
+    from gaunegf_amd.surfGTester import surfGTest
+    from gaunegf_amd.transport import SigmaCalculator, calculate_local_transmission
+    for n, nc in ((40, 5), (130, 12)):
+        F, S = random_system(n, 300 + n)
+        g = surfGTest(F, S, [list(range(nc)), list(range(n - nc, n))], -0.25j)
+        E = np.array([-1.0, 0.3, _near_eigenvalue(F, S), 2.0])
+        tab = calculate_local_transmission(F, S, SigmaCalculator(g), E)
+        _check_parity(tab, F, S, lambda k: [g.sig[0], g.sig[1]], E, f"surfGTest n={n}")
+
+
+def _chain_system(n, nc, seed, solver):
+    from gaunegf_amd.surfG1D import surfG
+    F, S = random_system(n, seed)
+    lead = [chain_lead(nc, 40 + k) for k in range(2)]
+    ci = [list(range(nc)), list(range(n - nc, n))]
+    rng = np.random.default_rng(seed)
+    taus = [0.2 * rng.standard_normal((nc, nc)) for _ in range(2)]
+    staus = [0.02 * rng.standard_normal((nc, nc)) for _ in range(2)]
+    g = surfG(F, S, ci, taus=taus, staus=staus, alphas=[l[0] for l in lead], aOverlaps=[l[1] for l in lead],
+              betas=[l[2] for l in lead], bOverlaps=[l[3] for l in lead], eta=1e-3, solver=solver)
+    return F, S, g, ci
+
+
+@pytest.mark.parametrize("solver,n,nc", [("fixed-point", 130, 20), ("doubling", 130, 20), ("fixed-point", 60, 8),
+                                         ("doubling", 300, 50)])
+def test_chain_parity_and_conservation(engine, solver, n, nc):
+    from gaunegf_amd.transport import SigmaCalculator, calculate_local_transmission, calculate_transmission, localTransE
+    F, S, g, ci = _chain_system(n, nc, 7 + n, solver)
+    E = np.array([-1.0, 0.3, _near_eigenvalue(F, S), 1.1])
+    groups = br.aligned_groups(n, (nc, nc), 10)
+    sc = SigmaCalculator(g)
+    orb = calculate_local_transmission(F, S, sc, E)
+    grp = calculate_local_transmission(F, S, sc, E, groups=groups)
+    T = calculate_transmission(F, S, sc, E)
+    h = g._negf_lower(engine)
+    sL = engine.sigma_eval(h, 0, E, 2); sR = engine.sigma_eval(h, 1, E, 2)
+    _check_parity(orb, F, S, lambda k: [sL[k], sR[k]], E, f"chain {solver} n={n}")
+    case = br.BondCase.__new__(br.BondCase)
+    case.n, case.nc, case.seed = n, (nc, nc), n
+    for k, e in enumerate(E):
+        ref = br.group_table(br.flow(F, S, [sL[k], sR[k]], e), groups)
+        assert _rel(grp[k], ref) <= BAR
+        _check_conservation(grp[k], T[k], (nc, nc), groups, case.group_cuts(groups), f"chain {solver} n={n} E={e:.6g}",
+                            restated=ref)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        assert np.array_equal(localTransE(E, F, S, g, groups=groups), grp)
+
+
+def test_chain_cache_hit_equals_miss(engine):
+    F, S, g, ci = _chain_system(130, 20, 5, "fixed-point")
+    E = np.linspace(-1.0, 1.0, 9)
+    w = np.full(E.size, 0.25)
+    groups = br.aligned_groups(130, (20, 20), 10)
+    engine.set_system(F, S)
+    h = g._negf_lower(engine)
+    engine.chain_cache_clear()
+    s0 = engine.chain_cache_stats()
+    miss = engine.local_transmission(h, 0, E, groups)
+    s1 = engine.chain_cache_stats()
+    hit = engine.local_transmission(h, 0, E, groups)
+    hit_int = engine.bond_int(h, 0, E, w)
+    s2 = engine.chain_cache_stats()
+    engine.chain_cache_clear()
+    miss_int = engine.bond_int(h, 0, E, w)
+    assert s1["misses"] > s0["misses"] and s2["hits"] >= s1["hits"] + 2
+    assert np.array_equal(miss, hit) and np.array_equal(miss_int, hit_int)
+
+
+def test_bethe_parity_and_conservation(engine):
+    from gaunegf_amd.surfGBethe import read_bethe_params, construct_sk_matrix, gen_neighbors
+    here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaunegf_amd", "data", "Au")
+    ne, Ed, Vd, Sd, H0 = read_bethe_params(here)
+    dirs = gen_neighbors(np.array([0.0, 0.0, 1.0]), np.array([1.0, 0.2, 0.0]))
+    Sl = np.array([construct_sk_matrix(Sd, d) for d in dirs]); Vl = np.array([construct_sk_matrix(Vd, d) for d in dirs])
+    n = 45
+    F, S = random_system(n, 17)
+    F = F - 5.0 * S                                                       # around the Au d band
+    orbs = [[list(range(9))], [list(range(n - 18, n - 9)), list(range(n - 9, n))]]
+    nbs = [[[0, 1, 2]], [[0, 1, 2], [6, 7, 8]]]
+    groups = br.aligned_groups(n, (9, 18), 9)
+    engine.set_system(F, S)
+    h = engine.sigma_bethe(orbs, nbs, [H0, H0], [Sl, Sl], [Vl, Vl], None, 1e-4, 1e-8)
+    try:
+        E = np.linspace(-3.8, -2.6, 5)
+        orb = engine.local_transmission(h, 0, E)
+        grp = engine.local_transmission(h, 0, E, groups)
+        T = engine.transmission(h, 0, 1, E)
+        sL = engine.sigma_eval(h, 0, E, 2); sR = engine.sigma_eval(h, 1, E, 2)
+    finally:
+        engine.sigma_free(h)
+    _check_parity(orb, F, S, lambda k: [sL[k], sR[k]], E, "Bethe n=45")
+    case = br.BondCase.__new__(br.BondCase)
+    case.n, case.nc, case.seed = n, (9, 18), 45
+    for k, e in enumerate(E):
+        ref = br.group_table(br.flow(F, S, [sL[k], sR[k]], e), groups)
+        _check_conservation(grp[k], T[k], (9, 18), groups, case.group_cuts(groups), f"Bethe E={e:.6g}", restated=ref)
+
+
+def test_precomputed_sigma_and_refused_gammas(engine):
+    """PRECOMPUTED with per-contact Sigma is served (a foreign, energy-dependent provider staged per energy); coupling
+    matrices handed in by the caller need not be Hermitian and are refused -- never a silently wrong table."""
+    from gaunegf_amd.transport import SigmaCalculator, calculate_local_transmission
+    c = br.const_cases()[1]
+    E = c.energies
+
+    class Foreign:
+        def sigmaTot(self, e):
+            return self.sigma(e, 0) + self.sigma(e, 1)
+
+        def sigma(self, e, ind):
+            return c.sigmas[0 if ind == 0 else 1] * (1.0 + 0.1 * e)
+
+    sc = SigmaCalculator(Foreign(), energy_dependent=True)
+    tab = calculate_local_transmission(c.F, c.S, sc, E)
+    _check_parity(tab, c.F, c.S, lambda k: [s * (1.0 + 0.1 * E[k]) for s in c.sigmas], E, "PRECOMPUTED n=60")
+    engine.set_system(c.F, c.S)
+    gam = np.stack([np.stack([br.gamma(s) for s in c.sigmas])] * E.size)
+    h = engine.sigma_precomputed(np.stack([c.sigmas[0] + c.sigmas[1]] * E.size), gammas=gam)
+    try:
+        with pytest.raises(NotImplementedError, match="Hermitian"):
+            engine.local_transmission(h, 0, E)
+        with pytest.raises(NotImplementedError, match="Hermitian"):
+            engine.bond_int(h, 0, E, np.ones(E.size))
+    finally:
+        engine.sigma_free(h)
+    with pytest.raises(ValueError):
+        engine.local_transmission(0, 0, E, groups=np.zeros(c.n - 1, dtype=int))
+
+
+# --------------------------------------------------------------------------- groups
+def test_group_maps(engine):
+    c = br.const_cases()[2]
+    E = c.energies
+    groups = c.atom_groups()
+    ng = int(groups.max()) + 1
+    engine.set_system(c.F, c.S)
+    h = engine.sigma_const(c.sigmas)
+    try:
+        orb = engine.local_transmission(h, 0, E)
+        ident = engine.local_transmission(h, 0, E, np.arange(c.n))
+        grp = engine.local_transmission(h, 0, E, groups)
+        relabel = np.random.default_rng(1).permutation(ng)                # group g is now called relabel[g]
+        perm = engine.local_transmission(h, 0, E, relabel[groups])
+        # a scattered partition (orbital i in group i mod 7) through the sorted map
+        scat = engine.local_transmission(h, 0, E, np.arange(c.n) % 7)
+        one = engine.local_transmission(h, 0, E, np.zeros(c.n, dtype=int))
+        sparse = engine.local_transmission(h, 0, E, groups, n_groups=ng + 3)   # trailing empty groups
+    finally:
+        engine.sigma_free(h)
+    assert np.array_equal(orb, ident)                                     # identity map = orbital table, bitwise
+    assert np.array_equal(perm[:, relabel[:, None], relabel[None, :]], grp)   # permuted labels: bitwise
+    assert sparse.shape == (E.size, ng + 3, ng + 3) and np.array_equal(sparse[:, :ng, :ng], grp)
+    assert np.all(sparse[:, ng:, :] == 0.0) and np.all(sparse[:, :, ng:] == 0.0)
+    for k in range(E.size):
+        assert _rel(scat[k], br.group_table(orb[k], np.arange(c.n) % 7)) <= 1e-12
+        assert one[k].shape == (1, 1) and abs(one[k][0, 0]) <= BAR * np.abs(orb[k]).sum()
+
+
+def test_empty_grid(engine):
+    c = br.const_cases()[0]
+    engine.set_system(c.F, c.S)
+    h = engine.sigma_const(c.sigmas)
+    try:
+        assert engine.local_transmission(h, 0, []).shape == (0, c.n, c.n)
+        assert engine.local_transmission(h, 0, [], c.atom_groups()).shape[0] == 0
+        out = engine.bond_int(h, 0, [], [])
+    finally:
+        engine.sigma_free(h)
+    assert out.shape == (c.n, c.n) and not np.any(out)
+
+
+# --------------------------------------------------------------------------- the integrated form
+@pytest.mark.parametrize("kind", ["const60", "const130", "chain130"])
+def test_bond_int_identities(engine, kind):
+    """sum_k w_k flow(E_k) against 2 Im[S_ij (sum w E A)_ji - F_ij (sum w A)_ji] from two GrLessInt calls of the engine
+    (K is linear in E), and against the weighted sum of the per-energy tables."""
+    from scipy.special import roots_legendre
+    x, w = roots_legendre(40)
+    E = 2.0 * x; w = 2.0 * w
+    if kind.startswith("const"):
+        c = br.const_cases()[1 if kind == "const60" else 2]
+        F, S = c.F, c.S
+        engine.set_system(F, S)
+        h, free = engine.sigma_const(c.sigmas), True
+    else:
+        F, S, g, ci = _chain_system(130, 20, 9, "fixed-point")
+        engine.set_system(F, S)
+        h, free = g._negf_lower(engine), False
+    try:
+        out = engine.bond_int(h, 0, E, w)
+        A0 = engine.gless_int(h, 0, E, w)
+        A1 = engine.gless_int(h, 0, E, w * E)
+        tabs = engine.local_transmission(h, 0, E)
+    finally:
+        if free:
+            engine.sigma_free(h)
+    two = 2.0 * np.imag(np.asarray(S) * A1.T - np.asarray(F) * A0.T)
+    e1 = _rel(out, two)
+    e2 = _rel(out, np.tensordot(w, tabs, axes=1))
+    print(f"bond_int {kind}: vs two GrLessInt {e1:.3g}, vs weighted sum of the tables {e2:.3g} (bar {BAR:g})")
+    assert e1 <= BAR and e2 <= BAR
+    assert out.dtype == np.float64 and np.abs(out + out.T).max() <= BAR * np.abs(out).max()
+
+
+def test_bond_currents_match_calculate_current(engine):
+    from gaunegf_amd.transport import SigmaCalculator, calculate_bond_currents, calculate_current
+    c = br.const_cases()[1]
+    F, S = np.real(c.F), np.real(c.S)                                     # a real symmetric system
+    sc = SigmaCalculator(c.sigmas[0], c.sigmas[1])
+    groups = c.atom_groups()
+    for T_, qV in ((0, 0.3), (0, -0.3), (300.0, 0.2), (300.0, -0.2)):
+        I = calculate_current(F, S, sc, 0.1, qV, T=T_, dE=0.01)
+        bc = calculate_bond_currents(F, S, sc, 0.1, qV, T=T_, groups=groups, dE=0.01)
+        bo = calculate_bond_currents(F, S, sc, 0.1, qV, T=T_, dE=0.01)
+        assert bc.shape == (groups.max() + 1,) * 2 and bo.shape == (c.n, c.n)
+        for P in c.group_cuts(groups):
+            cut = bc[np.ix_(P, ~P)].sum()
+            assert abs(cut - I) <= 1e-8 * abs(I), (T_, qV, cut, I)
+        for P in c.cuts():
+            assert abs(bo[np.ix_(P, ~P)].sum() - I) <= 1e-8 * abs(I), (T_, qV)
+        assert np.sign(bc[np.ix_(c.group_cuts(groups)[0], ~c.group_cuts(groups)[0])].sum()) == np.sign(qV)
+    z = calculate_bond_currents(F, S, sc, 0.1, 0.0, groups=groups)
+    assert z.shape == bc.shape and not np.any(z)
+
+
+def test_spin_layouts(engine):
+    from gaunegf_amd.transport import SigmaCalculator, calculate_bond_currents, calculate_current, \
+        calculate_local_transmission
+    c = br.const_cases()[0]
+    N = c.n
+    Fa = np.real(c.F); S = np.real(c.S)
+    Fb, _ = random_system(N, 72)
+    Z = np.zeros((N, N))
+    F2 = np.block([[Fa, Z], [Z, Fb]]); S2 = np.block([[S, Z], [Z, S]])
+    sc = SigmaCalculator(c.sigmas[0], c.sigmas[1])
+    E = c.energies
+    groups = c.atom_groups()
+    # spin-diagonal 'u': (up, down) from two N-sized solves
+    up, down = calculate_local_transmission(F2, S2, sc, E, groups=groups, spin='u')
+    assert np.array_equal(up, calculate_local_transmission(Fa, S, sc, E, groups=groups))
+    assert np.array_equal(down, calculate_local_transmission(Fb, S, sc, E, groups=groups))
+    I, Is = calculate_current(F2, S2, sc, 0.1, 0.3, T=0, spin='u', dE=0.01)
+    bu, bd = calculate_bond_currents(F2, S2, sc, 0.1, 0.3, T=0, groups=groups, spin='u', dE=0.01)
+    for P in c.group_cuts(groups):
+        assert abs(bu[np.ix_(P, ~P)].sum() - Is[0]) <= 1e-8 * abs(Is[0])
+        assert abs(bd[np.ix_(P, ~P)].sum() - Is[3]) <= 1e-8 * abs(Is[3])
+    # spin mixing: the 2N system as a whole; groups of length 2N (an atom holds its up and its down orbitals)
+    F2m = F2.copy(); F2m[1, N + 2] = F2m[N + 2, 1] = 0.05; F2m[N - 6, 2 * N - 7] = F2m[2 * N - 7, N - 6] = -0.03
+    g2 = np.concatenate([groups, groups])
+    # (the cuts carry the full trace Tr[Gamma_L G Gamma_R G^H] of the 2N system.  The spin-block sum of
+    #  calculate_transmission pairs G_ud with (G^H)_ud, as the reference's kernel does, and is that trace only without
+    #  spin mixing: the yardstick here is numpy's trace)
+    sig2 = [np.kron(np.eye(2), s) for s in c.sigmas]
+    Tm = np.array([br.transmission(F2m, S2, sig2, e) for e in E])
+    tm = calculate_local_transmission(F2m, S2, sc, E, groups=g2, spin='u')
+    # 'g': the same physical system in spinor order [a0, b0, a1, b1, ...]
+    perm = np.concatenate([np.arange(0, 2 * N, 2), np.arange(1, 2 * N, 2)])       # spinor -> block
+    inv = np.argsort(perm)
+    Fg = F2m[np.ix_(inv, inv)]; Sg = S2[np.ix_(inv, inv)]
+    tg = calculate_local_transmission(Fg, Sg, sc, E, groups=np.repeat(groups, 2), spin='g')
+    og = calculate_local_transmission(Fg, Sg, sc, E, spin='g')            # per orbital pair, in the caller's order
+    for k in range(E.size):
+        for P in c.group_cuts(groups):
+            for tab, T in ((tm[k], Tm[k]), (tg[k], Tm[k])):
+                blockPQ = tab[np.ix_(P, ~P)]
+                assert abs(blockPQ.sum() - T) <= BAR * max(abs(T), np.abs(blockPQ).sum())
+        assert _rel(tg[k], tm[k]) <= 1e-10                                # 'u' and 'g' stage the same block-form system
+        assert _rel(br.group_table(og[k], np.repeat(groups, 2)), tg[k]) <= 1e-10
+
+
+# --------------------------------------------------------------------------- bitwise
+def test_bitwise_run_to_run_and_batch(engine):
+    c = br.const_cases()[2]
+    E = np.linspace(-2.0, 2.0, 75)                                        # 75 energies: chunks of 32 cut by batches of 7
+    w = np.cos(np.arange(E.size)) + 1.5
+    groups = c.atom_groups()
+    engine.set_system(c.F, c.S)
+    h = engine.sigma_const(c.sigmas)
+    try:
+        ref = [engine.local_transmission(h, 0, E), engine.local_transmission(h, 0, E, groups), engine.bond_int(h, 0, E, w)]
+        again = [engine.local_transmission(h, 0, E), engine.local_transmission(h, 0, E, groups), engine.bond_int(h, 0, E, w)]
+        for batch in (1, 7, 40):
+            engine.set_batch(batch)
+            try:
+                cut = [engine.local_transmission(h, 0, E), engine.local_transmission(h, 0, E, groups),
+                       engine.bond_int(h, 0, E, w)]
+            finally:
+                engine.set_batch(0)
+            for a, b in zip(ref, cut):
+                assert np.array_equal(a, b), batch
+    finally:
+        engine.sigma_free(h)
+    for a, b in zip(ref, again):
+        assert np.array_equal(a, b)
+
+
+# --------------------------------------------------------------------------- failure semantics
+@pytest.mark.parametrize("n", [8, 120])
+def test_singular_energy(engine, n):
+    """An exactly singular energy: its table is NaN, its neighbours are what they are without it, info is set."""
+    sL = np.zeros((n, n), complex); sL[0, 0] = -0.5j
+    sR = np.zeros((n, n), complex); sR[n - 1, n - 1] = -0.25j
+    S = np.eye(n, dtype=complex)
+    F = S - sL - sR                                                       # E S - F - Sigma = (E - 1) S: zero at E = 1
+    E = np.array([0.3, 1.0, 1.7])
+    groups = np.arange(n) // 2
+    engine.set_system(F, S)
+    h = engine.sigma_const([sL, sR])
+    try:
+        with pytest.warns(RuntimeWarning, match="singular"):
+            orb = engine.local_transmission(h, 0, E)
+        assert engine.last_info[1] > 0 and engine.last_info[0] == 0 and engine.last_info[2] == 0
+        with pytest.warns(RuntimeWarning, match="singular"):
+            grp = engine.local_transmission(h, 0, E, groups)
+        clean_orb = engine.local_transmission(h, 0, E[[0, 2]])
+        clean_grp = engine.local_transmission(h, 0, E[[0, 2]], groups)
+        with pytest.warns(RuntimeWarning, match="singular"):
+            engine.bond_int(h, 0, E, np.ones(3))
+        assert engine.last_info[1] > 0
+    finally:
+        engine.sigma_free(h)
+    assert np.all(np.isnan(orb[1])) and np.all(np.isnan(grp[1]))
+    assert np.array_equal(orb[[0, 2]], clean_orb) and np.array_equal(grp[[0, 2]], clean_grp)
+    assert np.all(np.isfinite(clean_orb))
+
+
+# --------------------------------------------------------------------------- neighbours keep their bits
+def test_neighbouring_entry_points_unchanged(engine):
+    """negf_gless_int and negf_transmission before and after the new calls in one process (the shared workspace is what
+    could leak), on a CONST and a CHAIN1D system."""
+    c = br.const_cases()[1]
+    Fc, Sc, g, ci = _chain_system(130, 20, 3, "fixed-point")
+    E = np.linspace(-1.5, 1.5, 41)
+    w = (np.cos(np.arange(E.size)) + 1.5) + 0.0j
+    for F, S, make, n in ((c.F, c.S, lambda: (engine.sigma_const(c.sigmas), True), c.n),
+                          (Fc, Sc, lambda: (g._negf_lower(engine), False), 130)):
+        engine.set_system(F, S)
+        h, free = make()
+        try:
+            before = (engine.transmission(h, 0, 1, E), engine.gless_int(h, 0, E, w), engine.gless_int(h, None, E, w))
+            engine.local_transmission(h, 0, E)
+            engine.local_transmission(h, 0, E, np.arange(n) // 5)
+            engine.bond_int(h, 0, E, np.real(w))
+            engine.set_batch(7)
+            try:
+                engine.bond_int(h, 1, E, np.real(w))
+                engine.local_transmission(h, 1, E, np.arange(n) % 3)
+            finally:
+                engine.set_batch(0)
+            after = (engine.transmission(h, 0, 1, E), engine.gless_int(h, 0, E, w), engine.gless_int(h, None, E, w))
+        finally:
+            if free:
+                engine.sigma_free(h)
+        for a, b in zip(before, after):
+            assert np.array_equal(a, b)
+
+
+# --------------------------------------------------------------------------- sharded = local
+def _free_port():
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
+
+
+def _front_ends():
+    from gaunegf_amd.transport import SigmaCalculator, calculate_bond_currents, calculate_local_transmission
+    c = br.const_cases()[1]
+    sc = SigmaCalculator(c.sigmas[0], c.sigmas[1])
+    groups = c.atom_groups()
+    return {"tables": calculate_local_transmission(c.F, c.S, sc, np.linspace(-1.0, 1.0, 13), groups=groups),
+            "currents": calculate_bond_currents(np.real(c.F), np.real(c.S), sc, 0.1, 0.3, T=300.0, groups=groups, dE=0.01)}
+
+
+def _worker(port, q):
+    import torch.distributed as dist
+    from gaunegf_amd import distributed as D
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    os.environ["LOCAL_RANK"] = "0"
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    try:
+        D.enable(single_rank_ok=True)
+        assert D.is_active()
+        q.put(_front_ends())
+    finally:
+        D.disable()
+        dist.destroy_process_group()
+
+
+def test_sharded_equals_local(engine):
+    """The sharded legs (all-gather of the tables, all-reduce of the n x n current sum) in a one-rank group."""
+    import queue
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_worker, args=(_free_port(), q))
+    p.start()
+    res = None
+    for _ in range(60):
+        try:
+            res = q.get(timeout=5)
+            break
+        except queue.Empty:
+            if p.exitcode not in (None, 0):
+                break
+    if res is None:
+        p.kill()
+        pytest.fail("the rank died (its traceback is on stderr)")
+    p.join(timeout=120)
+    assert p.exitcode == 0
+    ref = _front_ends()
+    assert np.array_equal(res["tables"], ref["tables"])
+    assert np.linalg.norm(res["currents"] - ref["currents"]) <= 1e-13 * np.linalg.norm(ref["currents"])
