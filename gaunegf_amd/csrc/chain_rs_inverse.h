@@ -41,6 +41,10 @@ constexpr int RS_NB = RS_PANEL;           // panel width of the small inverse: h
 #ifndef RS_UPD_3M
 #define RS_UPD_3M 1                   // trailing / look-ahead updates (K = 8): 1 = three real products per tile and k-step (3M: operand
 #endif                                //    sums and a 12-instruction recombination per tile), 0 = four (no vector work per tile at all)
+#ifndef RS_HALF_STRIPS
+#define RS_HALF_STRIPS 1              // panels of 8: an update that may write only 8 columns of a full column tile (look-ahead, the
+#endif                                //    other half of the panel's tile / of the next tile) runs as two 16 x 4 column strips on the
+                                      //    4x4x4 instruction (half the matrix-pipe time, half the C traffic); 0 = whole tile, store masked
 #ifndef RS_ABLATE
 #define RS_ABLATE 0                   // diagnostic builds only (wrong results; timing with force_iters): 1 = no panel factoring (the chain
 #endif                                //    wave's pivot steps), 2 = no trailing / look-ahead updates, 4 = no products, 8 = no mixing phase
@@ -354,6 +358,73 @@ __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof,
     }
 }
 
+// ---- half tiles.  With panels of 8 many updates may write only 8 columns [c0, c0 + 8) of a full column tile: the
+// look-ahead, the other half of the panel's own tile, the other half of the next tile.  Such a 16 x 8 block is two
+// column strips at base columns c0 and c0 + 4 (see the remainder tiles above): one P fragment, one Q fragment per strip
+// (every 4-column block of the B operand holds the strip's columns c0 + 4 s + (l&3)), 2 x NKS x 3 4x4x4 instructions
+// -- half the matrix-pipe time of the whole tile -- and TWO values per lane, elements
+// (ti*16 + 4 (fi>>2) + fk, c0 + 4 s + (fi&3)): half the C loads, seeds, recombinations and stores as well.
+constexpr bool rs_half_strips(int nks) { return RS_HALF_STRIPS && RS_NB == 8 && nks == RS_NB / 4; }
+
+template <int P, int NKS>
+__device__ __forceinline__ void rs_load_qh(const cplx* W, const int* pivrow, int c0, int p0, int pw, int fi, int fk,
+                                           cplx (&qh)[2][NKS])
+{
+    const int col = c0 + (fi & 3);
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+        const int k = ks * 4 + fk;
+        const cplx* q = W + pivrow[p0 + k] * P + col;        // k >= pw: some valid row, zeroed below
+        const cplx v0 = q[0], v1 = q[4];
+        const bool ok = k < pw;
+        qh[0][ks] = cmake(ok ? v0.x : 0.0, ok ? v0.y : 0.0);
+        qh[1][ks] = cmake(ok ? v1.x : 0.0, ok ? v1.y : 0.0);
+    }
+}
+
+// the two strips of one row tile: cv (+)= pa qh, cv = this lane's two C elements (seeds, then results)
+template <int P, int NKS>
+__device__ __forceinline__ void rs_half_mma(cplx (&cv)[2], const cplx (&pa)[NKS], const cplx (&qh)[2][NKS], const double (&qs)[2][NKS])
+{
+    constexpr bool M3 = RS_UPD_3M && P > 35;                 // 3M (mfma3s) in the 168-VGPR kernels
+    if (M3) {
+        double ua[2], ub[2] = {0.0, 0.0}, uc[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) { ua[s] = cv[s].x; uc[s] = cv[s].x + cv[s].y; }
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const double ps = pa[ks].x + pa[ks].y;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) mfma3s(ua[s], ub[s], uc[s], pa[ks].x, pa[ks].y, ps, qh[s][ks].x, qh[s][ks].y, qs[s][ks]);
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) cv[s] = cmake(ua[s] - ub[s], uc[s] - ua[s] - ub[s]);
+    } else {
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) zmfma4(cv[s].x, cv[s].y, pa[ks], qh[s][ks]);
+    }
+}
+
+// one half tile (row tile ti, columns [c0, c0 + 8) inside the matrix) with its own operand loads: the look-ahead
+template <int P, int NKS, bool FULLROWS /* all 16 rows of the tile lie inside the matrix */, bool MASK>
+__device__ __forceinline__ void rs_update_half(int n, cplx* W, const int* colof, int ti, int p0, int pw, int fi, int fk,
+                                               const cplx (&qh)[2][NKS], int c0)
+{
+    const int row = ti * 16 + 4 * (fi >> 2) + fk;
+    cplx* cptr = W + row * P + c0 + (fi & 3);
+    const cplx* pbase = W + (ti * 16 + fi) * P + p0 + fk;
+    const int cf = MASK ? colof[row] : -1;
+    cplx cv[2] = {cptr[0], cptr[4]}, pa[NKS];
+    double qs[2][NKS];
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) { pa[ks] = pbase[ks * 4]; qs[0][ks] = qh[0][ks].x + qh[0][ks].y; qs[1][ks] = qh[1][ks].x + qh[1][ks].y; }
+    if (MASK && cf >= p0 && cf < p0 + pw) { cv[0] = cmake(0.0, 0.0); cv[1] = cmake(0.0, 0.0); }   // a pivot row of the panel (both values: one row)
+    rs_half_mma<P, NKS>(cv, pa, qh, qs);
+    if (FULLROWS || row < n) { cptr[0] = cv[0]; cptr[4] = cv[1]; }
+}
+
 // column tile tj, all row tiles, by the wave that owns the column tile in this stage.  The Q fragment is read
 // into registers before the first store, so the owner needs no snapshot of the pivot rows; it then zeroes them, so
 // that every tile of the column is a pure accumulation.
@@ -364,6 +435,36 @@ __device__ __forceinline__ void rs_update_col(int n, cplx* W, const int* pivrow,
     constexpr int FT = TR >= 0 ? TR : T16;                   // full row tiles
     const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
     cplx qf[NKS];
+    if (rs_half_strips(NKS) && chi - clo == 8 && chi <= n && !(TR >= 0 && tj == TR)) {
+        // a half tile: two column strips per row tile (rs_half_mma), row tile ti+1 requested before tile ti is stored
+        cplx qh[2][NKS];
+        double qs[2][NKS];
+        if (TR >= 0) rs_load_qf<P, NKS, TR>(W, pivrow, tj, p0, pw, fi, fk, qf);       // the row strip's 16-column fragment
+        rs_load_qh<P, NKS>(W, pivrow, clo, p0, pw, fi, fk, qh);
+        rs_zero_pivot_rows<P, NKS, TR>(n, W, pivrow, tj, p0, pw, fi, fk, clo, chi);
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) { qs[0][ks] = qh[0][ks].x + qh[0][ks].y; qs[1][ks] = qh[1][ks].x + qh[1][ks].y; }
+        const int row = 4 * (fi >> 2) + fk;
+        cplx* cbase = W + row * P + clo + (fi & 3);          // C elements (ti*16 + row, clo + 4 s + (fi&3))
+        const cplx* pbase = W + fi * P + p0 + fk;
+        cplx cv[2][2], pa[2][NKS];
+        auto fetch = [&](int ti, int s) __attribute__((always_inline)) {
+            cv[s][0] = cbase[ti * 16 * P]; cv[s][1] = cbase[ti * 16 * P + 4];
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) pa[s][ks] = pbase[ti * 16 * P + ks * 4];
+        };
+        fetch(0, 0);
+#pragma unroll
+        for (int ti = 0; ti < FT; ++ti) {
+            const int s = ti & 1;
+            if (ti + 1 < FT) fetch(ti + 1, s ^ 1);
+            rs_half_mma<P, NKS>(cv[s], pa[s], qh, qs);
+            if (TR >= 0 || ti * 16 + row < n) { cbase[ti * 16 * P] = cv[s][0]; cbase[ti * 16 * P + 4] = cv[s][1]; }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (TR >= 0) rs_update_tile<P, NKS, TR, false>(n, W, colof, TR, tj, p0, pw, fi, fk, qf, clo, chi);    // the row strip
+        return;
+    }
     rs_load_qf<P, NKS, TR>(W, pivrow, tj, p0, pw, fi, fk, qf);
     rs_zero_pivot_rows<P, NKS, TR>(n, W, pivrow, tj, p0, pw, fi, fk, clo, chi);
     if (TR >= 0 && tj == TR) {                               // the column strip: every tile on the 4x4x4 instruction
@@ -442,8 +543,13 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
             // look-ahead: the columns of panel sgi+1 (a whole column tile, or one half of one), one row tile per wave
             // (T16 <= 4 = number of waves)
             const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
-            cplx qf[RS_NB / 4];
-            rs_load_qf<P, RS_NB / 4, TR>(W, pivrow, tl, p0, pw, fi, fk, qf);
+            // the next panel is half of a full column tile: this wave's row tile is a half tile, two column strips with a Q
+            // fragment each (the row strip keeps its own form: one 4x4x4 instruction per k-step covers 16 columns already)
+            const bool half = !RS_LA_FLAGS && rs_half_strips(RS_NB / 4) && n0 + RS_NB <= n && !(TR >= 0 && (tl == TR || wave == TR));
+            cplx qh[2][RS_NB / 4];
+            cplx (&qf)[RS_NB / 4] = qh[0];                      // (one or the other)
+            if (half) rs_load_qh<P, RS_NB / 4>(W, pivrow, n0, p0, pw, fi, fk, qh);
+            else rs_load_qf<P, RS_NB / 4, TR>(W, pivrow, tl, p0, pw, fi, fk, qf);
 #if RS_LA_FLAGS
             // No workgroup barrier in the look-ahead (there were two, seven times a sweep): two LDS counters instead.
             // la_cnt[0] counts the waves whose Q fragment -- the panel's pivot rows in the next panel's columns, rows that
@@ -458,7 +564,10 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
             if (wave == fw) rs_wait_count(&la_cnt[1], la_epoch);
 #else
             __syncthreads();
-            if (!(RS_ABLATE & 2) && wave < T16 && wave * 16 < n) rs_update_tile<P, RS_NB / 4, TR, true>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB);
+            if (!(RS_ABLATE & 2) && wave < T16 && wave * 16 < n) {
+                if (half) rs_update_half<P, RS_NB / 4, TR >= 0, true>(n, W, colof, wave, p0, pw, fi, fk, qh, n0);
+                else rs_update_tile<P, RS_NB / 4, TR, true>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB);
+            }
             __syncthreads();
 #endif
         }
