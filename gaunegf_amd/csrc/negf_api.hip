@@ -73,6 +73,22 @@ int dev_alloc(T** p, size_t count, bool may_drop_caches = true /* false: the all
 template <typename T>
 void dev_free(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
 
+// Grow-only device buffers (DevBuf): nothing happens while the buffer holds `need` elements; otherwise the context's
+// stream is drained first (queued work may still read the old buffer), the buffer freed and a new one allocated.
+template <typename T>
+int ensure_cap(negf_ctx* c, DevBuf<T>& b, size_t need)
+{
+    if (need <= b.cap) return NEGF_OK;
+    NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
+    dev_free(b.p); b.cap = 0;
+    int rc = dev_alloc(&b.p, need);
+    if (rc) return rc;
+    b.cap = need;
+    return NEGF_OK;
+}
+template <typename... B>
+void release_bufs(B&... b) { ((dev_free(b.p), b.cap = 0), ...); }
+
 template <typename T>
 int upload(negf_ctx* c, T* dst, const T* src, size_t count)
 {
@@ -99,16 +115,17 @@ void free_provider(SigmaProvider* p)
     dev_free(p->d_tau); dev_free(p->d_Stau);
     dev_free(p->d_atom_orbs); dev_free(p->d_nb_off); dev_free(p->d_nb_dirs);
     dev_free(p->d_H); dev_free(p->d_Slist); dev_free(p->d_Vlist); dev_free(p->d_xi);
-    dev_free(p->d_pre_tot); dev_free(p->d_pre_c); dev_free(p->d_order); dev_free(p->d_prevE); dev_free(p->d_prev_iters); dev_free(p->d_curE); dev_free(p->d_cur_iters);
+    dev_free(p->d_pre_tot); dev_free(p->d_pre_c); release_bufs(p->d_order); dev_free(p->d_prevE); dev_free(p->d_prev_iters); dev_free(p->d_curE); dev_free(p->d_cur_iters);
     delete p;
 }
 
-void free_workspace(negf_ctx* c)
+// the work areas sized by the batch, and the grow-only buffers that scale with it (all of the latter: all = true)
+void free_workspace(negf_ctx* c, bool all = false)
 {
-    dev_free(c->d_A); dev_free(c->d_T1); dev_free(c->d_T2); dev_free(c->d_blk);
-    dev_free(c->d_ipiv); dev_free(c->d_site); dev_free(c->d_scratch); dev_free(c->d_gsmall);
-    dev_free(c->d_small_part);
-    c->batch = 0; c->blk_cap = 0; c->scratch_cap = 0; c->gsmall_cap = 0; c->small_part_cap = 0;
+    dev_free(c->d_A); dev_free(c->d_T1); dev_free(c->d_T2); dev_free(c->d_ipiv); dev_free(c->d_site);
+    c->batch = 0;
+    release_bufs(c->d_blk, c->d_scratch, c->d_gsmall, c->d_small_part);
+    if (all) release_bufs(c->d_seg_out, c->d_ref_P, c->d_chan, c->d_chan_rank, c->d_chan_T, c->d_bond_map, c->d_bond_carry, c->d_bond_T);
 }
 
 void free_mbuffers(negf_ctx* c)
@@ -265,14 +282,7 @@ int ensure_workspace(negf_ctx* c, int m, int blk_stride, int min_batch = 1)
         if ((rc = dev_alloc(&c->d_site, (size_t)c->n * want))) return rc;
         c->batch = want;
     }
-    const int need_blk = blk_stride * c->batch;
-    if (need_blk > c->blk_cap) {
-        dev_free(c->d_blk);
-        int rc = dev_alloc(&c->d_blk, (size_t)need_blk);
-        if (rc) return rc;
-        c->blk_cap = need_blk;
-    }
-    return NEGF_OK;
+    return ensure_cap(c, c->d_blk, (size_t)blk_stride * c->batch);
 }
 
 // Wait for the context's stream at the end of a host-pointer call.  hipStreamSynchronize parks the thread and is woken
@@ -296,27 +306,21 @@ int wait_stream(negf_ctx* c)
     return NEGF_OK;
 }
 
-int ensure_blk(negf_ctx* c, size_t elems)
+void free_pinned(negf_ctx* c)
 {
-    if (elems <= (size_t)c->blk_cap) return NEGF_OK;
-    NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    dev_free(c->d_blk); c->blk_cap = 0;
-    int rc = dev_alloc(&c->d_blk, elems);
-    if (rc) return rc;
-    c->blk_cap = (int)elems;
-    return NEGF_OK;
-}
-
-int ensure_pinned(negf_ctx* c, size_t bytes)
-{
-    if (bytes <= c->h_pin_cap) return NEGF_OK;
-    NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));           // copies from / into the old buffer
     if (c->h_pin) { (void)hipHostFree(c->h_pin); c->h_pin = nullptr; c->h_pin_cap = 0; }
     if (c->gj_side.ok) {
         (void)hipEventDestroy(c->gj_side.fork);
         for (int g = 0; g < GjSideStreams::MAXG - 1; ++g) { (void)hipStreamDestroy(c->gj_side.s[g]); (void)hipEventDestroy(c->gj_side.join[g]); }
         c->gj_side.ok = false;
     }
+}
+
+int ensure_pinned(negf_ctx* c, size_t bytes)
+{
+    if (bytes <= c->h_pin_cap) return NEGF_OK;
+    NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));           // copies from / into the old buffer
+    free_pinned(c);
     const size_t cap = std::max(bytes + bytes / 2, (size_t)1 << 20);
     void* q = nullptr;
     if (hipHostMalloc(&q, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return NEGF_ENOMEM; }
@@ -420,148 +424,137 @@ int run_inverse(negf_ctx* c, int nb, int* info)
     return NEGF_OK;
 }
 
+// One chain launch through the g(E) cache.  launch(g, mode) issues the solver's kernel: mode 2 on a hit -- only
+// Sigma = t g t^H is formed from the entry's g, and the sweep counts and flags of the launch that filled the entry are
+// copied out --, mode 1 otherwise, storing the final iterates into the entry when there is one to fill (g = nullptr: none).
+template <typename Launch>
+int chain_cached_launch(negf_ctx* c, ChainGEntry* ent, bool hit, int jobs, int* iters, int* conv, Launch launch)
+{
+    const size_t ib = (size_t)jobs * sizeof(int);
+    if (hit) {
+        launch(ent->d_g, 2);
+        if (iters) NEGF_HIP_CHECK(hipMemcpyAsync(iters, ent->d_it, ib, hipMemcpyDeviceToDevice, c->stream));
+        if (conv) NEGF_HIP_CHECK(hipMemcpyAsync(conv, ent->d_cv, ib, hipMemcpyDeviceToDevice, c->stream));
+        return NEGF_OK;
+    }
+    if (ent && (!iters || !conv)) ent = nullptr;    // (an entry carries the counts and flags of its launch)
+    launch(ent ? ent->d_g : nullptr, 1);
+    if (ent) {
+        NEGF_HIP_CHECK(hipMemcpyAsync(ent->d_it, iters, ib, hipMemcpyDeviceToDevice, c->stream));
+        NEGF_HIP_CHECK(hipMemcpyAsync(ent->d_cv, conv, ib, hipMemcpyDeviceToDevice, c->stream));
+        NEGF_HIP_CHECK(hipGetLastError());                 // an entry whose launch failed never becomes a hit
+        ent->valid = true;
+    }
+    return NEGF_OK;
+}
+
+// The job order of a fixed-point chain launch, learned from the provider's previous evaluation.
+// Jobs run in the order of decreasing sweep counts: the counts are predicted from the previous evaluation of this
+// provider -- for each energy the count of the nearest energy evaluated then (Fermi searches and SCF cycles evaluate
+// the same or slightly moved grids over and over; the same grid gets exactly its learned order) -- and sorted on the
+// device, no host sync; the first evaluation runs in launch order.  What the order is for: a launch with FEWER jobs
+// than resident slots (the SCF-sized grids) is dispatched to the compute units in this order, so the long jobs are
+// spread over the chip instead of sharing a unit with their neighbours in energy (648 jobs: 42 against 48 ms); a
+// launch with MORE jobs runs them round robin (k_chain1d_rs.hip) and only takes the order as the initial content of
+// its queue.
+// record = false, before the launch: *order = the predicted order (nullptr: launch order), *trusted = false when the
+// prediction comes from fewer than half as many energies as the launch evaluates -- a guess: such a launch runs round robin.
+// record = true, after it: the chunk's energies and counts are appended to the record of the evaluation in progress.
+int chain_learn_order(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, const int* iters, int m0, bool record,
+                      const int** order = nullptr, bool* trusted = nullptr)
+{
+    const int jobs = nb * p->n_contacts;
+    if (!record) {
+        int rc = ensure_cap(c, p->d_order, (size_t)jobs);
+        if (rc) return rc;
+        if (m0 == 0 && p->cur_n > 0) {
+            // a new evaluation begins: the one recorded so far becomes the reference
+            std::swap(p->d_prevE, p->d_curE); std::swap(p->d_prev_iters, p->d_cur_iters);
+            std::swap(p->prev_cap, p->cur_cap);
+            p->prev_n = p->cur_n; p->cur_n = 0;
+        }
+        *trusted = 2 * (p->prev_n > 0 ? p->prev_n : p->cur_n) >= nb;
+        if (p->prev_n > 0) {
+            launch_chain1d_predict_order(c->stream, p->d_prevE, p->d_prev_iters, p->prev_n, p->n_contacts, E, nb, p->d_order);
+            *order = p->d_order;
+        } else if (p->cur_n > 0) {
+            // the first evaluation ever, arriving in chunks: the chunks so far are all there is to learn from
+            launch_chain1d_predict_order(c->stream, p->d_curE, p->d_cur_iters, p->cur_n, p->n_contacts, E, nb, p->d_order);
+            *order = p->d_order;
+        }
+        return NEGF_OK;
+    }
+    if (m0 != 0 && m0 != p->cur_n) return NEGF_OK;
+    if (m0 == 0) p->cur_n = 0;
+    if (m0 + nb > p->cur_cap) {
+        const int cap = std::max(m0 + nb, 2 * p->cur_cap);
+        cplx* nE = nullptr; int* nI = nullptr;
+        int rc;
+        if ((rc = dev_alloc(&nE, (size_t)cap)) || (rc = dev_alloc(&nI, (size_t)cap * p->n_contacts))) { dev_free(nE); return rc; }
+        if (p->cur_n > 0) {
+            NEGF_HIP_CHECK(hipMemcpyAsync(nE, p->d_curE, (size_t)p->cur_n * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
+            NEGF_HIP_CHECK(hipMemcpyAsync(nI, p->d_cur_iters, (size_t)p->cur_n * p->n_contacts * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+        }
+        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
+        dev_free(p->d_curE); dev_free(p->d_cur_iters);
+        p->d_curE = nE; p->d_cur_iters = nI; p->cur_cap = cap;
+    }
+    NEGF_HIP_CHECK(hipMemcpyAsync(p->d_curE + m0, E, (size_t)nb * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
+    NEGF_HIP_CHECK(hipMemcpyAsync(p->d_cur_iters + (size_t)m0 * p->n_contacts, iters, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+    p->cur_n = m0 + nb;
+    return NEGF_OK;
+}
+
 // Sigma blocks of a block provider for energies E[0..nb) -> c->d_blk
 // (m0 = position of this chunk in the grid being evaluated: the sweep-count prediction keeps whole evaluations)
 int run_sigma_blocks(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, int* iters, int* conv, int m0)
 {
-    if (p->kind == SK_CHAIN1D) {
-        static int force_v1 = -1;
-        if (force_v1 < 0) { const char* e = getenv("NEGF_CHAIN1D_ALGO"); force_v1 = (e && strcmp(e, "global") == 0) ? 1 : 0; }
-        const bool lds_path = chain1d_lds_supported(p->nc_max) && (!force_v1 || p->solver == 1);
-        // the g(E) cache (ChainGEntry): a launch whose lead and energies were evaluated before only forms Sigma = t g t^H
-        ChainGEntry* ent = nullptr;
-        bool hit = false;
-        struct Pin { negf_ctx* c; ~Pin() { c->gcache_pinned = false; } } pin{c};      // `ent` points into the cache until this block ends
-        c->gcache_pinned = true;
-        if (lds_path && c->gcache_max > 0) {
-            std::vector<cplx> tmp;
-            ent = gcache_lookup(c, p, host_energies(c, E, nb, tmp), nb, &hit);
-        }
-        ProfScope ps(c, p->solver == 1 ? (hit ? "chain1d_rd_hit" : "chain1d_rd") : (hit ? "chain1d_hit" : "chain1d"));
-        if (p->solver == 1) {
-            // renormalisation-decimation: one launch, no job order (units differ by at most a factor two in length)
-            const size_t need = chain1d_rd_scratch_elems(p->nc_max, p->n_contacts, nb);
-            if (need > c->scratch_cap) {
-                NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-                dev_free(c->d_scratch); c->scratch_cap = 0;
-                int rc = dev_alloc(&c->d_scratch, need);
-                if (rc) return rc;
-                c->scratch_cap = need;
-            }
-            const int jobs = nb * p->n_contacts;
-            if (hit) {
-                launch_chain1d_rd(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, ent->d_g, 2);
-                if (iters) NEGF_HIP_CHECK(hipMemcpyAsync(iters, ent->d_it, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                if (conv) NEGF_HIP_CHECK(hipMemcpyAsync(conv, ent->d_cv, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                return NEGF_OK;
-            }
-            if (ent && (!iters || !conv)) ent = nullptr;
-            launch_chain1d_rd(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, ent ? ent->d_g : nullptr, 1);
-            if (ent) {
-                NEGF_HIP_CHECK(hipMemcpyAsync(ent->d_it, iters, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                NEGF_HIP_CHECK(hipMemcpyAsync(ent->d_cv, conv, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                NEGF_HIP_CHECK(hipGetLastError());
-                ent->valid = true;
-            }
-            return NEGF_OK;
-        }
-        if (lds_path) {
-            const size_t need = chain1d_lds_scratch_elems(p->nc_max, p->n_contacts, nb, std::max(p->max_iter, p->force_iters), c->chain_rr_quantum);
-            if (need > c->scratch_cap) {
-                NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-                dev_free(c->d_scratch); c->scratch_cap = 0;
-                int rc = dev_alloc(&c->d_scratch, need);
-                if (rc) return rc;
-                c->scratch_cap = need;
-            }
-            const int jobs = nb * p->n_contacts;
-            if (hit) {
-                launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, nullptr, ent->d_g, 2);
-                if (iters) NEGF_HIP_CHECK(hipMemcpyAsync(iters, ent->d_it, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                if (conv) NEGF_HIP_CHECK(hipMemcpyAsync(conv, ent->d_cv, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                return NEGF_OK;
-            }
-            if (ent && (!iters || !conv)) ent = nullptr;    // (an entry carries the counts and flags of its launch)
-            // jobs in the order of decreasing sweep counts: the counts are predicted from the previous evaluation of
-            // this provider -- for each energy the count of the nearest energy evaluated then (Fermi searches and SCF
-            // cycles evaluate the same or slightly moved grids over and over; the same grid gets exactly its learned
-            // order) -- and sorted on the device, no host sync; the first evaluation runs in launch order.  What the
-            // order is for: a launch with FEWER jobs than resident slots (the SCF-sized grids) is dispatched to the
-            // compute units in this order, so the long jobs are spread over the chip instead of sharing a unit with
-            // their neighbours in energy (648 jobs: 42 against 48 ms); a launch with MORE jobs runs them round robin
-            // (k_chain1d_rs.hip) and only takes the order as the initial content of its queue.
-            const bool can_order = p->force_iters < 0 && iters && chain1d_order_supported(jobs);
-            const int* order = nullptr;
-            bool order_trusted = true;                      // a prediction from fewer than half as many energies as this
-            if (can_order) {                                //  launch evaluates is a guess: such a launch runs round robin
-                if (jobs > p->order_cap) {
-                    NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-                    dev_free(p->d_order); p->order_cap = 0;
-                    int rc = dev_alloc(&p->d_order, (size_t)jobs);
-                    if (rc) return rc;
-                    p->order_cap = jobs;
-                }
-                if (m0 == 0 && p->cur_n > 0) {
-                    // a new evaluation begins: the one recorded so far becomes the reference
-                    std::swap(p->d_prevE, p->d_curE); std::swap(p->d_prev_iters, p->d_cur_iters);
-                    std::swap(p->prev_cap, p->cur_cap);
-                    p->prev_n = p->cur_n; p->cur_n = 0;
-                }
-                order_trusted = 2 * (p->prev_n > 0 ? p->prev_n : p->cur_n) >= nb;
-                if (p->prev_n > 0) {
-                    launch_chain1d_predict_order(c->stream, p->d_prevE, p->d_prev_iters, p->prev_n, p->n_contacts, E, nb, p->d_order);
-                    order = p->d_order;
-                } else if (p->cur_n > 0) {
-                    // the first evaluation ever, arriving in chunks: the chunks so far are all there is to learn from
-                    launch_chain1d_predict_order(c->stream, p->d_curE, p->d_cur_iters, p->cur_n, p->n_contacts, E, nb, p->d_order);
-                    order = p->d_order;
-                }
-            }
-            launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, order,
-                               ent ? ent->d_g : nullptr, 1, c->chain_rr_quantum, c->chain_rr_slots, order_trusted);
-            if (ent) {
-                NEGF_HIP_CHECK(hipMemcpyAsync(ent->d_it, iters, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                NEGF_HIP_CHECK(hipMemcpyAsync(ent->d_cv, conv, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                NEGF_HIP_CHECK(hipGetLastError());                 // an entry whose launch failed never becomes a hit
-                ent->valid = true;
-            }
-            if (can_order && (m0 == 0 || m0 == p->cur_n)) {
-                // append this chunk's energies and counts to the record of the evaluation in progress
-                if (m0 == 0) p->cur_n = 0;
-                if (m0 + nb > p->cur_cap) {
-                    const int cap = std::max(m0 + nb, 2 * p->cur_cap);
-                    cplx* nE = nullptr; int* nI = nullptr;
-                    int rc;
-                    if ((rc = dev_alloc(&nE, (size_t)cap)) || (rc = dev_alloc(&nI, (size_t)cap * p->n_contacts))) { dev_free(nE); return rc; }
-                    if (p->cur_n > 0) {
-                        NEGF_HIP_CHECK(hipMemcpyAsync(nE, p->d_curE, (size_t)p->cur_n * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
-                        NEGF_HIP_CHECK(hipMemcpyAsync(nI, p->d_cur_iters, (size_t)p->cur_n * p->n_contacts * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                    }
-                    NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-                    dev_free(p->d_curE); dev_free(p->d_cur_iters);
-                    p->d_curE = nE; p->d_cur_iters = nI; p->cur_cap = cap;
-                }
-                NEGF_HIP_CHECK(hipMemcpyAsync(p->d_curE + m0, E, (size_t)nb * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
-                NEGF_HIP_CHECK(hipMemcpyAsync(p->d_cur_iters + (size_t)m0 * p->n_contacts, iters, (size_t)jobs * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                p->cur_n = m0 + nb;
-            }
-            return NEGF_OK;
-        }
-        const size_t per = chain1d_scratch_per_wg(p->nc_max);
-        const size_t need = per * p->n_contacts * nb;
-        if (need > c->scratch_cap) {
-            NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-            dev_free(c->d_scratch); c->scratch_cap = 0;
-            int rc = dev_alloc(&c->d_scratch, need);
-            if (rc) return rc;
-            c->scratch_cap = need;
-        }
-        launch_chain1d(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, per);
-    } else if (p->kind == SK_BETHE) {
+    if (p->kind == SK_BETHE) {
         ProfScope ps(c, "bethe");
         launch_bethe(c->stream, *p, nb, E, c->d_blk, iters, conv);
+        return NEGF_OK;
     }
-    return NEGF_OK;
+    if (p->kind != SK_CHAIN1D) return NEGF_OK;
+    static int force_v1 = -1;
+    if (force_v1 < 0) { const char* e = getenv("NEGF_CHAIN1D_ALGO"); force_v1 = (e && strcmp(e, "global") == 0) ? 1 : 0; }
+    const bool rd = p->solver == 1;       // renormalisation-decimation: one launch, no job order (units differ by at most a factor two in length)
+    const bool lds_path = chain1d_lds_supported(p->nc_max) && (!force_v1 || rd);
+    // the g(E) cache (ChainGEntry): a launch whose lead and energies were evaluated before only forms Sigma = t g t^H
+    ChainGEntry* ent = nullptr;
+    bool hit = false;
+    struct Pin { negf_ctx* c; ~Pin() { c->gcache_pinned = false; } } pin{c};      // `ent` points into the cache until this function ends
+    c->gcache_pinned = true;
+    if (lds_path && c->gcache_max > 0) {
+        std::vector<cplx> tmp;
+        ent = gcache_lookup(c, p, host_energies(c, E, nb, tmp), nb, &hit);
+    }
+    ProfScope ps(c, rd ? (hit ? "chain1d_rd_hit" : "chain1d_rd") : (hit ? "chain1d_hit" : "chain1d"));
+    const size_t per = rd || lds_path ? 0 : chain1d_scratch_per_wg(p->nc_max);
+    int rc = ensure_cap(c, c->d_scratch,
+                        rd ? chain1d_rd_scratch_elems(p->nc_max, p->n_contacts, nb)
+                        : lds_path ? chain1d_lds_scratch_elems(p->nc_max, p->n_contacts, nb, std::max(p->max_iter, p->force_iters), c->chain_rr_quantum)
+                                   : per * p->n_contacts * nb);
+    if (rc) return rc;
+    const int jobs = nb * p->n_contacts;
+    if (rd)
+        return chain_cached_launch(c, ent, hit, jobs, iters, conv, [&](cplx* g, int mode) {
+            launch_chain1d_rd(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, g, mode);
+        });
+    if (!lds_path) {
+        launch_chain1d(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, per);
+        return NEGF_OK;
+    }
+    const bool learn = !hit && p->force_iters < 0 && iters && chain1d_order_supported(jobs);
+    const int* order = nullptr;
+    bool order_trusted = true;
+    if (learn && (rc = chain_learn_order(c, p, nb, E, iters, m0, false, &order, &order_trusted))) return rc;
+    rc = chain_cached_launch(c, ent, hit, jobs, iters, conv, [&](cplx* g, int mode) {
+        if (mode == 2) launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, nullptr, g, 2);
+        else launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, order, g, 1,
+                                c->chain_rr_quantum, c->chain_rr_slots, order_trusted);
+    });
+    if (rc || !learn) return rc;
+    return chain_learn_order(c, p, nb, E, iters, m0, true);
 }
 
 // assemble A_b = E_b S - F - Sigma_b for batch [m0, m0+nb) into c->d_A
@@ -710,18 +703,11 @@ int run_gamma_small(negf_ctx* c, SigmaProvider* p, int contact, int nb, int slot
     for (int k = c0; k < c1; ++k) K += p->nc[k];
     int Kmax = 0;
     for (int k : p->nc) Kmax += k;
-    const size_t need = (size_t)2 * nb * Kmax * Kmax;
-    if (need > c->gsmall_cap) {
-        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-        dev_free(c->d_gsmall); c->gsmall_cap = 0;
-        int rc = dev_alloc(&c->d_gsmall, need);
-        if (rc) return rc;
-        c->gsmall_cap = need;
-    }
+    if (int rc = ensure_cap(c, c->d_gsmall, (size_t)2 * nb * Kmax * Kmax)) return rc;
     cplx* out = c->d_gsmall + (size_t)slot * nb * Kmax * Kmax;
     const bool constant = p->kind == SK_CONST;
     launch_gamma_small(c->stream, K, c0, c1, constant ? 1 : nb, p->d_nc, p->d_blk_off, p->d_inds_off,
-                       constant ? p->d_const_blk : c->d_blk, constant ? 0 : (size_t)p->blk_stride, out,
+                       constant ? p->d_const_blk : c->d_blk.p, constant ? 0 : (size_t)p->blk_stride, out,
                        (size_t)K * K);
     g->mat = out; g->stride = constant ? 0 : (size_t)K * K; g->idx = p->d_inds + p->inds_off[c0]; g->K = K;
     return NEGF_OK;
@@ -734,6 +720,60 @@ int check_ready(negf_ctx* c, SigmaProvider* p, int m)
     if (m < 0) return NEGF_EINVAL;
     if (p->kind == SK_PRECOMPUTED && m > p->m_pre) return NEGF_EINVAL;
     return NEGF_OK;
+}
+
+// What opens an entry point that evaluates a provider: the handle is resolved, check_ready decides between NEGF_ESTATE
+// and NEGF_EINVAL, the contact indices the entry point names (indA -> *ctA, indB -> *ctB; nullptr: none) are normalised
+// and invalid ones refused, and the context's device is selected.  The entry point's own argument checks follow.
+int open_call(negf_ctx* c, int handle, int m, SigmaProvider** p, int indA = 0, int* ctA = nullptr, int indB = 0, int* ctB = nullptr)
+{
+    *p = get_provider(c, handle);
+    int rc = check_ready(c, *p, m);
+    if (rc) return rc;
+    if (ctA && (*ctA = norm_contact(*p, indA)) == -2) return NEGF_EINVAL;
+    if (ctB && (*ctB = norm_contact(*p, indB)) == -2) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    return NEGF_OK;
+}
+
+// sweep counts and flags of a provider without a fixed point: none run, all converged
+void fill_trivial_iters(size_t cnt, int* iters, int* converged)
+{
+    for (size_t i = 0; i < cnt; ++i) { if (iters) iters[i] = 0; if (converged) converged[i] = 1; }
+}
+
+// NEGF_GATHER_FUSED=0: the weighted sums of G run the gather + accumulate sequence
+bool gather_fused()
+{
+    static int fused = -1;
+    if (fused < 0) { const char* e = getenv("NEGF_GATHER_FUSED"); fused = e ? atoi(e) : 1; }
+    return fused != 0;
+}
+
+// assemble + inverse for a weighted sum of G, which needs no G itself: the windowed inverse leaves its gather out and
+// the sum reads the reduced matrices through the pivot bookkeeping.  *perm: that is how the result was left (in c->W1,
+// with c->d_ipiv); otherwise it is in c->G as usual.
+int run_inverse_for_sum(negf_ctx* c, SigmaProvider* p, int m0, int nb, const cplx* E, bool* perm)
+{
+    c->defer_gather = gather_fused();
+    const int rc = run_assemble_inverse(c, p, m0, nb, E);
+    c->defer_gather = false;
+    *perm = c->G_deferred;
+    c->G_deferred = false;
+    return rc;
+}
+
+// the share of every segment (consecutive, ending at seg_end[s]) in the batch [m0, m0 + nb): energies [lo, hi) of the
+// batch, counted from its first one, belong to segment slot; empty shares are left out
+struct SegShares { std::vector<int> lo, hi, slot; };
+SegShares batch_shares(int nseg, const int* seg_end, int m0, int nb)
+{
+    SegShares sh;
+    for (int sg = 0, start = 0; sg < nseg; start = seg_end[sg], ++sg) {
+        const int lo = std::max(start, m0), hi = std::min(seg_end[sg], m0 + nb);
+        if (hi > lo) { sh.lo.push_back(lo - m0); sh.hi.push_back(hi - m0); sh.slot.push_back(sg); }
+    }
+    return sh;
 }
 
 int reduce_info(negf_ctx* c, int m, int* info_host)
@@ -801,18 +841,11 @@ void negf_destroy(negf_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (auto* p : c->providers) free_provider(p);
-    free_workspace(c); free_mbuffers(c); free_gcache(c);
-    if (c->h_pin) { (void)hipHostFree(c->h_pin); c->h_pin = nullptr; c->h_pin_cap = 0; }
-    if (c->gj_side.ok) {
-        (void)hipEventDestroy(c->gj_side.fork);
-        for (int g = 0; g < GjSideStreams::MAXG - 1; ++g) { (void)hipStreamDestroy(c->gj_side.s[g]); (void)hipEventDestroy(c->gj_side.join[g]); }
-        c->gj_side.ok = false;
-    }
+    free_workspace(c, true); free_mbuffers(c); free_gcache(c);
+    free_pinned(c);
     for (auto& sl : c->sys) { dev_free(sl.dF); dev_free(sl.dS); }
     c->d_F = c->d_S = nullptr;
-    dev_free(c->d_acc); dev_free(c->d_seg_out); dev_free(c->d_ref_P); dev_free(c->d_ref_meta);
-    dev_free(c->d_chan); dev_free(c->d_chan_rank); dev_free(c->d_chan_T);
-    dev_free(c->d_bond_map); dev_free(c->d_bond_carry); dev_free(c->d_bond_T);
+    dev_free(c->d_acc); dev_free(c->d_ref_meta);
     prof_resolve(c);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     delete c;
@@ -1284,11 +1317,10 @@ int negf_sigma_free(negf_ctx* c, int handle)
 int negf_gr_int_dev(negf_ctx* c, int handle, int m, const double* E_dev, const double* w_dev,
                     double* out_dev)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     const size_t n2 = (size_t)c->n * c->n;
     if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
     if (small_path(c, p) && m > 0) {
@@ -1301,14 +1333,8 @@ int negf_gr_int_dev(negf_ctx* c, int handle, int m, const double* E_dev, const d
         constexpr int SMALL_CHUNK = 16384;
         const bool blocks = p->kind == SK_CHAIN1D || p->kind == SK_BETHE;
         const int chunk = std::min(m, SMALL_CHUNK);
-        if (blocks && (rc = ensure_blk(c, (size_t)chunk * p->blk_stride))) return rc;
-        const size_t part_need = (size_t)small_fused_grid(c->n, chunk) * n2 + (m > chunk ? n2 : 0);
-        if (part_need > c->small_part_cap) {
-            NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-            dev_free(c->d_small_part); c->small_part_cap = 0;
-            if ((rc = dev_alloc(&c->d_small_part, part_need))) return rc;
-            c->small_part_cap = part_need;
-        }
+        if (blocks && (rc = ensure_cap(c, c->d_blk, (size_t)chunk * p->blk_stride))) return rc;
+        if ((rc = ensure_cap(c, c->d_small_part, (size_t)small_fused_grid(c->n, chunk) * n2 + (m > chunk ? n2 : 0)))) return rc;
         cplx* chunk_sum = c->d_small_part + (size_t)small_fused_grid(c->n, chunk) * n2;   // (only with several chunks)
         for (int m0 = 0; m0 < m; m0 += chunk) {
             const int nb = std::min(chunk, m - m0);
@@ -1332,18 +1358,11 @@ int negf_gr_int_dev(negf_ctx* c, int handle, int m, const double* E_dev, const d
     NEGF_HIP_CHECK(hipMemsetAsync(out, 0, n2 * sizeof(cplx), c->stream));
     for (int m0 = 0; m0 < m; m0 += c->batch) {
         const int nb = std::min(c->batch, m - m0);
-        // the weighted sum needs no G: the windowed inverse leaves its gather out and the sum reads the reduced matrices
-        // through the pivot bookkeeping (NEGF_GATHER_FUSED=0: the gather + accumulate sequence)
-        static int fused = -1;
-        if (fused < 0) { const char* e = getenv("NEGF_GATHER_FUSED"); fused = e ? atoi(e) : 1; }
-        c->defer_gather = fused != 0;
-        rc = run_assemble_inverse(c, p, m0, nb, E);
-        c->defer_gather = false;
-        if (rc) return rc;
+        bool perm;
+        if ((rc = run_inverse_for_sum(c, p, m0, nb, E, &perm))) return rc;
         ProfScope ps(c, "accumulate");
-        if (c->G_deferred) launch_accumulate_perm(c->stream, c->n, nb, w + m0, c->W1, c->d_ipiv, c->d_info + m0, out, c->W2);
+        if (perm) launch_accumulate_perm(c->stream, c->n, nb, w + m0, c->W1, c->d_ipiv, c->d_info + m0, out, c->W2);
         else launch_accumulate(c->stream, (int)n2, nb, w + m0, c->G, out, c->W2);
-        c->G_deferred = false;
     }
     c->last_m = m;
     NEGF_HIP_CHECK(hipGetLastError());
@@ -1407,10 +1426,9 @@ static int gless_core(negf_ctx* c, SigmaProvider* p, int contact, int m, const c
     auto accumulate = [&](const cplx* X, int m0, int nb) {
         ProfScope ps(c, "accumulate");
         if (nseg == 0) { launch_accumulate(c->stream, (int)n2, nb, w + m0, X, out, c->W2); return; }
-        for (int sg = 0, start = 0; sg < nseg; start = seg_end[sg], ++sg) {
-            const int lo = std::max(start, m0), hi = std::min(seg_end[sg], m0 + nb);
-            if (hi > lo) launch_accumulate(c->stream, (int)n2, hi - lo, w + lo, X + (size_t)(lo - m0) * n2, out + (size_t)sg * n2, c->W2);
-        }
+        const SegShares sh = batch_shares(nseg, seg_end, m0, nb);
+        for (size_t k = 0; k < sh.slot.size(); ++k)
+            launch_accumulate(c->stream, (int)n2, sh.hi[k] - sh.lo[k], w + m0 + sh.lo[k], X + (size_t)sh.lo[k] * n2, out + (size_t)sh.slot[k] * n2, c->W2);
     };
     for (int m0 = 0; m0 < m; m0 += c->batch) {
         const int nb = std::min(c->batch, m - m0);
@@ -1425,13 +1443,11 @@ static int gless_core(negf_ctx* c, SigmaProvider* p, int contact, int m, const c
 int negf_gless_int_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev,
                        const double* w_dev, double* out_dev)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int contact;
+    int rc = open_call(c, handle, m, &p, ind, &contact);
     if (rc) return rc;
     if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
-    const int contact = norm_contact(p, ind);
-    if (contact == -2) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     return gless_core(c, p, contact, m, reinterpret_cast<const cplx*>(E_dev), reinterpret_cast<const cplx*>(w_dev),
                       reinterpret_cast<cplx*>(out_dev), 0, nullptr);
 }
@@ -1439,15 +1455,13 @@ int negf_gless_int_dev(negf_ctx* c, int handle, int ind, int m, const double* E_
 int negf_transmission_dev(negf_ctx* c, int handle, int contact_L, int contact_R, int spin_mode,
                           int m, const double* E_dev, double* T_dev, double* Tspin_dev)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int cL, cR;
+    int rc = open_call(c, handle, m, &p, contact_L, &cL, contact_R, &cR);
     if (rc) return rc;
     if (!T_dev || (m > 0 && !E_dev)) return NEGF_EINVAL;
     if (spin_mode != NEGF_SPIN_RESTRICTED && spin_mode != NEGF_SPIN_BLOCK) return NEGF_EINVAL;
     if (spin_mode == NEGF_SPIN_BLOCK && (!Tspin_dev || (c->n & 1))) return NEGF_EINVAL;
-    const int cL = norm_contact(p, contact_L), cR = norm_contact(p, contact_R);
-    if (cL == -2 || cR == -2) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     const int n = c->n;
     const size_t n2 = (size_t)n * n;
     if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
@@ -1567,7 +1581,7 @@ int negf_last_iters(negf_ctx* c, int handle, int m, int* iters, int* converged)
         if (iters && (rc = download(c, iters, c->d_iters, cnt))) return rc;
         if (converged && (rc = download(c, converged, c->d_conv, cnt))) return rc;
     } else {
-        for (size_t i = 0; i < cnt; ++i) { if (iters) iters[i] = 0; if (converged) converged[i] = 1; }
+        fill_trivial_iters(cnt, iters, converged);
     }
     return NEGF_OK;
 }
@@ -1577,40 +1591,54 @@ int negf_last_iters(negf_ctx* c, int handle, int m, int* iters, int* converged)
 // copies and no synchronisation (the buffer is ours; the call's final synchronisation covers them), the result and the
 // per-energy info come down into [out | info] and are handed over after ONE synchronisation.  (Pageable copies with a
 // synchronisation each made a 2-point integral of a 60-orbital system cost 0.5 ms of host time: bench.py --config scf.)
-static int stage_grid(negf_ctx* c, int m, int contacts, const double* E, const double* w)
+// THE layout of that buffer for a grid of m energies: [E | w | result | extra | info] -- byte offsets of the parts and
+// the size of the whole.  `extra` is whatever else a call brings back behind its result (negf_gr_int_refine's level tables).
+struct PinLayout {
+    size_t E = 0, w, result, extra, info, bytes;
+    PinLayout(int m, size_t result_bytes, size_t extra_bytes = 0)
+    {
+        const size_t gb = (size_t)m * sizeof(cplx);
+        w = gb; result = 2 * gb; extra = result + result_bytes; info = extra + extra_bytes;
+        bytes = info + (size_t)m * sizeof(int) + 64;
+    }
+};
+
+// the grid goes up; the pinned buffer has room for a result of result_bytes (at least one n x n matrix) + extra_bytes
+static int stage_grid(negf_ctx* c, int m, int contacts, const double* E, const double* w, size_t result_bytes = 0,
+                      size_t extra_bytes = 0)
 {
     int rc = ensure_mbuffers(c, m, contacts);
     if (rc) return rc;
+    const PinLayout L(m, std::max(result_bytes, (size_t)c->n * c->n * sizeof(cplx)), extra_bytes);
     const size_t gb = (size_t)m * sizeof(cplx);
-    const size_t n2b = (size_t)c->n * c->n * sizeof(cplx);
-    if ((rc = ensure_pinned(c, 2 * gb + n2b + (size_t)m * sizeof(int) + 64))) return rc;
+    if ((rc = ensure_pinned(c, L.bytes))) return rc;
     if (E && m > 0) {
         c->h_E_valid = false;
-        std::memcpy(c->h_pin, E, gb);
-        NEGF_HIP_CHECK(hipMemcpyAsync(c->d_E, c->h_pin, gb, hipMemcpyHostToDevice, c->stream));
+        std::memcpy(c->h_pin + L.E, E, gb);
+        NEGF_HIP_CHECK(hipMemcpyAsync(c->d_E, c->h_pin + L.E, gb, hipMemcpyHostToDevice, c->stream));
         const cplx* Eh = reinterpret_cast<const cplx*>(E);
         c->h_E.assign(Eh, Eh + m);
         c->h_E_valid = true;
     }
     if (w && m > 0) {
-        std::memcpy(c->h_pin + gb, w, gb);
-        NEGF_HIP_CHECK(hipMemcpyAsync(c->d_w, c->h_pin + gb, gb, hipMemcpyHostToDevice, c->stream));
+        std::memcpy(c->h_pin + L.w, w, gb);
+        NEGF_HIP_CHECK(hipMemcpyAsync(c->d_w, c->h_pin + L.w, gb, hipMemcpyHostToDevice, c->stream));
     }
     return NEGF_OK;
 }
 
-// result (n x n, from d_src) and per-energy info back to the caller: two asynchronous copies into the pinned buffer,
+// result (`bytes` from d_src) and per-energy info back to the caller: two asynchronous copies into the pinned buffer,
 // one synchronisation; returns NEGF_ESINGULAR when an energy reported a zero pivot
-static int fetch_matrix_and_info(negf_ctx* c, int m, const cplx* d_src, double* out_host, int* info_host)
+static int fetch_result_and_info(negf_ctx* c, int m, const void* d_src, size_t bytes, void* out_host, int* info_host,
+                                 size_t extra_bytes = 0)
 {
-    const size_t gb = (size_t)m * sizeof(cplx);
-    const size_t n2b = (size_t)c->n * c->n * sizeof(cplx);
-    unsigned char* pout = c->h_pin + 2 * gb;
-    int* pinfo = reinterpret_cast<int*>(pout + n2b);
-    NEGF_HIP_CHECK(hipMemcpyAsync(pout, d_src, n2b, hipMemcpyDeviceToHost, c->stream));
-    if (m > 0) NEGF_HIP_CHECK(hipMemcpyAsync(pinfo, c->d_info, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    const PinLayout L(m, bytes, extra_bytes);
+    unsigned char* pout = c->h_pin + L.result;
+    const int* pinfo = reinterpret_cast<const int*>(c->h_pin + L.info);
+    NEGF_HIP_CHECK(hipMemcpyAsync(pout, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (m > 0) NEGF_HIP_CHECK(hipMemcpyAsync(c->h_pin + L.info, c->d_info, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     { const int wrc = wait_stream(c); if (wrc) return wrc; }
-    copy_bytes(out_host, pout, n2b);
+    copy_bytes(out_host, pout, bytes);
     int rc = NEGF_OK;
     for (int i = 0; i < m; ++i) { if (info_host) info_host[i] = pinfo[i]; if (pinfo[i] != 0) rc = NEGF_ESINGULAR; }
     return rc;
@@ -1619,15 +1647,14 @@ static int fetch_matrix_and_info(negf_ctx* c, int m, const cplx* d_src, double* 
 int negf_gr_int(negf_ctx* c, int handle, int m, const double* E, const double* w, double* out,
                 int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
     if ((rc = negf_gr_int_dev(c, handle, m, reinterpret_cast<double*>(c->d_E),
                               reinterpret_cast<double*>(c->d_w), reinterpret_cast<double*>(c->d_acc)))) return rc;
-    return fetch_matrix_and_info(c, m, c->d_acc, out, info);
+    return fetch_result_and_info(c, m, c->d_acc, (size_t)c->n * c->n * sizeof(cplx), out, info);
 }
 
 // Several integrals of the same system in ONE pass: the energies are nseg consecutive segments (seg_end[s] = index one
@@ -1650,13 +1677,8 @@ static int gr_seg_core(negf_ctx* c, SigmaProvider* p, int m, const cplx* Ed, con
     const size_t n2 = (size_t)c->n * c->n;
     if (m > 0 && small_path(c, p) && m <= 4096) {
         const bool blocks = p->kind == SK_CHAIN1D || p->kind == SK_BETHE;
-        if (blocks && (rc = ensure_blk(c, (size_t)m * p->blk_stride))) return rc;
-        if ((size_t)m * n2 > c->small_part_cap) {
-            NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-            dev_free(c->d_small_part); c->small_part_cap = 0;
-            if ((rc = dev_alloc(&c->d_small_part, (size_t)m * n2))) return rc;
-            c->small_part_cap = (size_t)m * n2;
-        }
+        if (blocks && (rc = ensure_cap(c, c->d_blk, (size_t)m * p->blk_stride))) return rc;
+        if ((rc = ensure_cap(c, c->d_small_part, (size_t)m * n2))) return rc;
         if (blocks && (rc = run_sigma_blocks(c, p, m, Ed, c->d_iters, c->d_conv, 0))) return rc;
         ProfScope ps(c, "small");
         SmallFusedArgs a = small_args(c, p, 0, m, Ed);
@@ -1666,37 +1688,24 @@ static int gr_seg_core(negf_ctx* c, SigmaProvider* p, int m, const cplx* Ed, con
     } else {
         if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
         NEGF_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)nseg * n2 * sizeof(cplx), c->stream));
-        static int fused = -1;
-        if (fused < 0) { const char* e = getenv("NEGF_GATHER_FUSED"); fused = e ? atoi(e) : 1; }
         for (int m0 = 0; m0 < m; m0 += c->batch) {
             const int nb = std::min(c->batch, m - m0);
-            // (as in negf_gr_int_dev: the sums read the windowed inverse through its pivot bookkeeping, no gather)
-            c->defer_gather = fused != 0;
-            rc = run_assemble_inverse(c, p, m0, nb, Ed);
-            c->defer_gather = false;
-            if (rc) return rc;
-            const bool perm = c->G_deferred;
-            c->G_deferred = false;
+            bool perm;
+            if ((rc = run_inverse_for_sum(c, p, m0, nb, Ed, &perm))) return rc;
             ProfScope ps(c, "accumulate");
-            {
-                // every segment's share of this batch in ONE launch pair (a joint arc + tail probe: 12 segments = 24 launches
-                // of a few microseconds each behind a millisecond of inverse)
-                std::vector<int> rlo, rhi, rslot;
-                for (int sg = 0, start = 0; sg < nseg; start = seg_end[sg], ++sg) {
-                    const int lo = std::max(start, m0), hi = std::min(seg_end[sg], m0 + nb);
-                    if (hi > lo) { rlo.push_back(lo - m0); rhi.push_back(hi - m0); rslot.push_back(sg); }
-                }
-                if (launch_accumulate_ranges(c->stream, c->n, perm, wd + m0, perm ? c->W1 : c->G, c->d_ipiv, c->d_info + m0,
-                                             (int)rlo.size(), rlo.data(), rhi.data(), rslot.data(), out, c->W2)) continue;
-            }
-            for (int sg = 0, start = 0; sg < nseg; start = seg_end[sg], ++sg) {
-                const int lo = std::max(start, m0), hi = std::min(seg_end[sg], m0 + nb);
-                if (hi <= lo) continue;
+            // every segment's share of this batch in ONE launch pair (a joint arc + tail probe: 12 segments = 24 launches
+            // of a few microseconds each behind a millisecond of inverse)
+            const SegShares sh = batch_shares(nseg, seg_end, m0, nb);
+            if (launch_accumulate_ranges(c->stream, c->n, perm, wd + m0, perm ? c->W1 : c->G, c->d_ipiv, c->d_info + m0,
+                                         (int)sh.slot.size(), sh.lo.data(), sh.hi.data(), sh.slot.data(), out, c->W2)) continue;
+            for (size_t k = 0; k < sh.slot.size(); ++k) {
+                const int lo = sh.lo[k], cnt = sh.hi[k] - lo;
+                cplx* dst = out + (size_t)sh.slot[k] * n2;
                 if (perm)
-                    launch_accumulate_perm(c->stream, c->n, hi - lo, wd + lo, c->W1 + (size_t)(lo - m0) * n2,
-                                           c->d_ipiv + (size_t)(lo - m0) * 2 * c->n, c->d_info + lo, out + (size_t)sg * n2, c->W2);
+                    launch_accumulate_perm(c->stream, c->n, cnt, wd + m0 + lo, c->W1 + (size_t)lo * n2,
+                                           c->d_ipiv + (size_t)lo * 2 * c->n, c->d_info + m0 + lo, dst, c->W2);
                 else
-                    launch_accumulate(c->stream, (int)n2, hi - lo, wd + lo, c->G + (size_t)(lo - m0) * n2, out + (size_t)sg * n2, c->W2);
+                    launch_accumulate(c->stream, (int)n2, cnt, wd + m0 + lo, c->G + (size_t)lo * n2, dst, c->W2);
             }
         }
     }
@@ -1708,11 +1717,10 @@ static int gr_seg_core(negf_ctx* c, SigmaProvider* p, int m, const cplx* Ed, con
 int negf_gr_int_seg_dev(negf_ctx* c, int handle, int m, const double* E_dev, const double* w_dev, int nseg,
                         const int* seg_end, double* out_dev)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (!out_dev || (m > 0 && (!E_dev || !w_dev)) || check_segments(m, nseg, seg_end)) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
     return gr_seg_core(c, p, m, reinterpret_cast<const cplx*>(E_dev), reinterpret_cast<const cplx*>(w_dev), nseg, seg_end,
                        reinterpret_cast<cplx*>(out_dev));
@@ -1721,32 +1729,16 @@ int negf_gr_int_seg_dev(negf_ctx* c, int handle, int m, const double* E_dev, con
 int negf_gr_int_seg(negf_ctx* c, int handle, int m, const double* E, const double* w, int nseg,
                     const int* seg_end, double* out, int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (!out || (m > 0 && (!E || !w)) || check_segments(m, nseg, seg_end)) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
-    const size_t n2 = (size_t)c->n * c->n;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
-    // results: [nseg][n*n] on the device, then one download
-    if ((size_t)nseg * n2 > c->seg_out_cap) {
-        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-        dev_free(c->d_seg_out); c->seg_out_cap = 0;
-        if ((rc = dev_alloc(&c->d_seg_out, (size_t)nseg * n2))) return rc;
-        c->seg_out_cap = (size_t)nseg * n2;
-    }
-    if ((rc = ensure_pinned(c, 2 * (size_t)m * sizeof(cplx) + nseg * n2 * sizeof(cplx) + (size_t)m * sizeof(int) + 64))) return rc;
+    // results: [nseg][n*n] on the device, then one download of all segment sums and the info, one synchronisation
+    const size_t cnt = (size_t)nseg * c->n * c->n;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, w, cnt * sizeof(cplx)))) return rc;
+    if ((rc = ensure_cap(c, c->d_seg_out, cnt))) return rc;
     if ((rc = gr_seg_core(c, p, m, c->d_E, c->d_w, nseg, seg_end, c->d_seg_out))) return rc;
-    // one download of all segment sums and the info, one synchronisation
-    unsigned char* pout = c->h_pin + 2 * (size_t)m * sizeof(cplx);
-    int* pinfo = reinterpret_cast<int*>(pout + nseg * n2 * sizeof(cplx));
-    NEGF_HIP_CHECK(hipMemcpyAsync(pout, c->d_seg_out, nseg * n2 * sizeof(cplx), hipMemcpyDeviceToHost, c->stream));
-    if (m > 0) NEGF_HIP_CHECK(hipMemcpyAsync(pinfo, c->d_info, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_stream(c))) return rc;
-    copy_bytes(out, pout, nseg * n2 * sizeof(cplx));
-    rc = NEGF_OK;
-    for (int i = 0; i < m; ++i) { if (info) info[i] = pinfo[i]; if (pinfo[i] != 0) rc = NEGF_ESINGULAR; }
-    return rc;
+    return fetch_result_and_info(c, m, c->d_seg_out, cnt * sizeof(cplx), out, info);
 }
 
 // Adaptive nested quadrature with the refinement ON THE DEVICE (integratePointsAdaptiveANT, density.py:211-273): the m energies
@@ -1761,8 +1753,8 @@ int negf_gr_int_refine(negf_ctx* c, int handle, int m, const double* E, const do
                        const int* seg_end, const double* ratio, double tol, const double* P_in, double* P_out,
                        int* level_out, double* maxdp_out, int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (!P_out || !level_out || !maxdp_out || !nlev || !ratio || nint <= 0 || nint > REF_MAX_INTS || (m > 0 && (!E || !w))) return NEGF_EINVAL;
     int nseg = 0;
@@ -1773,33 +1765,19 @@ int negf_gr_int_refine(negf_ctx* c, int handle, int m, const double* E, const do
         for (int s = first[k] + 1; s < first[k + 1]; ++s) if (ratio[s] != ratio[s]) return NEGF_EINVAL;      // only a first level starts an integration
         if (ratio[first[k]] == ratio[first[k]] && !P_in) return NEGF_EINVAL;                                  // a continued one needs its running value
     }
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     const size_t n2 = (size_t)c->n * c->n;
-    const size_t gb = (size_t)m * sizeof(cplx), pb = (size_t)nint * n2 * sizeof(cplx);
+    const size_t pb = (size_t)nint * n2 * sizeof(cplx);
     const size_t meta_b = (size_t)REF_MAX_LEVELS * 24 + (size_t)(2 * REF_MAX_INTS + 1 + REF_MAX_LEVELS) * 4;
-    if ((rc = ensure_pinned(c, 2 * gb + pb + meta_b + (size_t)m * sizeof(int) + 256))) return rc;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
-    if ((size_t)nseg * n2 > c->seg_out_cap) {
-        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-        dev_free(c->d_seg_out); c->seg_out_cap = 0;
-        if ((rc = dev_alloc(&c->d_seg_out, (size_t)nseg * n2))) return rc;
-        c->seg_out_cap = (size_t)nseg * n2;
-    }
-    if ((size_t)nint * n2 > c->ref_P_cap) {
-        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-        dev_free(c->d_ref_P); c->ref_P_cap = 0;
-        if ((rc = dev_alloc(&c->d_ref_P, (size_t)nint * n2))) return rc;
-        c->ref_P_cap = (size_t)nint * n2;
-    }
+    // pinned layout: the result is P (in, then out), the extra part ratio | maxdp | first | level
+    const PinLayout L(m, pb, meta_b);
+    if ((rc = stage_grid(c, m, p->n_contacts, E, w, pb, meta_b))) return rc;
+    if ((rc = ensure_cap(c, c->d_seg_out, (size_t)nseg * n2)) || (rc = ensure_cap(c, c->d_ref_P, (size_t)nint * n2))) return rc;
     if (!c->d_ref_meta && (rc = dev_alloc(&c->d_ref_meta, meta_b))) return rc;
-    // pinned layout: [E | w | P (in, then out) | ratio | maxdp | first | level | info]
-    unsigned char* pP = c->h_pin + 2 * gb;
-    unsigned char* pmeta = pP + pb;
-    double* h_ratio = reinterpret_cast<double*>(pmeta);
+    unsigned char* pP = c->h_pin + L.result;
+    double* h_ratio = reinterpret_cast<double*>(c->h_pin + L.extra);
     double* h_maxdp = h_ratio + REF_MAX_LEVELS;
     int* h_first = reinterpret_cast<int*>(h_maxdp + 2 * REF_MAX_LEVELS);          // (the host side mirrors the device layout)
     int* h_level = h_first + REF_MAX_INTS + 1;
-    int* pinfo = h_level + REF_MAX_INTS + REF_MAX_LEVELS;
     double* d_ratio = reinterpret_cast<double*>(c->d_ref_meta);
     double* d_maxdp = d_ratio + REF_MAX_LEVELS;
     unsigned long long* d_maxbits = reinterpret_cast<unsigned long long*>(d_maxdp + REF_MAX_LEVELS);
@@ -1840,16 +1818,12 @@ int negf_gr_int_refine(negf_ctx* c, int handle, int m, const double* E, const do
         }
     }
     NEGF_HIP_CHECK(hipGetLastError());
-    NEGF_HIP_CHECK(hipMemcpyAsync(pP, c->d_ref_P, pb, hipMemcpyDeviceToHost, c->stream));
     NEGF_HIP_CHECK(hipMemcpyAsync(h_maxdp, d_maxdp, (size_t)nseg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     NEGF_HIP_CHECK(hipMemcpyAsync(h_level, d_level, (size_t)nint * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (m > 0) NEGF_HIP_CHECK(hipMemcpyAsync(pinfo, c->d_info, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_stream(c))) return rc;
-    copy_bytes(P_out, pP, pb);
+    rc = fetch_result_and_info(c, m, c->d_ref_P, pb, P_out, info, meta_b);
+    if (rc < 0) return rc;
     std::memcpy(maxdp_out, h_maxdp, (size_t)nseg * sizeof(double));
     std::memcpy(level_out, h_level, (size_t)nint * sizeof(int));
-    rc = NEGF_OK;
-    for (int i = 0; i < m; ++i) { if (info) info[i] = pinfo[i]; if (pinfo[i] != 0) rc = NEGF_ESINGULAR; }
     return rc;
 }
 
@@ -1857,44 +1831,26 @@ int negf_gr_int_refine(negf_ctx* c, int handle, int m, const double* E, const do
 int negf_gless_int_seg(negf_ctx* c, int handle, int ind, int m, const double* E, const double* w, int nseg,
                        const int* seg_end, double* out, int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int contact;
+    int rc = open_call(c, handle, m, &p, ind, &contact);
     if (rc) return rc;
     if (!out || (m > 0 && (!E || !w)) || check_segments(m, nseg, seg_end)) return NEGF_EINVAL;
-    const int contact = norm_contact(p, ind);
-    if (contact == -2) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
-    const size_t n2 = (size_t)c->n * c->n;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
-    if ((size_t)nseg * n2 > c->seg_out_cap) {
-        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-        dev_free(c->d_seg_out); c->seg_out_cap = 0;
-        if ((rc = dev_alloc(&c->d_seg_out, (size_t)nseg * n2))) return rc;
-        c->seg_out_cap = (size_t)nseg * n2;
-    }
-    if ((rc = ensure_pinned(c, 2 * (size_t)m * sizeof(cplx) + nseg * n2 * sizeof(cplx) + (size_t)m * sizeof(int) + 64))) return rc;
+    const size_t cnt = (size_t)nseg * c->n * c->n;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, w, cnt * sizeof(cplx)))) return rc;
+    if ((rc = ensure_cap(c, c->d_seg_out, cnt))) return rc;
     if ((rc = gless_core(c, p, contact, m, c->d_E, c->d_w, c->d_seg_out, nseg, seg_end))) return rc;
-    unsigned char* pout = c->h_pin + 2 * (size_t)m * sizeof(cplx);
-    int* pinfo = reinterpret_cast<int*>(pout + nseg * n2 * sizeof(cplx));
-    NEGF_HIP_CHECK(hipMemcpyAsync(pout, c->d_seg_out, nseg * n2 * sizeof(cplx), hipMemcpyDeviceToHost, c->stream));
-    if (m > 0) NEGF_HIP_CHECK(hipMemcpyAsync(pinfo, c->d_info, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = wait_stream(c))) return rc;
-    copy_bytes(out, pout, nseg * n2 * sizeof(cplx));
-    rc = NEGF_OK;
-    for (int i = 0; i < m; ++i) { if (info) info[i] = pinfo[i]; if (pinfo[i] != 0) rc = NEGF_ESINGULAR; }
-    return rc;
+    return fetch_result_and_info(c, m, c->d_seg_out, cnt * sizeof(cplx), out, info);
 }
 
 int negf_gless_int_seg_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev, const double* w_dev, int nseg,
                            const int* seg_end, double* out_dev)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int contact;
+    int rc = open_call(c, handle, m, &p, ind, &contact);
     if (rc) return rc;
     if (!out_dev || (m > 0 && (!E_dev || !w_dev)) || check_segments(m, nseg, seg_end)) return NEGF_EINVAL;
-    const int contact = norm_contact(p, ind);
-    if (contact == -2) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     return gless_core(c, p, contact, m, reinterpret_cast<const cplx*>(E_dev), reinterpret_cast<const cplx*>(w_dev),
                       reinterpret_cast<cplx*>(out_dev), nseg, seg_end);
 }
@@ -1902,24 +1858,22 @@ int negf_gless_int_seg_dev(negf_ctx* c, int handle, int ind, int m, const double
 int negf_gless_int(negf_ctx* c, int handle, int ind, int m, const double* E, const double* w,
                    double* out, int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
     if ((rc = negf_gless_int_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E),
                                  reinterpret_cast<double*>(c->d_w), reinterpret_cast<double*>(c->d_acc)))) return rc;
-    return fetch_matrix_and_info(c, m, c->d_acc, out, info);
+    return fetch_result_and_info(c, m, c->d_acc, (size_t)c->n * c->n * sizeof(cplx), out, info);
 }
 
 int negf_gr_batch(negf_ctx* c, int handle, int m, const double* E, double* G_out, int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (m > 0 && (!E || !G_out)) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     const size_t n2 = (size_t)c->n * c->n;
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
@@ -1935,12 +1889,11 @@ int negf_gr_batch(negf_ctx* c, int handle, int m, const double* E, double* G_out
 int negf_transmission(negf_ctx* c, int handle, int contact_L, int contact_R, int spin_mode, int m,
                       const double* E, double* T, double* Tspin, int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (m > 0 && (!E || !T)) return NEGF_EINVAL;
     if (spin_mode == NEGF_SPIN_BLOCK && !Tspin) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     double* dT = c->d_scal;                 // [m]
     double* dTs = c->d_scal + c->m_cap;     // [m][4]
@@ -1961,11 +1914,10 @@ int negf_transmission(negf_ctx* c, int handle, int contact_L, int contact_R, int
 int negf_dos(negf_ctx* c, int handle, int m, const double* E, double* dos_total, double* dos_site,
              int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (m > 0 && (!E || !dos_total)) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
     for (int m0 = 0; m0 < m; m0 += c->batch) {
@@ -1982,13 +1934,11 @@ int negf_dos(negf_ctx* c, int handle, int m, const double* E, double* dos_total,
 int negf_sigma_eval(negf_ctx* c, int handle, int contact, int m, const double* E, double* sigma_out,
                     int* iters, int* converged)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int ct;
+    int rc = open_call(c, handle, m, &p, contact, &ct);
     if (rc) return rc;
     if (m > 0 && (!E || !sigma_out)) return NEGF_EINVAL;
-    const int ct = norm_contact(p, contact);
-    if (ct == -2) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     const size_t n2 = (size_t)c->n * c->n;
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
@@ -2033,8 +1983,7 @@ int negf_sigma_eval(negf_ctx* c, int handle, int contact, int m, const double* E
         if (iters && (rc = download(c, iters, c->d_iters, (size_t)m * p->n_contacts))) return rc;
         if (converged && (rc = download(c, converged, c->d_conv, (size_t)m * p->n_contacts))) return rc;
     } else {
-        if (iters) for (int i = 0; i < m * p->n_contacts; ++i) iters[i] = 0;
-        if (converged) for (int i = 0; i < m * p->n_contacts; ++i) converged[i] = 1;
+        fill_trivial_iters((size_t)m * p->n_contacts, iters, converged);
     }
     NEGF_HIP_CHECK(hipGetLastError());
     return NEGF_OK;
@@ -2113,13 +2062,12 @@ int negf_channel_count(negf_ctx* c, int handle, int contact_L, int contact_R, in
 int negf_transmission_channels_dev(negf_ctx* c, int handle, int contact_L, int contact_R, int m, const double* E_dev,
                                    int nchan, double* T_dev)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     ChanPlan pl;
     if ((rc = chan_plan(c, p, contact_L, contact_R, &pl))) return rc;
     if (nchan < 1 || !T_dev || (m > 0 && !E_dev)) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     const int n = c->n;
     const size_t n2 = (size_t)n * n;
     if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
@@ -2132,12 +2080,7 @@ int negf_transmission_channels_dev(negf_ctx* c, int handle, int contact_L, int c
     const size_t kk = (size_t)Ks * Ko, ks2 = (size_t)Ks * Ks, per = 3 * kk + ks2;
     const size_t need = per * batch + ks2 * (constant ? 1 : batch);
     const size_t need_r = constant ? 1 : (size_t)batch;      // pivoted Cholesky ranks
-    if (need > c->chan_cap || need_r > c->chan_rank_cap) {
-        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-        dev_free(c->d_chan); dev_free(c->d_chan_rank); c->chan_cap = 0; c->chan_rank_cap = 0;
-        if ((rc = dev_alloc(&c->d_chan, need)) || (rc = dev_alloc(&c->d_chan_rank, need_r))) return rc;
-        c->chan_cap = need; c->chan_rank_cap = need_r;
-    }
+    if ((rc = ensure_cap(c, c->d_chan, need)) || (rc = ensure_cap(c, c->d_chan_rank, need_r))) return rc;
     cplx* Glr = c->d_chan;
     cplx* Z = Glr + kk * batch;
     cplx* W = Z + kk * batch;
@@ -2183,22 +2126,16 @@ int negf_transmission_channels_dev(negf_ctx* c, int handle, int contact_L, int c
 int negf_transmission_channels(negf_ctx* c, int handle, int contact_L, int contact_R, int m, const double* E,
                                int nchan, double* T_chan, int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int rc = check_ready(c, p, m);
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (nchan < 1 || (m > 0 && (!E || !T_chan))) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     const size_t cnt = (size_t)m * nchan;
-    if (cnt > c->chan_T_cap) {
-        NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-        dev_free(c->d_chan_T); c->chan_T_cap = 0;
-        if ((rc = dev_alloc(&c->d_chan_T, cnt))) return rc;
-        c->chan_T_cap = cnt;
-    }
+    if ((rc = ensure_cap(c, c->d_chan_T, cnt))) return rc;
     if ((rc = negf_transmission_channels_dev(c, handle, contact_L, contact_R, m, reinterpret_cast<double*>(c->d_E), nchan,
                                              c->d_chan_T))) return rc;
-    if ((rc = download(c, T_chan, c->d_chan_T, cnt))) return rc;
+    if ((rc = download(c, T_chan, c->d_chan_T.p, cnt))) return rc;
     return reduce_info(c, m, info);
 }
 
@@ -2237,29 +2174,14 @@ int negf_eigvalsh_batched(negf_ctx* c, int K, int m, const double* A, double* w,
 // then one pass of k_bond.hip over A_c where GrLessInt runs launch_accumulate.  The reference has no such function.
 namespace {
 
-// a context-owned device buffer that only grows
-extern "C++" template <typename T>
-int ensure_cap(negf_ctx* c, T** p, size_t* cap, size_t need)
-{
-    if (need <= *cap) return NEGF_OK;
-    NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
-    dev_free(*p); *cap = 0;
-    int rc = dev_alloc(p, need);
-    if (rc) return rc;
-    *cap = need;
-    return NEGF_OK;
-}
-
 // providers served: all that negf_gless_int serves, except coupling matrices handed in by the caller (they need not
 // be Hermitian, and the kernels read A_ji as conj(A_ij))
-int bond_check(negf_ctx* c, SigmaProvider* p, int m, int ind, int* contact)
+int bond_open(negf_ctx* c, int handle, int m, int ind, SigmaProvider** p, int* contact)
 {
-    int rc = check_ready(c, p, m);
+    int rc = open_call(c, handle, m, p, ind, contact);
     if (rc) return rc;
-    if (p->kind == SK_PRECOMPUTED && p->pre_is_gamma) return NEGF_EINVAL;
-    if (c->n > bond_max_n()) return NEGF_EINVAL;
-    *contact = norm_contact(p, ind);
-    return *contact == -2 ? NEGF_EINVAL : NEGF_OK;
+    if ((*p)->kind == SK_PRECOMPUTED && (*p)->pre_is_gamma) return NEGF_EINVAL;
+    return c->n > bond_max_n() ? NEGF_EINVAL : NEGF_OK;
 }
 
 // The orbital -> group map sorted once per call: perm = the orbitals by group, ascending inside a group; goff = the
@@ -2283,9 +2205,9 @@ int bond_stage_groups(negf_ctx* c, int n_groups, const int* group_of, bool* iden
     for (int g = 0; g < n_groups; ++g) goff[g + 1] += goff[g];
     std::vector<int> next(goff, goff + n_groups);
     for (int i = 0; i < n; ++i) perm[next[group_of[i]]++] = i;
-    int rc = ensure_cap(c, &c->d_bond_map, &c->bond_map_cap, map.size());
+    int rc = ensure_cap(c, c->d_bond_map, map.size());
     if (rc) return rc;
-    return upload(c, c->d_bond_map, map.data(), map.size());
+    return upload(c, c->d_bond_map.p, map.data(), map.size());
 }
 
 }  // namespace
@@ -2293,12 +2215,11 @@ int bond_stage_groups(negf_ctx* c, int n_groups, const int* group_of, bool* iden
 int negf_local_transmission_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev, int n_groups,
                                 const int* group_of, double* out_dev)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int contact = -2;
-    int rc = bond_check(c, p, m, ind, &contact);
+    SigmaProvider* p;
+    int contact;
+    int rc = bond_open(c, handle, m, ind, &p, &contact);
     if (rc) return rc;
     if (m > 0 && (!E_dev || !out_dev)) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     bool identity = true;
     if ((rc = bond_stage_groups(c, n_groups, group_of, &identity))) return rc;
     const int n = c->n;
@@ -2323,33 +2244,31 @@ int negf_local_transmission_dev(negf_ctx* c, int handle, int ind, int m, const d
 int negf_local_transmission(negf_ctx* c, int handle, int ind, int m, const double* E, int n_groups, const int* group_of,
                             double* out, int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int contact = -2;
-    int rc = bond_check(c, p, m, ind, &contact);
+    SigmaProvider* p;
+    int contact;
+    int rc = bond_open(c, handle, m, ind, &p, &contact);
     if (rc) return rc;
     if (n_groups < 1 || (m > 0 && (!E || !out))) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     const size_t cnt = (size_t)m * n_groups * n_groups;
-    if ((rc = ensure_cap(c, &c->d_bond_T, &c->bond_T_cap, cnt))) return rc;
+    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
     if ((rc = negf_local_transmission_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), n_groups, group_of,
                                           c->d_bond_T))) return rc;
-    if ((rc = download(c, out, c->d_bond_T, cnt))) return rc;
+    if ((rc = download(c, out, c->d_bond_T.p, cnt))) return rc;
     return reduce_info(c, m, info);
 }
 
 int negf_bond_int_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev, const double* w_dev, double* out_dev)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int contact = -2;
-    int rc = bond_check(c, p, m, ind, &contact);
+    SigmaProvider* p;
+    int contact;
+    int rc = bond_open(c, handle, m, ind, &p, &contact);
     if (rc) return rc;
     if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     const size_t n2 = (size_t)c->n * c->n;
     if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
     if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
-    if ((rc = ensure_cap(c, &c->d_bond_carry, &c->bond_carry_cap, n2))) return rc;
+    if ((rc = ensure_cap(c, c->d_bond_carry, n2))) return rc;
     NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, n2 * sizeof(double), c->stream));
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
     for (int m0 = 0; m0 < m; m0 += c->batch) {
@@ -2367,32 +2286,23 @@ int negf_bond_int_dev(negf_ctx* c, int handle, int ind, int m, const double* E_d
 
 int negf_bond_int(negf_ctx* c, int handle, int ind, int m, const double* E, const double* w, double* out, int* info)
 {
-    SigmaProvider* p = get_provider(c, handle);
-    int contact = -2;
-    int rc = bond_check(c, p, m, ind, &contact);
+    SigmaProvider* p;
+    int contact;
+    int rc = bond_open(c, handle, m, ind, &p, &contact);
     if (rc) return rc;
     if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     // the real weights ride in the [w] part of the pinned buffer and of d_w (m doubles of their m complex values)
-    const size_t gb = (size_t)m * sizeof(cplx);
+    const size_t ob = (size_t)c->n * c->n * sizeof(double);
+    unsigned char* pw = c->h_pin + PinLayout(m, ob).w;
     double* dw = reinterpret_cast<double*>(c->d_w);
     if (m > 0) {
-        std::memcpy(c->h_pin + gb, w, (size_t)m * sizeof(double));
-        NEGF_HIP_CHECK(hipMemcpyAsync(dw, c->h_pin + gb, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        std::memcpy(pw, w, (size_t)m * sizeof(double));
+        NEGF_HIP_CHECK(hipMemcpyAsync(dw, pw, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     double* dout = reinterpret_cast<double*>(c->d_acc);          // n^2 doubles of its n^2 complex values
     if ((rc = negf_bond_int_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), dw, dout))) return rc;
-    const size_t ob = (size_t)c->n * c->n * sizeof(double);
-    unsigned char* pout = c->h_pin + 2 * gb;
-    int* pinfo = reinterpret_cast<int*>(pout + ob);
-    NEGF_HIP_CHECK(hipMemcpyAsync(pout, dout, ob, hipMemcpyDeviceToHost, c->stream));
-    if (m > 0) NEGF_HIP_CHECK(hipMemcpyAsync(pinfo, c->d_info, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    { const int wrc = wait_stream(c); if (wrc) return wrc; }
-    copy_bytes(out, pout, ob);
-    rc = NEGF_OK;
-    for (int i = 0; i < m; ++i) { if (info) info[i] = pinfo[i]; if (pinfo[i] != 0) rc = NEGF_ESINGULAR; }
-    return rc;
+    return fetch_result_and_info(c, m, dout, ob, out, info);
 }
 
 // ------------------------------------------------------------ g(E) cache knob
@@ -2442,7 +2352,7 @@ int negf_workspace_bytes(negf_ctx* c, long long* work, long long* blocks)
 {
     if (!c) return NEGF_EINVAL;
     if (work) *work = c->batch > 0 ? 3LL * ((long long)c->n * c->n * c->batch + 64) * (long long)sizeof(cplx) : 0;
-    if (blocks) *blocks = (long long)c->blk_cap * (long long)sizeof(cplx);
+    if (blocks) *blocks = (long long)c->d_blk.cap * (long long)sizeof(cplx);
     return NEGF_OK;
 }
 

@@ -63,6 +63,15 @@ __host__ __device__ __forceinline__ cplx crecip(cplx a) {
     } while (0)
 
 // ------------------------------------------------------------------- context
+// A device buffer of the context (or of a provider) that only grows: ensure_cap() / release_bufs() in negf_api.hip are
+// the one place where such a buffer is allocated and freed.  Reads as the pointer it holds.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;                // elements
+    operator T*() const { return p; }
+};
+
 enum SigmaKind { SK_CONST = 0, SK_CHAIN1D = 2, SK_BETHE = 3, SK_PRECOMPUTED = 4 };
 
 struct SigmaProvider {
@@ -97,8 +106,7 @@ struct SigmaProvider {
     // force_iters its force_steps, relFactor is unused (1)
     int solver = 0;
     // job order of the next chain launch (predicted on the device)
-    int* d_order = nullptr;
-    int order_cap = 0;
+    DevBuf<int> d_order;
     // energies and sweep counts of the previous evaluation: the order of a NEW grid is predicted from them.
     // An evaluation may arrive in several batch chunks (m0 = 0, nb, 2 nb ...): the chunks are appended to
     // cur*, and the chunk with m0 = 0 of the NEXT evaluation promotes cur* to prev*.
@@ -198,10 +206,8 @@ struct negf_ctx {
     cplx* G = nullptr;             // where the last inverse left its result (d_A or d_T1)
     cplx* W1 = nullptr;            // the other of (d_A, d_T1): free work area after the inverse
     cplx* W2 = nullptr;            // = d_T2
-    cplx* d_blk = nullptr;         // [batch][blk_stride] contact blocks of Sigma(E)
-    int blk_cap = 0;
-    cplx* d_scratch = nullptr;     // per-workgroup scratch of the Sigma kernels
-    size_t scratch_cap = 0;
+    DevBuf<cplx> d_blk;            // [batch][blk_stride] contact blocks of Sigma(E)
+    DevBuf<cplx> d_scratch;        // per-workgroup scratch of the Sigma kernels
     int* d_ipiv = nullptr;         // [batch][2][n] pivot bookkeeping of the large-matrix inverse
     int* d_info = nullptr;         // [m_cap]
     int* d_iters = nullptr;        // [m_cap][contacts]
@@ -226,31 +232,22 @@ struct negf_ctx {
     bool G_deferred = false;       // ... and the last run_inverse did leave its result un-gathered in W1 (with d_ipiv)
     int inverse_algo = 0;
     int gamma_algo = 0;            // 0: compact Gamma products when the provider allows, 1: always dense
-    cplx* d_gsmall = nullptr;      // small Gamma matrices of a batch (compact path)
-    size_t gsmall_cap = 0;
-    cplx* d_seg_out = nullptr;     // [segments][n*n] results of negf_gr_int_seg
-    size_t seg_out_cap = 0;
-    cplx* d_ref_P = nullptr;       // [integrals][n*n] running values of negf_gr_int_refine
-    size_t ref_P_cap = 0;
+    DevBuf<cplx> d_gsmall;         // small Gamma matrices of a batch (compact path)
+    DevBuf<cplx> d_seg_out;        // [segments][n*n] results of negf_gr_int_seg
+    DevBuf<cplx> d_ref_P;          // [integrals][n*n] running values of negf_gr_int_refine
     unsigned char* d_ref_meta = nullptr;   // its level table: ratio | maxdp | maxbits [REF_MAX_LEVELS each] | first[REF_MAX_INTS + 1] | level[REF_MAX_INTS] | nanflag[REF_MAX_LEVELS]
-    cplx* d_small_part = nullptr;  // per-workgroup partial sums of the small fused kernel
-    size_t small_part_cap = 0;
-    cplx* d_chan = nullptr;        // eigenchannel work area: G[I_L, I_R], the products and H per energy, and L^H (negf_transmission_channels)
-    size_t chan_cap = 0;
-    int* d_chan_rank = nullptr;    // rank of the pivoted Cholesky factor per energy
-    size_t chan_rank_cap = 0;
-    double* d_chan_T = nullptr;    // [m][nchan] staging of the host-pointer entry point
-    size_t chan_T_cap = 0;
-    int* d_bond_map = nullptr;     // local transmission: perm [n] | goff [ng + 1] of the call's orbital -> group map
-    size_t bond_map_cap = 0;
-    double* d_bond_carry = nullptr; // [n*n] running sum of the 32-energy chunk a batch boundary cuts (negf_bond_int)
-    size_t bond_carry_cap = 0;
-    double* d_bond_T = nullptr;    // [m][ng][ng] staging of the host-pointer entry point
-    size_t bond_T_cap = 0;
+    DevBuf<cplx> d_small_part;     // per-workgroup partial sums of the small fused kernel
+    DevBuf<cplx> d_chan;           // eigenchannel work area: G[I_L, I_R], the products and H per energy, and L^H (negf_transmission_channels)
+    DevBuf<int> d_chan_rank;       // rank of the pivoted Cholesky factor per energy
+    DevBuf<double> d_chan_T;       // [m][nchan] staging of the host-pointer entry point
+    DevBuf<int> d_bond_map;        // local transmission: perm [n] | goff [ng + 1] of the call's orbital -> group map
+    DevBuf<double> d_bond_carry;   // [n*n] running sum of the 32-energy chunk a batch boundary cuts (negf_bond_int)
+    DevBuf<double> d_bond_T;       // [m][ng][ng] staging of the host-pointer entry point
     GjSideStreams gj_side;
     int chain_rr_quantum = -1, chain_rr_slots = 0;   // negf_set_chain_round_robin
     int small_algo = 0;            // 0: n <= 96 takes the fused single-kernel path, 1: never (negf_set_small_algo)
     // pinned host staging of the host-pointer entry points: [E | w] up, [result | info] down, ONE synchronisation
+    // (the layout: PinLayout, negf_api.hip)
     unsigned char* h_pin = nullptr;
     size_t h_pin_cap = 0;
     int last_m = 0;
