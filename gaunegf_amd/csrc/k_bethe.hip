@@ -132,15 +132,19 @@ __device__ void wave_bgb(const double* __restrict__ S, const double* __restrict_
     __builtin_amdgcn_wave_barrier();
 }
 
+// max that keeps a NaN (fmax drops it): a sweep that produced NaNs must give diff = NaN, which ends the loop
+// and leaves the record flagged not converged, as numpy's max does in the reference.
+__device__ __forceinline__ double nanmax(double a, double b) { return (b > a || b != b) ? b : a; }
+
 __device__ double block_max(double v, double* red, int tid)
 {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+    for (int off = 32; off > 0; off >>= 1) v = nanmax(v, __shfl_down(v, off, 64));
     __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     double m = red[0];
-    for (int w = 1; w < BE_WAVES; ++w) m = fmax(m, red[w]);
+    for (int w = 1; w < BE_WAVES; ++w) m = nanmax(m, red[w]);
     return m;
 }
 
@@ -208,8 +212,8 @@ __global__ __launch_bounds__(BE_THREADS) void bethe_kernel(
         double num = 0.0, den = 0.0;
         for (int t = tid; t < 12 * D2; t += BE_THREADS) {
             const cplx s = sig[t], o = sold[t];
-            num = fmax(num, hypot(s.x - o.x, s.y - o.y));
-            den = fmax(den, hypot(o.x, o.y));
+            num = nanmax(num, hypot(s.x - o.x, s.y - o.y));
+            den = nanmax(den, hypot(o.x, o.y));
         }
         num = block_max(num, red, tid);
         den = block_max(den, red2, tid);
@@ -260,8 +264,8 @@ __global__ __launch_bounds__(BE_THREADS) void bethe_kernel(
         double num = 0.0, den = 0.0;
         for (int t = tid; t < 9 * D2; t += BE_THREADS) {
             const cplx s = sig[t], o = sold[t];
-            num = fmax(num, hypot(s.x - o.x, s.y - o.y));
-            den = fmax(den, hypot(o.x, o.y));
+            num = nanmax(num, hypot(s.x - o.x, s.y - o.y));
+            den = nanmax(den, hypot(o.x, o.y));
         }
         num = block_max(num, red, tid);
         den = block_max(den, red2, tid);
