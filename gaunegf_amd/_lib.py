@@ -68,6 +68,10 @@ SIGNATURES = {
     "negf_channel_count": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip]),
     "negf_transmission_channels": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
     "negf_transmission_channels_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    "negf_eigh_batched": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "negf_channel_states_count": (C.c_int, [_vp, C.c_int, C.c_int, _ip]),
+    "negf_channel_states": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "negf_channel_states_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
     "negf_local_transmission": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "negf_local_transmission_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
     "negf_bond_int": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),

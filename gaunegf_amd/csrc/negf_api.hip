@@ -125,7 +125,7 @@ void free_workspace(negf_ctx* c, bool all = false)
     dev_free(c->d_A); dev_free(c->d_T1); dev_free(c->d_T2); dev_free(c->d_ipiv); dev_free(c->d_site);
     c->batch = 0;
     release_bufs(c->d_blk, c->d_scratch, c->d_gsmall, c->d_small_part);
-    if (all) release_bufs(c->d_seg_out, c->d_ref_P, c->d_chan, c->d_chan_rank, c->d_chan_T, c->d_bond_map, c->d_bond_carry, c->d_bond_T);
+    if (all) release_bufs(c->d_seg_out, c->d_ref_P, c->d_chan, c->d_chan_rank, c->d_chan_T, c->d_chan_psi, c->d_bond_map, c->d_bond_carry, c->d_bond_T);
 }
 
 void free_mbuffers(negf_ctx* c)
@@ -2161,6 +2161,170 @@ int negf_eigvalsh_batched(negf_ctx* c, int K, int m, const double* A, double* w,
     if (!rc) rc = download(c, w, dw, (size_t)K * m);
     if (!rc) rc = download(c, hi.data(), di, (size_t)m);
     dev_free(dA); dev_free(dw); dev_free(di);
+    if (rc) return rc;
+    for (int i = 0; i < m; ++i) {
+        if (info) info[i] = hi[i];
+        if (hi[i] != 0) rc = NEGF_ESINGULAR;
+    }
+    return rc;
+}
+
+// ------------------------------------------------------- eigenchannel scattering states
+// psi_n = G[:, I_s] L u_n with Gamma_s = L L^H (pivoted Cholesky) and H u_n = T_n u_n, H = L^H G_ds^H Gamma_d G_ds L,
+// G_ds = G[I_d, I_s]: the eigenproblem always on the SOURCE contact (no division by sqrt(T_n): closed channels keep
+// well-defined states).  H is built as the mirror form of the channels above builds it; the eigenvector kernel starts
+// its accumulator from L, so it leaves C = L U, stored as C^H; conj(Psi) = C^H G[:, I_s]^H is one product, and the
+// gauge pass conjugates it back while it fixes the phases.
+namespace {
+
+struct StatePlan { int cs, cd, Ks, Kd; };
+
+int state_plan(negf_ctx* c, SigmaProvider* p, int contact_src, int contact_dst, bool need_dst, StatePlan* pl)
+{
+    if (!c || c->n <= 0) return NEGF_ESTATE;
+    if (!p) return NEGF_EINVAL;
+    const bool ok = (p->kind == SK_CONST && p->has_blocks) ||
+                    ((p->kind == SK_CHAIN1D || p->kind == SK_BETHE) && !p->d_xi);
+    if (!ok) return NEGF_EINVAL;
+    const int cs = norm_contact(p, contact_src), cd = need_dst ? norm_contact(p, contact_dst) : cs;
+    if (cs < 0 || cd < 0) return NEGF_EINVAL;                   // (the total self-energy is not a contact)
+    pl->cs = cs; pl->cd = cd; pl->Ks = p->nc[cs]; pl->Kd = p->nc[cd];
+    if (pl->Ks < 1 || pl->Kd < 1 || pl->Ks > channels_kmax()) return NEGF_EINVAL;   // (K_d is not limited)
+    return NEGF_OK;
+}
+
+}  // namespace
+
+int negf_channel_states_count(negf_ctx* c, int handle, int contact_src, int* count)
+{
+    if (!count) return NEGF_EINVAL;
+    StatePlan pl;
+    const int rc = state_plan(c, get_provider(c, handle), contact_src, 0, false, &pl);
+    if (rc) return rc;
+    *count = pl.Ks;
+    return NEGF_OK;
+}
+
+int negf_channel_states_dev(negf_ctx* c, int handle, int contact_src, int contact_dst, int m, const double* E_dev,
+                            int nchan, double* T_dev, double* psi_dev)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    StatePlan pl;
+    if ((rc = state_plan(c, p, contact_src, contact_dst, true, &pl))) return rc;
+    if (nchan < 1 || !T_dev || !psi_dev || (m > 0 && !E_dev)) return NEGF_EINVAL;
+    const int n = c->n;
+    const size_t n2 = (size_t)n * n;
+    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
+    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
+    const bool constant = p->kind == SK_CONST;
+    const int Ks = pl.Ks, Kd = pl.Kd, batch = c->batch;
+    const int nce = std::min(nchan, Ks);                     // channels computed; the columns beyond are zeros
+    // work area per energy: G_ds | Z | W (K_s K_d each) | H | C^H (K_s^2 each), then L^H (one for CONST, else one per
+    // energy) and the eigenvector kernel's scratch; G[:, I_s] and conj(Psi) (n K_s, nce n <= n^2) go to the free n x n
+    // work areas W2 and W1
+    const size_t kk = (size_t)Ks * Kd, ks2 = (size_t)Ks * Ks, per = 3 * kk + 2 * ks2, xg_per = eigh_scratch_elems(Ks);
+    const size_t need = per * batch + ks2 * (constant ? 1 : batch) + xg_per * batch;
+    if ((rc = ensure_cap(c, c->d_chan, need)) || (rc = ensure_cap(c, c->d_chan_rank, constant ? 1 : (size_t)batch))) return rc;
+    cplx* Gds = c->d_chan;
+    cplx* Z = Gds + kk * batch;
+    cplx* W = Z + kk * batch;
+    cplx* H = W + kk * batch;
+    cplx* Ch = H + ks2 * batch;
+    cplx* Lh = Ch + ks2 * batch;
+    cplx* xg = xg_per ? Lh + ks2 * (constant ? 1 : batch) : nullptr;
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    cplx* psi = reinterpret_cast<cplx*>(psi_dev);
+    for (int m0 = 0; m0 < m; m0 += batch) {
+        const int nb = std::min(batch, m - m0);
+        if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
+        GammaSmall gs, gd;
+        {
+            ProfScope ps(c, "gamma");
+            if ((rc = run_gamma_small(c, p, pl.cs, nb, 0, &gs))) return rc;
+            if ((rc = run_gamma_small(c, p, pl.cd, nb, 1, &gd))) return rc;
+        }
+        const size_t lstride = constant ? 0 : ks2;
+        if (!constant || m0 == 0) {
+            ProfScope ps(c, "eig");
+            if (!launch_pivoted_cholesky(c->stream, Ks, constant ? 1 : nb, gs.mat, gs.stride, Lh, ks2, c->d_chan_rank))
+                return NEGF_EINVAL;
+        }
+        {
+            ProfScope ps(c, "zgemm");
+            launch_gather_block(c->stream, n, Kd, Ks, nb, c->G, n2, gd.idx, gs.idx, Gds, kk);
+            // Z = L^H G_ds^H (G_ds stored K_d x K_s: opB = 1), W = Z Gamma_d, H = W Z^H
+            launch_zgemm(c->stream, Ks, Kd, Ks, nb, Lh, Ks, lstride, Gds, Ks, kk, 1, Z, Kd, kk);
+            launch_zgemm(c->stream, Ks, Kd, Kd, nb, Z, Kd, kk, gd.mat, Kd, gd.stride, 0, W, Kd, kk);
+            launch_zgemm(c->stream, Ks, Ks, Kd, nb, W, Kd, kk, Z, Kd, kk, 1, H, Ks, ks2);
+        }
+        {
+            ProfScope ps(c, "eig");
+            // X0 = L, read out of L^H; the sorted columns of C = L U leave as the rows of C^H (nce x K_s)
+            JacVec v{};
+            v.x0 = Lh; v.x0_stride = lstride; v.x0_ri = 1; v.x0_cj = Ks; v.x0_conj = 1;
+            v.xg = xg;
+            v.out = Ch; v.out_stride = ks2; v.out_ri = 1; v.out_cj = Ks; v.out_conj = 1; v.ncol = nce;
+            if (!launch_eigh_batched(c->stream, Ks, nb, H, Ks, ks2, c->d_chan_rank, constant ? 0 : 1, T_dev + (size_t)m0 * nchan,
+                                     nchan, nchan, true, c->d_info + m0, true, -1, v)) return NEGF_EINVAL;
+        }
+        ProfScope ps(c, "zgemm");
+        launch_gather_block(c->stream, n, n, Ks, nb, c->G, n2, nullptr, gs.idx, c->W2, n2);
+        // conj(Psi) = C^H G[:, I_s]^H (nce x n; G[:, I_s] stored n x K_s: opB = 1)
+        launch_zgemm(c->stream, nce, n, Ks, nb, Ch, Ks, ks2, c->W2, Ks, n2, 1, c->W1, n, n2);
+        launch_channel_gauge(c->stream, n, nce, nchan, nb, c->W1, n2, c->d_chan_rank, constant ? 0 : 1, c->d_info + m0,
+                             psi + (size_t)m0 * nchan * n);
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_channel_states(negf_ctx* c, int handle, int contact_src, int contact_dst, int m, const double* E, int nchan,
+                        double* T_chan, double* psi, int* info)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    if (nchan < 1 || (m > 0 && (!E || !T_chan || !psi))) return NEGF_EINVAL;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    const size_t cnt = (size_t)m * nchan, pcnt = cnt * c->n;
+    if ((rc = ensure_cap(c, c->d_chan_T, std::max<size_t>(cnt, 1))) || (rc = ensure_cap(c, c->d_chan_psi, std::max<size_t>(pcnt, 1)))) return rc;
+    if ((rc = negf_channel_states_dev(c, handle, contact_src, contact_dst, m, reinterpret_cast<double*>(c->d_E), nchan,
+                                      c->d_chan_T, reinterpret_cast<double*>(c->d_chan_psi.p)))) return rc;
+    if ((rc = download(c, T_chan, c->d_chan_T.p, cnt))) return rc;
+    if ((rc = download(c, reinterpret_cast<cplx*>(psi), c->d_chan_psi.p, pcnt))) return rc;
+    return reduce_info(c, m, info);
+}
+
+int negf_eigh_batched(negf_ctx* c, int K, int m, const double* A, double* w, double* V, int* info)
+{
+    if (!c) return NEGF_EINVAL;
+    if (K < 1 || K > channels_kmax() || m < 0 || (m > 0 && (!A || !w || !V))) return NEGF_EINVAL;
+    if (m == 0) return NEGF_OK;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    const size_t k2 = (size_t)K * K, xg_per = eigh_scratch_elems(K);
+    cplx *dA = nullptr, *dV = nullptr, *dx = nullptr; double* dw = nullptr; int* di = nullptr;
+    int rc;
+    if ((rc = dev_alloc(&dA, k2 * m)) || (rc = dev_alloc(&dV, k2 * m)) || (rc = dev_alloc(&dw, (size_t)K * m)) ||
+        (rc = dev_alloc(&di, (size_t)m)) || (xg_per && (rc = dev_alloc(&dx, xg_per * m)))) {
+        dev_free(dA); dev_free(dV); dev_free(dw); dev_free(di); return rc;
+    }
+    std::vector<int> hi((size_t)m);
+    rc = upload(c, dA, reinterpret_cast<const cplx*>(A), k2 * m);
+    if (!rc) {
+        ProfScope ps(c, "eig");
+        JacVec v{};
+        v.xg = dx;
+        v.out = dV; v.out_stride = k2; v.out_ri = K; v.out_cj = 1; v.ncol = K;      // eigenvector j in column j
+        if (!launch_eigh_batched(c->stream, K, m, dA, K, k2, nullptr, 0, dw, K, K, false, di, false, 1, v)) rc = NEGF_EINVAL;
+    }
+    if (!rc && hipGetLastError() != hipSuccess) rc = NEGF_EHIP;
+    if (!rc) rc = download(c, w, dw, (size_t)K * m);
+    if (!rc) rc = download(c, reinterpret_cast<cplx*>(V), dV, k2 * m);
+    if (!rc) rc = download(c, hi.data(), di, (size_t)m);
+    dev_free(dA); dev_free(dV); dev_free(dw); dev_free(di); dev_free(dx);
     if (rc) return rc;
     for (int i = 0; i < m; ++i) {
         if (info) info[i] = hi[i];

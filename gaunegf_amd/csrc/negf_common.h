@@ -240,6 +240,7 @@ struct negf_ctx {
     DevBuf<cplx> d_chan;           // eigenchannel work area: G[I_L, I_R], the products and H per energy, and L^H (negf_transmission_channels)
     DevBuf<int> d_chan_rank;       // rank of the pivoted Cholesky factor per energy
     DevBuf<double> d_chan_T;       // [m][nchan] staging of the host-pointer entry point
+    DevBuf<cplx> d_chan_psi;       // [m][nchan][n] staging of negf_channel_states
     DevBuf<int> d_bond_map;        // local transmission: perm [n] | goff [ng + 1] of the call's orbital -> group map
     DevBuf<double> d_bond_carry;   // [n*n] running sum of the 32-energy chunk a batch boundary cuts (negf_bond_int)
     DevBuf<double> d_bond_T;       // [m][ng][ng] staging of the host-pointer entry point
@@ -414,6 +415,28 @@ struct SmallFusedArgs {
 int channels_kmax();
 bool launch_eigvalsh_batched(hipStream_t st, int K, int nb, const cplx* A, int lda, size_t strideA, const int* rank,
                              int rank_stride, double* w, int ldw, int nout, bool descending, int* info, bool chk_in, int flag_sign);
+// The same solver with the rotations accumulated, X = X0 J_1 J_2 ... (K rows; the eigenvalues are bitwise those of
+// launch_eigvalsh_batched).  x0 (null: the identity, X = the eigenvectors): element (i, j) of X0, i < K, j < rank, at
+// x0[b * x0_stride + i * x0_ri + j * x0_cj], conjugated when x0_conj (L is read out of a stored L^H that way).
+// out: column `pos` of the sorted result (the position its eigenvalue is written at) goes to out[b * out_stride +
+// i * out_ri + pos * out_cj], conjugated when out_conj, for pos < ncol; columns rank <= pos < ncol are zeros, and a NaN
+// row of w comes with NaN in all ncol of them.  xg: nb * eigh_scratch_elems(K) values of scratch (none for the K
+// whose X fits in LDS).  rows, xg_stride: set by the launcher.
+struct JacVec {
+    const cplx* x0; size_t x0_stride; int x0_ri, x0_cj, x0_conj;
+    cplx* xg; size_t xg_stride;
+    cplx* out; size_t out_stride; int out_ri, out_cj, out_conj;
+    int rows, ncol;
+};
+size_t eigh_scratch_elems(int K);
+bool launch_eigh_batched(hipStream_t st, int K, int nb, const cplx* A, int lda, size_t strideA, const int* rank,
+                         int rank_stride, double* w, int ldw, int nout, bool descending, int* info, bool chk_in, int flag_sign,
+                         JacVec vec);
+// psi[b][c][0..n), c < nchan, from Pc[b * strideP + c * n + i] = conj(psi_c[i]) (c < nce): phase fixed so that the
+// component of largest modulus is real positive (lowest index on ties); zeros for c >= min(rank, nce), NaN where
+// info[b] is neither 0 nor -2
+void launch_channel_gauge(hipStream_t st, int n, int nce, int nchan, int nb, const cplx* Pc, size_t strideP, const int* rank,
+                          int rank_stride, const int* info, cplx* psi);
 // Pivoted Cholesky of the Hermitian PSD K x K matrices G[b]: Lh[b] = L^H (K x K, rows >= rank[b] zero), G ~ L L^H
 bool launch_pivoted_cholesky(hipStream_t st, int K, int nb, const cplx* G, size_t strideG, cplx* Lh, size_t strideL,
                              int* rank);

@@ -493,6 +493,83 @@ class Engine:
                                                        C.c_void_p(E_ptr), int(nchan), C.c_void_p(T_ptr)),
               "negf_transmission_channels_dev")
 
+    # ------------------------------------------ eigenchannel scattering states
+    def eigh(self, A):
+        """(w, V) of the Hermitian matrices A [m, K, K] (or one [K, K]), K <= 96, as numpy.linalg.eigh: w ascending and
+        bitwise equal to ``eigvalsh(A)`` (the same Jacobi rotations), V[..., :, j] the eigenvector of w[..., j]
+        (negf_eigh_batched).  A matrix whose input is not finite gives NaN in w and V; ``last_info`` as eigvalsh."""
+        A = np.asarray(A)
+        single = A.ndim == 2
+        A = _c128(A[None] if single else A)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise ValueError(f"eigh: expected [m, K, K] Hermitian matrices, got shape {A.shape}")
+        m, K = A.shape[0], A.shape[1]
+        if not 1 <= K <= self.EIG_KMAX:
+            raise ValueError(f"eigh: K = {K} outside 1 .. {self.EIG_KMAX} (the matrix is held in one compute unit's LDS)")
+        w = np.zeros((m, K), dtype=np.float64)
+        V = np.zeros((m, K, K), dtype=np.complex128)
+        info = np.zeros(max(m, 1), dtype=np.int32)
+        rc = check(self._lib.negf_eigh_batched(self._ctx, K, m, _ptr(A), _ptr(w), _ptr(V), _ptr(info)), "negf_eigh_batched")
+        self.last_info = info[:m]
+        if rc == _lib.NEGF_ESINGULAR:
+            bad = np.nonzero(info[:m])[0]
+            warnings.warn(f"eigh: non-finite input or no convergence for matrices {bad[:8].tolist()}"
+                          f"{'...' if bad.size > 8 else ''}", RuntimeWarning)
+        return (w[0], V[0]) if single else (w, V)
+
+    _STATES_REFUSED = ("eigenchannel scattering states need a self-energy provider whose couplings live on known contact "
+                       "orbital lists (constant Sigma with a nonzero support per contact, 1-D chain leads, Bethe leads "
+                       "without the Xi Sigma Xi transform) and a source contact of at most 96 orbitals; this provider / "
+                       "contact pair is not served")
+
+    def channel_states_count(self, handle, contact_src):
+        """K_s: the number of scattering states contact_src injects (negf_channel_states_count).  NotImplementedError
+        for providers whose couplings are not confined to an orbital list, and for K_s > 96."""
+        nc = C.c_int(0)
+        rc = self._lib.negf_channel_states_count(self._ctx, int(handle), int(contact_src), C.byref(nc))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._STATES_REFUSED)
+        check(rc, "negf_channel_states_count")
+        return nc.value
+
+    def channel_states(self, handle, contact_src, contact_dst, E, nchan=None):
+        """(T [m, nchan], psi [m, nchan, n]): the eigenchannels of the current injected by contact_src and collected by
+        contact_dst, T descending, and their scattering states psi_n = G[:, I_s] L u_n (negf_channel_states); nchan
+        defaults to channel_states_count().  Each state's largest component is real positive; columns beyond the rank
+        of Gamma_src are exact zeros; rows of singular energies are NaN (with a warning, as transmission_channels)."""
+        count = self.channel_states_count(handle, contact_src)
+        nchan = count if nchan is None else int(nchan)
+        if nchan < 1:
+            raise ValueError("nchan must be at least 1")
+        E, _ = self._grid(E)
+        T = np.zeros((E.size, nchan), dtype=np.float64)
+        psi = np.zeros((E.size, nchan, self.n), dtype=np.complex128)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lib.negf_channel_states(self._ctx, int(handle), int(contact_src), int(contact_dst), E.size, _ptr(E),
+                                           nchan, _ptr(T), _ptr(psi), _ptr(info))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._STATES_REFUSED)
+        check(rc, "negf_channel_states")
+        info = info[:E.size]
+        self._numerical(_lib.NEGF_ESINGULAR if np.any(info > 0) else 0, np.where(info > 0, info, 0), "channel_states")
+        self.last_info = info
+        bad = np.nonzero(info < 0)[0]
+        if bad.size:
+            what = {-1: "non-finite H", -2: "Jacobi not converged within its sweep limit"}
+            kinds = sorted({what.get(int(v), str(int(v))) for v in info[bad]})
+            warnings.warn(f"channel_states: eigensolver flags ({', '.join(kinds)}) at energy indices "
+                          f"{bad[:8].tolist()}{'...' if bad.size > 8 else ''}", RuntimeWarning)
+        return T, psi
+
+    def channel_states_dev(self, handle, contact_src, contact_dst, m, E_ptr, nchan, T_ptr, psi_ptr):
+        """negf_channel_states_dev: the grid, T [m, nchan] and psi [m, nchan, n] stay in HBM; asynchronous."""
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        rc = self._lib.negf_channel_states_dev(self._ctx, int(handle), int(contact_src), int(contact_dst), int(m),
+                                               C.c_void_p(E_ptr), int(nchan), C.c_void_p(T_ptr), C.c_void_p(psi_ptr))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._STATES_REFUSED)
+        check(rc, "negf_channel_states_dev")
+
     # ------------------------------------------- local (bond) transmission
     BOND_MAX_N = 8192
 

@@ -314,6 +314,55 @@ def _channel_count(F, S, sigma_calc, spin):
             eng.sigma_free(h)
 
 
+def _channel_states_run(F, S, sigma_calc, energies, spin, fn):
+    """What _channels_batch and _channel_count do around their engine call, for the scattering states: the same spin
+    and provider restrictions with the same messages; ``fn(engine, handle)`` on the lowered provider of an 'r' system,
+    a pair of such results for a spin-diagonal 'u' / 'ro' one."""
+    if spin not in ('r', 'u', 'ro', 'g'):
+        raise ValueError(f"Unknown spin configuration '{spin}'. Use 'r', 'u', 'ro', or 'g'")
+    F = np.asarray(F)
+    S = np.asarray(S)
+    size = F.shape[0]
+    if spin == 'g':
+        raise NotImplementedError("transmission eigenchannels: the spinor ('g') layout mixes spins inside each contact "
+                                  "block; channels are served for 'r' and for spin-diagonal 'u' / 'ro' systems only")
+    if spin in ('u', 'ro'):
+        blocks = _spin_diagonal_blocks(F, S) if _sigma_is_spin_expanded(sigma_calc, size) else None
+        if blocks is None:
+            raise NotImplementedError("transmission eigenchannels with spin 'u' / 'ro' need an exactly block-diagonal "
+                                      "(spin-diagonal) F, S and a spin-expanded N x N self-energy; spin mixing is not served")
+        return (_channel_states_run(blocks[0], blocks[1], sigma_calc, energies, 'r', fn),
+                _channel_states_run(blocks[2], blocks[3], sigma_calc, energies, 'r', fn))
+    eng = get_engine()
+    eng.set_system(F, S)
+    if sigma_calc.energy_dependent and not hasattr(sigma_calc.sig1, "_negf_lower"):
+        raise NotImplementedError("transmission eigenchannels need a provider the engine lowers itself (surfGTest, "
+                                  "surfG, surfGB or static matrices); this self-energy object is evaluated on the host")
+    h, temp = sigma_calc._lower(eng, energies, 'r', size)
+    try:
+        if temp:
+            raise NotImplementedError("transmission eigenchannels: this self-energy is staged per energy (no contact "
+                                      "orbital lists); use static matrices or a native surfG / surfGB / surfGTest object")
+        return fn(eng, h)
+    finally:
+        if temp:
+            eng.sigma_free(h)
+
+
+def _channel_states_batch(F, S, sigma_calc, energies, spin, nchan, source):
+    """(T [m, nchan], psi [m, nchan, N]) ('r') or ((T, psi) up, (T, psi) down) for all ``energies`` on the GPU."""
+    energies = np.asarray(energies)
+    dest = -1 if source == 0 else 0
+    return _channel_states_run(F, S, sigma_calc, energies, spin,
+                               lambda eng, h: eng.channel_states(h, source, dest, energies, nchan))
+
+
+def _channel_states_count(F, S, sigma_calc, spin, source):
+    """Number of states calculate_channel_states reports by default (K_s of the lowered provider's source contact)."""
+    res = _channel_states_run(F, S, sigma_calc, np.zeros(0), spin, lambda eng, h: eng.channel_states_count(h, source))
+    return res[0] if spin in ('u', 'ro') else res
+
+
 def _bond_layout(F, S, sigma_calc, spin):
     """How the local transmission of (F, S, spin) is evaluated: [(F, S, perm)] -- one system for 'r' (perm None), the two
     N x N spin blocks for a spin-diagonal 'u' / 'ro' system with a spin-expanded self-energy, and otherwise the whole
@@ -570,6 +619,51 @@ def calculate_transmission_channels(F, S, sigma_calculator, energy_list, spin=No
     return res[:, :nchan], res[:, nchan:]
 
 
+def calculate_channel_states(F, S, sigma_calculator, energy_list, source=0, spin=None, nchan=None):
+    """Eigenchannel scattering states: WHICH orbitals carry channel n.  With Gamma_s = L L^H the coupling of the source
+    contact (``source`` = 0 or -1; the destination d is the other end) on its orbitals I_s, T_n and u_n the eigenpairs of
+    H = L^H G[I_d, I_s]^H Gamma_d G[I_d, I_s] L, and psi_n = G[:, I_s] L u_n: the state the retarded G injects from the
+    source in channel n, normalised to unit incoming flux.  Returns (T [m, nchan], psi [m, nchan, N]) for spin 'r' and
+    ((T_up, psi_up), (T_down, psi_down)) for 'u' / 'ro' on a spin-diagonal system with a spin-expanded self-energy.
+    T is descending per energy and equals calculate_transmission_channels' nonzero values; psi_a^H Gamma_d psi_b =
+    T_a delta_ab; with all channels sum_n psi_n psi_n^H = G Gamma_s G^H, the source's spectral function.  Closed
+    channels have well-defined states (nothing is divided by sqrt(T_n)).  Each psi_n carries the phase that makes its
+    component of largest modulus real and positive (lowest index on ties); the states of a degenerate cluster of T_n
+    are an arbitrary orthogonal basis of that cluster.  Columns beyond the rank of Gamma_s are exact zeros, rows of
+    singular energies NaN.  ``nchan`` defaults to K_s, the source contact's orbital count (at most 96; K_d is not
+    limited).  Providers, 'g' and spin mixing as calculate_transmission_channels."""
+    energy_list = np.asarray(energy_list)
+    if spin is None:
+        spin = 'r'
+    if spin not in ('r', 'u', 'ro', 'g'):
+        raise ValueError(f"Unknown spin configuration '{spin}'. Use 'r', 'u', 'ro', or 'g'")
+    if source not in (0, -1):
+        raise ValueError("source must be 0 (the first contact) or -1 (the last one)")
+    if nchan is None:
+        nchan = _channel_states_count(F, S, sigma_calculator, spin, source)
+    nchan = int(nchan)
+    m = len(energy_list)
+    N = np.asarray(F).shape[0] // (2 if spin in ('u', 'ro') else 1)
+    row = nchan * (1 + 2 * N)                                # T | Re, Im of psi: one row of doubles per energy
+
+    def pack(T, psi):
+        return np.concatenate([T, np.ascontiguousarray(psi).view(np.float64).reshape(len(T), -1)], axis=1)
+
+    def unpack(rows):
+        rows = np.ascontiguousarray(rows)
+        return rows[:, :nchan].copy(), rows[:, nchan:].copy().view(np.complex128).reshape(len(rows), nchan, N)
+
+    if spin == 'r':
+        return unpack(_dist.sharded_map(
+            lambda idx: pack(*_channel_states_batch(F, S, sigma_calculator, energy_list[idx], spin, nchan, source)), m, (row,)))
+
+    def both(idx):
+        up, down = _channel_states_batch(F, S, sigma_calculator, energy_list[idx], spin, nchan, source)
+        return np.concatenate([pack(*up), pack(*down)], axis=1)
+    res = _dist.sharded_map(both, m, (2 * row,))
+    return unpack(res[:, :row]), unpack(res[:, row:])
+
+
 def calculate_local_transmission(F, S, sigma_calculator, energy_list, groups=None, contact=0, spin=None):
     """Local (bond) transmission: WHERE the transmission injected by ``contact`` flows.  Per energy, with K = E S - F
     (no self-energies) and A = G Gamma_c G^H, flow[i, j] = 2 Im[K_ij A_ji] is the transmission flowing from orbital i to
@@ -815,6 +909,17 @@ def cohTransChannels(Elist, F, S, sig1, sig2, nchan=None):
 def cohTransChannelsE(Elist, F, S, g, nchan=None):
     """Transmission eigenchannels [M, nchan] with an energy-dependent provider ``g`` (next to cohTransE)."""
     return calculate_transmission_channels(F, S, _dynamic_calc(g), Elist, spin='r', nchan=nchan)
+
+
+def cohTransChannelStates(Elist, F, S, sig1, sig2, nchan=None, source=0):
+    """(T [M, nchan], psi [M, nchan, N]): eigenchannels and their scattering states with energy-independent
+    self-energies (next to cohTransChannels); ``source`` = 0 injects from sig1's contact, -1 from sig2's."""
+    return calculate_channel_states(F, S, _static_calc(sig1, sig2), Elist, source=source, spin='r', nchan=nchan)
+
+
+def cohTransChannelStatesE(Elist, F, S, g, nchan=None, source=0):
+    """(T, psi) with an energy-dependent provider ``g`` (next to cohTransChannelsE)."""
+    return calculate_channel_states(F, S, _dynamic_calc(g), Elist, source=source, spin='r', nchan=nchan)
 
 
 def localTrans(Elist, F, S, sig1, sig2, groups=None):

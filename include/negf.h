@@ -308,6 +308,39 @@ int negf_transmission_channels(negf_ctx* ctx, int handle, int contact_L, int con
 int negf_transmission_channels_dev(negf_ctx* ctx, int handle, int contact_L, int contact_R, int m, const double* E_dev,
                                    int nchan, double* T_chan_dev);
 
+/* ------------------------------------------------------ eigenchannel scattering states
+ * Which orbitals carry channel n (Paulsson and Brandbyge's eigenchannels; the reference has no such function).  For a
+ * source contact s and a destination contact d with orbital lists I_s, I_d (K_s, K_d):
+ *   Gamma_s = L L^H by the pivoted Cholesky above (rank r <= K_s),
+ *   H = L^H G[I_d,I_s]^H Gamma_d G[I_d,I_s] L   (r x r, Hermitian PSD),   H u_n = T_n u_n, T_n descending,
+ *   psi_n = G[:, I_s] L u_n   (an n-vector): the state injected from contact s by the retarded G in channel n,
+ *   normalised to unit incoming flux.
+ * The eigenproblem always lives on the SOURCE contact: nothing is divided by sqrt(T_n), closed channels have
+ * well-defined states too.  To rounding: psi_a^H Gamma_d psi_b = T_a delta_ab (Gamma_d the n x n coupling of d);
+ * sum_n T_n = negf_transmission(contact_L = d, contact_R = s); the nonzero T_n are those of
+ * negf_transmission_channels(d, s); with all r channels sum_n psi_n psi_n^H = G Gamma_s G^H, the spectral function of
+ * contact s (what negf_gless_int integrates).  Gauge: each psi_n carries the unit phase that makes its component of
+ * largest |psi_i|^2 real and positive (lowest index on ties).  States inside a degenerate cluster of T_n are an
+ * arbitrary orthogonal basis of that cluster.  All sums have a fixed order: results do not depend on negf_set_batch.
+ * Providers as for negf_transmission_channels. */
+
+/* numpy.linalg.eigh for m Hermitian K x K matrices (K <= 96), read from their lower triangles: w [m][K] ascending --
+ * bitwise what negf_eigvalsh_batched returns, the same rotations --, V_c128 [m][K][K] with eigenvector j in column j
+ * (the accumulated rotations, orthonormal to rounding).  info as in negf_eigvalsh_batched; a non-finite input gives
+ * a NaN row of w and a NaN matrix V. */
+int negf_eigh_batched(negf_ctx* ctx, int K, int m, const double* A_c128, double* w, double* V_c128, int* info);
+/* K_s, the number of states contact_src injects; NEGF_EINVAL for providers the channels do not serve, for the total
+ * self-energy as a contact and for K_s > 96 (K_d is not limited) */
+int negf_channel_states_count(negf_ctx* ctx, int handle, int contact_src, int* count);
+/* T_chan [m][nchan] descending and psi_c128 [m][nchan][n], each state contiguous.  Columns at or beyond the rank, or
+ * at or beyond K_s, are exact zeros in both; a singular energy gives NaN rows in both and sets its info; info [m] or
+ * NULL as in negf_transmission_channels (-1 / -2: the eigensolver met a non-finite H / did not converge).  The _dev
+ * form keeps the grid and both results in HBM and is asynchronous. */
+int negf_channel_states(negf_ctx* ctx, int handle, int contact_src, int contact_dst, int m, const double* E_c128,
+                        int nchan, double* T_chan, double* psi_c128, int* info);
+int negf_channel_states_dev(negf_ctx* ctx, int handle, int contact_src, int contact_dst, int m, const double* E_dev,
+                            int nchan, double* T_chan_dev, double* psi_dev);
+
 /* ------------------------------------------------------ local (bond) transmission
  * Where in the junction the current injected by contact `ind` flows (the reference has no such function; it is the
  * orbital-resolved form of its transmission, transport.py:150-157, built on the products of GrLessInt,
