@@ -94,6 +94,9 @@ SIGNATURES = {
     "negf_set_small_algo": (C.c_int, [_vp, C.c_int]),
     "negf_set_chain_round_robin": (C.c_int, [_vp, C.c_int, C.c_int]),
     "negf_selftest_mfma": (C.c_int, [_vp, _dp]),
+    "negf_zgemm_batched": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_longlong,
+                                     _vp, C.c_int, C.c_longlong, C.c_int, _vp, C.c_int, C.c_longlong, C.c_int]),
+    "negf_zgemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _ip, C.c_int]),
 }
 
 _lib = None

@@ -8,7 +8,8 @@
 //   S1 += Ar*Br ; S2 += Ai*Bi ; S3 += (Ar+Ai)*(Br+Bi)   =>   Cr = S1 - S2 ,  Ci = S3 - S1 - S2
 // (one addition per operand fragment and k-step instead of a fourth matrix instruction; the FP64 matrix
 // instruction holds its SIMD's vector issue for most of its 64 cycles, so matrix-pipe time is the kernel's time;
-// the result differs from the four-product form by a few ulp of |A||B|, five orders inside the 1e-8 bar).
+// the result differs from the four-product form by a few ulp of |A||B|, five orders inside the 1e-8 bar; the imaginary
+// part is held per element to the 3M bound by tests/test_zgemm_accuracy_gpu.py).
 // Fragment layout of v_mfma_f64_16x16x4_f64 (guide section 3):
 //   A operand: lane l holds A[i = l&15][k = l>>4]       (one f64 per lane)
 //   B operand: lane l holds B[k = l>>4][j = l&15]
@@ -43,7 +44,7 @@ static constexpr int ZG_BPITCH = ZG_BN + 1;
 // T+1 blocks, pair gp = z * P + p (P = ceil(T/2) pairs per matrix) goes to XCD gp mod 8, and an XCD walks down a pair's
 // blocks in turn -- the B operand of a block column stays in that XCD's L2.  the batch size comes as a kernel argument (blockIdx.z is 0);
 // (x, y) of a full T x T grid with the lower blocks returning at once loaded the XCDs unevenly: slower than the full product.
-__device__ __forceinline__ bool zg_herm_decode(int T, int nb, int L, int* by, int* bx, int* b)
+__host__ __device__ __forceinline__ bool zg_herm_decode(int T, int nb, int L, int* by, int* bx, int* b)
 {
     if (T & 1) {
         // an odd number of block columns leaves the middle one without a partner (half a pair's work: XCDs 2 : 1 at
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(ZF_THREADS) void zgemm_flex_kernel(
         toffB[s] = fk * ZF_BPITCH + tj * 16 + fi;
     }
     // staging: A block rows x 16, B block 16 x cols; element e of a thread's share: index tid + e * 512
-    constexpr int NE = (ZF_ROWS * ZG_BK + ZF_THREADS - 1) / ZF_THREADS;          // 4 (3.5 rounded up)
+    constexpr int NE = (ZF_ROWS * ZG_BK + ZF_THREADS - 1) / ZF_THREADS;          // 3 (80 * 16 / 512 = 2.5 rounded up)
     cplx ra[NE], rb[NE];
     auto fetch = [&](int k0) __attribute__((always_inline)) {
 #pragma unroll
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(ZF_THREADS) void zgemm_flex_kernel(
                 const int r = idx >> 4, k = idx & 15, gi = row0 + r, gk = k0 + k;
                 ra[e] = (r < rows && gi < M && gk < K) ? A[(size_t)gi * lda + gk] : cmake(0.0, 0.0);
             }
-            if (opB == 0) {   // B[k][j]: k = idx / cols16, j = idx % cols16 with cols16 = 112
+            if (opB == 0) {   // B[k][j]: k = idx / ZF_ROWS, j = idx % ZF_ROWS (a K-tile row holds the block's widest 80 columns)
                 const int k = idx / ZF_ROWS, j = idx - k * ZF_ROWS, gk = k0 + k, gj = col0 + j;
                 rb[e] = (k < ZG_BK && j < cols && gk < K && gj < N) ? B[(size_t)gk * ldb + gj] : cmake(0.0, 0.0);
             } else {          // op(B)[k][j] = conj(B[j][k]); B stored N x K: j = idx / 16, k = idx % 16
@@ -361,9 +362,9 @@ __global__ __launch_bounds__(ZF_THREADS) void zgemm_flex_kernel(
     }
 }
 
-// Plain VALU version (no matrix cores): kept as the independent cross-check of
-// the MFMA fragment maps (tests compare the two) and selectable with
-// NEGF_ZGEMM_ALGO=valu for debugging.
+// Plain VALU version (no matrix cores, the four-product form): kept as the independent cross-check of
+// the MFMA fragment maps (tests/test_zgemm_accuracy_gpu.py compares the three kernels through
+// negf_zgemm_batched) and selectable with NEGF_ZGEMM_ALGO=valu for debugging.
 __global__ __launch_bounds__(256) void zgemm_valu_kernel(
     int M, int N, int K,
     const cplx* __restrict__ Aall, int lda, size_t strideA,
@@ -432,16 +433,45 @@ static int zgemm_algo()
     return algo;
 }
 
-void launch_zgemm(hipStream_t st, int M, int N, int K, int nb,
-                  const cplx* A, int lda, size_t strideA,
-                  const cplx* B, int ldb, size_t strideB, int opB,
-                  cplx* C, int ldc, size_t strideC)
+// The production rule: how much of the 64 x 64 blocks' area is padding beyond the 16-granular tiles?  Above 20 % the
+// flexible-block kernel (balanced blocks of <= 5 x 5 sub-tiles) is used.
+static int zg_route(int M, int N)
+{
+    const long tm16 = (M + 15) >> 4, tn16 = (N + 15) >> 4;
+    const long bm64 = (M + ZG_BM - 1) / ZG_BM, bn64 = (N + ZG_BN - 1) / ZG_BN;
+    return 10 * (bm64 * 4 * bn64 * 4) > 12 * (tm16 * tn16) ? ZGEMM_FLEX : ZGEMM_MFMA;
+}
+// the Hermitian form needs a square result, stored as it is
+static int zg_effective_opB(int M, int N, int opB, bool herm_on)
+{
+    if ((opB & 2) && (M != N || (opB & 4) || !herm_on)) opB &= ~2;
+    return opB;
+}
+// block counts (rows, columns) and the grid of `kernel` (not ZGEMM_AUTO) for the effective opB
+static void zg_geometry(int kernel, int M, int N, int nb, int opB, int* nbm, int* nbn, dim3* grid)
+{
+    if (kernel == ZGEMM_VALU) {
+        *nbm = (M + 31) / 32; *nbn = (N + 31) / 32;
+        *grid = dim3(*nbn, *nbm, nb);
+        return;
+    }
+    if (kernel == ZGEMM_FLEX) {
+        const long tm16 = (M + 15) >> 4, tn16 = (N + 15) >> 4;
+        *nbm = (int)((tm16 + ZF_MAXT - 1) / ZF_MAXT); *nbn = (int)((tn16 + ZF_MAXT - 1) / ZF_MAXT);
+    } else {
+        *nbm = (M + ZG_BM - 1) / ZG_BM; *nbn = (N + ZG_BN - 1) / ZG_BN;
+    }
+    *grid = dim3(*nbn, *nbm, nb);
+    if (opB & 2) *grid = dim3(zg_herm_grid(*nbn, nb), 1, 1);
+}
+
+void launch_zgemm_as(hipStream_t st, int kernel, bool herm_on, int M, int N, int K, int nb,
+                     const cplx* A, int lda, size_t strideA,
+                     const cplx* B, int ldb, size_t strideB, int opB,
+                     cplx* C, int ldc, size_t strideC)
 {
     if (M <= 0 || N <= 0 || nb <= 0) return;
-    if ((opB & 2) && (M != N || (opB & 4))) opB &= ~2;   // the Hermitian form needs a square result, stored as it is
-    static int herm_env = -1;                    // NEGF_ZGEMM_HERM=0: compute Hermitian products in full (A/B, tests)
-    if (herm_env < 0) { const char* e = getenv("NEGF_ZGEMM_HERM"); herm_env = e ? atoi(e) : 1; }
-    if (!herm_env) opB &= ~2;
+    opB = zg_effective_opB(M, N, opB, herm_on);
     {   // flop accounting (negf_common.h, FlopCount): 16 x 16 sub-tiles that hold part of the result, K padded to the
         // staged K-tile, three real products per sub-tile and k-step; a Hermitian product runs the sub-tiles of the
         // block tiles on and above the diagonal only
@@ -456,33 +486,62 @@ void launch_zgemm(hipStream_t st, int M, int N, int K, int nb,
         // 8 K flops each (N (N + 1) / 2 of the N^2: the mirrored half is a copy, not arithmetic) -- so that no fraction
         // derived from it can exceed the peak (round 4 charged 8 M N K and reported 1.30 "of peak" for C5's products)
         const double alg = (opB & 2) ? 8.0 * K * 0.5 * N * ((double)N + 1.0) * nb : 8.0 * M * (double)N * K * nb;
-        negf_count_flops(alg, zgemm_algo() == 1 ? 0.0 : 3.0 * 2.0 * 256.0 * kp * tiles * nb);
+        negf_count_flops(alg, kernel == ZGEMM_VALU ? 0.0 : 3.0 * 2.0 * 256.0 * kp * tiles * nb);
     }
-    if (zgemm_algo() == 1) {
-        dim3 grid((N + 31) / 32, (M + 31) / 32, nb);
+    if (kernel == ZGEMM_AUTO) kernel = zg_route(M, N);
+    int nbm, nbn;
+    dim3 grid;
+    zg_geometry(kernel, M, N, nb, opB, &nbm, &nbn, &grid);
+    if (kernel == ZGEMM_VALU) {
         hipLaunchKernelGGL(zgemm_valu_kernel, grid, dim3(256), 0, st, M, N, K, A, lda, strideA, B, ldb,
                            strideB, opB, C, ldc, strideC);
+    } else if (kernel == ZGEMM_FLEX) {
+        hipLaunchKernelGGL(zgemm_flex_kernel, grid, dim3(ZF_THREADS), 0, st, M, N, K, nbm, nbn, A, lda, strideA,
+                           B, ldb, strideB, opB, C, ldc, strideC, nb);
     } else {
-        // how much of the 64 x 64 blocks' area is padding beyond the 16-granular tiles?  Above 20 % the
-        // flexible-block kernel (balanced blocks of <= 7 x 7 sub-tiles) is used
-        const long tm16 = (M + 15) >> 4, tn16 = (N + 15) >> 4;
-        const long bm64 = (M + ZG_BM - 1) / ZG_BM, bn64 = (N + ZG_BN - 1) / ZG_BN;
-        static int flex_env = -1;
-        if (flex_env < 0) { const char* e = getenv("NEGF_ZGEMM_FLEX"); flex_env = e ? atoi(e) : 1; }
-        const bool padded = 10 * (bm64 * 4 * bn64 * 4) > 12 * (tm16 * tn16);
-        if (flex_env == 2 || (flex_env == 1 && padded)) {
-            const int nbm = (int)((tm16 + ZF_MAXT - 1) / ZF_MAXT), nbn = (int)((tn16 + ZF_MAXT - 1) / ZF_MAXT);
-            dim3 grid(nbn, nbm, nb);
-            if (opB & 2) grid = dim3(zg_herm_grid(nbn, nb), 1, 1);
-            hipLaunchKernelGGL(zgemm_flex_kernel, grid, dim3(ZF_THREADS), 0, st, M, N, K, nbm, nbn, A, lda, strideA,
-                               B, ldb, strideB, opB, C, ldc, strideC, nb);
-        } else {
-            dim3 grid((unsigned)bn64, (unsigned)bm64, nb);
-            if (opB & 2) grid = dim3(zg_herm_grid(bn64, nb), 1, 1);
-            hipLaunchKernelGGL(zgemm_mfma_kernel, grid, dim3(256), 0, st, M, N, K, A, lda, strideA, B, ldb,
-                               strideB, opB, C, ldc, strideC, nb);
+        hipLaunchKernelGGL(zgemm_mfma_kernel, grid, dim3(256), 0, st, M, N, K, A, lda, strideA, B, ldb,
+                           strideB, opB, C, ldc, strideC, nb);
+    }
+}
+
+// The production entry: the kernel by the padding rule and the Hermitian form on, unless the environment says otherwise
+// (read once per process: NEGF_ZGEMM_ALGO=valu, NEGF_ZGEMM_FLEX=0 / 2: never / always the flexible kernel,
+// NEGF_ZGEMM_HERM=0: compute Hermitian products in full -- A/B runs; tests choose through negf_zgemm_batched).
+void launch_zgemm(hipStream_t st, int M, int N, int K, int nb,
+                  const cplx* A, int lda, size_t strideA,
+                  const cplx* B, int ldb, size_t strideB, int opB,
+                  cplx* C, int ldc, size_t strideC)
+{
+    static int herm_env = -1, flex_env = -1;
+    if (herm_env < 0) { const char* e = getenv("NEGF_ZGEMM_HERM"); herm_env = e ? atoi(e) : 1; }
+    if (flex_env < 0) { const char* e = getenv("NEGF_ZGEMM_FLEX"); flex_env = e ? atoi(e) : 1; }
+    const int kernel = zgemm_algo() == 1 ? ZGEMM_VALU : flex_env == 2 ? ZGEMM_FLEX : flex_env == 1 ? ZGEMM_AUTO : ZGEMM_MFMA;
+    launch_zgemm_as(st, kernel, herm_env != 0, M, N, K, nb, A, lda, strideA, B, ldb, strideB, opB, C, ldc, strideC);
+}
+
+// What launch_zgemm_as(kernel, herm on) does with a shape, without a device: see negf_zgemm_plan (negf.h).
+int zgemm_plan(int M, int N, int K, int opB, int nb, int kernel, int* kernel_used, int* opB_eff, int* blocks, int* grid,
+               int* decode, int decode_cap)
+{
+    if (M < 1 || N < 1 || K < 0 || nb < 1 || opB < 0 || opB > 7 || kernel < ZGEMM_AUTO || kernel > ZGEMM_VALU) return NEGF_EINVAL;
+    opB = zg_effective_opB(M, N, opB, true);
+    if (kernel == ZGEMM_AUTO) kernel = zg_route(M, N);
+    int nbm, nbn;
+    dim3 g;
+    zg_geometry(kernel, M, N, nb, opB, &nbm, &nbn, &g);
+    if (kernel_used) *kernel_used = kernel;
+    if (opB_eff) *opB_eff = opB;
+    if (blocks) { blocks[0] = nbm; blocks[1] = nbn; }
+    if (grid) { grid[0] = (int)g.x; grid[1] = (int)g.y; grid[2] = (int)g.z; }
+    if (decode && (opB & 2) && kernel != ZGEMM_VALU) {
+        if (decode_cap < (int)g.x) return NEGF_EINVAL;
+        for (int L = 0; L < (int)g.x; ++L) {
+            int by = -1, bx = -1, b = -1;
+            if (!zg_herm_decode(nbn, nb, L, &by, &bx, &b)) by = bx = b = -1;
+            decode[3 * L] = by; decode[3 * L + 1] = bx; decode[3 * L + 2] = b;
         }
     }
+    return NEGF_OK;
 }
 
 // ------------------------------------------------------------------ self test

@@ -2333,6 +2333,45 @@ int negf_eigh_batched(negf_ctx* c, int K, int m, const double* A, double* w, dou
     return rc;
 }
 
+// ------------------------------------------------------- the product kernels, called directly (diagnostic)
+int negf_zgemm_plan(int M, int N, int K, int opB, int nb, int kernel, int* kernel_used, int* opB_eff, int* blocks,
+                    int* grid, int* decode, int decode_cap)
+{
+    return zgemm_plan(M, N, K, opB, nb, kernel, kernel_used, opB_eff, blocks, grid, decode, decode_cap);
+}
+
+int negf_zgemm_batched(negf_ctx* c, int M, int N, int K, int nb, const double* A, int lda, long long strideA,
+                       const double* B, int ldb, long long strideB, int opB, double* C, int ldc, long long strideC,
+                       int kernel)
+{
+    if (!c || M < 1 || N < 1 || K < 0 || nb < 1 || opB < 0 || opB > 7 || kernel < ZGEMM_AUTO || kernel > ZGEMM_VALU) return NEGF_EINVAL;
+    if (!A || !B || !C) return NEGF_EINVAL;
+    const bool bh = (opB & 1) != 0, ct = (opB & 4) != 0;
+    const long long b_rows = bh ? N : K, b_cols = bh ? K : N, c_rows = ct ? N : M, c_cols = ct ? M : N;
+    if (lda < std::max(K, 1) || ldb < std::max<long long>(b_cols, 1) || ldc < c_cols) return NEGF_EINVAL;
+    const long long ea = (long long)M * lda, eb = b_rows * ldb, ec = c_rows * ldc;
+    if ((strideA != 0 && strideA < ea) || (strideB != 0 && strideB < eb) || strideC < ec) return NEGF_EINVAL;
+    const long long na = strideA ? strideA * nb : ea, nbb = strideB ? strideB * nb : eb, nc = strideC * nb;
+    if (std::max(na, std::max(nbb, nc)) > (1LL << 31)) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    cplx *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    int rc;
+    if ((rc = dev_alloc(&dA, (size_t)na)) || (rc = dev_alloc(&dB, (size_t)nbb)) || (rc = dev_alloc(&dC, (size_t)nc))) {
+        dev_free(dA); dev_free(dB); return rc;
+    }
+    if (!(rc = upload(c, dA, reinterpret_cast<const cplx*>(A), (size_t)na)) &&
+        !(rc = upload(c, dB, reinterpret_cast<const cplx*>(B), (size_t)nbb)) &&
+        !(rc = upload(c, dC, reinterpret_cast<const cplx*>(C), (size_t)nc))) {
+        ProfScope ps(c, "zgemm");
+        launch_zgemm_as(c->stream, kernel, true, M, N, K, nb, dA, lda, (size_t)strideA, dB, ldb, (size_t)strideB, opB,
+                        dC, ldc, (size_t)strideC);
+    }
+    if (!rc && hipGetLastError() != hipSuccess) rc = NEGF_EHIP;
+    if (!rc) rc = download(c, reinterpret_cast<cplx*>(C), dC, (size_t)nc);
+    dev_free(dA); dev_free(dB); dev_free(dC);
+    return rc;
+}
+
 // ------------------------------------------------------- local (bond) transmission
 // flow[i][j](E) = 2 Im[(E S - F)_ij A_c,ji],  A_c = G Gamma_c G^H: the GrLessInt sequence up to A_c (run_gless_products),
 // then one pass of k_bond.hip over A_c where GrLessInt runs launch_accumulate.  The reference has no such function.

@@ -324,6 +324,15 @@ void launch_zgemm(hipStream_t st, int M, int N, int K, int nb,
                   const cplx* A, int lda, size_t strideA,
                   const cplx* B, int ldb, size_t strideB, int opB,
                   cplx* C, int ldc, size_t strideC);
+// the same with the kernel and the Hermitian switch chosen by the caller instead of the rule and the environment
+// (negf_zgemm_batched); zgemm_plan: what such a launch does with a shape, computed on the host (negf_zgemm_plan)
+enum { ZGEMM_AUTO = 0, ZGEMM_MFMA = 1, ZGEMM_FLEX = 2, ZGEMM_VALU = 3 };
+void launch_zgemm_as(hipStream_t st, int kernel, bool herm_on, int M, int N, int K, int nb,
+                     const cplx* A, int lda, size_t strideA,
+                     const cplx* B, int ldb, size_t strideB, int opB,
+                     cplx* C, int ldc, size_t strideC);
+int zgemm_plan(int M, int N, int K, int opB, int nb, int kernel, int* kernel_used, int* opB_eff, int* blocks, int* grid,
+               int* decode, int decode_cap);
 
 // out[b*out_stride] = Re sum_{i<nr, j<ncol} X[b][i*ldx+j] * conj(G[b][i*ldg+j])
 void launch_trace_dot(hipStream_t st, int nr, int ncol, int nb, const cplx* X, int ldx,

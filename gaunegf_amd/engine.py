@@ -742,6 +742,39 @@ class Engine:
         check(self._lib.negf_selftest_mfma(self._ctx, C.byref(err)), "negf_selftest_mfma")
         return err.value
 
+    def zgemm(self, M, N, K, nb, A, lda, strideA, B, ldb, strideB, opB, C_in, ldc, strideC, kernel=0):
+        """The batched product kernels on flat complex128 arrays with explicit leading dimensions and batch strides
+        (negf_zgemm_batched, a diagnostic call; include/negf.h has the layout, opB and kernel).  ``C_in`` is what the
+        device result array holds before the launch; the whole array comes back, so the caller sees what was written."""
+        A, B = _c128(A).ravel(), _c128(B).ravel()
+        out = np.array(C_in, dtype=np.complex128).ravel()             # a copy: C_in stays as it is
+        rows_b, rows_c = (N if opB & 1 else K), (N if opB & 4 else M)
+        need = ((strideA * nb if strideA else M * lda), (strideB * nb if strideB else rows_b * ldb), strideC * nb)
+        if A.size < need[0] or B.size < need[1] or out.size < need[2] or strideC < rows_c * ldc:
+            raise ValueError(f"zgemm: arrays of {A.size}, {B.size}, {out.size} elements, the layout needs {need}")
+        check(self._lib.negf_zgemm_batched(self._ctx, int(M), int(N), int(K), int(nb), _ptr(A), int(lda), int(strideA),
+                                           _ptr(B), int(ldb), int(strideB), int(opB), _ptr(out), int(ldc), int(strideC),
+                                           int(kernel)), "negf_zgemm_batched")
+        return out
+
+    @staticmethod
+    def zgemm_plan(M, N, K=1, opB=0, nb=1, kernel=0):
+        """What ``zgemm`` does with a shape (negf_zgemm_plan; needs no GPU): a dict with ``kernel`` (1 = 64 x 64 blocks,
+        2 = flexible blocks, 3 = vector unit), ``opB`` after the demotion of the Hermitian bit, ``blocks`` (rows,
+        columns), ``grid`` (x, y, z) and, for a Hermitian launch of kernel 1 or 2, ``decode``: int32 [grid x, 3], the
+        (block row, block column, batch member) of every workgroup, -1 for one that returns at once (else None)."""
+        lib = _lib.load()
+        ku, oe = C.c_int(0), C.c_int(0)
+        blocks, grid = (C.c_int * 2)(), (C.c_int * 3)()
+        args = (int(M), int(N), int(K), int(opB), int(nb), int(kernel), C.byref(ku), C.byref(oe), blocks, grid)
+        check(lib.negf_zgemm_plan(*args, None, 0), "negf_zgemm_plan")
+        decode = None
+        if (oe.value & 2) and ku.value != 3:
+            decode = np.zeros((grid[0], 3), dtype=np.int32)
+            check(lib.negf_zgemm_plan(*args, decode.ctypes.data_as(C.POINTER(C.c_int)), int(grid[0])), "negf_zgemm_plan")
+        return {"kernel": ku.value, "opB": oe.value, "blocks": (blocks[0], blocks[1]),
+                "grid": (grid[0], grid[1], grid[2]), "decode": decode}
+
 
 def get_engine(device=None):
     """Process-wide engine for ``device`` (default: LOCAL_RANK, else 0)."""

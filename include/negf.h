@@ -418,6 +418,31 @@ int negf_set_gamma_algo(negf_ctx* ctx, int algo);
 /* run the FP64 MFMA fragment-layout probe; max abs error vs an exact integer
  * product (0.0 expected) */
 int negf_selftest_mfma(negf_ctx* ctx, double* max_err);
+/* The batched complex product kernels behind every G Gamma G^H, transmission and channel product, called directly on
+ * operands of the caller's choice (a diagnostic call for tests: every call allocates, uploads and downloads):
+ *     C_b = A_b op(B_b),  b < nb,   A_b M x K (row-major, leading dimension lda >= K),
+ * opB bit 0: op(B) = B^H with B stored N x K (ldb >= K), else B is K x N (ldb >= N); bit 1: the caller promises a
+ * Hermitian product (M == N): the block tiles on and above the diagonal are computed, those above it mirrored; bit 2:
+ * the result is stored conjugate-transposed, N x M (ldc >= M; else M x N, ldc >= N).  Bit 1 is dropped where M != N
+ * or bit 2 is set.  Strides are in complex elements; strideA / strideB = 0 shares the operand among the batch,
+ * otherwise a stride is at least rows * ld, and so is strideC always.  The host arrays hold nb * stride complex values
+ * (rows * ld for a shared operand).  ALL of C is uploaded before the launch and downloaded after it, so the caller
+ * sees which elements the kernel wrote.  kernel: 0 = the production rule (negf_zgemm_plan), 1 = the 64 x 64 block
+ * kernel, 2 = the flexible-block kernel, 3 = the vector-unit kernel (four-product form, ignores bit 1).  K = 0 gives
+ * zeros.  NEGF_EINVAL: a null pointer, M or N < 1, K < 0, nb < 1, opB outside 0 .. 7, kernel outside 0 .. 3, a
+ * leading dimension or stride below the above, an array of more than 2^31 elements. */
+int negf_zgemm_batched(negf_ctx* ctx, int M, int N, int K, int nb, const double* A_c128, int lda, long long strideA,
+                       const double* B_c128, int ldb, long long strideB, int opB, double* C_c128, int ldc,
+                       long long strideC, int kernel);
+/* What negf_zgemm_batched does with a shape; a host function that needs no device.  kernel as above (0: the rule the
+ * library's own products follow -- the flexible kernel where the 64 x 64 blocks would be more than a sixth padding;
+ * the NEGF_ZGEMM_* environment switches are not consulted).  Outputs, each may be NULL: kernel_used (1 .. 3), opB_eff
+ * (opB after the demotion of bit 1), blocks[2] = block rows and columns, grid[3] = the launch grid (x, y, z).  For a
+ * Hermitian launch of kernel 1 or 2 (opB_eff bit 1) and decode != NULL: decode[3 L .. 3 L + 2] = (block row, block
+ * column, batch member) of workgroup L < grid[0], or (-1, -1, -1) for a workgroup that returns at once; decode_cap
+ * (in triples) below grid[0] is NEGF_EINVAL, as are the invalid arguments of negf_zgemm_batched. */
+int negf_zgemm_plan(int M, int N, int K, int opB, int nb, int kernel, int* kernel_used, int* opB_eff, int* blocks,
+                    int* grid, int* decode, int decode_cap);
 
 #ifdef __cplusplus
 }

@@ -212,8 +212,9 @@ def test_windowed_inverse_large_batches(engine, N, M):
 
 @pytest.mark.parametrize("N,M", [(12, 12), (60, 100), (200, 64), (150, 6), (330, 5)])
 def test_GrInt_GrLessInt_const_sigma(engine, N, M):
-    # (G Gamma G^H runs as a Hermitian product: block tiles above the diagonal computed and mirrored -- one block
-    #  at N <= 64, the flexible-block kernel at N = 200, 3 x 3 and 6 x 6 blocks of 64 with a ragged edge at 150 / 330)
+    # (G Gamma G^H runs as a Hermitian product: block tiles above the diagonal computed and mirrored -- one 64 x 64 block
+    #  at N <= 64; by launch_zgemm's padding rule the flexible-block kernel at N = 150, 200 and 330, as 2 x 2, 3 x 3 and
+    #  5 x 5 balanced blocks with a ragged edge.  The 64-block enumeration is held directly by test_zgemm_accuracy_gpu.py)
     from gaunegf_amd.integrate import GrInt, GrLessInt
     F, S, g_dev, g_ref = _const_provider(N, 7 + N)
     E, w = oracle.contour_grid(-4.0, 0.2, M if M % 2 == 0 else M + 1, 300.0)
@@ -626,8 +627,9 @@ def test_dense_hermitian_products_read_a_stored_conjugate_transpose(engine, N):
     """The dense products X G^H (G Gamma G^H, integrate.py:79-81; Tr[Gamma_L G Gamma_R G^H],
     transport.py:156-157) are taken as G X^H with X^H stored by the first product (both second operands plain) instead of
     conjugate-transposing tiles of G on the fly; the Hermitian form still computes the upper block tiles only and
-    mirrors the rest (N = 200: the flexible-block kernel; 330: 6 x 6 block tiles, an edge block of 10 columns; 650: 11 x 11,
-    the odd enumeration; 720: 12 x 12, edge 16).
+    mirrors the rest (N = 200 and 330: the flexible-block kernel by launch_zgemm's padding rule, 3 x 3 and 5 x 5 balanced
+    blocks; 650: the 64 x 64 block kernel, 11 x 11 block tiles, the odd enumeration, an edge block of 10 columns; 720:
+    12 x 12, the even enumeration, edge 16).
     Dense products forced (negf_set_gamma_algo 1) against the compact path and the oracle."""
     from gaunegf_amd.integrate import GrLessInt
     E = np.linspace(-2, 2, 6); w = np.full(6, 4.0 / 6) + 0j
