@@ -125,7 +125,7 @@ void free_workspace(negf_ctx* c, bool all = false)
     dev_free(c->d_A); dev_free(c->d_T1); dev_free(c->d_T2); dev_free(c->d_ipiv); dev_free(c->d_site);
     c->batch = 0;
     release_bufs(c->d_blk, c->d_scratch, c->d_gsmall, c->d_small_part);
-    if (all) release_bufs(c->d_seg_out, c->d_ref_P, c->d_chan, c->d_chan_rank, c->d_chan_T, c->d_chan_psi, c->d_bond_map, c->d_bond_carry, c->d_bond_T);
+    if (all) release_bufs(c->d_seg_out, c->d_ref_P, c->d_chan, c->d_chan_rank, c->d_chan_T, c->d_chan_psi, c->d_bond_map, c->d_bond_carry, c->d_bond_T, c->d_pop_W, c->d_pop_Wt);
 }
 
 void free_mbuffers(negf_ctx* c)
@@ -2506,6 +2506,141 @@ int negf_bond_int(negf_ctx* c, int handle, int ind, int m, const double* E, cons
     double* dout = reinterpret_cast<double*>(c->d_acc);          // n^2 doubles of its n^2 complex values
     if ((rc = negf_bond_int_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), dw, dout))) return rc;
     return fetch_result_and_info(c, m, dout, ob, out, info);
+}
+
+// ------------------------------------------------------- populations and projected DOS
+// pop[i][j] = -(1/pi) Im[G_ij conj(X_ij)] (retarded) or (1/2 pi) Re[A_c,ij conj(X_ij)] (contact c), X = S or F: negf_dos's
+// sequence up to G, or the GrLessInt sequence up to A_c (run_gless_products), then ONE pass of k_population.hip.  The
+// reference has no such function.
+namespace {
+
+// ind = NEGF_IND_RETARDED: every provider negf_dos serves; otherwise what the local transmission serves (bond_open)
+int pop_open(negf_ctx* c, int handle, int m, int ind, SigmaProvider** p, int* contact)
+{
+    if (ind != NEGF_IND_RETARDED) return bond_open(c, handle, m, ind, p, contact);
+    *contact = -1;
+    int rc = open_call(c, handle, m, p);
+    if (rc) return rc;
+    return c->n > bond_max_n() ? NEGF_EINVAL : NEGF_OK;
+}
+
+// G (retarded) or A_c (contact) of the batch [m0, m0 + nb); *free_area: a work area of nb n^2 values the result does not use
+int pop_matrix(negf_ctx* c, SigmaProvider* p, int ind, int contact, int m0, int nb, const cplx* E, const cplx** M,
+               cplx** free_area)
+{
+    int rc;
+    if (ind == NEGF_IND_RETARDED) {
+        if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
+        *M = c->G; *free_area = c->W1;
+        return NEGF_OK;
+    }
+    if ((rc = run_gless_products(c, p, contact, m0, nb, E))) return rc;
+    *M = c->W1; *free_area = c->W2;
+    return NEGF_OK;
+}
+
+}  // namespace
+
+int negf_population_dev(negf_ctx* c, int handle, int ind, int op, int rows_only, int m, const double* E_dev, int n_groups,
+                        const int* group_of, double* out_dev)
+{
+    SigmaProvider* p;
+    int contact;
+    int rc = pop_open(c, handle, m, ind, &p, &contact);
+    if (rc) return rc;
+    if ((op != 0 && op != 1) || (rows_only != 0 && rows_only != 1)) return NEGF_EINVAL;
+    if (m > 0 && (!E_dev || !out_dev)) return NEGF_EINVAL;
+    bool identity = true;
+    if ((rc = bond_stage_groups(c, n_groups, group_of, &identity))) return rc;
+    const int n = c->n;
+    const int* perm = identity ? nullptr : c->d_bond_map;
+    const int* goff = identity ? nullptr : c->d_bond_map + n;
+    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
+    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    const cplx* X = op == 0 ? c->d_S : c->d_F;
+    const size_t per = rows_only ? (size_t)n_groups : (size_t)n_groups * n_groups;
+    for (int m0 = 0; m0 < m; m0 += c->batch) {
+        const int nb = std::min(c->batch, m - m0);
+        const cplx* M;
+        cplx* unused;
+        if ((rc = pop_matrix(c, p, ind, contact, m0, nb, E, &M, &unused))) return rc;
+        ProfScope ps(c, "pop");
+        if (!launch_population(c->stream, n, nb, ind == NEGF_IND_RETARDED, X, M, c->d_info + m0, rows_only, n_groups, perm,
+                               goff, out_dev + per * m0)) return NEGF_EINVAL;
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_population(negf_ctx* c, int handle, int ind, int op, int rows_only, int m, const double* E, int n_groups,
+                    const int* group_of, double* out, int* info)
+{
+    SigmaProvider* p;
+    int contact;
+    int rc = pop_open(c, handle, m, ind, &p, &contact);
+    if (rc) return rc;
+    if (n_groups < 1 || n_groups > c->n || (rows_only != 0 && rows_only != 1) || (m > 0 && (!E || !out))) return NEGF_EINVAL;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    const size_t cnt = (size_t)m * n_groups * (rows_only ? 1 : n_groups);
+    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
+    if ((rc = negf_population_dev(c, handle, ind, op, rows_only, m, reinterpret_cast<double*>(c->d_E), n_groups, group_of,
+                                  c->d_bond_T))) return rc;
+    if ((rc = download(c, out, c->d_bond_T.p, cnt))) return rc;
+    return reduce_info(c, m, info);
+}
+
+int negf_projected_dos_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev, int k, const double* W_dev,
+                           double* out_dev)
+{
+    SigmaProvider* p;
+    int contact;
+    int rc = pop_open(c, handle, m, ind, &p, &contact);
+    if (rc) return rc;
+    const int n = c->n;
+    if (k < 1 || k > n || !W_dev || (m > 0 && (!E_dev || !out_dev))) return NEGF_EINVAL;
+    if (m == 0) { c->last_m = 0; return NEGF_OK; }
+    const size_t nk = (size_t)n * k, n2 = (size_t)n * n;
+    if ((rc = ensure_cap(c, c->d_pop_Wt, nk))) return rc;
+    cplx* Wt = c->d_pop_Wt;
+    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
+    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
+    { ProfScope ps(c, "pop"); launch_pop_transpose_w(c->stream, n, k, reinterpret_cast<const cplx*>(W_dev), Wt); }
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    for (int m0 = 0; m0 < m; m0 += c->batch) {
+        const int nb = std::min(c->batch, m - m0);
+        const cplx* M;
+        cplx* Y;
+        if ((rc = pop_matrix(c, p, ind, contact, m0, nb, E, &M, &Y))) return rc;
+        // Y_b = M_b Wt (n x k): Wt shared by the batch
+        { ProfScope ps(c, "zgemm"); launch_zgemm(c->stream, n, k, n, nb, M, n, n2, Wt, k, 0, 0, Y, k, nk); }
+        ProfScope ps(c, "pop");
+        launch_pop_coldot(c->stream, n, k, nb, ind == NEGF_IND_RETARDED, Wt, Y, nk, c->d_info + m0, out_dev + (size_t)k * m0);
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_projected_dos(negf_ctx* c, int handle, int ind, int m, const double* E, int k, const double* W, double* out,
+                       int* info)
+{
+    SigmaProvider* p;
+    int contact;
+    int rc = pop_open(c, handle, m, ind, &p, &contact);
+    if (rc) return rc;
+    const int n = c->n;
+    if (k < 1 || k > n || !W || (m > 0 && (!E || !out))) return NEGF_EINVAL;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    const size_t nk = (size_t)n * k, cnt = (size_t)m * k;
+    if ((rc = ensure_cap(c, c->d_pop_W, nk))) return rc;
+    if ((rc = upload(c, c->d_pop_W.p, reinterpret_cast<const cplx*>(W), nk))) return rc;
+    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
+    if ((rc = negf_projected_dos_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), k,
+                                     reinterpret_cast<const double*>(c->d_pop_W.p), c->d_bond_T))) return rc;
+    if ((rc = download(c, out, c->d_bond_T.p, cnt))) return rc;
+    return reduce_info(c, m, info);
 }
 
 // ------------------------------------------------------------ g(E) cache knob

@@ -243,7 +243,9 @@ struct negf_ctx {
     DevBuf<cplx> d_chan_psi;       // [m][nchan][n] staging of negf_channel_states
     DevBuf<int> d_bond_map;        // local transmission: perm [n] | goff [ng + 1] of the call's orbital -> group map
     DevBuf<double> d_bond_carry;   // [n*n] running sum of the 32-energy chunk a batch boundary cuts (negf_bond_int)
-    DevBuf<double> d_bond_T;       // [m][ng][ng] staging of the host-pointer entry point
+    DevBuf<double> d_bond_T;       // [m][ng][ng] staging of the host-pointer entry point (negf_population / negf_projected_dos stage here too)
+    DevBuf<cplx> d_pop_W;          // projected DOS: the vectors W [k][n] of the host-pointer entry point
+    DevBuf<cplx> d_pop_Wt;         // ... and their transpose Wt [n][k], the second operand of Y = M Wt
     GjSideStreams gj_side;
     int chain_rr_quantum = -1, chain_rr_slots = 0;   // negf_set_chain_round_robin
     int small_algo = 0;            // 0: n <= 96 takes the fused single-kernel path, 1: never (negf_set_small_algo)
@@ -463,6 +465,18 @@ bool launch_bond_tables(hipStream_t st, int n, int nb, const cplx* E, const cplx
 size_t bond_int_scratch_doubles(int n2, int nb);
 void launch_bond_int(hipStream_t st, int n2, int m, int m0, int nb, const cplx* E, const double* w, const cplx* S,
                      const cplx* F, const cplx* A, double* carry, double* part, double* out);
+
+// Overlap / Hamilton populations and projected DOS (k_population.hip).  M = G (retarded: -(1/pi) Im[M_ij conj(X_ij)]) or
+// the Hermitian A_c = G Gamma_c G^H (contact: (1/2 pi) Re[M_ij conj(X_ij)]), X = S or F.
+// launch_population: out [nb][ng][ng] (rows_only = 0) or [nb][ng] (rows_only = 1: the sums of the table's rows, in one pass,
+// the table never stored); perm / goff as in launch_bond_tables (null: every orbital its own group, ng = n).
+// info[b] != 0 -> NaN.  false: n exceeds bond_max_n(), or the LDS of the row kernel could not be had (nothing launched).
+bool launch_population(hipStream_t st, int n, int nb, bool retarded, const cplx* X, const cplx* M, const int* info,
+                       int rows_only, int ng, const int* perm, const int* goff, double* out);
+// Wt [n][k] = the transpose of W [k][n];  out[b][a] = factor * Im / Re [sum_i conj(Wt[i][a]) Y[b][i][a]], Y [nb][n][k] = M Wt
+void launch_pop_transpose_w(hipStream_t st, int n, int k, const cplx* W, cplx* Wt);
+void launch_pop_coldot(hipStream_t st, int n, int k, int nb, bool retarded, const cplx* Wt, const cplx* Y, size_t strideY,
+                       const int* info, double* out);
 
 bool small_fused_supported(int n);
 int small_fused_grid(int n, int m);

@@ -14,7 +14,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from ._lib import NEGF_IND_TOTAL, NEGF_SPIN_BLOCK, NEGF_SPIN_RESTRICTED, check
+from ._lib import NEGF_IND_RETARDED, NEGF_IND_TOTAL, NEGF_SPIN_BLOCK, NEGF_SPIN_RESTRICTED, check
 from .config import SURFACE_DOUBLING_MAX_STEPS, SURFACE_DOUBLING_TOL
 
 _engines = {}
@@ -646,7 +646,83 @@ class Engine:
             raise NotImplementedError(self._BOND_REFUSED)
         check(rc, "negf_bond_int_dev")
 
+    # ------------------------------------------- populations and projected DOS
+    RETARDED = NEGF_IND_RETARDED                  # ``ind`` of the retarded form of population / projected_dos
+
+    _POP_REFUSED = ("the contact form of population / projected_dos reads A = G Gamma_c G^H as Hermitian: coupling matrices "
+                    "handed in by the caller (sigma_precomputed(gammas=...)) are not served (the retarded form, "
+                    "ind = Engine.RETARDED, is), nor are systems of more than 8192 orbitals; an invalid contact index, op, "
+                    "or number of vectors is refused the same way")
+    _POP_OPS = {'S': 0, 'F': 1, 0: 0, 1: 1}
+
+    def _pop_op(self, op):
+        if not isinstance(op, (str, int)) or op not in self._POP_OPS:
+            raise ValueError(f"op must be 'S' (overlap population) or 'F' (Hamilton population), got {op!r}")
+        return self._POP_OPS[op]
+
+    def _pop_ind(self, ind):
+        return NEGF_IND_RETARDED if ind == 'retarded' else _ind(ind)
+
+    def population(self, handle, ind, E, op='S', groups=None, n_groups=None, rows=False):
+        """Overlap (``op='S'``, COOP) or Hamilton (``op='F'``, COHP) populations per energy (negf_population).
+        ``ind = Engine.RETARDED``: pop[i, j] = -(1/pi) Im[G_ij conj(X_ij)]; a contact index or None (all contacts):
+        that contact's share (1/2pi) Re[(G Gamma_c G^H)_ij conj(X_ij)].  Returns the tables [m, n_g, n_g] summed over
+        ``groups`` (orbital -> group labels, None = per orbital pair), or with ``rows=True`` their row sums [m, n_g] --
+        for ``op='S'`` the projected DOS of each orbital / atom / fragment, -Im (G S)_ii / pi summed over the group --
+        in one pass, without the table.  Singular energies give NaN (with a warning, as transmission)."""
+        op = self._pop_op(op)
+        ng, g = self._groups(groups, n_groups)
+        E, _ = self._grid(E)
+        out = np.zeros((E.size, ng) if rows else (E.size, ng, ng), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lib.negf_population(self._ctx, int(handle), self._pop_ind(ind), op, int(bool(rows)), E.size,
+                                       _ptr(E), ng, _ptr(g), _ptr(out), _ptr(info))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._POP_REFUSED)
+        self._numerical(check(rc, "negf_population"), info[:E.size], "population")
+        return out
+
+    def population_dev(self, handle, ind, m, E_ptr, out_ptr, op='S', groups=None, n_groups=None, rows=False):
+        """negf_population_dev: grid and the [m, n_g, n_g] / [m, n_g] result in HBM; ``groups`` stays a host array."""
+        op = self._pop_op(op)
+        ng, g = self._groups(groups, n_groups)
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        rc = self._lib.negf_population_dev(self._ctx, int(handle), self._pop_ind(ind), op, int(bool(rows)),
+                                           int(m), C.c_void_p(E_ptr), ng, _ptr(g), C.c_void_p(out_ptr))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._POP_REFUSED)
+        check(rc, "negf_population_dev")
+
+    def projected_dos(self, handle, ind, E, W):
+        """Projection on the vectors W [k, n] (negf_projected_dos): p[m, a] = -(1/pi) Im[w_a^H G w_a] for
+        ``ind = Engine.RETARDED``, (1/2pi) Re[w_a^H G Gamma_c G^H w_a] for a contact.  For orbitals with coefficients c
+        in a non-orthogonal basis pass w = S c."""
+        W = np.ascontiguousarray(np.atleast_2d(np.asarray(W)), dtype=np.complex128)
+        if W.ndim != 2 or W.shape[1] != self.n:
+            raise ValueError(f"W must be [k, n] with n = {self.n}, got {W.shape}")
+        E, _ = self._grid(E)
+        k = W.shape[0]
+        out = np.zeros((E.size, k), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lib.negf_projected_dos(self._ctx, int(handle), self._pop_ind(ind), E.size, _ptr(E), k, _ptr(W), _ptr(out),
+                                          _ptr(info))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._POP_REFUSED)
+        self._numerical(check(rc, "negf_projected_dos"), info[:E.size], "projected_dos")
+        return out
+
+    def projected_dos_dev(self, handle, ind, m, E_ptr, k, W_ptr, out_ptr):
+        """negf_projected_dos_dev: E complex128 [m], W complex128 [k, n] and out float64 [m, k] in HBM."""
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        rc = self._lib.negf_projected_dos_dev(self._ctx, int(handle), self._pop_ind(ind), int(m), C.c_void_p(E_ptr), int(k),
+                                              C.c_void_p(W_ptr), C.c_void_p(out_ptr))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._POP_REFUSED)
+        check(rc, "negf_projected_dos_dev")
+
     def dos(self, handle, E, per_site=True):
+        """negf_dos: -Im diag G / pi, the reference's _dos_kernel -- it ignores the overlap matrix.  In a non-orthogonal
+        basis the population is ``population(handle, Engine.RETARDED, E, rows=True)``."""
         E, _ = self._grid(E)
         tot = np.zeros(E.size, dtype=np.float64)
         site = np.zeros((E.size, self.n), dtype=np.float64) if per_site else None

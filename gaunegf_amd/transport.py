@@ -458,6 +458,72 @@ def _group_count(groups, n):
     return int(g.max()) + 1
 
 
+def _pop_ind(contact):
+    """contact=None: the retarded form; 0 / 1 / -1: that contact's share."""
+    from .engine import Engine
+    return Engine.RETARDED if contact is None else _check_contact(contact)
+
+
+def _pop_batch(layout, sigma_calc, energies, spin, call):
+    """call(engine, handle, pos, perm) -> [m, ...] for system ``pos`` of the layout, stacked: [len(layout), m, ...]."""
+    energies = np.asarray(energies)
+    eng = get_engine()
+    out = []
+    for pos, (F, S, perm) in enumerate(layout):
+        h, temp = _bond_handle(eng, F, S, perm, sigma_calc, energies, spin)
+        try:
+            out.append(call(eng, h, pos, perm))
+        finally:
+            if temp:
+                eng.sigma_free(h)
+    return np.stack(out)
+
+
+def _pop_population(eng, h, ind, energies, op, groups, n_g, perm, rows):
+    """Engine.population for a system staged in block form (position q holds the caller's orbital perm[q]; perm None: as
+    it is): a group map is handed over in the staged order; without one the per-orbital kernels run as they are and the
+    result is put back into the caller's order here."""
+    if perm is None:
+        return eng.population(h, ind, energies, op, groups, n_g, rows=rows)
+    if groups is not None:
+        return eng.population(h, ind, energies, op, np.asarray(groups)[perm], n_g, rows=rows)
+    out = eng.population(h, ind, energies, op, rows=rows)
+    back = np.empty_like(out)
+    if rows:
+        back[:, perm] = out
+    else:
+        back[:, perm[:, None], perm[None, :]] = out
+    return back
+
+
+def _pop_sharded(layout, m, shape, run):
+    """run(idx) -> [len(layout), len(idx), *shape], sharded over the energies; one array, or (up, down) for two systems."""
+    k = len(layout)
+    flat = int(np.prod(shape))
+    res = _dist.sharded_map(lambda idx: np.moveaxis(run(idx), 0, 1).reshape(-1, k * flat), m, (k * flat,))
+    res = np.asarray(res).reshape((m, k) + tuple(shape))
+    return res[:, 0] if k == 1 else (res[:, 0], res[:, 1])
+
+
+def fragment_orbitals(F, S, indices):
+    """Molecular orbitals of the fragment ``indices``: the generalised eigenproblem F_ff c = e S_ff c of the fragment's
+    blocks, solved on the host (Cholesky of S_ff, then a Hermitian eigenproblem).  Returns (energies [k] ascending,
+    C [n, k]): the eigenvectors embedded in the full basis (zero outside the fragment) and S-normalised, C^H S C = 1."""
+    F = np.asarray(F)
+    S = np.asarray(S)
+    idx = np.asarray(indices, dtype=int).ravel()
+    if idx.size == 0 or np.unique(idx).size != idx.size or idx.min() < 0 or idx.max() >= F.shape[0]:
+        raise ValueError("fragment must be a non-empty list of distinct orbital indices")
+    Fff = F[np.ix_(idx, idx)].astype(complex)
+    Sff = S[np.ix_(idx, idx)].astype(complex)
+    Linv = np.linalg.inv(np.linalg.cholesky((Sff + Sff.conj().T) / 2))
+    A = Linv @ ((Fff + Fff.conj().T) / 2) @ Linv.conj().T
+    e, V = np.linalg.eigh((A + A.conj().T) / 2)
+    C = np.zeros((F.shape[0], idx.size), dtype=complex)
+    C[idx] = Linv.conj().T @ V
+    return e, C
+
+
 def _dos_batch(F, S, sigma_calc, energies, spin):
     F = np.asarray(F)
     S = np.asarray(S)
@@ -731,10 +797,90 @@ def calculate_bond_currents(F, S, sigma_calculator, fermi, qV, T=TEMPERATURE, gr
     return flow[0] if k == 1 else (flow[0], flow[1])
 
 
+def calculate_pdos(F, S, sigma_calculator, energy_list, groups=None, contact=None, spin=None):
+    """Projected DOS in a non-orthogonal basis [m, n_g]: the Mulliken population per energy of every orbital
+    (``groups=None``) or of every group of orbitals (atoms, fragments), row a = sum_{i in a} -Im (G S)_ii / pi; the rows
+    of an energy sum to -Im Tr(G S) / pi.  ``contact=None``: the retarded form above; 0 or 1 / -1: the share injected by
+    that contact, sum_{i in a} (G Gamma_c G^H S)_ii / 2pi -- for real energies the contacts' shares add up to the rows of the
+    symmetrised table (pop + pop^T) / 2, and their grand total to the retarded form's, -Im Tr(G S) / pi.  One pass over G (or G Gamma_c G^H) per energy on the GPU; the [n_g, n_g] table is never formed.
+    This -- not calculate_dos, which keeps the reference's -Im diag G / pi and ignores S -- is the DOS a user with a
+    non-orthogonal (Gaussian) basis wants.  spin as calculate_local_transmission: (up, down) for a spin-diagonal
+    'u' / 'ro' system with a spin-expanded self-energy, otherwise the 2N system with ``groups`` of length 2N."""
+    energy_list = np.asarray(energy_list)
+    if spin is None:
+        spin = 'r'
+    ind = _pop_ind(contact)
+    layout = _bond_layout(F, S, sigma_calculator, spin)
+    n_g = _group_count(groups, layout[0][0].shape[0])
+    return _pop_sharded(layout, len(energy_list), (n_g,), lambda idx: _pop_batch(
+        layout, sigma_calculator, energy_list[idx], spin,
+        lambda eng, h, pos, perm: _pop_population(eng, h, ind, energy_list[idx], 'S', groups, n_g, perm, True)))
+
+
+def calculate_overlap_population(F, S, sigma_calculator, energy_list, op='S', groups=None, contact=None, spin=None):
+    """Energy-resolved overlap (``op='S'``, COOP) or Hamilton (``op='F'``, COHP) populations [m, n_g, n_g]:
+    entry [k, a, b] = sum_{i in a, j in b} -(1/pi) Im[G_ij X_ji](E_k), X = S or F; with ``contact`` 0 or 1 / -1 that
+    contact's share (1/2pi) Re[(G Gamma_c G^H)_ij X_ji].  The rows of the S table sum to calculate_pdos; for real energies
+    the contacts' shares add up to the symmetrised retarded table.  ``groups``, spin as calculate_pdos."""
+    energy_list = np.asarray(energy_list)
+    if spin is None:
+        spin = 'r'
+    if op not in ('S', 'F'):
+        raise ValueError(f"op must be 'S' or 'F', got {op!r}")
+    ind = _pop_ind(contact)
+    layout = _bond_layout(F, S, sigma_calculator, spin)
+    n_g = _group_count(groups, layout[0][0].shape[0])
+    return _pop_sharded(layout, len(energy_list), (n_g, n_g), lambda idx: _pop_batch(
+        layout, sigma_calculator, energy_list[idx], spin,
+        lambda eng, h, pos, perm: _pop_population(eng, h, ind, energy_list[idx], op, groups, n_g, perm, False)))
+
+
+def calculate_projected_dos(F, S, sigma_calculator, energy_list, orbitals=None, fragment=None, contact=None, spin=None):
+    """DOS projected on orbitals |phi_a> = sum_i c_ia |i> of the non-orthogonal basis [m, k]:
+    p_a(E) = -(1/pi) Im <phi_a|G|phi_a> = -(1/pi) Im[c_a^H S G S c_a]; with ``contact`` 0 or 1 / -1 the share injected by
+    that contact, (1/2pi) Re[c_a^H S G Gamma_c G^H S c_a].  Give either ``orbitals`` = C [n, k] (columns; S-normalise them
+    for a DOS) or ``fragment`` = orbital indices: the fragment's molecular orbitals (fragment_orbitals) are projected on,
+    and the result is (p [m, k], energies [k]).  A complete S-orthonormal set sums to calculate_pdos's total.
+    spin as calculate_pdos: (up, down) -- and with ``fragment`` ((p_up, p_down), (e_up, e_down)) -- for a spin-diagonal
+    'u' / 'ro' system (C has the N rows of a spin block there), otherwise C has the 2N rows of the whole system."""
+    energy_list = np.asarray(energy_list)
+    if spin is None:
+        spin = 'r'
+    if (orbitals is None) == (fragment is None):
+        raise ValueError("give either orbitals=C [n, k] or fragment=indices")
+    ind = _pop_ind(contact)
+    layout = _bond_layout(F, S, sigma_calculator, spin)
+    Ws, es = [], []
+    for Fs, Ss, perm in layout:
+        n = Fs.shape[0]
+        if fragment is not None:
+            e, Cmat = fragment_orbitals(Fs, Ss, fragment)
+            es.append(e)
+        else:
+            Cmat = np.asarray(orbitals)
+            if Cmat.ndim == 1:
+                Cmat = Cmat[:, None]
+            if Cmat.ndim != 2 or Cmat.shape[0] != n or not 1 <= Cmat.shape[1] <= n:
+                raise ValueError(f"orbitals must be [n, k] with n = {n} rows and 1 <= k <= n, got {Cmat.shape}")
+        W = (np.asarray(Ss) @ Cmat).T
+        if perm is not None:                       # block form: position q holds the caller's orbital perm[q]
+            W = W[:, perm]
+        Ws.append(np.ascontiguousarray(W))
+    k = Ws[0].shape[0]
+
+    p = _pop_sharded(layout, len(energy_list), (k,), lambda idx: _pop_batch(
+        layout, sigma_calculator, energy_list[idx], spin,
+        lambda eng, h, pos, perm: eng.projected_dos(h, ind, energy_list[idx], Ws[pos])))
+    if fragment is None:
+        return p
+    return p, (es[0] if len(es) == 1 else tuple(es))
+
+
 def calculate_dos(F, S, sigma_calculator, energy_list, spin=None, checkpoint_file=None,
                   checkpoint_interval=10):
     """DOS over ``energy_list`` with checkpointing (transport.py:486-607): keys ``dos_total``,
-    ``dos_per_site``, ``dos_spin``, ``energy_list``."""
+    ``dos_per_site``, ``dos_spin``, ``energy_list``.  This is the reference's -Im diag G / pi, kept for parity: it ignores
+    the overlap matrix.  In a non-orthogonal basis use calculate_pdos (populations, -Im (G S)_ii / pi)."""
     energy_list = np.asarray(energy_list)
     n_energies = len(energy_list)
     n_sites = F.shape[0]
@@ -954,6 +1100,13 @@ def DOS(Elist, F, S, sig1, sig2):
     return tot.tolist(), site
 
 
+def PDOS(Elist, F, S, sig1, sig2, groups=None):
+    """(total list, projected DOS [M, n_g]) in a non-orthogonal basis with energy-independent self-energies (next to DOS,
+    which ignores S): calculate_pdos and its sum over the groups, -Im Tr(G S) / pi."""
+    pd = calculate_pdos(F, S, _static_calc(sig1, sig2), Elist, groups=groups, spin='r')
+    return pd.sum(axis=1).tolist(), pd
+
+
 def cohTransE(Elist, F, S, g):
     """T(E) list with an energy-dependent provider (transport.py:1001-1034)."""
     T_ = calculate_transmission(F, S, _dynamic_calc(g), Elist, spin='r')
@@ -971,3 +1124,11 @@ def DOSE(Elist, F, S, g):
     tot, site = calculate_dos(F, S, _dynamic_calc(g), Elist, spin='r')
     _report(Elist, tot, "DOS")
     return tot.tolist(), site
+
+
+def PDOSE(Elist, F, S, g, groups=None):
+    """(total list, projected DOS [M, n_g]) with an energy-dependent provider ``g`` (next to DOSE)."""
+    pd = calculate_pdos(F, S, _dynamic_calc(g), Elist, groups=groups, spin='r')
+    tot = pd.sum(axis=1)
+    _report(Elist, tot, "PDOS")
+    return tot.tolist(), pd

@@ -50,6 +50,9 @@ typedef struct negf_ctx negf_ctx;
  * integrate.py:201-204).  Other negative values index from the end like Python
  * (ind=-1 is the last contact, scfE.py:441,444). */
 #define NEGF_IND_TOTAL  (-1000)
+/* selector of the RETARDED form of negf_population / negf_projected_dos (no contact: the quantity is built on G itself);
+ * no other entry point accepts it */
+#define NEGF_IND_RETARDED (-2000)
 
 /* spin layouts of transport.py:193-271 */
 #define NEGF_SPIN_RESTRICTED 0   /* 'r'                         */
@@ -372,9 +375,51 @@ int negf_bond_int(negf_ctx* ctx, int handle, int ind, int m, const double* E_c12
 int negf_bond_int_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, const double* w_dev,
                       double* out_dev);
 
+/* ------------------------------------------------------ overlap populations and projected DOS
+ * Where the states sit and which contact fills them (the reference has no such function; its only density of states,
+ * negf_dos = _dos_kernel, is -Im diag G / pi and ignores the overlap matrix: in a non-orthogonal basis that is not a
+ * population).  Per energy, with G = (E S - F - sum_c Sigma_c)^-1, Gamma_c = i (Sigma_c - Sigma_c^H),
+ * A_c = G Gamma_c G^H, and X = S (op = 0) or F (op = 1):
+ *     ind = NEGF_IND_RETARDED:               pop[i][j]   = -(1/pi)  Im[G_ij   conj(X_ij)]
+ *     ind = a contact / NEGF_IND_TOTAL
+ *           (read as negf_gless_int does):   pop_c[i][j] = (1/2 pi) Re[A_c,ij conj(X_ij)]
+ * conj(X_ij) is X_ji for the Hermitian F, S the quantities are defined for; otherwise the formula is applied literally.
+ * X = S: the energy-resolved overlap population (COOP), whose row sums are the Mulliken-projected DOS
+ * -Im (G S)_ii / pi and whose grand total is -Im Tr(G S) / pi; X = F: the Hamilton population (COHP).  For real E and
+ * Hermitian F, S, i (G - G^H) = sum_c A_c exactly, hence  sum_c pop_c[i][j] = (pop[i][j] + pop[j][i]) / 2  (the two
+ * sides come from different kernels and products).
+ * group_of / n_groups as in negf_local_transmission (NULL with n_groups = n: every orbital its own group; empty groups
+ * allowed).  rows_only = 0: out [m][n_groups][n_groups], out[k][a][b] = sum_{i in a, j in b} pop[i][j](E_k);
+ * rows_only = 1: out [m][n_groups], out[k][a] = sum_b table[k][a][b] -- the projected DOS of atom / fragment a, in one
+ * pass over G or A_c, the table never stored; each row is the sum of the very entries rows_only = 0 returns.
+ * Providers: the retarded form serves every provider negf_dos serves; the contact form what negf_local_transmission
+ * serves (coupling matrices handed in by the caller return NEGF_EINVAL: A_c need not be Hermitian then).  NEGF_EINVAL
+ * also for op or rows_only outside {0, 1}, an invalid map and n > 8192.  A singular energy gives a NaN table / row and
+ * its info, as negf_transmission.  All sums have a fixed order (no atomics): results are bitwise equal from run to run,
+ * do not depend on negf_set_batch, and relabelling the groups permutes table and rows bit for bit.  The _dev form keeps
+ * the grid and the result in HBM (group_of stays a host array) and is asynchronous. */
+int negf_population(negf_ctx* ctx, int handle, int ind, int op, int rows_only, int m, const double* E_c128, int n_groups,
+                    const int* group_of, double* out, int* info);
+int negf_population_dev(negf_ctx* ctx, int handle, int ind, int op, int rows_only, int m, const double* E_dev,
+                        int n_groups, const int* group_of, double* out_dev);
+/* Projection on k vectors w_a (W_c128 [k][n], each vector contiguous, 1 <= k <= n; fragment orbitals: pass w = S c for
+ * orbital coefficients c, <phi|G|phi> = c^H S G S c in a non-orthogonal basis):
+ *     ind = NEGF_IND_RETARDED:  p_a   = -(1/pi)  Im[w_a^H G   w_a]
+ *     contact form:             p_c,a = (1/2 pi) Re[w_a^H A_c w_a]
+ * out [m][k].  One batched product Y = G W^T (or A_c W^T) with W shared by the batch, then w_a^H y_a column by column.
+ * For real E and Hermitian F, S: sum_c p_c,a = p_a; for a complete S-orthonormal set C (C^H S C = 1, w = S c):
+ * sum_a p_a = -Im Tr(G S) / pi, the sum of negf_population's rows with X = S.  Providers, NaN / info and NEGF_EINVAL as
+ * for negf_population; k outside 1 .. n is NEGF_EINVAL.  Every sum has a fixed order that depends on n alone: bitwise
+ * equal from run to run, independent of negf_set_batch, and p_a does not depend on k or on the other vectors.  In the
+ * _dev form the grid, W and the result are in HBM. */
+int negf_projected_dos(negf_ctx* ctx, int handle, int ind, int m, const double* E_c128, int k, const double* W_c128,
+                       double* out, int* info);
+int negf_projected_dos_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, int k, const double* W_dev,
+                           double* out_dev);
+
 /* ------------------------------------------------------------- diagnostics */
 /* hipEvent timing of the library's own kernels, per kernel family
- * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig", "bond";
+ * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig", "bond", "pop";
  * "chain1d_rd": the renormalisation-decimation solver's launches, "chain1d_hit" / "chain1d_rd_hit": g(E) cache hits). */
 /* device bytes held by the context's energy workspace: the three n x n work areas per energy in flight (work) and the
  * staging of the self-energy blocks of CHAIN1D / BETHE providers (blocks); either pointer may be NULL */
