@@ -186,10 +186,11 @@ def eigh_ratios(A, w, V):
     return rr, np.linalg.norm(V.conj().T @ V - np.eye(K)) / (K * U_ROUND)
 
 
-def jacobi_eigh(A, max_sweeps=30):
+def jacobi_eigh(A, max_sweeps=30, stop_eps=None):
     """Plain numpy restatement of the device solver: cyclic two-sided complex Jacobi in round-robin order, K/2 disjoint
     rotations per step (phase of a_pq removed, real rotation zeroes it), the same skip threshold, power-of-two scaling
-    and stop rule, with the rotations accumulated into V.  (w ascending, V)."""
+    and stop rule, with the rotations accumulated into V.  (w ascending, V).  stop_eps replaces the machine epsilon of the stop
+    rule alone (tests/xprec_channels.py plants an early stop with it); the skip threshold stays."""
     K = A.shape[0]
     Ah = np.tril(A) + np.tril(A, -1).conj().T
     Ah[np.diag_indices(K)] = Ah.diagonal().real
@@ -201,7 +202,7 @@ def jacobi_eigh(A, max_sweeps=30):
     X = np.eye(N, dtype=complex)
     fro2 = np.sum(np.abs(M) ** 2)
     eps = np.finfo(float).eps
-    tol2 = eps * eps * fro2
+    tol2 = (eps if stop_eps is None else stop_eps) ** 2 * fro2
     skip = eps * np.sqrt(fro2) / (4.0 * max(N, 1))
     Mr = N - 1
     for sweep in range(max_sweeps + 1):
