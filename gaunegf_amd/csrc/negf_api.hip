@@ -125,7 +125,8 @@ void free_workspace(negf_ctx* c, bool all = false)
     dev_free(c->d_A); dev_free(c->d_T1); dev_free(c->d_T2); dev_free(c->d_ipiv); dev_free(c->d_site);
     c->batch = 0;
     release_bufs(c->d_blk, c->d_scratch, c->d_gsmall, c->d_small_part);
-    if (all) release_bufs(c->d_seg_out, c->d_ref_P, c->d_chan, c->d_chan_rank, c->d_chan_T, c->d_chan_psi, c->d_bond_map, c->d_bond_carry, c->d_bond_T, c->d_pop_W, c->d_pop_Wt);
+    if (all) release_bufs(c->d_seg_out, c->d_ref_P, c->d_chan, c->d_chan_rank, c->d_chan_T, c->d_chan_psi, c->d_bond_map, c->d_bond_carry, c->d_bond_T, c->d_pop_W, c->d_pop_Wt,
+                          c->d_tmat_H, c->d_tmat_sig, c->d_tmat_gam, c->d_tmat_work, c->d_tmat_tab);
 }
 
 void free_mbuffers(negf_ctx* c)
@@ -2640,6 +2641,198 @@ int negf_projected_dos(negf_ctx* c, int handle, int ind, int m, const double* E,
     if ((rc = negf_projected_dos_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), k,
                                      reinterpret_cast<const double*>(c->d_pop_W.p), c->d_bond_T))) return rc;
     if ((rc = download(c, out, c->d_bond_T.p, cnt))) return rc;
+    return reduce_info(c, m, info);
+}
+
+// ------------------------------------------------- multi-terminal transmission matrix
+// T[a][b](E) = Re Tr[Gamma_a G Gamma_b G^H] between all C terminals -- the provider's contacts followed by the call's
+// probes -- from one inverse per energy (k_tmatrix.hip).  The probes' Sigma blocks enter A = E S - F - Sigma through an
+// n x n copy of F (of F + Sigma_tot for a CONST provider) that carries them and stands in for the original while the
+// call assembles; no existing kernel knows about probes.  The reference has no such function.
+namespace {
+
+// the copy of F / hbase with the probes added stands in for the original until the guard goes out of scope
+struct TmatSwap {
+    cplx** slot = nullptr; cplx* keep = nullptr;
+    void set(cplx** s, cplx* with) { slot = s; keep = *s; *s = with; }
+    ~TmatSwap() { if (slot) *slot = keep; }
+};
+
+struct TmatPlan {
+    int C = 0, nc = 0;
+    std::vector<int> K, ioff, goff, gstride, soff, order, idx;
+    std::vector<int> pairs[3];                             // by tmat_pair_class
+    int max_elems[3] = {0, 0, 0};
+    size_t psum = 0, csum = 0, big_kk = 0;                 // sum K_p^2, sum K_c^2, largest K_a K_b of class 0
+    bool per_energy = false;                               // the contacts' Gamma blocks depend on E (block providers)
+};
+
+// providers whose Gamma_c is confined to a known orbital list, as for the eigenchannels; the probe lists are checked
+int tmat_plan(negf_ctx* c, SigmaProvider* p, int n_probes, const int* probe_nk, const int* probe_inds,
+              const cplx* probe_sigma, TmatPlan* pl)
+{
+    const bool ok = (p->kind == SK_CONST && p->has_blocks) || ((p->kind == SK_CHAIN1D || p->kind == SK_BETHE) && !p->d_xi);
+    if (!ok) return NEGF_EINVAL;
+    if (n_probes < 0 || (n_probes > 0 && (!probe_nk || !probe_inds || !probe_sigma))) return NEGF_EINVAL;
+    const int n = c->n, nc = p->n_contacts;
+    if ((long)nc + n_probes > TMAT_MAX_TERMINALS) return NEGF_EINVAL;
+    const int C = nc + n_probes;
+    pl->C = C; pl->nc = nc; pl->per_energy = p->kind != SK_CONST;
+    pl->K.resize(C); pl->ioff.resize(C); pl->goff.resize(C); pl->gstride.resize(C); pl->soff.resize(C);
+    std::vector<size_t> sig_at(C, 0);
+    size_t psum = 0, isum = 0;
+    std::vector<char> seen(n);
+    for (int q = 0; q < n_probes; ++q) {
+        const int k = probe_nk[q];
+        if (k < 1 || k > n) return NEGF_EINVAL;
+        std::fill(seen.begin(), seen.end(), 0);
+        for (int i = 0; i < k; ++i) {
+            const int v = probe_inds[isum + i];
+            if (v < 0 || v >= n || seen[v]) return NEGF_EINVAL;
+            seen[v] = 1;
+        }
+        isum += k; psum += (size_t)k * k;
+        if (psum > ((size_t)1 << 30)) return NEGF_EINVAL;
+    }
+    size_t csum = 0;
+    for (int k : p->nc) csum += (size_t)k * k;
+    if (csum > ((size_t)1 << 30)) return NEGF_EINVAL;
+    pl->psum = psum; pl->csum = csum;
+    pl->idx = p->h_inds;
+    pl->idx.insert(pl->idx.end(), probe_inds, probe_inds + isum);
+    for (int t = 0; t < nc; ++t) {
+        pl->K[t] = p->nc[t]; pl->ioff[t] = p->inds_off[t]; pl->soff[t] = p->blk_off[t];
+        pl->goff[t] = (int)psum + p->blk_off[t]; pl->gstride[t] = pl->per_energy ? (int)csum : 0;
+    }
+    int io = (int)p->h_inds.size(), so = 0;
+    for (int q = 0; q < n_probes; ++q) {
+        const int t = nc + q, k = probe_nk[q];
+        pl->K[t] = k; pl->ioff[t] = io; pl->soff[t] = so; pl->goff[t] = so; pl->gstride[t] = 0;
+        io += k; so += k * k;
+    }
+    // the order in which the probes are added to H: by content (orbital list, then the block's values compared as
+    // numbers, which a scaling by a power of two keeps), so that it does not follow the caller's order
+    pl->order.resize(n_probes);
+    for (int q = 0; q < n_probes; ++q) pl->order[q] = nc + q;
+    const double* sg = reinterpret_cast<const double*>(probe_sigma);
+    std::stable_sort(pl->order.begin(), pl->order.end(), [&](int a, int b) {
+        const int ka = pl->K[a], kb = pl->K[b];
+        if (ka != kb) return ka < kb;
+        const int* ia = pl->idx.data() + pl->ioff[a];
+        const int* ib = pl->idx.data() + pl->ioff[b];
+        for (int i = 0; i < ka; ++i) if (ia[i] != ib[i]) return ia[i] < ib[i];
+        const double* xa = sg + 2 * (size_t)pl->soff[a];
+        const double* xb = sg + 2 * (size_t)pl->soff[b];
+        for (int i = 0; i < 2 * ka * ka; ++i) if (xa[i] != xb[i]) return xa[i] < xb[i];
+        return false;
+    });
+    for (int a = 0; a < C; ++a)
+        for (int b = 0; b < C; ++b) {
+            const int cls = tmat_pair_class(pl->K[a], pl->K[b]);
+            const int ne = pl->K[a] * pl->K[b];
+            pl->pairs[cls].push_back(a * C + b);
+            pl->max_elems[cls] = std::max(pl->max_elems[cls], ne);
+            if (cls == 0) pl->big_kk = std::max(pl->big_kk, (size_t)pl->K[a] * pl->K[b]);
+        }
+    return NEGF_OK;
+}
+
+}  // namespace
+
+int negf_transmission_matrix_dev(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                                 const double* probe_sigma, int m, const double* E_dev, double* T_dev)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    TmatPlan pl;
+    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
+    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &pl))) return rc;
+    if (m > 0 && (!E_dev || !T_dev)) return NEGF_EINVAL;
+    if (m == 0) { c->last_m = 0; return NEGF_OK; }
+    const int n = c->n, C = pl.C, nc = pl.nc;
+    const size_t n2 = (size_t)n * n, C2 = (size_t)C * C;
+    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
+    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
+    const int batch = c->batch;
+    // the tables: K | ioff | goff | gstride | soff | probe order | orbital lists | the pair lists of the three classes
+    std::vector<int> tab;
+    tab.reserve((size_t)5 * C + n_probes + pl.idx.size() + C2);
+    for (const std::vector<int>* v : {&pl.K, &pl.ioff, &pl.goff, &pl.gstride, &pl.soff, &pl.order, &pl.idx})
+        tab.insert(tab.end(), v->begin(), v->end());
+    size_t pair_at[3];
+    for (int k = 0; k < 3; ++k) { pair_at[k] = tab.size(); tab.insert(tab.end(), pl.pairs[k].begin(), pl.pairs[k].end()); }
+    if ((rc = ensure_cap(c, c->d_tmat_tab, tab.size())) || (rc = upload(c, c->d_tmat_tab.p, tab.data(), tab.size()))) return rc;
+    const int* dK = c->d_tmat_tab;
+    const int *d_ioff = dK + C, *d_goff = dK + 2 * C, *d_gstride = dK + 3 * C, *d_soff = dK + 4 * C;
+    const int* d_order = dK + 5 * C;
+    const int* d_idx = d_order + n_probes;
+    if ((rc = ensure_cap(c, c->d_tmat_gam, pl.psum + pl.csum * (pl.per_energy ? batch : 1)))) return rc;
+    if ((rc = ensure_cap(c, c->d_tmat_work, pl.big_kk * batch))) return rc;
+    cplx* gam = c->d_tmat_gam;
+    TmatSwap swap;
+    {
+        ProfScope ps(c, "tmat");
+        if (n_probes > 0) {
+            if ((rc = ensure_cap(c, c->d_tmat_sig, pl.psum)) || (rc = upload(c, c->d_tmat_sig.p, psig, pl.psum))) return rc;
+            if ((rc = ensure_cap(c, c->d_tmat_H, n2))) return rc;
+            cplx** base = p->kind == SK_CONST ? &p->d_hbase : &c->d_F;
+            NEGF_HIP_CHECK(hipMemcpyAsync(c->d_tmat_H.p, *base, n2 * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
+            launch_tmat_add_probes(c->stream, n, n_probes, d_order, dK, d_ioff, d_soff, d_idx, c->d_tmat_sig, c->d_tmat_H);
+            launch_tmat_gamma(c->stream, nc, n_probes, 1, dK, d_soff, d_goff, d_gstride, c->d_tmat_sig, 0, gam);
+            swap.set(base, c->d_tmat_H.p);
+        }
+        if (!pl.per_energy) launch_tmat_gamma(c->stream, 0, nc, 1, dK, d_soff, d_goff, d_gstride, p->d_const_blk, 0, gam);
+    }
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    for (int m0 = 0; m0 < m; m0 += batch) {
+        const int nb = std::min(batch, m - m0);
+        if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
+        ProfScope ps(c, "tmat");
+        double* T = T_dev + C2 * m0;
+        if (pl.per_energy)
+            launch_tmat_gamma(c->stream, 0, nc, nb, dK, d_soff, d_goff, d_gstride, c->d_blk, (size_t)p->blk_stride, gam);
+        double cmadds = 0;
+        for (int cls = 1; cls <= 2; ++cls) {
+            launch_tmat_pairs(c->stream, cls, n, C, (int)pl.pairs[cls].size(), pl.max_elems[cls], nb,
+                              c->d_tmat_tab.p + pair_at[cls], dK, d_ioff, d_goff, d_gstride, d_idx, c->G, gam, T);
+            for (int pr : pl.pairs[cls]) {
+                const double ka = pl.K[pr / C], kb = pl.K[pr % C];
+                cmadds += ka * kb * (ka + kb);
+            }
+        }
+        negf_count_flops(8.0 * cmadds * nb, 0.0);
+        // pairs of two lead-sized blocks (and blocks beyond the LDS of the pair kernel): G_ab gathered, X = Gamma_a G_ab,
+        // Y = X Gamma_b on the matrix cores, T = Re sum Y conj(G_ab)
+        for (int pr : pl.pairs[0]) {
+            const int a = pr / C, b = pr - a * C, Ka = pl.K[a], Kb = pl.K[b];
+            const size_t kk = (size_t)Ka * Kb;
+            cplx* Gab = c->d_tmat_work;
+            launch_gather_block(c->stream, n, Ka, Kb, nb, c->G, n2, d_idx + pl.ioff[a], d_idx + pl.ioff[b], Gab, kk);
+            launch_zgemm(c->stream, Ka, Kb, Ka, nb, gam + pl.goff[a], Ka, (size_t)pl.gstride[a], Gab, Kb, kk, 0, c->W1, Kb, n2);
+            launch_zgemm(c->stream, Ka, Kb, Kb, nb, c->W1, Kb, n2, gam + pl.goff[b], Kb, (size_t)pl.gstride[b], 0, c->W2, Kb, n2);
+            launch_trace_dot(c->stream, Ka, Kb, nb, c->W2, Kb, n2, Gab, Kb, kk, T + (size_t)a * C + b, (int)C2);
+        }
+        launch_tmat_nan(c->stream, C, nb, c->d_info + m0, T);
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_transmission_matrix(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                             const double* probe_sigma, int m, const double* E, double* T, int* info)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    if (n_probes < 0 || (long)p->n_contacts + n_probes > TMAT_MAX_TERMINALS || (m > 0 && (!E || !T))) return NEGF_EINVAL;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    const size_t C = (size_t)p->n_contacts + n_probes, cnt = (size_t)m * C * C;
+    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
+    if ((rc = negf_transmission_matrix_dev(c, handle, n_probes, probe_nk, probe_inds, probe_sigma, m,
+                                           reinterpret_cast<double*>(c->d_E), c->d_bond_T))) return rc;
+    if ((rc = download(c, T, c->d_bond_T.p, cnt))) return rc;
     return reduce_info(c, m, info);
 }
 

@@ -246,6 +246,11 @@ struct negf_ctx {
     DevBuf<double> d_bond_T;       // [m][ng][ng] staging of the host-pointer entry point (negf_population / negf_projected_dos stage here too)
     DevBuf<cplx> d_pop_W;          // projected DOS: the vectors W [k][n] of the host-pointer entry point
     DevBuf<cplx> d_pop_Wt;         // ... and their transpose Wt [n][k], the second operand of Y = M Wt
+    DevBuf<cplx> d_tmat_H;         // transmission matrix: [n*n] F (CONST: F + Sigma_tot) with the call's probe blocks added
+    DevBuf<cplx> d_tmat_sig;       // the probes' Sigma blocks, concatenated
+    DevBuf<cplx> d_tmat_gam;       // Gamma blocks: probes and CONST contacts once | [batch][sum K_c^2] of a block provider's contacts
+    DevBuf<cplx> d_tmat_work;      // [batch][K_a K_b] G_ab of the pairs that take the gather / product / trace kernels
+    DevBuf<int> d_tmat_tab;        // K | ioff | goff | gstride | soff [C each] | probe order [n_probes] | orbital lists | pair lists
     GjSideStreams gj_side;
     int chain_rr_quantum = -1, chain_rr_slots = 0;   // negf_set_chain_round_robin
     int small_algo = 0;            // 0: n <= 96 takes the fused single-kernel path, 1: never (negf_set_small_algo)
@@ -477,6 +482,25 @@ bool launch_population(hipStream_t st, int n, int nb, bool retarded, const cplx*
 void launch_pop_transpose_w(hipStream_t st, int n, int k, const cplx* W, cplx* Wt);
 void launch_pop_coldot(hipStream_t st, int n, int k, int nb, bool retarded, const cplx* Wt, const cplx* Y, size_t strideY,
                        const int* info, double* out);
+
+// Multi-terminal transmission matrix (k_tmatrix.hip).  Terminal tables on the device, C entries each: tK = block size,
+// ioff = start of the orbital list in idx, goff / gstride = where Gamma_t of energy b sits in gam (gam + b * gstride[t] +
+// goff[t]; gstride 0: one block for all energies), soff = where Sigma_t sits in the source of launch_tmat_gamma.
+constexpr int TMAT_SMALL_K = 15, TMAT_TINY_ELEMS = 128, TMAT_LDS_ELEMS = 1536, TMAT_MAX_TERMINALS = 1024;
+// Gamma_t = i (Sigma_t - Sigma_t^H) for the terminals [t0, t0 + nt) and nb energies (src_stride 0, nb 1: constant blocks)
+void launch_tmat_gamma(hipStream_t st, int t0, int nt, int nb, const int* tK, const int* soff, const int* goff,
+                       const int* gstride, const cplx* src, size_t src_stride, cplx* dst);
+// H[I_p, I_p] += Sigma_p for the probes order[0 .. n_probes) (terminal numbers), one after the other
+void launch_tmat_add_probes(hipStream_t st, int n, int n_probes, const int* order, const int* tK, const int* ioff,
+                            const int* soff, const int* idx, const cplx* sig, cplx* H);
+// 0: the pair (K_a, K_b) takes the gather / product / trace kernels, 1 / 2: launch_tmat_pairs with 64 / 256 threads
+int tmat_pair_class(int Ka, int Kb);
+// T[b][a][b'] for the pairs (a * C + b') of one class and nb energies; max_elems >= K_a K_b of every pair listed
+void launch_tmat_pairs(hipStream_t st, int cls, int n, int C, int npairs, int max_elems, int nb, const int* pairs,
+                       const int* tK, const int* ioff, const int* goff, const int* gstride, const int* idx, const cplx* G,
+                       const cplx* gam, double* T);
+// T[b][..] = NaN where info[b] != 0
+void launch_tmat_nan(hipStream_t st, int C, int nb, const int* info, double* T);
 
 bool small_fused_supported(int n);
 int small_fused_grid(int n, int m);

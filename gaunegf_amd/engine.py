@@ -183,12 +183,17 @@ class Engine:
         return conv, 0
 
     # ------------------------------------------------------------ providers
+    def _made(self, handle, n_contacts):
+        """Remember how many contacts the provider behind ``handle`` has (transmission_matrix sizes its result by it)."""
+        self.__dict__.setdefault("_n_contacts", {})[int(handle)] = int(n_contacts)
+        return handle
+
     def sigma_const(self, sigmas):
         sig = _c128(np.stack([np.asarray(s) for s in sigmas]))
         assert sig.shape[1:] == (self.n, self.n), "sigma shape must match F"
         h = C.c_int(-1)
         check(self._lib.negf_sigma_const(self._ctx, sig.shape[0], _ptr(sig), C.byref(h)), "negf_sigma_const")
-        return h.value
+        return self._made(h.value, sig.shape[0])
 
     def sigma_chain1d(self, inds_list, alphas, Salphas, betas, Sbetas, taus, Staus,
                       eta, conv, relFactor, max_iter=2000, force_iters=-1, solver='fixed-point',
@@ -216,12 +221,12 @@ class Engine:
                                                   _ptr(b), _ptr(Sb), _ptr(t), _ptr(St), float(eta), float(tol),
                                                   int(max_steps), int(force_iters), C.byref(h)),
                   "negf_sigma_chain1d_rd")
-            return h.value
+            return self._made(h.value, len(nc))
         check(self._lib.negf_sigma_chain1d(self._ctx, len(nc), _ptr(nc), _ptr(inds), _ptr(a), _ptr(Sa),
                                            _ptr(b), _ptr(Sb), _ptr(t), _ptr(St), float(eta), float(conv),
                                            float(relFactor), int(max_iter), int(force_iters), C.byref(h)),
               "negf_sigma_chain1d")
-        return h.value
+        return self._made(h.value, len(nc))
 
     def sigma_bethe(self, atom_orbs, atom_nbs, H, Slist, Vlist, xi, eta, conv, mix=0.5,
                     max_iter=1000, force_iters=-1):
@@ -243,7 +248,7 @@ class Engine:
                                          _ptr(nb), _ptr(Hc), _ptr(Sc), _ptr(Vc), _ptr(xi_c), float(eta),
                                          float(conv), float(mix), int(max_iter), int(force_iters),
                                          C.byref(h)), "negf_sigma_bethe")
-        return h.value
+        return self._made(h.value, len(n_atoms))
 
     def bethe_raw(self, H, Slist, Vlist, eta, conv, E, which, mix=0.5, max_iter=1000, force_iters=-1):
         """surfGBAt.sigmaK (which=1 -> [m,12,9,9]) / surfGBAt.sigma (which=2 -> [m,9,9,9])."""
@@ -284,7 +289,7 @@ class Engine:
         h = C.c_int(-1)
         check(self._lib.negf_sigma_precomputed(self._ctx, m, _ptr(st), ncc, _ptr(sc), C.byref(h)),
               "negf_sigma_precomputed")
-        return h.value
+        return self._made(h.value, max(abs(ncc), 1))
 
     def sigma_free(self, handle):
         if getattr(self, "_ctx", None):
@@ -719,6 +724,66 @@ class Engine:
         if rc == _lib.NEGF_EINVAL:
             raise NotImplementedError(self._POP_REFUSED)
         check(rc, "negf_projected_dos_dev")
+
+    # ------------------------------------------------ multi-terminal transmission matrix
+    _TMAT_REFUSED = ("the transmission matrix needs a self-energy provider whose couplings live on known contact orbital "
+                     "lists (constant Sigma with a nonzero support per contact, 1-D chain leads, Bethe leads without the "
+                     "Xi Sigma Xi transform) and at most 1024 terminals; this provider is not served")
+
+    def _probes(self, probes):
+        """(n_probes, sizes int32, concatenated indices int32, concatenated blocks complex128) of a list of
+        (indices, block); ValueError for an invalid list."""
+        if not probes:
+            return 0, None, None, None
+        nk, inds, blocks = [], [], []
+        for q, (idx, blk) in enumerate(probes):
+            idx = np.asarray(idx).ravel()
+            if idx.size < 1 or not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError(f"probe {q}: the orbital list must be a non-empty list of integers")
+            if idx.min() < 0 or idx.max() >= self.n or np.unique(idx).size != idx.size:
+                raise ValueError(f"probe {q}: orbital indices must be distinct and lie in [0, {self.n})")
+            blk = np.asarray(blk)
+            if blk.shape != (idx.size, idx.size):
+                raise ValueError(f"probe {q}: expected a {idx.size}x{idx.size} block, got {blk.shape}")
+            nk.append(idx.size); inds.append(idx.astype(np.int32)); blocks.append(_c128(blk).ravel())
+        return (len(nk), np.array(nk, dtype=np.int32), np.ascontiguousarray(np.concatenate(inds)),
+                np.ascontiguousarray(np.concatenate(blocks)))
+
+    def terminal_count(self, handle, probes=None):
+        """C = the provider's contacts + the probes: the size of transmission_matrix's result."""
+        nc = self.__dict__.get("_n_contacts", {}).get(int(handle))
+        if nc is None:
+            raise ValueError(f"handle {handle} was not created by this engine")
+        return nc + (len(probes) if probes else 0)
+
+    def transmission_matrix(self, handle, E, probes=None):
+        """T [m, C, C] between all terminals of the junction from one inverse per energy (negf_transmission_matrix):
+        T[k, a, b] = Re Tr[Gamma_a G Gamma_b G^H](E_k), the transmission from b into a; the terminals are the provider's
+        contacts followed by ``probes``, a list of (orbital indices, K x K complex block Sigma_p) -- fictitious,
+        energy-independent contacts whose blocks are subtracted from E S - F - Sigma on their orbitals.  Matrices of
+        singular energies are NaN (with a warning, as transmission).  NotImplementedError for providers without
+        contact orbital lists."""
+        npr, nk, inds, sig = self._probes(probes)
+        Cn = self.terminal_count(handle, probes)
+        E, _ = self._grid(E)
+        T = np.zeros((E.size, Cn, Cn), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lib.negf_transmission_matrix(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig), E.size,
+                                                _ptr(E), _ptr(T), _ptr(info))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._TMAT_REFUSED)
+        self._numerical(check(rc, "negf_transmission_matrix"), info[:E.size], "transmission_matrix")
+        return T
+
+    def transmission_matrix_dev(self, handle, m, E_ptr, T_ptr, probes=None):
+        """negf_transmission_matrix_dev: grid and the [m, C, C] result in HBM; ``probes`` stays a host list (or None)."""
+        npr, nk, inds, sig = self._probes(probes)
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        rc = self._lib.negf_transmission_matrix_dev(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig), int(m),
+                                                    C.c_void_p(E_ptr), C.c_void_p(T_ptr))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._TMAT_REFUSED)
+        check(rc, "negf_transmission_matrix_dev")
 
     def dos(self, handle, E, per_site=True):
         """negf_dos: -Im diag G / pi, the reference's _dos_kernel -- it ignores the overlap matrix.  In a non-orthogonal

@@ -995,6 +995,184 @@ def calculate_current(F, S, sigma_calculator, fermi, qV, T=TEMPERATURE, spin=Non
 
 
 # --------------------------------------------------------------------------- #
+# multi-terminal transmission matrix and dephasing probes
+# --------------------------------------------------------------------------- #
+TMAT_CALL_DOUBLES = 1 << 27     # one engine call returns at most this many doubles (1 GiB)
+
+
+def dephasing_probes(S, groups, gamma):
+    """Buettiker / D'Amato-Pastawski dephasing probes for Engine.transmission_matrix and the front ends below: the list
+    of (indices, block) with  Sigma_p = -(i gamma_p / 2) S[I_p, I_p],  hence Gamma_p = gamma_p S_pp -- positive definite
+    in the non-orthogonal basis, and -i gamma / 2 for S = 1.  ``groups``: an orbital -> probe label map of length n
+    (negative: no probe on that orbital; probe p takes the orbitals labelled p, in ascending order; labels without an
+    orbital are skipped) or a list of index lists.  ``gamma``: a scalar or one value per probe."""
+    S = np.asarray(S)
+    n = S.shape[0]
+    if len(groups) > 0 and np.ndim(groups[0]) > 0:
+        lists = [np.asarray(g, dtype=int).ravel() for g in groups]
+    else:
+        g = np.asarray(groups).ravel()
+        if g.size != n or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError(f"groups must be an integer label per orbital (length {n}) or a list of index lists")
+        lists = [np.nonzero(g == lab)[0] for lab in range(int(g.max()) + 1 if g.size else 0)]
+        lists = [ix for ix in lists if ix.size]
+    gam = np.broadcast_to(np.asarray(gamma, dtype=float), (len(lists),)) if np.ndim(gamma) == 0 else np.asarray(gamma, dtype=float).ravel()
+    if gam.size != len(lists):
+        raise ValueError(f"gamma must be a scalar or one value per probe ({len(lists)}), got {gam.size}")
+    out = []
+    for ix, gp in zip(lists, gam):
+        if ix.size == 0 or ix.min() < 0 or ix.max() >= n or np.unique(ix).size != ix.size:
+            raise ValueError(f"a probe must be a non-empty list of distinct orbital indices in [0, {n})")
+        out.append((ix, -0.5j * gp * S[np.ix_(ix, ix)].astype(complex)))
+    return out
+
+
+def effective_transmission(T, n_real, source=0, drain=-1):
+    """T_eff [m] between the real terminals ``drain`` and ``source`` of transmission matrices T [m, C, C] whose
+    terminals n_real .. C - 1 are probes that float at every energy (no net current):
+        To = T with zero diagonal,  W_pp = sum_{c != p} To[p][c] (c over ALL terminals),  W_pq = -To[p][q],
+        P' = probes with W_pp > 0 (decoupled probes drop out),
+        T_eff[d][s] = To[d][s] + To[d][P'] W^-1 To[P'][s].
+    One numpy.linalg.solve batched over the energies; NaN matrices (singular energies) give NaN."""
+    T = np.asarray(T, dtype=float)
+    m, C = T.shape[0], T.shape[1]
+    d = drain + n_real if drain < 0 else drain
+    s_ = source + n_real if source < 0 else source
+    if not (0 <= d < n_real and 0 <= s_ < n_real) or d == s_:
+        raise ValueError(f"source and drain must be two different real terminals (0 .. {n_real - 1})")
+    To = T.copy()
+    To[:, np.arange(C), np.arange(C)] = 0.0
+    coh = To[:, d, s_].copy()
+    npr = C - n_real
+    if npr == 0 or m == 0:
+        return coh
+    bad = ~np.isfinite(To).all(axis=(1, 2))
+    To[bad] = 0.0
+    Wd = To[:, n_real:, :].sum(axis=2)                       # [m, npr]
+    on = Wd > 0
+    W = -To[:, n_real:, n_real:]
+    W = W * (on[:, :, None] & on[:, None, :])
+    ar = np.arange(npr)
+    W[:, ar, ar] = np.where(on, Wd, 1.0)
+    rhs = np.where(on, To[:, n_real:, s_], 0.0)
+    row = np.where(on, To[:, d, n_real:], 0.0)
+    x = np.linalg.solve(W, rhs[:, :, None])[:, :, 0]
+    out = coh + np.einsum("mp,mp->m", row, x)
+    out[bad] = np.nan
+    return out
+
+
+def _tmat_contacts(sigma_calc):
+    if not sigma_calc.energy_dependent:
+        return 2
+    nc = getattr(sigma_calc.sig1, "num_contacts", 2)
+    return int(nc() if callable(nc) else nc)
+
+
+def _tmat_layout(F, S, sigma_calc, spin):
+    """[(F, S, perm, static)] as _bond_layout; static: the system is 2N-sized with spin mixing or in the spinor layout
+    and is served for static (sig1, sig2) only, lowered as a CONST provider."""
+    layout = _bond_layout(F, S, sigma_calc, spin)
+    size = np.asarray(F).shape[0]
+    big = spin in ('u', 'ro', 'g') and len(layout) == 1 and size != _sigma_size(sigma_calc)
+    if (spin == 'g' or big) and sigma_calc.energy_dependent:
+        raise NotImplementedError("transmission matrix: the spinor ('g') layout and 'u' / 'ro' systems with spin mixing are "
+                                  "served for static (sig1, sig2) only; energy-dependent providers need 'r' or a "
+                                  "spin-diagonal 'u' / 'ro' system with a spin-expanded N x N self-energy")
+    return [(f, s_, perm, spin == 'g' or big) for f, s_, perm in layout]
+
+
+def _tmat_batch(layout, sigma_calc, energies, spin, probes):
+    """Transmission matrices of all ``energies``: [len(layout), m, C, C]."""
+    energies = np.asarray(energies)
+    eng = get_engine()
+    out = []
+    for F, S, perm, static in layout:
+        size = F.shape[0]
+        pr = probes
+        if sigma_calc.energy_dependent and not hasattr(sigma_calc.sig1, "_negf_lower"):
+            raise NotImplementedError("transmission matrix needs a provider the engine lowers itself (surfGTest, surfG, "
+                                      "surfGB or static matrices); this self-energy object is evaluated on the host")
+        if perm is not None:
+            # block form: position q holds the caller's orbital perm[q]; the probes' indices follow
+            ix = np.ix_(perm, perm)
+            inv = np.empty(size, dtype=int); inv[perm] = np.arange(size)
+            eng.set_system(F[ix], S[ix])
+            sig = [np.asarray(sigma_calc.get_sigma(None, k, spin, size))[ix] for k in (0, -1)]
+            h, temp = eng.sigma_const(sig), True
+            pr = None if not probes else [(inv[np.asarray(i, dtype=int).ravel()], b) for i, b in probes]
+        else:
+            h, temp = _bond_handle(eng, F, S, None, sigma_calc, energies, spin)
+        try:
+            if temp and perm is None:
+                raise NotImplementedError("transmission matrix: this self-energy is staged per energy (no contact orbital "
+                                          "lists); use static matrices or a native surfG / surfGB / surfGTest object")
+            Cn = eng.terminal_count(h, pr)
+            step = max(1, TMAT_CALL_DOUBLES // (Cn * Cn))
+            parts = [eng.transmission_matrix(h, energies[k:k + step], pr) for k in range(0, len(energies), step)]
+            out.append(np.concatenate(parts) if parts else np.zeros((0, Cn, Cn)))
+        finally:
+            if temp:
+                eng.sigma_free(h)
+    return np.stack(out)
+
+
+def calculate_transmission_matrix(F, S, sigma_calculator, energy_list, probes=None, spin=None):
+    """Transmission matrix [m, C, C] between all terminals of the junction, one inverse per energy on the GPU
+    (Engine.transmission_matrix): T[k, a, b] = Re Tr[Gamma_a G Gamma_b G^H](E_k), the transmission from b into a.  The
+    terminals are the contacts of ``sigma_calculator`` followed by ``probes``, a list of (indices, block) -- see
+    dephasing_probes.  T[k, 0, -1] without probes is calculate_transmission's T(E_k).
+    spin: 'r' as is; 'u' / 'ro' on a spin-diagonal system with a spin-expanded N x N self-energy: (up, down), with the
+    probes given on the N orbitals; 'g', and 'u' / 'ro' with spin mixing: static (sig1, sig2) only, on the 2N system
+    with the probes' indices in the caller's orbital order.  Energies are sharded over the ranks."""
+    energy_list = np.asarray(energy_list)
+    if spin is None:
+        spin = 'r'
+    layout = _tmat_layout(F, S, sigma_calculator, spin)
+    Cn = _tmat_contacts(sigma_calculator) + (len(probes) if probes else 0)
+    return _pop_sharded(layout, len(energy_list), (Cn, Cn),
+                        lambda idx: _tmat_batch(layout, sigma_calculator, energy_list[idx], spin, probes))
+
+
+def calculate_effective_transmission(F, S, sigma_calculator, energy_list, probes, source=0, drain=-1, spin=None):
+    """(T_eff [m], T_coherent [m]) between the contacts ``source`` and ``drain`` with the ``probes`` floating at every
+    energy (effective_transmission on calculate_transmission_matrix's result; the solve runs on the host).  T_coherent
+    is the direct term T[drain][source] in the presence of the probes; T_eff = T_coherent for probes of zero strength.
+    A spin-diagonal 'u' / 'ro' system gives the sums over the two spin blocks."""
+    T = calculate_transmission_matrix(F, S, sigma_calculator, energy_list, probes=probes, spin=spin)
+    n_real = _tmat_contacts(sigma_calculator)
+    parts = T if isinstance(T, tuple) else (T,)
+    eff = sum(effective_transmission(t, n_real, source, drain) for t in parts)
+    d = drain + n_real if drain < 0 else drain
+    s_ = source + n_real if source < 0 else source
+    coh = sum(t[:, d, s_] for t in parts)
+    return eff, coh
+
+
+def calculate_effective_current(F, S, sigma_calculator, fermi, qV, probes, T=TEMPERATURE, spin=None, dE=ENERGY_STEP):
+    """Current at bias qV with dephasing probes: calculate_current's grid, occupation factor, trapezoid rule, e/h and
+    spin factor, applied to calculate_effective_transmission's T_eff."""
+    if fermi is None or qV is None:
+        raise ValueError("fermi and qV must be provided for current calculations")
+    if spin is None:
+        spin = 'r'
+    if np.allclose(0, qV):
+        return 0.0
+    energies, muL, muR = current_grid(fermi, qV, T, dE)
+    if len(energies) == 0:
+        raise ValueError("No energies in integration window. Check fermi, qV, and dE.")
+    t_eff, _ = calculate_effective_transmission(F, S, sigma_calculator, energies, probes, spin=spin)
+    if T == 0:
+        total = eoverh * trapezoid(t_eff, energies)
+    else:
+        occupation = np.abs(1 / (np.exp((energies - muR) / (kB * T)) + 1) - 1 / (np.exp((energies - muL) / (kB * T)) + 1))
+        total = eoverh * trapezoid(t_eff * occupation, energies)
+    if spin == 'r':
+        total *= 2
+    return total
+
+
+# --------------------------------------------------------------------------- #
 # Legacy wrappers (gauNEGF/transport.py:724-1107): thin adapters kept so that existing
 # user scripts run unchanged; each one builds a SigmaCalculator and forwards to the
 # batch front-ends above (i.e. to the GPU engine).
@@ -1066,6 +1244,31 @@ def cohTransChannelStates(Elist, F, S, sig1, sig2, nchan=None, source=0):
 def cohTransChannelStatesE(Elist, F, S, g, nchan=None, source=0):
     """(T, psi) with an energy-dependent provider ``g`` (next to cohTransChannelsE)."""
     return calculate_channel_states(F, S, _dynamic_calc(g), Elist, source=source, spin='r', nchan=nchan)
+
+
+def cohTransMatrix(Elist, F, S, sig1, sig2, probes=None):
+    """Transmission matrix [M, C, C] with energy-independent self-energies (next to cohTrans): the two contacts followed
+    by ``probes``."""
+    return calculate_transmission_matrix(F, S, _static_calc(sig1, sig2), Elist, probes=probes, spin='r')
+
+
+def cohTransMatrixE(Elist, F, S, g, probes=None):
+    """Transmission matrix [M, C, C] with an energy-dependent provider ``g`` (next to cohTransE)."""
+    return calculate_transmission_matrix(F, S, _dynamic_calc(g), Elist, probes=probes, spin='r')
+
+
+def cohTransDephased(Elist, F, S, sig1, sig2, probes):
+    """Effective T(E) list with floating dephasing probes, energy-independent self-energies (next to cohTrans)."""
+    T_, _ = calculate_effective_transmission(F, S, _static_calc(sig1, sig2), Elist, probes, spin='r')
+    _report(Elist, T_, "Effective transmission")
+    return T_.tolist()
+
+
+def cohTransDephasedE(Elist, F, S, g, probes):
+    """Effective T(E) list with floating dephasing probes and an energy-dependent provider ``g`` (next to cohTransE)."""
+    T_, _ = calculate_effective_transmission(F, S, _dynamic_calc(g), Elist, probes, spin='r')
+    _report(Elist, T_, "Effective transmission")
+    return T_.tolist()
 
 
 def localTrans(Elist, F, S, sig1, sig2, groups=None):

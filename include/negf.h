@@ -417,9 +417,40 @@ int negf_projected_dos(negf_ctx* ctx, int handle, int ind, int m, const double* 
 int negf_projected_dos_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, int k, const double* W_dev,
                            double* out_dev);
 
+/* --------------------------------------------- multi-terminal transmission matrix and probes
+ * All transmissions between the terminals of a junction from ONE inverse per energy (negf_transmission serves one pair
+ * per call and inverts again for the next; the reference has no such function, and lists decoherence under "Future
+ * development" of its constant self-energy provider).  Terminals: the provider's contacts 0 .. n_c - 1, followed by
+ * n_probes probes, C = n_c + n_probes.  Probe p is an orbital list I_p (probe_nk[p] distinct indices in [0, n),
+ * concatenated in probe_inds) and a K_p x K_p complex block Sigma_p (concatenated in probe_sigma_c128, row-major): a
+ * fictitious, energy-independent contact (Buettiker / D'Amato-Pastawski).  The block need not be anti-Hermitian;
+ * probes may overlap each other and the leads.  Per energy
+ *     A(E)   = E S - F - Sigma_provider(E) - sum_p scatter(Sigma_p on I_p x I_p),    G = A^-1
+ *     Gamma_a = i (Sigma_a - Sigma_a^H)      on terminal a's orbital list (a contact's block, or a probe's)
+ *     T[a][b] = Re Tr[Gamma_a G Gamma_b G^H] = Re sum_{i in I_a, j in I_b} (Gamma_a G_ab Gamma_b)_ij conj(G_ab,ij),
+ *     G_ab = G[I_a, I_b]
+ * T [m][C][C].  T[a][b] is the transmission from b into a: T[L][R] is what negf_transmission(L, R) returns.  The
+ * diagonal is the same formula with a = b (not a reflection).  For real E, Hermitian F, S and Gamma >= 0: T[a][b] >= 0,
+ * the sums of row a and of column a agree (current conservation), T = T^T for real-symmetric F, S, Sigma and in general
+ * NOT for complex-Hermitian F.  n_probes = 0 (the pointers may be NULL): the matrix over the contacts alone.
+ * Providers: those whose Gamma_c lives on a known orbital list, as for negf_transmission_channels -- CONST with a
+ * nonzero support per contact, CHAIN1D (both solvers; the g(E) cache behaves as in any other call), BETHE without Xi;
+ * the lists may cover any share of the orbitals.  NEGF_EINVAL: any other provider, an invalid probe list (size outside
+ * 1 .. n, an index outside [0, n) or named twice in one probe), C > 1024.  The total self-energy is not a terminal.
+ * A singular energy gives a NaN matrix and its info, as negf_transmission; the other energies are unaffected.
+ * Work per energy: K_tot sum_a K_a^2 complex multiply-adds (K_tot = sum_a K_a) behind the one inverse.  No atomics,
+ * every sum in an order fixed by the pair's own (K_a, K_b): results are bitwise equal from run to run, do not depend on
+ * negf_set_batch, and permuting the probes permutes rows and columns of T bit for bit.  The _dev form keeps the grid
+ * and the result in HBM (the probe arrays stay host arrays) and is asynchronous; info via negf_last_info.
+ * Profile family: "tmat". */
+int negf_transmission_matrix(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                             const double* probe_sigma_c128, int m, const double* E_c128, double* T, int* info);
+int negf_transmission_matrix_dev(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                                 const double* probe_sigma_c128, int m, const double* E_dev, double* T_dev);
+
 /* ------------------------------------------------------------- diagnostics */
 /* hipEvent timing of the library's own kernels, per kernel family
- * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig", "bond", "pop";
+ * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig", "bond", "pop", "tmat";
  * "chain1d_rd": the renormalisation-decimation solver's launches, "chain1d_hit" / "chain1d_rd_hit": g(E) cache hits). */
 /* device bytes held by the context's energy workspace: the three n x n work areas per energy in flight (work) and the
  * staging of the self-energy blocks of CHAIN1D / BETHE providers (blocks); either pointer may be NULL */
