@@ -126,7 +126,8 @@ void free_workspace(negf_ctx* c, bool all = false)
     c->batch = 0;
     release_bufs(c->d_blk, c->d_scratch, c->d_gsmall, c->d_small_part);
     if (all) release_bufs(c->d_seg_out, c->d_ref_P, c->d_chan, c->d_chan_rank, c->d_chan_T, c->d_chan_psi, c->d_bond_map, c->d_bond_carry, c->d_bond_T, c->d_pop_W, c->d_pop_Wt,
-                          c->d_tmat_H, c->d_tmat_sig, c->d_tmat_gam, c->d_tmat_work, c->d_tmat_tab);
+                          c->d_tmat_H, c->d_tmat_sig, c->d_tmat_gam, c->d_tmat_work, c->d_tmat_tab,
+                          c->d_deph_T, c->d_deph_R, c->d_deph_work, c->d_deph_D, c->d_deph_tab);
 }
 
 void free_mbuffers(negf_ctx* c)
@@ -2737,19 +2738,21 @@ int tmat_plan(negf_ctx* c, SigmaProvider* p, int n_probes, const int* probe_nk, 
     return NEGF_OK;
 }
 
-}  // namespace
-
-int negf_transmission_matrix_dev(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
-                                 const double* probe_sigma, int m, const double* E_dev, double* T_dev)
-{
-    SigmaProvider* p;
-    int rc = open_call(c, handle, m, &p);
-    if (rc) return rc;
+// What negf_transmission_matrix and the floating-probe calls share behind tmat_plan: the device tables, the probes added
+// to the copy of F that stands in for the original while the call runs (swap), the Gamma blocks that do not depend on E.
+struct TmatRun {
     TmatPlan pl;
-    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
-    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &pl))) return rc;
-    if (m > 0 && (!E_dev || !T_dev)) return NEGF_EINVAL;
-    if (m == 0) { c->last_m = 0; return NEGF_OK; }
+    size_t pair_at[3] = {0, 0, 0};
+    const int *dK = nullptr, *d_ioff = nullptr, *d_goff = nullptr, *d_gstride = nullptr, *d_soff = nullptr;
+    const int *d_order = nullptr, *d_idx = nullptr;
+    cplx* gam = nullptr;
+    TmatSwap swap;
+};
+
+int tmat_setup(negf_ctx* c, SigmaProvider* p, int n_probes, const cplx* psig, int m, TmatRun* r)
+{
+    int rc;
+    const TmatPlan& pl = r->pl;
     const int n = c->n, C = pl.C, nc = pl.nc;
     const size_t n2 = (size_t)n * n, C2 = (size_t)C * C;
     if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
@@ -2760,60 +2763,105 @@ int negf_transmission_matrix_dev(negf_ctx* c, int handle, int n_probes, const in
     tab.reserve((size_t)5 * C + n_probes + pl.idx.size() + C2);
     for (const std::vector<int>* v : {&pl.K, &pl.ioff, &pl.goff, &pl.gstride, &pl.soff, &pl.order, &pl.idx})
         tab.insert(tab.end(), v->begin(), v->end());
-    size_t pair_at[3];
-    for (int k = 0; k < 3; ++k) { pair_at[k] = tab.size(); tab.insert(tab.end(), pl.pairs[k].begin(), pl.pairs[k].end()); }
+    for (int k = 0; k < 3; ++k) { r->pair_at[k] = tab.size(); tab.insert(tab.end(), pl.pairs[k].begin(), pl.pairs[k].end()); }
     if ((rc = ensure_cap(c, c->d_tmat_tab, tab.size())) || (rc = upload(c, c->d_tmat_tab.p, tab.data(), tab.size()))) return rc;
     const int* dK = c->d_tmat_tab;
-    const int *d_ioff = dK + C, *d_goff = dK + 2 * C, *d_gstride = dK + 3 * C, *d_soff = dK + 4 * C;
-    const int* d_order = dK + 5 * C;
-    const int* d_idx = d_order + n_probes;
+    r->dK = dK; r->d_ioff = dK + C; r->d_goff = dK + 2 * C; r->d_gstride = dK + 3 * C; r->d_soff = dK + 4 * C;
+    r->d_order = dK + 5 * C;
+    r->d_idx = r->d_order + n_probes;
     if ((rc = ensure_cap(c, c->d_tmat_gam, pl.psum + pl.csum * (pl.per_energy ? batch : 1)))) return rc;
     if ((rc = ensure_cap(c, c->d_tmat_work, pl.big_kk * batch))) return rc;
-    cplx* gam = c->d_tmat_gam;
-    TmatSwap swap;
-    {
-        ProfScope ps(c, "tmat");
-        if (n_probes > 0) {
-            if ((rc = ensure_cap(c, c->d_tmat_sig, pl.psum)) || (rc = upload(c, c->d_tmat_sig.p, psig, pl.psum))) return rc;
-            if ((rc = ensure_cap(c, c->d_tmat_H, n2))) return rc;
-            cplx** base = p->kind == SK_CONST ? &p->d_hbase : &c->d_F;
-            NEGF_HIP_CHECK(hipMemcpyAsync(c->d_tmat_H.p, *base, n2 * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
-            launch_tmat_add_probes(c->stream, n, n_probes, d_order, dK, d_ioff, d_soff, d_idx, c->d_tmat_sig, c->d_tmat_H);
-            launch_tmat_gamma(c->stream, nc, n_probes, 1, dK, d_soff, d_goff, d_gstride, c->d_tmat_sig, 0, gam);
-            swap.set(base, c->d_tmat_H.p);
-        }
-        if (!pl.per_energy) launch_tmat_gamma(c->stream, 0, nc, 1, dK, d_soff, d_goff, d_gstride, p->d_const_blk, 0, gam);
+    r->gam = c->d_tmat_gam;
+    ProfScope ps(c, "tmat");
+    if (n_probes > 0) {
+        if ((rc = ensure_cap(c, c->d_tmat_sig, pl.psum)) || (rc = upload(c, c->d_tmat_sig.p, psig, pl.psum))) return rc;
+        if ((rc = ensure_cap(c, c->d_tmat_H, n2))) return rc;
+        cplx** base = p->kind == SK_CONST ? &p->d_hbase : &c->d_F;
+        NEGF_HIP_CHECK(hipMemcpyAsync(c->d_tmat_H.p, *base, n2 * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
+        launch_tmat_add_probes(c->stream, n, n_probes, r->d_order, dK, r->d_ioff, r->d_soff, r->d_idx, c->d_tmat_sig, c->d_tmat_H);
+        launch_tmat_gamma(c->stream, nc, n_probes, 1, dK, r->d_soff, r->d_goff, r->d_gstride, c->d_tmat_sig, 0, r->gam);
+        r->swap.set(base, c->d_tmat_H.p);
     }
+    if (!pl.per_energy) launch_tmat_gamma(c->stream, 0, nc, 1, dK, r->d_soff, r->d_goff, r->d_gstride, p->d_const_blk, 0, r->gam);
+    return NEGF_OK;
+}
+
+// the batch [m0, m0 + nb): assemble + inverse (c->G), the contacts' Gamma blocks of a block provider, and -- T != nullptr --
+// the pair / product sequence into T [nb][C][C], NaN for singular energies
+int tmat_batch(negf_ctx* c, SigmaProvider* p, const TmatRun& r, int m0, int nb, const cplx* E, double* T)
+{
+    int rc;
+    const TmatPlan& pl = r.pl;
+    const int n = c->n, C = pl.C, nc = pl.nc;
+    const size_t n2 = (size_t)n * n, C2 = (size_t)C * C;
+    if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
+    ProfScope ps(c, "tmat");
+    if (pl.per_energy)
+        launch_tmat_gamma(c->stream, 0, nc, nb, r.dK, r.d_soff, r.d_goff, r.d_gstride, c->d_blk, (size_t)p->blk_stride, r.gam);
+    if (!T) return NEGF_OK;
+    double cmadds = 0;
+    for (int cls = 1; cls <= 2; ++cls) {
+        launch_tmat_pairs(c->stream, cls, n, C, (int)pl.pairs[cls].size(), pl.max_elems[cls], nb,
+                          c->d_tmat_tab.p + r.pair_at[cls], r.dK, r.d_ioff, r.d_goff, r.d_gstride, r.d_idx, c->G, r.gam, T);
+        for (int pr : pl.pairs[cls]) {
+            const double ka = pl.K[pr / C], kb = pl.K[pr % C];
+            cmadds += ka * kb * (ka + kb);
+        }
+    }
+    negf_count_flops(8.0 * cmadds * nb, 0.0);
+    // pairs of two lead-sized blocks (and blocks beyond the LDS of the pair kernel): G_ab gathered, X = Gamma_a G_ab,
+    // Y = X Gamma_b on the matrix cores, T = Re sum Y conj(G_ab)
+    for (int pr : pl.pairs[0]) {
+        const int a = pr / C, b = pr - a * C, Ka = pl.K[a], Kb = pl.K[b];
+        const size_t kk = (size_t)Ka * Kb;
+        cplx* Gab = c->d_tmat_work;
+        launch_gather_block(c->stream, n, Ka, Kb, nb, c->G, n2, r.d_idx + pl.ioff[a], r.d_idx + pl.ioff[b], Gab, kk);
+        launch_zgemm(c->stream, Ka, Kb, Ka, nb, r.gam + pl.goff[a], Ka, (size_t)pl.gstride[a], Gab, Kb, kk, 0, c->W1, Kb, n2);
+        launch_zgemm(c->stream, Ka, Kb, Kb, nb, c->W1, Kb, n2, r.gam + pl.goff[b], Kb, (size_t)pl.gstride[b], 0, c->W2, Kb, n2);
+        launch_trace_dot(c->stream, Ka, Kb, nb, c->W2, Kb, n2, Gab, Kb, kk, T + (size_t)a * C + b, (int)C2);
+    }
+    launch_tmat_nan(c->stream, C, nb, c->d_info + m0, T);
+    return NEGF_OK;
+}
+
+// R [nb][P][n_c] of the batch whose matrices are in T; the global class of the response kernel goes through in chunks
+// of as many energies as its work area holds
+int deph_run_response(negf_ctx* c, const TmatRun& r, int nb, const double* T, double* R)
+{
+    const int C = r.pl.C, nc = r.pl.nc, P = C - nc;
+    if (P <= 0 || nc <= 0) return NEGF_OK;
+    const size_t per = deph_response_work_doubles(P, nc);
+    int chunk = nb;
+    if (per > 0) {
+        chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)nb, DEPH_WORK_BYTES / (per * sizeof(double))));
+        if (int rc = ensure_cap(c, c->d_deph_work, per * chunk)) return rc;
+    }
+    ProfScope ps(c, "deph");
+    for (int b0 = 0; b0 < nb; b0 += chunk)
+        launch_deph_response(c->stream, C, nc, std::min(chunk, nb - b0), r.d_order, T + (size_t)b0 * C * C, c->d_deph_work,
+                             R + (size_t)b0 * P * nc);
+    return NEGF_OK;
+}
+
+}  // namespace
+
+int negf_transmission_matrix_dev(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                                 const double* probe_sigma, int m, const double* E_dev, double* T_dev)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    TmatRun run;
+    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
+    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &run.pl))) return rc;
+    if (m > 0 && (!E_dev || !T_dev)) return NEGF_EINVAL;
+    if (m == 0) { c->last_m = 0; return NEGF_OK; }
+    if ((rc = tmat_setup(c, p, n_probes, psig, m, &run))) return rc;
+    const size_t C2 = (size_t)run.pl.C * run.pl.C;
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    for (int m0 = 0; m0 < m; m0 += batch) {
-        const int nb = std::min(batch, m - m0);
-        if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
-        ProfScope ps(c, "tmat");
-        double* T = T_dev + C2 * m0;
-        if (pl.per_energy)
-            launch_tmat_gamma(c->stream, 0, nc, nb, dK, d_soff, d_goff, d_gstride, c->d_blk, (size_t)p->blk_stride, gam);
-        double cmadds = 0;
-        for (int cls = 1; cls <= 2; ++cls) {
-            launch_tmat_pairs(c->stream, cls, n, C, (int)pl.pairs[cls].size(), pl.max_elems[cls], nb,
-                              c->d_tmat_tab.p + pair_at[cls], dK, d_ioff, d_goff, d_gstride, d_idx, c->G, gam, T);
-            for (int pr : pl.pairs[cls]) {
-                const double ka = pl.K[pr / C], kb = pl.K[pr % C];
-                cmadds += ka * kb * (ka + kb);
-            }
-        }
-        negf_count_flops(8.0 * cmadds * nb, 0.0);
-        // pairs of two lead-sized blocks (and blocks beyond the LDS of the pair kernel): G_ab gathered, X = Gamma_a G_ab,
-        // Y = X Gamma_b on the matrix cores, T = Re sum Y conj(G_ab)
-        for (int pr : pl.pairs[0]) {
-            const int a = pr / C, b = pr - a * C, Ka = pl.K[a], Kb = pl.K[b];
-            const size_t kk = (size_t)Ka * Kb;
-            cplx* Gab = c->d_tmat_work;
-            launch_gather_block(c->stream, n, Ka, Kb, nb, c->G, n2, d_idx + pl.ioff[a], d_idx + pl.ioff[b], Gab, kk);
-            launch_zgemm(c->stream, Ka, Kb, Ka, nb, gam + pl.goff[a], Ka, (size_t)pl.gstride[a], Gab, Kb, kk, 0, c->W1, Kb, n2);
-            launch_zgemm(c->stream, Ka, Kb, Kb, nb, c->W1, Kb, n2, gam + pl.goff[b], Kb, (size_t)pl.gstride[b], 0, c->W2, Kb, n2);
-            launch_trace_dot(c->stream, Ka, Kb, nb, c->W2, Kb, n2, Gab, Kb, kk, T + (size_t)a * C + b, (int)C2);
-        }
-        launch_tmat_nan(c->stream, C, nb, c->d_info + m0, T);
+    for (int m0 = 0; m0 < m; m0 += c->batch) {
+        const int nb = std::min(c->batch, m - m0);
+        if ((rc = tmat_batch(c, p, run, m0, nb, E, T_dev + C2 * m0))) return rc;
     }
     c->last_m = m;
     NEGF_HIP_CHECK(hipGetLastError());
@@ -2834,6 +2882,180 @@ int negf_transmission_matrix(negf_ctx* c, int handle, int n_probes, const int* p
                                            reinterpret_cast<double*>(c->d_E), c->d_bond_T))) return rc;
     if ((rc = download(c, T, c->d_bond_T.p, cnt))) return rc;
     return reduce_info(c, m, info);
+}
+
+// ------------------------------------------------- floating dephasing probes: response, G^<, G^r
+// The probes of negf_transmission_matrix left floating at every energy (k_dephase.hip): their response R to the real
+// contacts from the transmission matrices of the batch, and the lesser Green's function's weighted sum with the
+// dephased coupling D_s = Gamma_s + sum_p R_ps Gamma_p in the place of Gamma_s -- one inverse per energy, nothing
+// crosses to the host.  The reference has no such function.
+int negf_probe_response_dev(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                            const double* probe_sigma, int m, const double* E_dev, double* R_dev)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    TmatRun run;
+    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
+    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &run.pl))) return rc;
+    if (m > 0 && (!E_dev || (n_probes > 0 && !R_dev))) return NEGF_EINVAL;
+    if (m == 0) { c->last_m = 0; return NEGF_OK; }
+    if ((rc = tmat_setup(c, p, n_probes, psig, m, &run))) return rc;
+    const size_t C2 = (size_t)run.pl.C * run.pl.C, pc = (size_t)n_probes * run.pl.nc;
+    if ((rc = ensure_cap(c, c->d_deph_T, C2 * c->batch))) return rc;
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    for (int m0 = 0; m0 < m; m0 += c->batch) {
+        const int nb = std::min(c->batch, m - m0);
+        if ((rc = tmat_batch(c, p, run, m0, nb, E, c->d_deph_T))) return rc;
+        if ((rc = deph_run_response(c, run, nb, c->d_deph_T, R_dev + pc * m0))) return rc;
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_probe_response(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                        const double* probe_sigma, int m, const double* E, double* R, int* info)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    if (n_probes < 0 || (long)p->n_contacts + n_probes > TMAT_MAX_TERMINALS || (m > 0 && (!E || (n_probes > 0 && !R)))) return NEGF_EINVAL;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    const size_t cnt = (size_t)m * n_probes * p->n_contacts;
+    if ((rc = ensure_cap(c, c->d_deph_R, cnt))) return rc;
+    if ((rc = negf_probe_response_dev(c, handle, n_probes, probe_nk, probe_inds, probe_sigma, m,
+                                      reinterpret_cast<double*>(c->d_E), c->d_deph_R))) return rc;
+    if ((rc = download(c, R, c->d_deph_R.p, cnt))) return rc;
+    return reduce_info(c, m, info);
+}
+
+int negf_gless_int_probes_dev(negf_ctx* c, int handle, int ind, int n_probes, const int* probe_nk, const int* probe_inds,
+                              const double* probe_sigma, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    SigmaProvider* p;
+    int contact;
+    int rc = open_call(c, handle, m, &p, ind, &contact);
+    if (rc) return rc;
+    TmatRun run;
+    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
+    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &run.pl))) return rc;
+    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
+    const int n = c->n;
+    const size_t n2 = (size_t)n * n;
+    cplx* out = reinterpret_cast<cplx*>(out_dev);
+    if (m == 0) {
+        NEGF_HIP_CHECK(hipMemsetAsync(out, 0, n2 * sizeof(cplx), c->stream));
+        c->last_m = 0;
+        return NEGF_OK;
+    }
+    if ((rc = tmat_setup(c, p, n_probes, psig, m, &run))) return rc;
+    const TmatPlan& pl = run.pl;
+    const int C = pl.C, nc = pl.nc, batch = c->batch;
+    const bool floating = contact >= 0 && n_probes > 0;        // the total needs no response: every weight is 1
+    // the terminals that enter D, in the order they are added: the contact(s), then the probes in content order
+    std::vector<int> list;
+    if (contact >= 0) list.push_back(contact);
+    else for (int t = 0; t < nc; ++t) list.push_back(t);
+    list.insert(list.end(), pl.order.begin(), pl.order.end());
+    // U = the sorted union of their orbitals; the compact products when 2 K_U <= n, otherwise U = all orbitals and D is n x n
+    std::vector<int> where(n, -1), U;
+    for (int t : list)
+        for (int i = 0; i < pl.K[t]; ++i) where[pl.idx[pl.ioff[t] + i]] = 0;
+    for (int i = 0; i < n; ++i) if (where[i] == 0) U.push_back(i);
+    const bool compact = 2 * U.size() <= (size_t)n;
+    if (!compact) { U.resize(n); for (int i = 0; i < n; ++i) U[i] = i; }
+    const int KU = (int)U.size();
+    for (int k = 0; k < KU; ++k) where[U[k]] = k;
+    std::vector<int> tab(U);
+    for (int v : pl.idx) tab.push_back(where[v]);
+    tab.insert(tab.end(), list.begin(), list.end());
+    if ((rc = ensure_cap(c, c->d_deph_tab, tab.size())) || (rc = upload(c, c->d_deph_tab.p, tab.data(), tab.size()))) return rc;
+    const int* d_U = c->d_deph_tab;
+    const int* d_pos = d_U + KU;
+    const int* d_list = d_pos + pl.idx.size();
+    if (floating) {
+        if ((rc = ensure_cap(c, c->d_deph_T, (size_t)C * C * batch))) return rc;
+        if ((rc = ensure_cap(c, c->d_deph_R, (size_t)n_probes * nc * batch))) return rc;
+    }
+    if (compact && (rc = ensure_cap(c, c->d_deph_D, (size_t)KU * KU * batch))) return rc;
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    const cplx* w = reinterpret_cast<const cplx*>(w_dev);
+    NEGF_HIP_CHECK(hipMemsetAsync(out, 0, n2 * sizeof(cplx), c->stream));
+    for (int m0 = 0; m0 < m; m0 += batch) {
+        const int nb = std::min(batch, m - m0);
+        if ((rc = tmat_batch(c, p, run, m0, nb, E, floating ? c->d_deph_T.p : nullptr))) return rc;
+        if (floating && (rc = deph_run_response(c, run, nb, c->d_deph_T, c->d_deph_R))) return rc;
+        cplx* D = compact ? c->d_deph_D.p : c->W1;
+        const size_t sD = compact ? (size_t)KU * KU : n2;
+        {
+            ProfScope ps(c, "deph");
+            launch_deph_coupling(c->stream, KU, nc, n_probes, floating ? contact : -1, (int)list.size(), nb, d_list, run.dK,
+                                 run.d_ioff, run.d_goff, run.d_gstride, d_pos, run.gam, c->d_deph_R, D, sD);
+        }
+        {
+            // G D G^H as run_gless_products takes G Gamma G^H: X = (. D)^H stored conjugate-transposed, W1 = . X (Hermitian)
+            ProfScope ps(c, "zgemm");
+            if (compact) {
+                cplx* Gc = c->W2;                              // [nb][n x K_U]
+                cplx* X = c->W2 + (size_t)n * KU;              // [nb][n x K_U]   (2 n K_U <= n^2)
+                launch_gather_block(c->stream, n, n, KU, nb, c->G, n2, nullptr, d_U, Gc, n2);
+                launch_zgemm(c->stream, n, KU, KU, nb, Gc, KU, n2, D, KU, sD, 4, X, n, n2);
+                launch_zgemm(c->stream, n, n, KU, nb, Gc, KU, n2, X, n, n2, 2, c->W1, n, n2);
+            } else {
+                launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, D, n, sD, 4, c->W2, n, n2);
+                launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, c->W2, n, n2, 2, c->W1, n, n2);
+            }
+        }
+        ProfScope ps(c, "accumulate");
+        launch_accumulate(c->stream, (int)n2, nb, w + m0, c->W1, out, c->W2);
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_gless_int_probes(negf_ctx* c, int handle, int ind, int n_probes, const int* probe_nk, const int* probe_inds,
+                          const double* probe_sigma, int m, const double* E, const double* w, double* out, int* info)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    if (n_probes < 0 || (long)p->n_contacts + n_probes > TMAT_MAX_TERMINALS || !out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
+    if ((rc = negf_gless_int_probes_dev(c, handle, ind, n_probes, probe_nk, probe_inds, probe_sigma, m,
+                                        reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
+                                        reinterpret_cast<double*>(c->d_acc)))) return rc;
+    return fetch_result_and_info(c, m, c->d_acc, (size_t)c->n * c->n * sizeof(cplx), out, info);
+}
+
+// sum_k w_k G(E_k) with the probes in A: negf_gr_int_dev's pass while the copy of F that carries the probes stands in
+int negf_gr_int_probes_dev(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                           const double* probe_sigma, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    TmatRun run;
+    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
+    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &run.pl))) return rc;
+    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
+    if (m > 0 && (rc = tmat_setup(c, p, n_probes, psig, m, &run))) return rc;
+    return negf_gr_int_dev(c, handle, m, E_dev, w_dev, out_dev);
+}
+
+int negf_gr_int_probes(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                       const double* probe_sigma, int m, const double* E, const double* w, double* out, int* info)
+{
+    SigmaProvider* p;
+    int rc = open_call(c, handle, m, &p);
+    if (rc) return rc;
+    if (n_probes < 0 || (long)p->n_contacts + n_probes > TMAT_MAX_TERMINALS || !out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
+    if ((rc = negf_gr_int_probes_dev(c, handle, n_probes, probe_nk, probe_inds, probe_sigma, m,
+                                     reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
+                                     reinterpret_cast<double*>(c->d_acc)))) return rc;
+    return fetch_result_and_info(c, m, c->d_acc, (size_t)c->n * c->n * sizeof(cplx), out, info);
 }
 
 // ------------------------------------------------------------ g(E) cache knob

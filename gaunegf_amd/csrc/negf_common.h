@@ -251,6 +251,11 @@ struct negf_ctx {
     DevBuf<cplx> d_tmat_gam;       // Gamma blocks: probes and CONST contacts once | [batch][sum K_c^2] of a block provider's contacts
     DevBuf<cplx> d_tmat_work;      // [batch][K_a K_b] G_ab of the pairs that take the gather / product / trace kernels
     DevBuf<int> d_tmat_tab;        // K | ioff | goff | gstride | soff [C each] | probe order [n_probes] | orbital lists | pair lists
+    DevBuf<double> d_deph_T;       // floating probes: [batch][C*C] transmission matrices of the batch
+    DevBuf<double> d_deph_R;       // [batch][P][n_c] responses of the batch (negf_gless_int_probes) / [m][P][n_c] staging of negf_probe_response
+    DevBuf<double> d_deph_work;    // [energies in flight][P (P + n_c)] augmented matrices of the response kernel's global class
+    DevBuf<cplx> d_deph_D;         // [batch][K_U^2] dephased coupling matrices on the union of the orbitals involved
+    DevBuf<int> d_deph_tab;        // the union U [K_U] | the terminals' orbital lists as positions in U | the terminals added, in order
     GjSideStreams gj_side;
     int chain_rr_quantum = -1, chain_rr_slots = 0;   // negf_set_chain_round_robin
     int small_algo = 0;            // 0: n <= 96 takes the fused single-kernel path, 1: never (negf_set_small_algo)
@@ -501,6 +506,21 @@ void launch_tmat_pairs(hipStream_t st, int cls, int n, int C, int npairs, int ma
                        const cplx* gam, double* T);
 // T[b][..] = NaN where info[b] != 0
 void launch_tmat_nan(hipStream_t st, int C, int nb, const int* info, double* T);
+
+// Floating dephasing probes (k_dephase.hip).  The response kernel keeps its augmented matrix [W | rhs] in LDS for
+// P <= DEPH_LDS_MAX_P probes and n_c <= DEPH_LDS_MAX_RHS contacts (80 x 96 doubles = 60 KiB), otherwise in `work`
+// (deph_response_work_doubles per energy).  order [P]: the probes' terminal indices in content order.
+constexpr int DEPH_LDS_MAX_P = 80, DEPH_LDS_MAX_RHS = 16;
+constexpr size_t DEPH_WORK_BYTES = (size_t)256 << 20;      // the global class' work area: energies go through in chunks that fit
+bool deph_response_in_lds(int P, int nc);
+size_t deph_response_work_doubles(int P, int nc);
+// T [nb][C][C] -> R [nb][P][nc]; an energy whose T holds a non-finite entry gives a NaN R
+void launch_deph_response(hipStream_t st, int C, int nc, int nb, const int* order, const double* T, double* work, double* R);
+// D[b] [KU][KU] = sum over the terminals list[0 .. nlist), in that order, of weight * Gamma_t scattered through pos (the
+// terminal's orbital list as positions in U, at ioff[t]); weight = 1 for col < 0 and for contacts, R[b][t - nc][col] for probes
+void launch_deph_coupling(hipStream_t st, int KU, int nc, int P, int col, int nlist, int nb, const int* list, const int* tK,
+                          const int* ioff, const int* goff, const int* gstride, const int* pos, const cplx* gam,
+                          const double* R, cplx* D, size_t strideD);
 
 bool small_fused_supported(int n);
 int small_fused_grid(int n, int m);

@@ -34,7 +34,7 @@ def roots_legendre(N):
 
 from .config import (TEMPERATURE, ADAPTIVE_INTEGRATION_TOL, N_KT, MAX_CYCLES, MAX_GRID_POINTS)
 from . import integrate as _integrate
-from .integrate import GrInt, GrLessInt, GrIntSegments, GrLessIntSegments
+from .integrate import GrInt, GrLessInt, GrIntSegments, GrLessIntSegments, GrLessIntProbes
 
 _ENGINE_GRLESSINT = GrLessInt
 _ENGINE_GRINT = GrInt     # speculation over several levels only while GrInt is the engine's own: a rebound name
@@ -430,6 +430,13 @@ def densityGridN(F, S, g, mu1, mu2, ind=None, N=100, T=TEMPERATURE, showText=Tru
     if showText:
         print('Integration done!')
     return den / (2 * np.pi)
+
+
+def densityGridProbesN(F, S, g, mu1, mu2, probes, ind=None, N=100, T=TEMPERATURE):
+    """Non-equilibrium (bias-window) density with floating dephasing probes: densityGridN's grid, weights and 1 / 2 pi on
+    GrLessIntProbes (the adaptive variants are not served).  The reference has no such function."""
+    energies, weights = bias_window_grid(mu1, mu2, N, T)
+    return GrLessIntProbes(F, S, g, energies, weights, probes, ind) / (2 * np.pi)
 
 
 def densityGridTrap(F, S, g, mu1, mu2, ind=None, N=100, T=TEMPERATURE):

@@ -785,6 +785,98 @@ class Engine:
             raise NotImplementedError(self._TMAT_REFUSED)
         check(rc, "negf_transmission_matrix_dev")
 
+    # ------------------------------------------------ floating dephasing probes
+    # negf_common.h's DEPH_LDS_MAX_P / DEPH_LDS_MAX_RHS (test_dephase_host.test_size_class_constants_agree holds the copies together)
+    DEPH_LDS_MAX_P = 80                           # the response kernel solves in LDS up to this many probes, above in HBM
+    DEPH_LDS_MAX_RHS = 16                         # ... for providers of at most this many contacts
+
+    _DEPH_REFUSED = ("floating probes need a self-energy provider whose couplings live on known contact orbital lists "
+                     "(constant Sigma with a nonzero support per contact, 1-D chain leads, Bethe leads without the "
+                     "Xi Sigma Xi transform) and at most 1024 terminals; this provider is not served")
+
+    def probe_response(self, handle, E, probes):
+        """R [m, P, n_c]: the response of the floating ``probes`` to the provider's contacts (negf_probe_response), solved
+        on the device from the transmission matrices of Engine.transmission_matrix: probe p's occupation at E_k is
+        sum_c R[k, p, c] f_c(E_k).  Rows of decoupled probes are exact zeros; the other rows sum to 1.  Singular energies
+        give NaN (with a warning, as transmission_matrix)."""
+        npr, nk, inds, sig = self._probes(probes)
+        nc = self.terminal_count(handle)
+        E, _ = self._grid(E)
+        R = np.zeros((E.size, npr, nc), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lib.negf_probe_response(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig), E.size, _ptr(E),
+                                           _ptr(R), _ptr(info))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._DEPH_REFUSED)
+        self._numerical(check(rc, "negf_probe_response"), info[:E.size], "probe_response")
+        lost = np.nonzero(np.isnan(R).any(axis=(1, 2)) & (info[:E.size] == 0))[0] if npr else np.zeros(0, dtype=int)
+        if lost.size:
+            warnings.warn(f"probe_response: probes without a path to any contact (singular W, undefined occupations) at "
+                          f"energy indices {lost[:8].tolist()}{'...' if lost.size > 8 else ''}", RuntimeWarning)
+        return R
+
+    def probe_response_dev(self, handle, m, E_ptr, R_ptr, probes):
+        """negf_probe_response_dev: grid and the [m, P, n_c] result in HBM; ``probes`` stays a host list."""
+        npr, nk, inds, sig = self._probes(probes)
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        rc = self._lib.negf_probe_response_dev(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig), int(m),
+                                               C.c_void_p(E_ptr), C.c_void_p(R_ptr))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._DEPH_REFUSED)
+        check(rc, "negf_probe_response_dev")
+
+    def _deph_ind(self, handle, ind, where):
+        """an out-of-range contact index is the error gless_int raises for it, not a refused provider"""
+        nc = self.terminal_count(handle)
+        if ind is not None and not -nc <= int(ind) < nc:
+            check(_lib.NEGF_EINVAL, f"{where}: contact index {ind} outside [-{nc}, {nc})")
+        return _ind(ind)
+
+    def gless_int_probes(self, handle, ind, E, w, probes):
+        """sum_k w_k G D_s G^H [n, n] with the ``probes`` floating (negf_gless_int_probes): D_s = Gamma_s + sum_p R_ps Gamma_p,
+        G the inverse of the matrix that carries the probes; ``ind`` as gless_int (None: all terminals, no solve)."""
+        npr, nk, inds, sig = self._probes(probes)
+        E, w = self._grid(E, w)
+        out = np.zeros((self.n, self.n), dtype=np.complex128)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lib.negf_gless_int_probes(self._ctx, int(handle), self._deph_ind(handle, ind, "negf_gless_int_probes"), npr, _ptr(nk), _ptr(inds), _ptr(sig), E.size,
+                                             _ptr(E), _ptr(w), _ptr(out), _ptr(info))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._DEPH_REFUSED)
+        self._numerical(check(rc, "negf_gless_int_probes"), info[:E.size], "gless_int_probes")
+        return out
+
+    def gless_int_probes_dev(self, handle, ind, m, E_ptr, w_ptr, out_ptr, probes):
+        npr, nk, inds, sig = self._probes(probes)
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        rc = self._lib.negf_gless_int_probes_dev(self._ctx, int(handle), self._deph_ind(handle, ind, "negf_gless_int_probes_dev"), npr, _ptr(nk), _ptr(inds), _ptr(sig), int(m),
+                                                 C.c_void_p(E_ptr), C.c_void_p(w_ptr), C.c_void_p(out_ptr))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._DEPH_REFUSED)
+        check(rc, "negf_gless_int_probes_dev")
+
+    def gr_int_probes(self, handle, E, w, probes):
+        """sum_k w_k G(E_k) [n, n] with the ``probes`` in E S - F - Sigma (negf_gr_int_probes)."""
+        npr, nk, inds, sig = self._probes(probes)
+        E, w = self._grid(E, w)
+        out = np.zeros((self.n, self.n), dtype=np.complex128)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lib.negf_gr_int_probes(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig), E.size, _ptr(E),
+                                          _ptr(w), _ptr(out), _ptr(info))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._DEPH_REFUSED)
+        self._numerical(check(rc, "negf_gr_int_probes"), info[:E.size], "gr_int_probes")
+        return out
+
+    def gr_int_probes_dev(self, handle, m, E_ptr, w_ptr, out_ptr, probes):
+        npr, nk, inds, sig = self._probes(probes)
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        rc = self._lib.negf_gr_int_probes_dev(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig), int(m),
+                                              C.c_void_p(E_ptr), C.c_void_p(w_ptr), C.c_void_p(out_ptr))
+        if rc == _lib.NEGF_EINVAL:
+            raise NotImplementedError(self._DEPH_REFUSED)
+        check(rc, "negf_gr_int_probes_dev")
+
     def dos(self, handle, E, per_site=True):
         """negf_dos: -Im diag G / pi, the reference's _dos_kernel -- it ignores the overlap matrix.  In a non-orthogonal
         basis the population is ``population(handle, Engine.RETARDED, E, rows=True)``."""

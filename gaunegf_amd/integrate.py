@@ -357,6 +357,54 @@ def GrLessInt(F, S, g, Elist, weights, ind=None):
     return _dist.sharded_sum(lambda idx: _partial_gless(engine, g, E[idx], w[idx], ind), E.size)
 
 
+_PROBES_REFUSED = ("floating probes need a self-energy object the engine lowers itself (surfGTest, surfG, surfGB or a "
+                   "constant provider with _negf_lower); this one is evaluated on the host and has no contact orbital lists")
+
+
+def _probes_integral(F, S, g, Elist, weights, again, host, dev):
+    """What GrLessIntProbes and GrIntProbes share: GrLessInt's checks, the spin-diagonal split (the probes on the N
+    orbitals of a block), and the energy sharding -- device resident when the ranks are active, else a host sum."""
+    F = np.asarray(F)
+    S = np.asarray(S)
+    E, w = _as_grid(Elist, weights)
+    _check(F, S, E, w)
+    split = _blockwise(F, S, g, lambda Fb, Sb, gb: again(Fb, Sb, gb, E, w))
+    if split is not None:
+        return split
+    if not hasattr(g, "_negf_lower"):
+        raise NotImplementedError(_PROBES_REFUSED)
+    engine = get_engine()
+    engine.set_system(F, S)
+    E = np.ascontiguousarray(E.ravel(), dtype=np.complex128)
+    w = np.ascontiguousarray(w.ravel(), dtype=np.complex128)
+    h = g._negf_lower(engine)
+    if _dist.is_active() and getattr(engine, "device", None) is not None:
+        return _dist.sharded_device_sum(engine, lambda m, Ep, wp, op: dev(engine, h, m, Ep, wp, op), E, w)
+    zero = lambda: np.zeros((engine.n, engine.n), dtype=np.complex128)
+    # (a host-only engine -- the stub of the sharding test -- takes the host sum under active ranks as well)
+    return _dist.sharded_sum(lambda idx: host(engine, h, E[idx], w[idx]) if E[idx].size else zero(), E.size)
+
+
+def GrLessIntProbes(F, S, g, Elist, weights, probes, ind=None):
+    """Integrated lesser Green's function with floating dephasing probes, N x N complex: sum_k w_k G D_s G^H with
+    D_s = Gamma_s + sum_p R_ps(E_k) Gamma_p and the ``probes`` (a list of (indices, block), see
+    transport.dephasing_probes) in E S - F - Sigma (Engine.gless_int_probes).  ``ind`` as GrLessInt: None (all
+    terminals) or a contact index.  The reference has no such function."""
+    return _probes_integral(F, S, g, Elist, weights,
+                            lambda Fb, Sb, gb, E, w: GrLessIntProbes(Fb, Sb, gb, E, w, probes, ind),
+                            lambda eng, h, E, w: eng.gless_int_probes(h, ind, E, w, probes),
+                            lambda eng, h, m, Ep, wp, op: eng.gless_int_probes_dev(h, ind, m, Ep, wp, op, probes))
+
+
+def GrIntProbes(F, S, g, Elist, weights, probes):
+    """Integrated retarded Green's function with the ``probes`` in E S - F - Sigma (Engine.gr_int_probes): what completes
+    a density with decoherence next to GrLessIntProbes.  The probes do not depend on E: contour grids stay valid."""
+    return _probes_integral(F, S, g, Elist, weights,
+                            lambda Fb, Sb, gb, E, w: GrIntProbes(Fb, Sb, gb, E, w, probes),
+                            lambda eng, h, E, w: eng.gr_int_probes(h, E, w, probes),
+                            lambda eng, h, m, Ep, wp, op: eng.gr_int_probes_dev(h, m, Ep, wp, op, probes))
+
+
 def GrBatch(F, S, g, Elist):
     """[M,N,N] stack of G^r(E_m) (not in the reference API; used by parity tests and
     by callers that need G(E) itself, _gr_matrix_ops integrate.py:67-71)."""

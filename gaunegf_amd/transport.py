@@ -1062,6 +1062,49 @@ def effective_transmission(T, n_real, source=0, drain=-1):
     return out
 
 
+def probe_response(T, n_real):
+    """R [m, P, n_real]: the response of the floating probes (terminals n_real .. C - 1) to the real terminals, from
+    transmission matrices T [m, C, C] -- the host form of Engine.probe_response, next to effective_transmission and with
+    its masking:
+        To = T with zero diagonal,  W_pp = sum_{c != p} To[p][c] (c over ALL terminals),  W_pq = -To[p][q],
+        P' = probes with W_pp > 0,  R[P', :] = W^-1 To[P', 0:n_real];  rows of decoupled probes are exact zeros.
+    Probe p's occupation is f_p = sum_c R[p][c] f_c; for real energies every row over P' sums to 1 and 0 <= R <= 1 to
+    rounding.  One numpy.linalg.solve batched over the energies; NaN matrices (singular energies) give NaN, and so does
+    an energy whose W is singular (probes without a path to any contact)."""
+    T = np.asarray(T, dtype=float)
+    m, C = T.shape[0], T.shape[1]
+    npr = C - n_real
+    if not 0 < n_real <= C:
+        raise ValueError(f"n_real must lie in 1 .. {C}")
+    if npr == 0 or m == 0:
+        return np.zeros((m, npr, n_real))
+    To = T.copy()
+    To[:, np.arange(C), np.arange(C)] = 0.0
+    bad = ~np.isfinite(To).all(axis=(1, 2))
+    To[bad] = 0.0
+    Wd = To[:, n_real:, :].sum(axis=2)                       # [m, npr]
+    on = Wd > 0
+    W = -To[:, n_real:, n_real:]
+    W = W * (on[:, :, None] & on[:, None, :])
+    ar = np.arange(npr)
+    W[:, ar, ar] = np.where(on, Wd, 1.0)
+    rhs = np.where(on[:, :, None], To[:, n_real:, :n_real], 0.0)
+    try:
+        R = np.linalg.solve(W, rhs)
+    except np.linalg.LinAlgError:
+        # probes without a path to any contact (a cluster that sees only itself) make W singular at that energy: NaN
+        # for it, as the device form gives, and the other energies one by one
+        R = np.full(rhs.shape, np.nan)
+        for k in range(m):
+            try:
+                R[k] = np.linalg.solve(W[k], rhs[k])
+            except np.linalg.LinAlgError:
+                on[k] = True
+    R[~on] = 0.0
+    R[bad] = np.nan
+    return R
+
+
 def _tmat_contacts(sigma_calc):
     if not sigma_calc.energy_dependent:
         return 2
@@ -1082,8 +1125,9 @@ def _tmat_layout(F, S, sigma_calc, spin):
     return [(f, s_, perm, spin == 'g' or big) for f, s_, perm in layout]
 
 
-def _tmat_batch(layout, sigma_calc, energies, spin, probes):
-    """Transmission matrices of all ``energies``: [len(layout), m, C, C]."""
+def _tmat_batch(layout, sigma_calc, energies, spin, probes, run=None):
+    """Transmission matrices of all ``energies``: [len(layout), m, C, C]; or, per system, what
+    ``run(engine, handle, probes, energies)`` returns (the floating-probe front ends)."""
     energies = np.asarray(energies)
     eng = get_engine()
     out = []
@@ -1107,6 +1151,9 @@ def _tmat_batch(layout, sigma_calc, energies, spin, probes):
             if temp and perm is None:
                 raise NotImplementedError("transmission matrix: this self-energy is staged per energy (no contact orbital "
                                           "lists); use static matrices or a native surfG / surfGB / surfGTest object")
+            if run is not None:
+                out.append(run(eng, h, pr, energies))
+                continue
             Cn = eng.terminal_count(h, pr)
             step = max(1, TMAT_CALL_DOUBLES // (Cn * Cn))
             parts = [eng.transmission_matrix(h, energies[k:k + step], pr) for k in range(0, len(energies), step)]
@@ -1170,6 +1217,55 @@ def calculate_effective_current(F, S, sigma_calculator, fermi, qV, probes, T=TEM
     if spin == 'r':
         total *= 2
     return total
+
+
+def _deph_layout(F, S, sigma_calc, spin):
+    layout = _tmat_layout(F, S, sigma_calc, spin)
+    if any(static for *_, static in layout):
+        raise NotImplementedError("floating probes: the spinor ('g') layout and 'u' / 'ro' systems with spin mixing are not "
+                                  "served; use 'r' or a spin-diagonal 'u' / 'ro' system with a spin-expanded N x N self-energy")
+    return layout
+
+
+def calculate_probe_response(F, S, sigma_calculator, energy_list, probes, spin=None):
+    """R [m, P, n_c]: the response of the floating ``probes`` to the contacts at every energy, solved on the GPU behind
+    the transmission matrices (Engine.probe_response; the host form is probe_response on
+    calculate_transmission_matrix's result).  Probe p's occupation is sum_c R[k, p, c] f_c(E_k).
+    spin: 'r' as is; 'u' / 'ro' on a spin-diagonal system with a spin-expanded N x N self-energy: (up, down), with the
+    probes given on the N orbitals.  'g' and spin mixing raise NotImplementedError.  Energies are sharded over the ranks."""
+    energy_list = np.asarray(energy_list)
+    if spin is None:
+        spin = 'r'
+    layout = _deph_layout(F, S, sigma_calculator, spin)
+    nc = _tmat_contacts(sigma_calculator)
+    P = len(probes) if probes else 0
+    return _pop_sharded(layout, len(energy_list), (P, nc),
+                        lambda idx: _tmat_batch(layout, sigma_calculator, energy_list[idx], spin, probes,
+                                                run=lambda eng, h, pr, E: eng.probe_response(h, E, pr)))
+
+
+def calculate_probe_occupations(F, S, sigma_calculator, energy_list, probes, fermi, qV, T=TEMPERATURE, spin=None):
+    """f_p(E) [m, P]: the occupations the floating ``probes`` take at bias qV -- the local chemical-potential profile of a
+    dephased junction -- f_p = R[p][0] f_L + R[p][-1] f_R with calculate_current's muL = fermi + qV / 2,
+    muR = fermi - qV / 2 and Fermi functions (step functions at T = 0).  A probe that is the only path between two parts
+    of a device takes the occupation of the side that feeds it.  (up, down) for a spin-diagonal 'u' / 'ro' system."""
+    if fermi is None or qV is None:
+        raise ValueError("fermi and qV must be provided for probe occupations")
+    energy_list = np.asarray(energy_list)
+    if _tmat_contacts(sigma_calculator) != 2:
+        raise NotImplementedError("probe occupations at a bias are defined for two contacts; use calculate_probe_response "
+                                  "with your own occupations for more")
+    R = calculate_probe_response(F, S, sigma_calculator, energy_list, probes, spin=spin)
+    muL, muR = fermi + qV / 2, fermi - qV / 2
+    E = np.real(energy_list).astype(float)
+
+    def occ(mu):
+        if T == 0:
+            return (E < mu).astype(float) + 0.5 * (E == mu)
+        return 1 / (np.exp((E - mu) / (kB * T)) + 1)
+    f = np.stack([occ(muL), occ(muR)], axis=1)                # [m, 2]
+    one = lambda r: np.einsum("mpc,mc->mp", r, f)
+    return tuple(one(r) for r in R) if isinstance(R, tuple) else one(R)
 
 
 # --------------------------------------------------------------------------- #
@@ -1269,6 +1365,16 @@ def cohTransDephasedE(Elist, F, S, g, probes):
     T_, _ = calculate_effective_transmission(F, S, _dynamic_calc(g), Elist, probes, spin='r')
     _report(Elist, T_, "Effective transmission")
     return T_.tolist()
+
+
+def probeOccupations(Elist, F, S, sig1, sig2, probes, fermi, qV, T=TEMPERATURE):
+    """Occupations f_p(E) [M, P] of floating dephasing probes, energy-independent self-energies (next to cohTransDephased)."""
+    return calculate_probe_occupations(F, S, _static_calc(sig1, sig2), Elist, probes, fermi, qV, T=T, spin='r')
+
+
+def probeOccupationsE(Elist, F, S, g, probes, fermi, qV, T=TEMPERATURE):
+    """Occupations f_p(E) [M, P] of floating dephasing probes with an energy-dependent provider ``g``."""
+    return calculate_probe_occupations(F, S, _dynamic_calc(g), Elist, probes, fermi, qV, T=T, spin='r')
 
 
 def localTrans(Elist, F, S, sig1, sig2, groups=None):

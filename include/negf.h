@@ -448,9 +448,57 @@ int negf_transmission_matrix(negf_ctx* ctx, int handle, int n_probes, const int*
 int negf_transmission_matrix_dev(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
                                  const double* probe_sigma_c128, int m, const double* E_dev, double* T_dev);
 
+/* --------------------------------------------- floating dephasing probes: response, G^<, G^r
+ * The probes of negf_transmission_matrix (same arguments, same providers, same NEGF_EINVAL cases) left FLOATING: at every
+ * energy each probe takes the occupation at which it draws no net current.  Per energy, with T the transmission matrix
+ * over the C = n_c + n_probes terminals and To = T with zero diagonal,
+ *     W_pp = sum_{c != p} To[p][c] (c over ALL terminals),   W_pq = -To[p][q],   P' = the probes with W_pp > 0,
+ *     R[P', :] = W^-1 To[P', 0 .. n_c)        rows of probes outside P' (decoupled probes) are exact zeros
+ * R [m][n_probes][n_c] is the probes' response to the real contacts: probe p's occupation is f_p(E) = sum_c R[p][c] f_c(E).
+ * W is a weakly row-diagonally-dominant M-matrix and W 1 = To[P', real] 1: for real E, Hermitian F, S and Gamma >= 0
+ * every row of R over P' sums to 1 and 0 <= R <= 1 to rounding.  The floating condition is a real-axis notion; complex
+ * energies are not rejected and the formulas are applied literally (as negf_local_transmission applies its own).
+ * The solve is LU without pivoting (backward stable for such W; dominance survives elimination), one workgroup per
+ * energy, rows and columns in an order derived from the probes' content: results are bitwise equal from run to run, do
+ * not depend on negf_set_batch, and permuting the probes permutes the rows of R bit for bit.  An energy that is singular,
+ * or whose T holds a non-finite entry, gives a NaN R and its info, as negf_transmission_matrix.  Probes that reach no
+ * contact at an energy (a cluster that sees only itself) make W singular and leave the occupations undefined: the
+ * elimination meets a pivot that is not positive and the WHOLE R of that energy is NaN, info stays 0 (the inverse was
+ * regular); negf_gless_int_probes' sum for a contact is then NaN as well.  The test is on the pivot as computed: a cluster
+ * whose path to the contacts is merely tiny gives an ill-conditioned W and an R as inaccurate as that.  n_probes = 0: nothing
+ * is written (R may be NULL).  The _dev form keeps the grid and the result in HBM and is asynchronous.
+ * Profile families: "tmat" (the matrices), "deph" (the solve and the coupling assembly below). */
+int negf_probe_response(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                        const double* probe_sigma_c128, int m, const double* E_c128, double* R, int* info);
+int negf_probe_response_dev(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                            const double* probe_sigma_c128, int m, const double* E_dev, double* R_dev);
+/* The lesser Green's function's weighted sum with floating probes, G^< = i sum_c f_c G D_c G^H:
+ *     out = sum_k w_k G(E_k) D_s(E_k) G(E_k)^H,    D_s = scatter(Gamma_s on I_s) + sum_p R[p][s] scatter(Gamma_p on I_p)
+ * with G = A^-1 of the A that carries the probes (negf_transmission_matrix) -- one inverse per energy, the response and
+ * the coupling assembled on the device.  `ind` is read as negf_gless_int reads it; NEGF_IND_TOTAL: D = the sum of ALL
+ * terminals' Gamma (no solve).  The D_s of the contacts add up to that total, Re Tr[Gamma_d G D_s G^H] (d != s) is the
+ * effective transmission with the probes floating, and probes of zero strength give negf_gless_int's result.  The
+ * contacts' matrices are the blocks negf_transmission_matrix uses.  out is n x n, Hermitian for real weights.  A singular
+ * energy enters as negf_gless_int's does.  Overlapping probes are added in an order derived from their content: the
+ * result does not depend on the caller's probe order, nor on negf_set_batch. */
+int negf_gless_int_probes(negf_ctx* ctx, int handle, int ind, int n_probes, const int* probe_nk, const int* probe_inds,
+                          const double* probe_sigma_c128, int m, const double* E_c128, const double* w_c128,
+                          double* out_c128, int* info);
+int negf_gless_int_probes_dev(negf_ctx* ctx, int handle, int ind, int n_probes, const int* probe_nk, const int* probe_inds,
+                              const double* probe_sigma_c128, int m, const double* E_dev, const double* w_dev,
+                              double* out_dev);
+/* sum_k w_k G(E_k) with the probes in A: negf_gr_int's pass on the matrix that carries them.  The probes do not depend
+ * on the energy, so the contour integrals stay valid. */
+int negf_gr_int_probes(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                       const double* probe_sigma_c128, int m, const double* E_c128, const double* w_c128,
+                       double* out_c128, int* info);
+int negf_gr_int_probes_dev(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                           const double* probe_sigma_c128, int m, const double* E_dev, const double* w_dev,
+                           double* out_dev);
+
 /* ------------------------------------------------------------- diagnostics */
 /* hipEvent timing of the library's own kernels, per kernel family
- * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig", "bond", "pop", "tmat";
+ * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig", "bond", "pop", "tmat", "deph";
  * "chain1d_rd": the renormalisation-decimation solver's launches, "chain1d_hit" / "chain1d_rd_hit": g(E) cache hits). */
 /* device bytes held by the context's energy workspace: the three n x n work areas per energy in flight (work) and the
  * staging of the self-energy blocks of CHAIN1D / BETHE providers (blocks); either pointer may be NULL */
