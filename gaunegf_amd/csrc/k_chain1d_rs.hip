@@ -9,12 +9,15 @@
 //   * B = (E + i eta) Sb - b is not stored per workgroup at all: wave w needs only row tile w of B, as
 //     the A operand of T = B g (wave w owns row tile w of T) and, conjugated, as the B operand of
 //     M = A - T B^H (wave w owns column tile w of M); it streams those 16 x n elements from the lead
-//     matrices Sb, b (shared by all workgroups of the contact, L2-resident) a few k-steps ahead.
+//     matrices Sb, b (shared by all workgroups of the contact, L2-resident) a k-step ahead -- from copies of
+//     them that are zero-padded to 64 x 64 at pitch 64 (ChainRsArgs::pad): a lane's element of k-step ks is an
+//     immediate offset from one lane base, rows and columns >= n read zeros, nothing is clamped or selected.
+//     The A of M = A - T B^H is read from the padded alpha, Salpha the same way, a row tile's loads as one batch.
 //   * the iterate g is kept twice: in the work matrix at the start of a sweep (B operand of T = B g;
 //     overwritten by T, then M) and as the "old" g of the mixing step, which each lane writes and
-//     reads back for its own 13 elements only: in a second LDS matrix when two workgroups share
-//     the CU; when three do, the first slots in the unused rows of the work matrix and the rest in a
-//     lane-private global scratch record (L2-resident).
+//     reads back for its own elements only (chain_mix_map.h: 10 slots per lane at n_c = 50): in a second LDS
+//     matrix when two workgroups share the CU; when three do, the first slots in the unused rows of the work
+//     matrix and the rest in a lane-private global scratch record (L2-resident).
 //   * the in-place Gauss-Jordan inverse of M works on panels of 8 columns (RS_PANEL).  The wave on SIMD 0 -- the
 //     CHAIN wave (rs_wave_role: the roles follow the SIMD a wave runs on, because an FP64 matrix instruction holds
 //     its SIMD's vector issue) -- factors every panel: lane = row, DPP arg-max on the high word of |re| + |im|, the
@@ -36,13 +39,31 @@
 // Every job stops on ITS OWN convergence (the reference's vmap runs all energies until the
 // slowest lane converges; results are identical because a converged lane is frozen there).
 #include "negf_common.h"
+#include "chain_mix_map.h"          // the lane map of the mixing step
 #include "chain_rs_inverse.h"       // the small inverse (rs_factor ... rs_inverse) and the 3M helpers, shared with k_chain1d_rd.hip
 #include <algorithm>
+#include <type_traits>
+
+// The three phases around the inverse, each with a switch for A/B timing (1 = on, the default):
+#ifndef RS_PAD_LEADS
+#define RS_PAD_LEADS 1                // the streamed operands of both products and the A of M = A - T B^H are read from the zero-padded
+#endif                                //    lead matrices (ChainRsArgs::pad): one lane base + compile-time offsets, no clamp, no select
+#ifndef RS_BATCH_MSTORE
+#define RS_BATCH_MSTORE 1             // M = A - T B^H: the A loads of a row tile go out as one batch, then the tile is stored: one round trip
+#endif                                //    per row tile; full tiles of a remainder-strip class are stored unguarded (needs RS_PAD_LEADS)
+#ifndef RS_MSTORE_AHEAD
+#define RS_MSTORE_AHEAD 0             // 1: A of row tile ti + 1 requested BEFORE tile ti is stored.  Default 0: the loads of tile ti + 1 go out
+                                      //    AFTER the stores of tile ti (with 1: 39 spilled VGPRs in <51,3,true,false>)
+#endif
+#ifndef RS_DENSE_MIX
+#define RS_DENSE_MIX 1                // mixing on the dense lane map of chain_mix_map.h (10 slots at n_c = 50, not 13), the LDS slots and
+#endif                                //    the global slots of the old iterate as separate loops in their own address spaces
 
 namespace {
 
 struct ChainRsArgs {
     const cplx *alpha, *Salpha, *beta, *Sbeta, *tau, *Stau;   // concatenated per contact
+    const cplx* pad;                 // the same six, zero-padded: [matrix][contact][CHAIN_PAD][CHAIN_PAD] (SigmaProvider::d_lead_pad)
     const int* nc;
     const int* blk_off;
     int n_contacts, blk_stride;
@@ -120,6 +141,42 @@ __global__ void rs_rr_init_kernel(RsQueue* q, unsigned cap, unsigned jobs)
 // RR: the round-robin instantiation (a persistent workgroup that takes its jobs from the queue); the plain one -- a launch
 // whose jobs all fit the resident slots -- carries none of the job loop (its per-job values are loop invariants again:
 // 4.7 % fewer scalar instructions per sweep, 1.7 % faster).
+// a value / pointer that is the same in every lane, kept in scalar registers
+__device__ __forceinline__ double rs_uniform(double v)
+{
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+// Global accesses at  scalar base + compile-time byte offset + one 32-bit lane offset:  the base is the same in every
+// lane and is kept a scalar pair of its own (rs_scalar_base: opaque, so that nothing is re-associated into 64-bit vector
+// arithmetic or hoisted out of the sweep), the lane offset is one register for all accesses of a phase.
+typedef double rs_d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned long long rs_scalar_base(const void* p)
+{
+    unsigned long long b = reinterpret_cast<unsigned long long>(p);
+    asm volatile("" : "+s"(b));
+    return b;
+}
+// (a base advanced by a constant is made opaque again: two scalar instructions where it is used, not a pair of scalar
+//  registers per access kept alive across the sweep)
+__device__ __forceinline__ unsigned long long rs_scalar_advance(unsigned long long b, long long bytes)
+{
+    b += (unsigned long long)bytes;
+    asm volatile("" : "+s"(b));
+    return b;
+}
+__device__ __forceinline__ cplx rs_gload(unsigned long long base, unsigned const_bytes, unsigned lane_bytes)
+{
+    const __attribute__((address_space(1))) char* p = reinterpret_cast<const __attribute__((address_space(1))) char*>(base) + const_bytes;
+    const rs_d2 v = *reinterpret_cast<const __attribute__((address_space(1))) rs_d2*>(p + lane_bytes);
+    return cmake(v.x, v.y);
+}
+__device__ __forceinline__ void rs_gstore(unsigned long long base, unsigned const_bytes, unsigned lane_bytes, cplx v)
+{
+    __attribute__((address_space(1))) char* p = reinterpret_cast<__attribute__((address_space(1))) char*>(base) + const_bytes;
+    rs_d2 w; w.x = v.x; w.y = v.y;
+    *reinterpret_cast<__attribute__((address_space(1))) rs_d2*>(p + lane_bytes) = w;
+}
+
 template <int P, int OCC, bool GOLD_GLOBAL, bool RR>
 __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
     ChainRsArgs a, const cplx* __restrict__ E, cplx* __restrict__ blk, int* __restrict__ iters,
@@ -178,21 +235,29 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
     int job = 0, count = 0, c = 0, b = 0, n = 1, off = 0, ksteps = 1;
     bool resume = false;                                // a job that was set aside after `count` sweeps: its iterate waits in blk
     const int fi = lane & 15, fk = lane >> 4;
-    // the old iterate, element (ks*4 + fk, wave*16 + fi) of g at slot ks of this lane
-    // (global: [slot][thread], coalesced; LDS: a compact n x n matrix behind the work matrix)
-    // Slot ks < gold_lds_slots: LDS, a compact matrix (pitch n) at element gold_lds_off of the dynamic LDS --
-    // behind the work matrix when two workgroups share the CU; when three do, in the rows n_max+2 .. 16*T16-1
-    // of the work matrix itself, which only feed discarded output rows of the padded tiles and may hold any
-    // finite values.  The other slots: global scratch [slot][thread] (coalesced); with the LDS part taken
-    // off, the scratch of the workgroups of an XCD fits its 4 MB L2 and is rewritten there sweep after sweep.
+    // ---- the old iterate of the mixing step.  LIVE layout (RS_DENSE_MIX = 1): the dense lane map of chain_mix_map.h, see
+    // gather_mix_dense below; of the names that follow it uses a.gold and a.gold_lds_off only.  Both layouts keep their LDS
+    // part at element gold_lds_off of the dynamic LDS -- behind the work matrix when two workgroups share the CU; when
+    // three do, in the rows n_max+2 .. 16*T16-1 of the work matrix itself, which only feed discarded output rows of the
+    // padded tiles and may hold any finite values -- and the rest in global scratch [slot][thread] (coalesced); with the
+    // LDS part taken off, the scratch of the workgroups of an XCD fits its 4 MB L2 and is rewritten there sweep after sweep.
+    // LEGACY layout (RS_DENSE_MIX = 0, kept for A/B timing: gather_mix, gold_g, gold_l, LS_CT, lds_slots, and
+    // a.gold_lds_slots of the launcher): element (ks*4 + fk, wave*16 + fi) of g at slot ks of this lane; slot
+    // ks < gold_lds_slots in LDS as a compact matrix (pitch n), the other slots in global scratch.
     cplx* gold_g = GOLD_GLOBAL ? a.gold + ((size_t)slot * KS) * RS_THREADS + tid : nullptr;
     cplx* gold_l = Ws;
-    // LDS slots of the old iterate: LS_CT (what fits when n = P, a compile-time number) or one more
+    // (legacy layout) LDS slots of the old iterate: LS_CT (what fits when n = P, a compile-time number) or one more
     constexpr int LS_FIT = (16 * T16 * P + 16 - (P + 2) * P) / (4 * P);
     constexpr int LS_CT = GOLD_GLOBAL ? (LS_FIT > 0 ? LS_FIT : 0) : KS;
     const int lds_slots = GOLD_GLOBAL ? a.gold_lds_slots : KS;
 
     const cplx *alpha = a.alpha, *Salpha = a.Salpha, *beta = a.beta, *Sbeta = a.Sbeta, *tau = a.tau, *Stau = a.Stau;
+    // RS_PAD_LEADS: matrix k (0 alpha, 1 Salpha, 2 beta, 3 Sbeta, 4 tau, 5 Stau) of the job's contact, padded.  One base and
+    // one stride stay live across the sweep, not six pointers
+    const cplx* pad_c = a.pad; unsigned pad_ps = 0;
+    RsMixMap mm = rs_mix_map(1);                        // the job's lane map of the mixing step (RS_DENSE_MIX): scalars
+    bool final_pass = false;                            // the pass that runs Sigma = t g t^H through the two products
+    auto lead_p = [&](int k) __attribute__((always_inline)) { return pad_c + (size_t)k * pad_ps; };
     cplx e = cmake(0.0, 0.0), z = e;
     const double conv2 = a.conv * a.conv, rf = a.relFactor, rf1 = 1.0 - a.relFactor;
     auto sel = [](bool ok, cplx v) { return cmake(ok ? v.x : 0.0, ok ? v.y : 0.0); };
@@ -207,19 +272,27 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
     // (52-64 VGPRs that the three-workgroups-per-CU budget does not have): each product streams it from the
     // lead matrices, which every workgroup of the contact shares (L2 / L1 resident), PF k-steps ahead.
     // Rows >= n give garbage in output rows / columns >= n only (never stored); k >= n is zeroed.
-#ifndef RS_PF
-#define RS_PF 1
-#endif
-    constexpr int PF = RS_PF;                       // k-steps the streamed operand is requested ahead
-    const cplx* opS = Sbeta; const cplx* opM = beta; cplx opz = z;     // (set per job and per pass)
-    struct Stream { cplx s[PF], m[PF]; };
+    // Padded lead matrices (PADL): a lane's element of k-step ks sits ks * 64 bytes behind its first one -- an immediate
+    // offset, no clamp; rows and k >= n read zeros, and z * 0 - 0 is a zero of either sign, which multiplies finite
+    // values and is added to an accumulator that starts at +0: no stored value depends on the sign.
+    constexpr bool PADL = RS_PAD_LEADS;
+    constexpr int PF = 1;                           // k-steps the streamed operand is requested ahead: two named buffers
+    const cplx* opS = Sbeta; const cplx* opM = beta; cplx opz = z;     // (set per job and per pass; PADL: the padded matrices)
+    struct Stream { cplx s[2], m[2]; };
+    auto stream_row = [&](const cplx* op, int irow, int fk) __attribute__((always_inline)) {
+        return PADL ? op + (unsigned)(irow * CHAIN_PAD + fk) : op + min(irow, n - 1) * n;
+    };
     auto stream_fetch = [&](Stream& q, const cplx* sS, const cplx* sM, int ks, int fk) __attribute__((always_inline)) {
-        const int kc = min(ks * 4 + fk, n - 1);
-        q.s[ks % PF] = sS[kc]; q.m[ks % PF] = sM[kc];
+        const int kc = PADL ? ks * 4 : min(ks * 4 + fk, n - 1);
+        q.s[ks & 1] = sS[kc]; q.m[ks & 1] = sM[kc];
     };
     auto stream_elem = [&](const Stream& q, int ks, int fk) __attribute__((always_inline)) {
-        return sel(ks * 4 + fk < n, csub(cmul(opz, q.s[ks % PF]), q.m[ks % PF]));
+        const cplx v = csub(cmul(opz, q.s[ks & 1]), q.m[ks & 1]);
+        return PADL ? v : sel(ks * 4 + fk < n, v);
     };
+    // k-steps of this job's products: in a remainder-strip class every contact reaches into the strip (the launcher's
+    // class rule), n > 16 TR, so all KS k-steps run and the loops below carry no branch
+    const auto ksteps_of = [&]() __attribute__((always_inline)) { return (REM && PADL) ? KS : ksteps; };
 
     // wave w: acc[tj] = sum_k Op[w*16 + fi][k] * Ws[k][tj*16 + fi]  (row tile w of  Op Ws).  The padding of
     // Ws is zero / finite, output columns >= n are never stored.
@@ -228,8 +301,10 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
         const bool strip_wave = REM && wave == TR;      // this wave's row tile is the row strip
         const cplx* bb = Ws + fk * P + fi;
         const cplx* bb4 = Ws + fk * P + (fi & 3);       // column-strip B operand: column TR*16 + (l&3) in every block
-        const int irow = min(strip_wave ? TR * 16 + (fi & 3) : wave * 16 + fi, n - 1) * n;
-        const cplx* sS = opS + irow; const cplx* sM = opM + irow;
+        const int irow = strip_wave ? TR * 16 + (fi & 3) : wave * 16 + fi;
+        const cplx* sS = stream_row(PADL ? lead_p(final_pass ? 5 : 3) : opS, irow, fk);
+        const cplx* sM = stream_row(PADL ? lead_p(final_pass ? 4 : 2) : opM, irow, fk);
+        const int ksteps = ksteps_of();
         Stream q;
 #pragma unroll
         for (int ks = 0; ks < PF; ++ks) stream_fetch(q, sS, sM, ks, fk);
@@ -270,8 +345,10 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
         const bool strip_wave = REM && wave == TR;      // this wave's column tile is the column strip
         const cplx* ab = Ws + fi * P + fk;
         const cplx* ab4 = Ws + (fi & 3) * P + fk;       // row-strip A operand: row TR*16 + (l&3) in every block
-        const int irow = min(strip_wave ? TR * 16 + (fi & 3) : wave * 16 + fi, n - 1) * n;
-        const cplx* sS = opS + irow; const cplx* sM = opM + irow;
+        const int irow = strip_wave ? TR * 16 + (fi & 3) : wave * 16 + fi;
+        const cplx* sS = stream_row(PADL ? lead_p(final_pass ? 5 : 3) : opS, irow, fk);
+        const cplx* sM = stream_row(PADL ? lead_p(final_pass ? 4 : 2) : opM, irow, fk);
+        const int ksteps = ksteps_of();
         Stream q;
 #pragma unroll
         for (int ks = 0; ks < PF; ++ks) stream_fetch(q, sS, sM, ks, fk);
@@ -316,7 +393,7 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
     // Where a lane's accumulator values of tile (ti, tj) live: FULL and ROW-STRIP tiles use the 16 x 16 C layout
     // (rows ti*16 + fk + 4r, column tj*16 + fi; a row strip only fills r = 0), a COLUMN-STRIP tile (tj == TR of a
     // full row tile) holds one value per lane at (ti*16 + 4 (fi>>2) + fk, TR*16 + (fi&3)).
-    // f(i, j, re, im) is called for every element this lane holds.
+    // f(r, i, j, re, im) is called for every element this lane holds (r: its component, a compile-time number).
     auto for_tile = [&](int ti, int tj, const d4& va, const d4& vb, const d4& vc, bool cj, int fi, int fk, auto f) __attribute__((always_inline)) {
         d4 vr, vi;
 #pragma unroll
@@ -325,23 +402,33 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
             vi[r] = !M3G ? vb[r] : cj ? vc[r] - va[r] + vb[r] : vc[r] - va[r] - vb[r];
         }
         if (REM && tj == TR && ti != TR) {
-            f(ti * 16 + 4 * (fi >> 2) + fk, TR * 16 + (fi & 3), vr[0], vi[0]);
+            f(0, ti * 16 + 4 * (fi >> 2) + fk, TR * 16 + (fi & 3), vr[0], vi[0]);
         } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (!(REM && ti == TR) || r == 0) f(ti * 16 + fk + 4 * r, tj * 16 + fi, vr[r], vi[r]);
+                if (!(REM && ti == TR) || r == 0) f(r, ti * 16 + fk + 4 * r, tj * 16 + fi, vr[r], vi[r]);
         }
     };
     // store row tile `wave` held as accumulators (C layout: rows fk + 4r, column fi of tile tj)
     auto store_rowtile = [&](const d4 (&accr)[T16], const d4 (&acci)[T16], const d4 (&accc)[T16]) __attribute__((always_inline)) {
         const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
+        // a full tile of a remainder-strip class lies inside every contact of the launch (the launcher's class rule, as
+        // rs_update_col assumes): stored without the test
+        const bool inside = RS_BATCH_MSTORE && REM && wave < TR;
 #pragma unroll
-        for (int tj = 0; tj < T16; ++tj)
-            for_tile(wave, tj, accr[tj], acci[tj], accc[tj], false, fi, fk,
-                     [&](int i, int j, double re, double im) { if (i < n && j < n) Ws[i * P + j] = cmake(re, im); });
+        for (int tj = 0; tj < T16; ++tj) {
+            if (inside && tj < TR)
+                for_tile(wave, tj, accr[tj], acci[tj], accc[tj], false, fi, fk,
+                         [&](int r, int i, int j, double re, double im) { Ws[i * P + j] = cmake(re, im); });
+            else
+                for_tile(wave, tj, accr[tj], acci[tj], accc[tj], false, fi, fk,
+                         [&](int r, int i, int j, double re, double im) { if (i < n && j < n) Ws[i * P + j] = cmake(re, im); });
+        }
     };
     // g_new[k][col] = W[pivrow[k]][colof[col]] for this lane's elements; first: g = g_new, else the
     // reference's mixing and stopping test (surfG1D.py:276-284).  Leaves g in Ws and in gold.
+    // (RS_DENSE_MIX = 0: the lane map of the tiles, element (ks*4 + fk, wave*16 + fi) at slot ks; the default is
+    //  gather_mix_dense below)
     int over = 1, allok = 0;
     auto gather_mix = [&](bool first, unsigned long long* st) __attribute__((always_inline)) {
         const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
@@ -411,11 +498,112 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
         __syncthreads();
     };
 
+    // ---- the same on the dense lane map (chain_mix_map.h): lane t < RG n holds column t mod n of the rows t / n + RG s.
+    // Slot s of the old iterate lives at [s][t]: the first MLS slots in LDS (the spare rows of the work matrix, 256 lanes
+    // per slot; every slot as the compact n x n matrix behind the work matrix when two workgroups share the CU), the others
+    // in the global scratch record.  Two loops in two address spaces -- no generic pointer --, the global requests first,
+    // then the pivot indices as one batch, the LDS slots, the gathers.  In a remainder-strip class the slot count is
+    // known up to the last slot (n > 16 TR), so the loops carry no branch but that one.
+    constexpr int MIX_NLO = REM ? 16 * TR + 1 : 1;
+    constexpr int MS = rs_mix_max_slots(MIX_NLO, rs_class_nmax(P)), MSMIN = rs_mix_min_slots(MIX_NLO, rs_class_nmax(P));
+    constexpr int MLS = GOLD_GLOBAL ? (rs_class_lds_slots(P) < MS ? rs_class_lds_slots(P) : MS) : MS;
+    static_assert(MS <= KS, "the global scratch record holds KS slots per lane");
+    // where slot s of this lane's old iterate is (ta: the lane's linear index in slot 0, 0 for an idle lane)
+    auto old_lds = [&](int s, int t, int ta, bool ok) __attribute__((always_inline)) -> cplx* {
+        return GOLD_GLOBAL ? Ws + a.gold_lds_off + t + s * RS_MIX_LANES : Ws + a.gold_lds_off + (ok ? s * mm.stride + ta : 0);
+    };
+    auto old_glob = [&]() __attribute__((always_inline)) {       // this workgroup's record (a scalar base: rs_gload / rs_gstore)
+        return rs_scalar_base(a.gold + (size_t)slot * KS * RS_THREADS);
+    };
+    constexpr unsigned GSLOT = RS_THREADS * sizeof(cplx);       // bytes of a slot of the record
+    auto gather_mix_dense = [&](bool first, unsigned long long* st) __attribute__((always_inline)) {
+        const int t = rs_opaque(tid);
+        const int rg0 = (int)(((unsigned)t * mm.rcp) >> 16);
+        const bool active = rg0 < mm.rg;
+        const int ta = active ? t : 0, rga = active ? rg0 : 0, ca = ta - rga * n;
+        const int slots = mm.slots;
+        auto on = [&](int s) { return s < MSMIN || s < slots; };                                  // (wave-uniform)
+        auto valid = [&](int s) { return active && (s < MSMIN - 1 || rga + mm.rg * s < n); };     // only the last slot has rows >= n
+        cplx go[MS], gm[MS];
+        const unsigned long long gbase = GOLD_GLOBAL ? old_glob() : 0ull;
+        const unsigned tb = (unsigned)t * (unsigned)sizeof(cplx);
+        if (!first && GOLD_GLOBAL) {
+#pragma unroll
+            for (int s = MLS; s < MS; ++s) if (on(s)) go[s] = rs_gload(rs_scalar_advance(gbase, s * GSLOT), 0, tb);
+        }
+        int pr[MS];
+#pragma unroll
+        for (int s = 0; s < MS; ++s) pr[s] = on(s) ? pivrow[rga + mm.rg * s] : 0;
+        const cplx* gsrc = Ws + colof[ca];
+        if (!first) {
+#pragma unroll
+            for (int s = 0; s < MLS; ++s) if (on(s)) go[s] = *old_lds(s, t, ta, valid(s));
+        }
+#pragma unroll
+        for (int s = 0; s < MS; ++s) gm[s] = on(s) ? gsrc[pr[s] * P] : cmake(0.0, 0.0);
+        if (st && tid == 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st[5] = __builtin_amdgcn_s_memrealtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st[6] = __builtin_amdgcn_s_memrealtime(); }
+        bool lane_over = false, lane_ok = true;
+        if (!first) {
+#pragma unroll
+            for (int s = 0; s < MS; ++s) {
+                if (on(s)) {
+                    const cplx gn = gm[s];
+                    const double dx = gn.x - go[s].x, dy = gn.y - go[s].y;
+                    const double num2 = dx * dx + dy * dy;
+                    const double den2 = fmax(gn.x * gn.x + gn.y * gn.y, 1e-24);
+                    const bool v = valid(s);
+                    lane_over |= v && num2 > conv2 * den2;
+                    lane_ok &= !v || num2 <= conv2 * den2;
+                    gm[s] = cmake(gn.x * rf + go[s].x * rf1, gn.y * rf + go[s].y * rf1);
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < MLS; ++s) if (on(s) && valid(s)) *old_lds(s, t, ta, true) = gm[s];
+        if (GOLD_GLOBAL) {
+#pragma unroll
+            for (int s = MLS; s < MS; ++s) if (on(s) && valid(s)) rs_gstore(rs_scalar_advance(gbase, s * GSLOT), 0, tb, gm[s]);
+        }
+        if (!first) {
+            const bool w_over = __ballot(lane_over) != 0ull;
+            const bool w_ok = __ballot(!lane_ok) == 0ull;
+            if (lane == 0) { flags[wave] = w_over ? 1 : 0; flags[RS_WAVES + wave] = w_ok ? 1 : 0; }
+        }
+        if (st && tid == 0) st[7] = __builtin_amdgcn_s_memrealtime();
+        __syncthreads();                                // all gathers done: Ws may be overwritten
+        if (st && tid == 0) st[40] = __builtin_amdgcn_s_memrealtime();
+        if (tid < 64) colof[tid] = -1;                  // for the next inverse (every lane has read its colof)
+        cplx* gdst = Ws + rga * P + ca;
+#pragma unroll
+        for (int s = 0; s < MS; ++s)
+            if (on(s) && valid(s)) gdst[s * mm.rg * P] = gm[s];
+        if (!first) {
+            over = flags[0] | flags[1] | flags[2] | flags[3];
+            allok = flags[4] & flags[5] & flags[6] & flags[7];
+        }
+        __syncthreads();
+    };
+    // a job that was set aside continues: its old iterate is the iterate itself (gather_mix leaves the mixed g in both places)
+    auto resume_old_dense = [&]() __attribute__((always_inline)) {
+        const int t = rs_opaque(tid);
+        const int rg0 = (int)(((unsigned)t * mm.rcp) >> 16);
+        const bool active = rg0 < mm.rg;
+        const int ta = active ? t : 0, rga = active ? rg0 : 0, ca = ta - rga * n;
+        const unsigned long long gbase = GOLD_GLOBAL ? old_glob() : 0ull;
+#pragma unroll
+        for (int s = 0; s < MS; ++s) {
+            if (s < mm.slots && active && rga + mm.rg * s < n) {
+                const cplx v = Ws[(rga + mm.rg * s) * P + ca];
+                if (s < MLS) *old_lds(s, t, ta, true) = v; else rs_gstore(rs_scalar_advance(gbase, s * GSLOT), 0, (unsigned)t * (unsigned)sizeof(cplx), v);
+            }
+        }
+    };
+
     // ---- a job starts: g0 = inv(A) is the first pass through the inverse of a fresh job, so the work matrix starts as A
     // (its padding zero; it is never written afterwards).  A cache hit starts from the stored iterate instead and goes
     // straight to Sigma = t g t^H; a job that was set aside continues from its iterate with the products of its next sweep.
     const bool gc_hit = a.gc_mode == 2;
-    bool first = true, final_pass = false, skip = false;
+    bool first = true, skip = false;
     int q_end = 0;
     auto next_job = [&]() __attribute__((always_inline)) -> bool {
         if (rr) {
@@ -431,10 +619,15 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
         resume = count > 0;
         c = job % a.n_contacts; b = job / a.n_contacts;
         n = a.nc[c]; off = a.blk_off[c]; ksteps = (n + 3) >> 2;
-        gold_l = Ws + a.gold_lds_off + fk * n + wave * 16 + fi;
+        if (!RS_DENSE_MIX) gold_l = Ws + a.gold_lds_off + fk * n + wave * 16 + fi;     // (legacy layout)
         alpha = a.alpha + off; Salpha = a.Salpha + off; beta = a.beta + off; Sbeta = a.Sbeta + off;
         tau = a.tau + off; Stau = a.Stau + off;
+        if (RS_DENSE_MIX) mm = rs_mix_map(n);
+        if (RS_PAD_LEADS) {                             // (alpha, Salpha at pitch n still give the start A below)
+            pad_c = a.pad + (size_t)c * (CHAIN_PAD * CHAIN_PAD); pad_ps = (unsigned)a.n_contacts * (CHAIN_PAD * CHAIN_PAD);
+        }
         e = E[b]; z = cmake(e.x, e.y + a.eta);
+        if (RS_PAD_LEADS) { e = cmake(rs_uniform(e.x), rs_uniform(e.y)); z = cmake(rs_uniform(z.x), rs_uniform(z.y)); }   // (the same for every lane: scalar registers)
         opS = Sbeta; opM = beta; opz = z;
         over = 1; allok = 0;
         first = !resume; skip = resume; final_pass = false;
@@ -456,15 +649,18 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
         if (resume) {
             // the old iterate of the mixing step is the iterate itself (gather_mix leaves the mixed g in both places)
             __syncthreads();
-            const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
-            const int col = wave * 16 + fi;
-            cplx* gl = rs_opaque(gold_l);
-            cplx* gg = GOLD_GLOBAL ? rs_opaque(gold_g) : nullptr;
+            if (RS_DENSE_MIX) resume_old_dense();
+            else {                                      // (legacy layout)
+                const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
+                const int col = wave * 16 + fi;
+                cplx* gl = rs_opaque(gold_l);
+                cplx* gg = GOLD_GLOBAL ? rs_opaque(gold_g) : nullptr;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                if (ks < ksteps && col < n && ks * 4 + fk < n) {
-                    const cplx v = Ws[(ks * 4 + fk) * P + col];
-                    if (!GOLD_GLOBAL || ks < LS_CT || (ks == LS_CT && lds_slots > LS_CT)) gl[ks * 4 * n] = v; else gg[ks * RS_THREADS] = v;
+                for (int ks = 0; ks < KS; ++ks) {
+                    if (ks < ksteps && col < n && ks * 4 + fk < n) {
+                        const cplx v = Ws[(ks * 4 + fk) * P + col];
+                        if (!GOLD_GLOBAL || ks < LS_CT || (ks == LS_CT && lds_slots > LS_CT)) gl[ks * 4 * n] = v; else gg[ks * RS_THREADS] = v;
+                    }
                 }
             }
         }
@@ -488,7 +684,7 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
         if (!gc_hit && !skip) {
             rs_inverse<T16, P, REM ? TR : -1>(n, Ws, pivrow, colof, rowline, tid, wave, chain_roles, la_cnt, la_epoch, st ? st + 8 : nullptr);   // st + 8: stage stamps, st + 24: factor
             if (st && tid == 0) st[1] = __builtin_amdgcn_s_memrealtime();
-            if (!(RS_ABLATE & 8) || first) gather_mix(first, st);
+            if (!(RS_ABLATE & 8) || first) { if (RS_DENSE_MIX) gather_mix_dense(first, st); else gather_mix(first, st); }
             else { if (tid < 64) colof[tid] = -1; __syncthreads(); }
             if (st && tid == 0) st[2] = __builtin_amdgcn_s_memrealtime();
             if (!first) ++count;
@@ -541,7 +737,7 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
 #pragma unroll
             for (int ti = 0; ti < T16; ++ti)
                 for_tile(ti, wave, mr[ti], mi[ti], mc[ti], true, fis, fks,
-                         [&](int i, int j, double re, double im) { if (i < n && j < n) out[i * n + j] = cmake(re, im); });
+                         [&](int r, int i, int j, double re, double im) { if (i < n && j < n) out[i * n + j] = cmake(re, im); });
             if (tid == 0 && !gc_hit) {                  // (a hit's counts and flags are copied from the cache by the launcher's caller)
                 if (iters) iters[(size_t)b * a.n_contacts + c] = count;
                 if (converged) converged[(size_t)b * a.n_contacts + c] = (count > 0 && allok) ? 1 : 0;
@@ -551,14 +747,79 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
             continue;
         }
         __syncthreads();
-        // M = A - T B^H
+        // M = A - T B^H.  With the padded alpha, Salpha no load needs the store's guard: the (up to) eight loads of a
+        // row tile go out together and are consumed in order as they arrive (a ladder of vmcnt waits, one round trip per
+        // tile); those of tile ti + 1 go out after tile ti is stored (before it with RS_MSTORE_AHEAD = 1, which spills)
+        if (RS_BATCH_MSTORE && RS_PAD_LEADS) {
+            // SC: this wave's column tile is the column strip (its tiles ti < TR use the strip's lane map, see for_tile).
+            // Every element is a compile-time row offset from one lane base, in the padded alpha / Salpha and in Ws.
+            // Tests: none for a full tile of a remainder-strip class (inside every contact of the launch by the launcher's
+            // class rule), the strip's own rows / columns against n; every element in the other classes.
+            auto mstore = [&](auto sc) __attribute__((always_inline)) {
+                constexpr bool SC = decltype(sc)::value;
+                const int ljn = wave * 16 + fis, lis = 4 * (fis >> 2) + fks, ljs = TR * 16 + (fis & 3);
+                const unsigned lon = (unsigned)(fks * CHAIN_PAD + ljn), los = (unsigned)(lis * CHAIN_PAD + ljs);
+                cplx* wn = Ws + fks * P + ljn;
+                cplx* wsc = Ws + lis * P + ljs;
+                auto smap = [](int ti) { return SC && ti < TR; };
+                auto nel = [&](int ti) { return smap(ti) || (REM && ti == TR) ? 1 : 4; };
+                auto rowc = [&](int ti, int r) { return ti * 16 + (smap(ti) ? 0 : 4 * r); };
+                cplx as[2][4], aa[2][4];
+                const unsigned long long bS = rs_scalar_base(lead_p(1)), bA = rs_scalar_base(lead_p(0));
+                const unsigned lbn = lon * (unsigned)sizeof(cplx), lbs = los * (unsigned)sizeof(cplx);
+                unsigned long long curS = bS, curA = bA;        // the bases at row cur_row
+                int cur_row = 0;
+                auto load_a = [&](int ti, cplx (&s)[4], cplx (&m)[4]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int ti = 0; ti < T16; ++ti) {
-            for_tile(ti, wave, mr[ti], mi[ti], mc[ti], true, fis, fks, [&](int i, int j, double re, double im) {
-                const cplx av = Aat(i, j);
-                if (i < n && j < n) Ws[i * P + j] = cmake(av.x - re, av.y - im);
-            });
-            __builtin_amdgcn_sched_barrier(0);          // the A elements of one tile in flight, not of all
+                    for (int r = 0; r < nel(ti); ++r) {
+                        const unsigned lb = smap(ti) ? lbs : lbn;
+                        const long long adv = (long long)(rowc(ti, r) - cur_row) * CHAIN_PAD * (long long)sizeof(cplx);
+                        if (adv) { curS = rs_scalar_advance(curS, adv); curA = rs_scalar_advance(curA, adv); cur_row = rowc(ti, r); }
+                        s[r] = rs_gload(curS, 0, lb); m[r] = rs_gload(curA, 0, lb);
+                    }
+                };
+                load_a(0, as[0], aa[0]);
+                // T B^H out of the 3M sums first, in place: two values per element are live beside the A buffers, not three
+                if (M3G) {
+#pragma unroll
+                    for (int ti = 0; ti < T16; ++ti)
+#pragma unroll
+                        for (int r = 0; r < nel(ti); ++r) {
+                            const double va = mr[ti][r], vb = mi[ti][r], vc = mc[ti][r];
+                            mr[ti][r] = va + vb; mi[ti][r] = vc - va + vb;
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int ti = 0; ti < T16; ++ti) {
+                    if (RS_MSTORE_AHEAD && ti + 1 < T16) load_a(ti + 1, as[(ti + 1) & 1], aa[(ti + 1) & 1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    const cplx (&s)[4] = as[RS_MSTORE_AHEAD ? ti & 1 : 0];
+                    const cplx (&m)[4] = aa[RS_MSTORE_AHEAD ? ti & 1 : 0];
+#pragma unroll
+                    for (int r = 0; r < nel(ti); ++r) {
+                        const double re = mr[ti][r], im = mi[ti][r];
+                        const cplx av = csub(cmul(z, s[r]), m[r]);
+                        const int i = rowc(ti, r) + (smap(ti) ? lis : fks), j = smap(ti) ? ljs : ljn;
+                        const bool ok = !REM ? (i < n && j < n) : ((ti < TR || i < n) && (!SC || j < n));
+                        if (ok) (smap(ti) ? wsc : wn)[rowc(ti, r) * P] = cmake(av.x - re, av.y - im);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (!RS_MSTORE_AHEAD && ti + 1 < T16) load_a(ti + 1, as[0], aa[0]);
+                }
+            };
+            if (!REM || wave < TR) mstore(std::false_type{});
+            else if (wave == TR) mstore(std::true_type{});
+            // (a remainder-strip class's wave > TR owns no column of the matrix)
+        } else {
+#pragma unroll
+            for (int ti = 0; ti < T16; ++ti) {
+                for_tile(ti, wave, mr[ti], mi[ti], mc[ti], true, fis, fks, [&](int r, int i, int j, double re, double im) {
+                    const cplx av = Aat(i, j);
+                    if (i < n && j < n) Ws[i * P + j] = cmake(av.x - re, av.y - im);
+                });
+                __builtin_amdgcn_sched_barrier(0);      // the A elements of one tile in flight, not of all
+            }
         }
         __syncthreads();
         if (st && tid == 0) st[4] = __builtin_amdgcn_s_memrealtime();
@@ -580,7 +841,7 @@ int rs_rr_quantum(int user)
 }
 size_t rs_gold_elems(int nc_max, int n_contacts, int nb)
 {
-    return (size_t)4 * ((nc_max + 15) >> 4) * RS_THREADS * n_contacts * nb;     // >= KS slots per lane
+    return (size_t)rs_mix_reserved_slots(nc_max) * RS_THREADS * n_contacts * nb;     // >= KS slots per lane
 }
 // entries of the job queue's ring: a job is queued at most once per quantum (0: no round robin for this launch)
 size_t rs_ring_entries(int n_contacts, int nb, int max_sweeps, int rr_user)
@@ -616,6 +877,7 @@ void chain1d_rs_launch(hipStream_t st, ChainRsArgs a, int n_max, int n_contacts,
     ChainRsArgs al = a; al.gold_lds_off = 16 * T16 * P + 16; al.gold_lds_slots = 1 << 20;
     // ... or its first slots in the unused rows n_max+2 .. of the work matrix, the rest in global scratch
     ChainRsArgs ag = a; ag.gold_lds_off = (n_max + 2) * P;
+    // (gold_lds_slots serves the legacy layout of RS_DENSE_MIX = 0 only: the dense map fixes its LDS slots at compile time)
     constexpr int LS_FIT = (16 * T16 * P + 16 - (P + 2) * P) / (4 * P);      // the kernel's LS_CT
     ag.gold_lds_slots = std::min(std::max(0, (16 * T16 * P + 16 - ag.gold_lds_off) / (4 * n_max)), std::max(LS_FIT, 0) + 1);
     if (ag.gold_lds_slots < std::max(LS_FIT, 0)) ag.gold_lds_slots = 0;       // (cannot happen: n_max <= P)
@@ -666,7 +928,7 @@ void launch_chain1d_lds(hipStream_t st, const SigmaProvider& p, const int* d_nc,
     a.order = order;
     a.gcache = gcache; a.gc_mode = gcache ? gc_mode : 0;
     a.alpha = p.d_alpha; a.Salpha = p.d_Salpha; a.beta = p.d_beta; a.Sbeta = p.d_Sbeta;
-    a.tau = p.d_tau; a.Stau = p.d_Stau;
+    a.tau = p.d_tau; a.Stau = p.d_Stau; a.pad = p.d_lead_pad;
     a.nc = d_nc; a.blk_off = d_blk_off;
     a.n_contacts = p.n_contacts; a.blk_stride = p.blk_stride;
     a.eta = p.eta; a.conv = p.conv; a.relFactor = p.relFactor;

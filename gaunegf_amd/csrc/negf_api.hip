@@ -112,7 +112,7 @@ void free_provider(SigmaProvider* p)
     dev_free(p->d_inds); dev_free(p->d_nc); dev_free(p->d_blk_off); dev_free(p->d_inds_off);
     dev_free(p->d_n_atoms); dev_free(p->d_atom_off); dev_free(p->d_pos);
     dev_free(p->d_alpha); dev_free(p->d_Salpha); dev_free(p->d_beta); dev_free(p->d_Sbeta);
-    dev_free(p->d_tau); dev_free(p->d_Stau);
+    dev_free(p->d_tau); dev_free(p->d_Stau); dev_free(p->d_lead_pad);
     dev_free(p->d_atom_orbs); dev_free(p->d_nb_off); dev_free(p->d_nb_dirs);
     dev_free(p->d_H); dev_free(p->d_Slist); dev_free(p->d_Vlist); dev_free(p->d_xi);
     dev_free(p->d_pre_tot); dev_free(p->d_pre_c); release_bufs(p->d_order); dev_free(p->d_prevE); dev_free(p->d_prev_iters); dev_free(p->d_curE); dev_free(p->d_cur_iters);
@@ -1201,6 +1201,18 @@ int negf_sigma_chain1d(negf_ctx* c, int n_contacts, const int* nc, const int* in
     for (int k = 0; k < 6; ++k) {
         if ((rc = dev_alloc(dsts[k], tot)) ||
             (rc = upload(c, *dsts[k], reinterpret_cast<const cplx*>(srcs[k]), tot))) { free_provider(p); return rc; }
+    }
+    if (chain1d_lds_supported(p->nc_max)) {
+        // zero-padded copies at a fixed pitch (SigmaProvider::d_lead_pad)
+        const size_t mat = (size_t)CHAIN_PAD * CHAIN_PAD;
+        std::vector<cplx> pad(6 * (size_t)n_contacts * mat, cmake(0.0, 0.0));
+        for (int k = 0; k < 6; ++k)
+            for (int q = 0; q < n_contacts; ++q) {
+                const cplx* src = reinterpret_cast<const cplx*>(srcs[k]) + p->blk_off[q];
+                cplx* dst = pad.data() + ((size_t)k * n_contacts + q) * mat;
+                for (int i = 0; i < nc[q]; ++i) std::copy(src + (size_t)i * nc[q], src + (size_t)(i + 1) * nc[q], dst + (size_t)i * CHAIN_PAD);
+            }
+        if ((rc = dev_alloc(&p->d_lead_pad, pad.size())) || (rc = upload(c, p->d_lead_pad, pad.data(), pad.size()))) { free_provider(p); return rc; }
     }
     // what g(E) depends on, for the context's g(E) cache
     p->h_lead = std::make_shared<std::vector<cplx>>();

@@ -72,6 +72,8 @@ struct DevBuf {
     operator T*() const { return p; }
 };
 
+constexpr int CHAIN_PAD = 64;      // rows and pitch of the padded lead matrices (SigmaProvider::d_lead_pad)
+
 enum SigmaKind { SK_CONST = 0, SK_CHAIN1D = 2, SK_BETHE = 3, SK_PRECOMPUTED = 4 };
 
 struct SigmaProvider {
@@ -95,6 +97,10 @@ struct SigmaProvider {
     // CHAIN1D matrices, concatenated [sum nc^2] each
     cplx *d_alpha = nullptr, *d_Salpha = nullptr, *d_beta = nullptr, *d_Sbeta = nullptr,
          *d_tau = nullptr, *d_Stau = nullptr;
+    // the same six matrices once more for the register-stationary chain kernel (k_chain1d_rs.hip, nc_max <= 64):
+    // [matrix, in the order above][contact][CHAIN_PAD][CHAIN_PAD], zero outside n x n -- a lane reads them at compile-
+    // time offsets from one base, without clamps.  Written where the six are uploaded, constant for the provider's life
+    cplx* d_lead_pad = nullptr;
     // host copy of alpha | Salpha | beta | Sbeta and its 64-bit hash: what the surface Green's function depends on
     // besides eta / conv / relFactor / max_iter -- the key of the context's g(E) cache (ChainGEntry)
     std::shared_ptr<std::vector<cplx>> h_lead;     // shared with the cache entries this provider fills
