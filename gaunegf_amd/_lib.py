@@ -89,6 +89,20 @@ SIGNATURES = {
     "negf_gless_int_probes_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "negf_gr_int_probes": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "negf_gr_int_probes_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "negf_layered_create": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _ip]),
+    "negf_layered_free": (C.c_int, [_vp, C.c_int]),
+    "negf_layered_terminal_const": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip]),
+    "negf_layered_terminal_chain": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _ip]),
+    "negf_layered_terminal_blocks": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _ip]),
+    "negf_layered_terminal_sigma": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "negf_layered_transmission": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "negf_layered_transmission_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "negf_layered_dos": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "negf_layered_dos_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "negf_layered_gr_int": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "negf_layered_gr_int_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "negf_layered_workspace_bytes": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_longlong)]),
     "negf_sync": (C.c_int, [_vp]),
     "negf_last_info": (C.c_int, [_vp, C.c_int, _vp]),
     "negf_last_iters": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),

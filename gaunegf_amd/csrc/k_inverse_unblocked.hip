@@ -17,7 +17,7 @@
 static constexpr int GJ_THREADS = 256;
 
 __global__ __launch_bounds__(GJ_THREADS) void gj_unblocked_kernel(int n, cplx* __restrict__ Aall,
-                                                                    int* __restrict__ info)
+                                                                    int* __restrict__ info, size_t stride)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cplx* rowk = reinterpret_cast<cplx*>(smem_raw);          // [n] scaled pivot row
@@ -28,7 +28,7 @@ __global__ __launch_bounds__(GJ_THREADS) void gj_unblocked_kernel(int n, cplx* _
     __shared__ int piv_row;
     __shared__ int bad;
 
-    cplx* A = Aall + (size_t)blockIdx.x * n * n;
+    cplx* A = Aall + (size_t)blockIdx.x * stride;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     if (tid == 0) bad = 0;
@@ -111,8 +111,9 @@ __global__ __launch_bounds__(GJ_THREADS) void gj_unblocked_kernel(int n, cplx* _
     if (tid == 0) info[blockIdx.x] = bad;
 }
 
-bool launch_inverse_unblocked(hipStream_t st, int n, int nb, cplx* A, int* info)
+bool launch_inverse_unblocked(hipStream_t st, int n, int nb, cplx* A, int* info, size_t stride)
 {
+    if (stride == 0) stride = (size_t)n * n;
     const size_t smem = (size_t)n * (2 * sizeof(cplx) + sizeof(int));       // pivot row, pivot column, ipiv
     const size_t limit = 158 * 1024;
     if (smem > limit) return false;                                          // n > 4494
@@ -125,6 +126,6 @@ bool launch_inverse_unblocked(hipStream_t st, int n, int nb, cplx* A, int* info)
         }
         attr_set = true;
     }
-    hipLaunchKernelGGL(gj_unblocked_kernel, dim3(nb), dim3(GJ_THREADS), smem, st, n, A, info);
+    hipLaunchKernelGGL(gj_unblocked_kernel, dim3(nb), dim3(GJ_THREADS), smem, st, n, A, info, stride);
     return true;
 }

@@ -1,0 +1,220 @@
+// Layer-wise passes of the recursive Green's function path (negf_layered_*, negf_layered_impl.h; gfx950).
+// The layer inverses and products are the dense path's own launchers; what is here is the HBM-bound work around them:
+//   rgf_diag      : D_b = E_b S_ii - F_ii - P_b - sum_t scatter(Sigma_t,b)     one pass, terminals and Schur term included
+//   rgf_coupling  : C_b = F_ij - E_b S_ij                                       the NEGATED coupling block -A_ij
+//   rgf_add       : G_ii = g_i + W                                              the backward sweep's update
+//   rgf_gamma     : Gamma = i (Sigma - Sigma^H) on a terminal's K x K block
+//   rgf_dos_*     : -Im G_rr / pi, and the rows of -Im (G S) / pi block by block
+//   rgf_accumulate: acc += sum_b w_b X_b, b ascending in ONE chain per element (bitwise independent of the batch cut)
+// Every matrix of a batch is compact row-major (leading dimension = its own column count) at a batch stride the
+// caller gives; consecutive lanes touch consecutive 16-byte elements.  No atomics.
+#include "negf_common.h"
+
+static constexpr int RGF_THREADS = 256;
+
+static __device__ __forceinline__ double rgf_wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+static int rgf_grid(size_t count)
+{
+    size_t gx = (count + RGF_THREADS - 1) / RGF_THREADS;
+    return (int)(gx > 256 ? 256 : (gx < 1 ? 1 : gx));
+}
+
+__global__ __launch_bounds__(RGF_THREADS) void rgf_diag_kernel(
+    int n, const cplx* __restrict__ E, const cplx* __restrict__ S, const cplx* __restrict__ F,
+    const cplx* __restrict__ P, size_t strideP, RgfTermArgs t, cplx* __restrict__ D, size_t strideD)
+{
+    const int b = blockIdx.y;
+    const cplx e = E[b];
+    const cplx* Pb = P ? P + (size_t)b * strideP : nullptr;
+    cplx* Db = D + (size_t)b * strideD;
+    const int n2 = n * n;
+    for (int i = blockIdx.x * RGF_THREADS + threadIdx.x; i < n2; i += gridDim.x * RGF_THREADS) {
+        const cplx s = S[i];
+        const cplx h = F[i];
+        cplx a = cmake(e.x * s.x - e.y * s.y - h.x, e.x * s.y + e.y * s.x - h.y);      // E S - F as the dense assemble forms it
+        if (Pb) a = csub(a, Pb[i]);
+        if (t.count > 0) {
+            const int r = i / n, c = i - r * n;
+            for (int k = 0; k < t.count; ++k) {                                       // terminal order: a fixed sum
+                const int pr = t.pos[k][r], pc = t.pos[k][c];
+                if (pr >= 0 && pc >= 0) a = csub(a, t.sig[k][(size_t)b * t.stride[k] + (size_t)pr * t.K[k] + pc]);
+            }
+        }
+        Db[i] = a;
+    }
+}
+
+void launch_rgf_diag(hipStream_t st, int n, int nb, const cplx* E, const cplx* S, const cplx* F, const cplx* P,
+                     size_t strideP, const RgfTermArgs& t, cplx* D, size_t strideD)
+{
+    hipLaunchKernelGGL(rgf_diag_kernel, dim3(rgf_grid((size_t)n * n), nb), dim3(RGF_THREADS), 0, st, n, E, S, F, P,
+                       strideP, t, D, strideD);
+}
+
+__global__ __launch_bounds__(RGF_THREADS) void rgf_coupling_kernel(
+    int count, const cplx* __restrict__ E, const cplx* __restrict__ S, const cplx* __restrict__ F,
+    cplx* __restrict__ C, size_t strideC)
+{
+    const int b = blockIdx.y;
+    const cplx e = E[b];
+    cplx* Cb = C + (size_t)b * strideC;
+    for (int i = blockIdx.x * RGF_THREADS + threadIdx.x; i < count; i += gridDim.x * RGF_THREADS) {
+        const cplx s = S[i];
+        const cplx h = F[i];
+        Cb[i] = cmake(h.x - (e.x * s.x - e.y * s.y), h.y - (e.x * s.y + e.y * s.x));
+    }
+}
+
+void launch_rgf_coupling(hipStream_t st, int count, int nb, const cplx* E, const cplx* S, const cplx* F, cplx* C,
+                         size_t strideC)
+{
+    hipLaunchKernelGGL(rgf_coupling_kernel, dim3(rgf_grid((size_t)count), nb), dim3(RGF_THREADS), 0, st, count, E, S, F,
+                       C, strideC);
+}
+
+__global__ __launch_bounds__(RGF_THREADS) void rgf_add_kernel(
+    int count, const cplx* __restrict__ g, size_t strideg, const cplx* __restrict__ W, size_t strideW,
+    cplx* __restrict__ G, size_t strideG)
+{
+    const int b = blockIdx.y;
+    const cplx* gb = g + (size_t)b * strideg;
+    const cplx* Wb = W + (size_t)b * strideW;
+    cplx* Gb = G + (size_t)b * strideG;
+    for (int i = blockIdx.x * RGF_THREADS + threadIdx.x; i < count; i += gridDim.x * RGF_THREADS)
+        Gb[i] = cadd(gb[i], Wb[i]);
+}
+
+void launch_rgf_add(hipStream_t st, int count, int nb, const cplx* g, size_t strideg, const cplx* W, size_t strideW,
+                    cplx* G, size_t strideG)
+{
+    hipLaunchKernelGGL(rgf_add_kernel, dim3(rgf_grid((size_t)count), nb), dim3(RGF_THREADS), 0, st, count, g, strideg, W,
+                       strideW, G, strideG);
+}
+
+__global__ __launch_bounds__(RGF_THREADS) void rgf_gamma_kernel(
+    int K, const cplx* __restrict__ sig, size_t stride_sig, cplx* __restrict__ out, size_t stride_out)
+{
+    const int b = blockIdx.y;
+    const cplx* s = sig + (size_t)b * stride_sig;
+    cplx* o = out + (size_t)b * stride_out;
+    for (int t = blockIdx.x * RGF_THREADS + threadIdx.x; t < K * K; t += gridDim.x * RGF_THREADS) {
+        const int i = t / K, j = t - i * K;
+        const cplx a = s[t], c = s[(size_t)j * K + i];
+        // i (a - conj(c))
+        o[t] = cmake(-(a.y + c.y), a.x - c.x);
+    }
+}
+
+void launch_rgf_gamma(hipStream_t st, int K, int nb, const cplx* sig, size_t stride_sig, cplx* out, size_t stride_out)
+{
+    hipLaunchKernelGGL(rgf_gamma_kernel, dim3(rgf_grid((size_t)K * K), nb), dim3(RGF_THREADS), 0, st, K, sig, stride_sig,
+                       out, stride_out);
+}
+
+__global__ __launch_bounds__(RGF_THREADS) void rgf_dos_diag_kernel(
+    int n, const cplx* __restrict__ G, size_t strideG, double* __restrict__ site, size_t site_stride)
+{
+    const int b = blockIdx.y;
+    const cplx* g = G + (size_t)b * strideG;
+    const double pi = 3.14159265358979323846;
+    for (int i = blockIdx.x * RGF_THREADS + threadIdx.x; i < n; i += gridDim.x * RGF_THREADS)
+        site[(size_t)b * site_stride + i] = -g[(size_t)i * n + i].y / pi;
+}
+
+void launch_rgf_dos_diag(hipStream_t st, int n, int nb, const cplx* G, size_t strideG, double* site, size_t site_stride)
+{
+    hipLaunchKernelGGL(rgf_dos_diag_kernel, dim3(rgf_grid((size_t)n), nb), dim3(RGF_THREADS), 0, st, n, G, strideG, site,
+                       site_stride);
+}
+
+// one wave per (energy, row): site[b][r] (+)= -Im sum_k G_b[r][k] conj(X[r][k]) / pi, where X[r][k] = S block read
+// through S_kr = conj(S_rk)
+__global__ __launch_bounds__(RGF_THREADS) void rgf_dos_rows_kernel(
+    int nr, int nk, const cplx* __restrict__ G, size_t strideG, const cplx* __restrict__ X,
+    double* __restrict__ site, size_t site_stride, int accumulate)
+{
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (RGF_THREADS / 64) + (threadIdx.x >> 6);
+    if (r >= nr) return;                                    // whole waves leave together
+    const cplx* g = G + (size_t)b * strideG + (size_t)r * nk;
+    const cplx* x = X + (size_t)r * nk;
+    double s = 0.0;
+    for (int k = lane; k < nk; k += 64) {
+        const cplx a = g[k], c = x[k];
+        s += a.y * c.x - a.x * c.y;                         // Im[a conj(c)]
+    }
+    s = rgf_wave_sum(s);
+    if (lane == 0) {
+        const double pi = 3.14159265358979323846;
+        double* o = site + (size_t)b * site_stride + r;
+        const double v = -s / pi;
+        *o = accumulate ? *o + v : v;
+    }
+}
+
+void launch_rgf_dos_rows(hipStream_t st, int nr, int nk, int nb, const cplx* G, size_t strideG, const cplx* X,
+                         double* site, size_t site_stride, bool accumulate)
+{
+    const int rows_per = RGF_THREADS / 64;
+    hipLaunchKernelGGL(rgf_dos_rows_kernel, dim3((nr + rows_per - 1) / rows_per, nb), dim3(RGF_THREADS), 0, st, nr, nk, G,
+                       strideG, X, site, site_stride, accumulate ? 1 : 0);
+}
+
+// tot[b] = sum_i site[b][i]: thread t adds its stride of orbitals in order, then a fixed tree
+__global__ __launch_bounds__(RGF_THREADS) void rgf_dos_total_kernel(
+    int N, const double* __restrict__ site, size_t site_stride, double* __restrict__ tot)
+{
+    __shared__ double part[RGF_THREADS / 64];
+    const int b = blockIdx.x;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < N; i += RGF_THREADS) s += site[(size_t)b * site_stride + i];
+    s = rgf_wave_sum(s);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int k = 0; k < RGF_THREADS / 64; ++k) t += part[k];
+        tot[b] = t;
+    }
+}
+
+void launch_rgf_dos_total(hipStream_t st, int N, int nb, const double* site, size_t site_stride, double* tot)
+{
+    hipLaunchKernelGGL(rgf_dos_total_kernel, dim3(nb), dim3(RGF_THREADS), 0, st, N, site, site_stride, tot);
+}
+
+__global__ __launch_bounds__(RGF_THREADS) void rgf_accumulate_kernel(
+    int count, int nb, const cplx* __restrict__ w, const cplx* __restrict__ X, size_t strideX, cplx* __restrict__ acc)
+{
+    const int i = blockIdx.x * RGF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    cplx v = acc[i];
+    for (int b = 0; b < nb; ++b) v = cfma(v, w[b], X[(size_t)b * strideX + i]);
+    acc[i] = v;
+}
+
+void launch_rgf_accumulate(hipStream_t st, int count, int nb, const cplx* w, const cplx* X, size_t strideX, cplx* acc)
+{
+    if (count <= 0 || nb <= 0) return;
+    hipLaunchKernelGGL(rgf_accumulate_kernel, dim3((count + RGF_THREADS - 1) / RGF_THREADS), dim3(RGF_THREADS), 0, st,
+                       count, nb, w, X, strideX, acc);
+}
+
+// info[b] = offset + linfo[b] for the first layer that reported a zero pivot
+__global__ void rgf_merge_info_kernel(int nb, int offset, const int* __restrict__ linfo, int* __restrict__ info)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < nb && info[b] == 0 && linfo[b] != 0) info[b] = offset + linfo[b];
+}
+
+void launch_rgf_merge_info(hipStream_t st, int nb, int offset, const int* linfo, int* info)
+{
+    hipLaunchKernelGGL(rgf_merge_info_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, nb, offset, linfo, info);
+}

@@ -509,11 +509,13 @@ int chain_learn_order(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, cons
 
 // Sigma blocks of a block provider for energies E[0..nb) -> c->d_blk
 // (m0 = position of this chunk in the grid being evaluated: the sweep-count prediction keeps whole evaluations)
-int run_sigma_blocks(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, int* iters, int* conv, int m0)
+// blk_out: another destination [nb][blk_stride] (the terminals of a layered system keep their own)
+int run_sigma_blocks(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, int* iters, int* conv, int m0, cplx* blk_out = nullptr)
 {
+    cplx* const blk = blk_out ? blk_out : c->d_blk.p;
     if (p->kind == SK_BETHE) {
         ProfScope ps(c, "bethe");
-        launch_bethe(c->stream, *p, nb, E, c->d_blk, iters, conv);
+        launch_bethe(c->stream, *p, nb, E, blk, iters, conv);
         return NEGF_OK;
     }
     if (p->kind != SK_CHAIN1D) return NEGF_OK;
@@ -540,10 +542,10 @@ int run_sigma_blocks(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, int* 
     const int jobs = nb * p->n_contacts;
     if (rd)
         return chain_cached_launch(c, ent, hit, jobs, iters, conv, [&](cplx* g, int mode) {
-            launch_chain1d_rd(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, g, mode);
+            launch_chain1d_rd(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, blk, iters, conv, c->d_scratch, g, mode);
         });
     if (!lds_path) {
-        launch_chain1d(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, per);
+        launch_chain1d(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, blk, iters, conv, c->d_scratch, per);
         return NEGF_OK;
     }
     const bool learn = !hit && p->force_iters < 0 && iters && chain1d_order_supported(jobs);
@@ -551,8 +553,8 @@ int run_sigma_blocks(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, int* 
     bool order_trusted = true;
     if (learn && (rc = chain_learn_order(c, p, nb, E, iters, m0, false, &order, &order_trusted))) return rc;
     rc = chain_cached_launch(c, ent, hit, jobs, iters, conv, [&](cplx* g, int mode) {
-        if (mode == 2) launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, nullptr, g, 2);
-        else launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, c->d_blk, iters, conv, c->d_scratch, order, g, 1,
+        if (mode == 2) launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, blk, iters, conv, c->d_scratch, nullptr, g, 2);
+        else launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, blk, iters, conv, c->d_scratch, order, g, 1,
                                 c->chain_rr_quantum, c->chain_rr_slots, order_trusted);
     });
     if (rc || !learn) return rc;
@@ -792,6 +794,8 @@ int reduce_info(negf_ctx* c, int m, int* info_host)
 
 }  // namespace
 
+void free_layered(LayeredSystem* ls);      // negf_layered_impl.h
+
 // =========================================================================== //
 extern "C" {
 
@@ -843,6 +847,7 @@ void negf_destroy(negf_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (auto* p : c->providers) free_provider(p);
+    for (auto* ls : c->layered) free_layered(ls);
     free_workspace(c, true); free_mbuffers(c); free_gcache(c);
     free_pinned(c);
     for (auto& sl : c->sys) { dev_free(sl.dF); dev_free(sl.dS); }
@@ -1069,7 +1074,7 @@ int negf_set_system_keyed(negf_ctx* c, int n, const double* F, const double* S, 
 }
 
 // ------------------------------------------------------------------ providers
-static int setup_blocks(negf_ctx* c, SigmaProvider* p, int n_contacts, const int* nc, const int* inds);
+static int setup_blocks(negf_ctx* c, SigmaProvider* p, int n_contacts, const int* nc, const int* inds, int n = -1);
 
 int negf_sigma_const(negf_ctx* c, int n_contacts, const double* sigma, int* handle)
 {
@@ -1140,22 +1145,24 @@ int negf_sigma_const(negf_ctx* c, int n_contacts, const double* sigma, int* hand
     return NEGF_OK;
 }
 
-static int setup_blocks(negf_ctx* c, SigmaProvider* p, int n_contacts, const int* nc, const int* inds)
+// n: the dimension the index lists live in (default: the dense system's; a layered terminal passes its layer's)
+static int setup_blocks(negf_ctx* c, SigmaProvider* p, int n_contacts, const int* nc, const int* inds, int n)
 {
+    if (n < 0) n = c->n;
     p->n_contacts = n_contacts;
     p->nc.assign(nc, nc + n_contacts);
     p->blk_off.resize(n_contacts); p->inds_off.resize(n_contacts);
     int off = 0, ioff = 0;
     p->nc_max = 0;
     for (int k = 0; k < n_contacts; ++k) {
-        if (nc[k] <= 0 || nc[k] > c->n) return NEGF_EINVAL;
+        if (nc[k] <= 0 || nc[k] > n) return NEGF_EINVAL;
         p->blk_off[k] = off; p->inds_off[k] = ioff;
         off += nc[k] * nc[k]; ioff += nc[k];
         p->nc_max = std::max(p->nc_max, nc[k]);
     }
     p->blk_stride = off;
     p->h_inds.assign(inds, inds + ioff);
-    for (int v : p->h_inds) if (v < 0 || v >= c->n) return NEGF_EINVAL;
+    for (int v : p->h_inds) if (v < 0 || v >= n) return NEGF_EINVAL;
     int rc;
     if ((rc = dev_alloc(&p->d_inds, (size_t)ioff)) || (rc = dev_alloc(&p->d_nc, (size_t)n_contacts)) ||
         (rc = dev_alloc(&p->d_blk_off, (size_t)n_contacts)) || (rc = dev_alloc(&p->d_inds_off, (size_t)n_contacts)))
@@ -1167,11 +1174,11 @@ static int setup_blocks(negf_ctx* c, SigmaProvider* p, int n_contacts, const int
         return rc;
     // position of every orbital in each contact's index list (the small fused kernel subtracts the contact blocks while
     // it assembles); a list that names an orbital twice has no such map and keeps the scatter kernels
-    std::vector<int> pos((size_t)n_contacts * c->n, -1);
+    std::vector<int> pos((size_t)n_contacts * n, -1);
     bool unique = true;
     for (int k = 0; k < n_contacts; ++k)
         for (int a = 0; a < nc[k]; ++a) {
-            int& slot = pos[(size_t)k * c->n + p->h_inds[p->inds_off[k] + a]];
+            int& slot = pos[(size_t)k * n + p->h_inds[p->inds_off[k] + a]];
             if (slot >= 0) unique = false;
             slot = a;
         }
@@ -1181,19 +1188,20 @@ static int setup_blocks(negf_ctx* c, SigmaProvider* p, int n_contacts, const int
     return NEGF_OK;
 }
 
-int negf_sigma_chain1d(negf_ctx* c, int n_contacts, const int* nc, const int* inds,
-                       const double* alpha, const double* Salpha, const double* beta,
-                       const double* Sbeta, const double* tau, const double* Stau,
-                       double eta, double conv, double relFactor, int max_iter, int force_iters,
-                       int* handle)
+// A CHAIN1D provider whose index lists live in a space of n orbitals (the dense system, or the end layer of a layered
+// one): *out is owned by the caller
+static int make_chain1d(negf_ctx* c, int n, int n_contacts, const int* nc, const int* inds,
+                        const double* alpha, const double* Salpha, const double* beta,
+                        const double* Sbeta, const double* tau, const double* Stau,
+                        double eta, double conv, double relFactor, int max_iter, int force_iters,
+                        SigmaProvider** out)
 {
-    if (!c || c->n <= 0) return NEGF_ESTATE;
-    if (n_contacts <= 0 || !nc || !inds || !alpha || !Salpha || !beta || !Sbeta || !tau || !Stau || !handle)
+    if (n_contacts <= 0 || !nc || !inds || !alpha || !Salpha || !beta || !Sbeta || !tau || !Stau || !out)
         return NEGF_EINVAL;
     NEGF_HIP_CHECK(hipSetDevice(c->device));
     SigmaProvider* p = new SigmaProvider();
     p->kind = SK_CHAIN1D;
-    int rc = setup_blocks(c, p, n_contacts, nc, inds);
+    int rc = setup_blocks(c, p, n_contacts, nc, inds, n);
     if (rc) { free_provider(p); return rc; }
     const size_t tot = (size_t)p->blk_stride;
     cplx** dsts[6] = {&p->d_alpha, &p->d_Salpha, &p->d_beta, &p->d_Sbeta, &p->d_tau, &p->d_Stau};
@@ -1224,6 +1232,22 @@ int negf_sigma_chain1d(negf_ctx* c, int n_contacts, const int* nc, const int* in
     p->lead_hash = hash_words(p->h_lead->data(), p->h_lead->size() * sizeof(cplx));
     p->eta = eta; p->conv = conv; p->relFactor = relFactor; p->max_iter = max_iter;
     p->force_iters = force_iters;
+    *out = p;
+    return NEGF_OK;
+}
+
+int negf_sigma_chain1d(negf_ctx* c, int n_contacts, const int* nc, const int* inds,
+                       const double* alpha, const double* Salpha, const double* beta,
+                       const double* Sbeta, const double* tau, const double* Stau,
+                       double eta, double conv, double relFactor, int max_iter, int force_iters,
+                       int* handle)
+{
+    if (!c || c->n <= 0) return NEGF_ESTATE;
+    if (!handle) return NEGF_EINVAL;
+    SigmaProvider* p = nullptr;
+    int rc = make_chain1d(c, c->n, n_contacts, nc, inds, alpha, Salpha, beta, Sbeta, tau, Stau, eta, conv, relFactor,
+                          max_iter, force_iters, &p);
+    if (rc) return rc;
     *handle = add_provider(c, p);
     return NEGF_OK;
 }
@@ -3150,3 +3174,6 @@ int negf_selftest_mfma(negf_ctx* c, double* max_err)
 }
 
 }  // extern "C"
+
+// the layered (recursive Green's function) entry points: negf_layered_*
+#include "negf_layered_impl.h"

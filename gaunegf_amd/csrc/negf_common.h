@@ -176,6 +176,10 @@ struct GjSideStreams {
     bool ok = false;
 };
 
+// A layered (block-tridiagonal) system of the recursive Green's function path: an object of its own inside the context
+// (negf_layered_*; defined in negf_layered_impl.h)
+struct LayeredSystem;
+
 struct ProfEntry { double ms = 0; int launches = 0; double flops_alg = 0, flops_mfma = 0; };
 
 // Flop accounting of the dense kernels, per kernel family (negf_profile_read_flops): the launchers add, for every
@@ -276,6 +280,7 @@ struct negf_ctx {
     std::vector<Pending> prof_pending;
     std::vector<hipEvent_t> ev_pool;
     std::vector<SigmaProvider*> providers;
+    std::vector<LayeredSystem*> layered;       // handles of negf_layered_create: a table that only grows, like providers
 };
 
 // Profiling bracket used by the orchestration code: two hipEvents recorded on the
@@ -302,7 +307,8 @@ void launch_assemble(hipStream_t st, int n, int nb, const cplx* E, const cplx* S
 
 // in-place inverse of nb matrices; info[b] = 0 or 1-based column of a zero pivot.  false: n exceeds what the
 // kernel's LDS staging holds (nothing launched)
-bool launch_inverse_unblocked(hipStream_t st, int n, int nb, cplx* A, int* info);
+// stride: elements between consecutive matrices (0: n * n, the dense path's layout)
+bool launch_inverse_unblocked(hipStream_t st, int n, int nb, cplx* A, int* info, size_t stride = 0);
 // out-of-place ping-pong between A and B (both [nb][stride]); returns true when the
 // inverses end up in B, false when in A
 // win_mode: 0 = the measured choice of window kernel per size and batch, 1 = the strip window kernel (gj_strip.h)
@@ -527,6 +533,32 @@ void launch_deph_response(hipStream_t st, int C, int nc, int nb, const int* orde
 void launch_deph_coupling(hipStream_t st, int KU, int nc, int P, int col, int nlist, int nb, const int* list, const int* tK,
                           const int* ioff, const int* goff, const int* gstride, const int* pos, const cplx* gam,
                           const double* R, cplx* D, size_t strideD);
+
+// Recursive Green's function passes (k_rgf.hip).  Matrices of a batch are compact row-major at the batch stride given.
+constexpr int RGF_MAX_TERM = 8;                 // terminals on one end layer
+// the terminals scattered into an end layer: pos[k] [n] = position of a layer orbital in terminal k's list (-1 outside),
+// sig[k] + b * stride[k] = its K[k] x K[k] block at energy b (stride 0: one block for all energies)
+struct RgfTermArgs { int count = 0; const int* pos[RGF_MAX_TERM]; const cplx* sig[RGF_MAX_TERM]; size_t stride[RGF_MAX_TERM]; int K[RGF_MAX_TERM]; };
+// D[b] = E_b S - F - P[b] - sum_k scatter(Sigma_k,b)   (n x n; P null: no Schur term)
+void launch_rgf_diag(hipStream_t st, int n, int nb, const cplx* E, const cplx* S, const cplx* F, const cplx* P,
+                     size_t strideP, const RgfTermArgs& t, cplx* D, size_t strideD);
+// C[b] = F - E_b S over `count` elements: the negated coupling block
+void launch_rgf_coupling(hipStream_t st, int count, int nb, const cplx* E, const cplx* S, const cplx* F, cplx* C,
+                         size_t strideC);
+// G[b] = g[b] + W[b]
+void launch_rgf_add(hipStream_t st, int count, int nb, const cplx* g, size_t strideg, const cplx* W, size_t strideW,
+                    cplx* G, size_t strideG);
+// out[b] = i (sig[b] - sig[b]^H), K x K
+void launch_rgf_gamma(hipStream_t st, int K, int nb, const cplx* sig, size_t stride_sig, cplx* out, size_t stride_out);
+// site[b * site_stride + r] = -Im G[b][r][r] / pi
+void launch_rgf_dos_diag(hipStream_t st, int n, int nb, const cplx* G, size_t strideG, double* site, size_t site_stride);
+// site[b * site_stride + r] (+)= -Im sum_k G[b][r][k] conj(X[r][k]) / pi   (G, X nr x nk)
+void launch_rgf_dos_rows(hipStream_t st, int nr, int nk, int nb, const cplx* G, size_t strideG, const cplx* X,
+                         double* site, size_t site_stride, bool accumulate);
+void launch_rgf_dos_total(hipStream_t st, int N, int nb, const double* site, size_t site_stride, double* tot);
+// acc[i] += sum_b w[b] X[b][i], one chain per element with b ascending
+void launch_rgf_accumulate(hipStream_t st, int count, int nb, const cplx* w, const cplx* X, size_t strideX, cplx* acc);
+void launch_rgf_merge_info(hipStream_t st, int nb, int offset, const int* linfo, int* info);
 
 bool small_fused_supported(int n);
 int small_fused_grid(int n, int m);

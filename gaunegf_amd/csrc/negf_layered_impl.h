@@ -1,0 +1,650 @@
+// Recursive Green's function path for layered (block-tridiagonal) devices: the negf_layered_* entry points of
+// include/negf.h.  Part of negf_api.hip's translation unit (included at its end): it uses that file's allocation,
+// staging and self-energy helpers as they are.
+//
+// A LayeredSystem is an object of its own inside the context: blocks, terminals and workspace are its own, the dense
+// system (negf_set_system), its providers and its workspace are never read or written here.  What is shared is
+// per-call staging with no meaning between calls: the grid / info / scalar buffers (ensure_mbuffers), the pinned host
+// buffer, the Sigma kernels' scratch and the g(E) cache of the chain leads.
+//
+// Per energy, with C_ij = F_ij - E S_ij (the NEGATED coupling -A_ij: every sign of the textbook recursion cancels):
+//   forward    g_0 = (A_00 - Sigma_left)^-1,   g_i = (A_ii - C_{i,i-1} g_{i-1} C_{i-1,i} - [i = L-1] Sigma_right)^-1
+//   corner     X_0 = g_0,  X_i = g_i C_{i,i-1} X_{i-1}  -> G_{L-1,0};    Y_i = Y_{i-1} C_{i-1,i} g_i  -> G_{0,L-1}
+//   backward   G_{L-1,L-1} = g_{L-1};  U = g_i C_{i,i+1},  V = C_{i+1,i} g_i:
+//              G_{i,i+1} = U G_{i+1,i+1},   G_{i+1,i} = G_{i+1,i+1} V,   G_ii = g_i + G_{i,i+1} V
+// Every layer matrix of a batch is compact row-major at ONE batch stride (the largest layer's n^2): the inverses and
+// products are the dense path's launchers, batched over the energies.
+
+struct RgfTerminal {
+    int end = 0;                   // 0: layer 0, 1: layer L - 1
+    int kind = 0;                  // 0 const, 1 chain, 2 blocks
+    int K = 0;
+    int* d_idx = nullptr;          // [K] orbitals inside the layer
+    int* d_pos = nullptr;          // [n_layer] position in the list, -1 outside
+    cplx* d_sig = nullptr;         // const: [K*K]; blocks: [m_blk][K*K]
+    int m_blk = 0;
+    SigmaProvider* chain = nullptr;
+    DevBuf<cplx> d_blk;            // chain: Sigma of the batch in flight [batch][K*K]
+};
+
+struct LayeredSystem {
+    int L = 0, N = 0, nmax = 0;
+    std::vector<int> n, off;                    // layer sizes, first orbital of each layer
+    std::vector<size_t> doff, uoff;             // start of diagonal block i / coupling block (i, i+1) in the flat arrays
+    size_t dtot = 0, utot = 0;
+    cplx *dFd = nullptr, *dSd = nullptr;        // diagonal blocks
+    cplx *dFu = nullptr, *dSu = nullptr;        // upper blocks (i, i+1), n_i x n_{i+1}
+    cplx *dFl = nullptr, *dSl = nullptr;        // lower blocks (i+1, i) = their conjugate transposes, n_{i+1} x n_i
+    std::vector<RgfTerminal*> terms;
+    size_t stride = 0;                          // elements between the matrices of a batch
+    DevBuf<cplx> d_pool;                        // [RGF_NBUF][batch][stride] work areas
+    DevBuf<cplx> d_gstore;                      // [L][batch][stride] the g_i of a backward sweep
+    DevBuf<cplx> d_small;                       // Gamma_a | Gamma_b | G_ab | X | Y of the transmission
+    DevBuf<cplx> d_out;                         // gr_int: the block lists, host-pointer entry point
+    DevBuf<double> d_site;                      // dos: [m][N] staging of the host-pointer entry point
+    DevBuf<int> d_piv, d_linfo, d_iters, d_conv;
+    int batch = 0;                              // energies the work areas are laid out for
+    long long work_bytes = 0;                   // of the last call: pool + stored g
+};
+
+constexpr int RGF_NBUF = 10;
+
+static void free_terminal(RgfTerminal* t)
+{
+    if (!t) return;
+    dev_free(t->d_idx); dev_free(t->d_pos); dev_free(t->d_sig);
+    release_bufs(t->d_blk);
+    if (t->chain) free_provider(t->chain);
+    delete t;
+}
+
+void free_layered(LayeredSystem* ls)
+{
+    if (!ls) return;
+    for (auto* t : ls->terms) free_terminal(t);
+    dev_free(ls->dFd); dev_free(ls->dSd); dev_free(ls->dFu); dev_free(ls->dSu); dev_free(ls->dFl); dev_free(ls->dSl);
+    release_bufs(ls->d_pool, ls->d_gstore, ls->d_small, ls->d_out);
+    release_bufs(ls->d_site);
+    release_bufs(ls->d_piv, ls->d_linfo, ls->d_iters, ls->d_conv);
+    delete ls;
+}
+
+namespace {
+
+LayeredSystem* get_layered(negf_ctx* c, int handle)
+{
+    if (!c || handle < 0 || handle >= (int)c->layered.size()) return nullptr;
+    return c->layered[handle];
+}
+
+// the index list of a terminal: inside its layer, no orbital twice
+bool rgf_valid_list(int n, int K, const int* inds)
+{
+    if (K < 1 || K > n || !inds) return false;
+    std::vector<char> seen((size_t)n, 0);
+    for (int a = 0; a < K; ++a) {
+        if (inds[a] < 0 || inds[a] >= n || seen[inds[a]]) return false;
+        seen[inds[a]] = 1;
+    }
+    return true;
+}
+
+// Opens a terminal on layer `layer` (0 or L - 1) of system h; validation only, nothing launched
+int rgf_new_terminal(negf_ctx* c, int h, int layer, int K, const int* inds, int* terminal, LayeredSystem** lsp, RgfTerminal** tp)
+{
+    LayeredSystem* ls = get_layered(c, h);
+    if (!ls || !terminal) return NEGF_EINVAL;
+    if (layer != 0 && layer != ls->L - 1) return NEGF_EINVAL;              // interior layers carry no terminal
+    const int end = layer == 0 ? 0 : 1;
+    const int nl = ls->n[layer];
+    if (!rgf_valid_list(nl, K, inds)) return NEGF_EINVAL;
+    int on_end = 0;
+    for (auto* t : ls->terms) on_end += t->end == end;
+    if (on_end >= RGF_MAX_TERM) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    RgfTerminal* t = new RgfTerminal();
+    t->end = end; t->K = K;
+    std::vector<int> pos((size_t)nl, -1);
+    for (int a = 0; a < K; ++a) pos[inds[a]] = a;
+    int rc;
+    if ((rc = dev_alloc(&t->d_idx, (size_t)K)) || (rc = dev_alloc(&t->d_pos, (size_t)nl)) ||
+        (rc = upload(c, t->d_idx, inds, (size_t)K)) || (rc = upload(c, t->d_pos, pos.data(), (size_t)nl))) { free_terminal(t); return rc; }
+    *lsp = ls; *tp = t;
+    return NEGF_OK;
+}
+
+int rgf_add_terminal(LayeredSystem* ls, RgfTerminal* t) { ls->terms.push_back(t); return (int)ls->terms.size() - 1; }
+
+struct RgfRun {
+    LayeredSystem* ls;
+    int nb_max;                 // energies per sweep
+    cplx* buf[RGF_NBUF];
+};
+
+// Energies per sweep and the work areas for them.  A sweep holds RGF_NBUF matrices of the largest layer per energy, a
+// backward sweep L more (the g_i); the budget is the dense path's (auto_batch): a quarter of the free HBM, at most 64 GB.
+int rgf_workspace(negf_ctx* c, LayeredSystem* ls, int m, bool backward, RgfRun* r)
+{
+    const size_t s = ls->stride;
+    const int nbufs = RGF_NBUF + (backward ? ls->L : 0);
+    int want;
+    if (c->batch_user > 0) want = std::min(c->batch_user, std::max(m, 1));
+    else {
+        const double per = 16.0 * (double)s * nbufs;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)24e9;
+        // (what this system already holds counts as free: it is reused)
+        const double held = 16.0 * (double)(ls->d_pool.cap + ls->d_gstore.cap);
+        const double budget = std::min(64.0e9, std::max(2.0e9, 0.25 * ((double)free_b + held)));
+        long b = (long)(budget / per);
+        b = std::max(1L, std::min(b, 4096L));
+        want = (int)std::min<long>(b, std::max(m, 1));
+    }
+    int rc;
+    if ((rc = ensure_cap(c, ls->d_pool, (size_t)RGF_NBUF * want * s + 64))) return rc;
+    if (backward && (rc = ensure_cap(c, ls->d_gstore, (size_t)ls->L * want * s + 64))) return rc;
+    if ((rc = ensure_cap(c, ls->d_piv, (size_t)2 * ls->nmax * want)) || (rc = ensure_cap(c, ls->d_linfo, (size_t)want)) ||
+        (rc = ensure_cap(c, ls->d_iters, (size_t)want)) || (rc = ensure_cap(c, ls->d_conv, (size_t)want))) return rc;
+    for (auto* t : ls->terms)
+        if (t->kind == 1 && (rc = ensure_cap(c, t->d_blk, (size_t)want * t->K * t->K))) return rc;
+    ls->batch = want;
+    ls->work_bytes = 16LL * (long long)s * want * nbufs;
+    r->ls = ls; r->nb_max = want;
+    for (int k = 0; k < RGF_NBUF; ++k) r->buf[k] = ls->d_pool + (size_t)k * want * s;
+    return NEGF_OK;
+}
+
+// What every call checks before it launches anything
+int rgf_open(negf_ctx* c, int h, int m, LayeredSystem** lsp)
+{
+    LayeredSystem* ls = get_layered(c, h);
+    if (!ls || m < 0) return NEGF_EINVAL;
+    for (auto* t : ls->terms) if (t->kind == 2 && m > t->m_blk) return NEGF_EINVAL;   // more energies than Sigma blocks supplied
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    *lsp = ls;
+    return NEGF_OK;
+}
+
+// Sigma blocks of the chain terminals for the energies [m0, m0 + nb) -> their d_blk
+int rgf_chain_sigmas(negf_ctx* c, LayeredSystem* ls, int m0, int nb, const cplx* E)
+{
+    for (auto* t : ls->terms) {
+        if (t->kind != 1) continue;
+        int rc = run_sigma_blocks(c, t->chain, nb, E + m0, ls->d_iters, ls->d_conv, m0, t->d_blk.p);
+        if (rc) return rc;
+    }
+    return NEGF_OK;
+}
+
+// where terminal t's Sigma of the batch starting at m0 lies, and its stride over the energies
+void rgf_sigma_of(const RgfTerminal* t, int m0, const cplx** sig, size_t* stride)
+{
+    const size_t kk = (size_t)t->K * t->K;
+    if (t->kind == 0) { *sig = t->d_sig; *stride = 0; }
+    else if (t->kind == 2) { *sig = t->d_sig + kk * m0; *stride = kk; }
+    else { *sig = t->d_blk.p; *stride = kk; }
+}
+
+RgfTermArgs rgf_term_args(const LayeredSystem* ls, int end, int m0)
+{
+    RgfTermArgs a;
+    for (int k = 0; k < RGF_MAX_TERM; ++k) { a.pos[k] = nullptr; a.sig[k] = nullptr; a.stride[k] = 0; a.K[k] = 0; }
+    for (auto* t : ls->terms) {
+        if (t->end != end) continue;
+        const int k = a.count++;
+        a.pos[k] = t->d_pos; a.K[k] = t->K;
+        rgf_sigma_of(t, m0, &a.sig[k], &a.stride[k]);
+    }
+    return a;
+}
+
+// D[b] = A_ii(E_b) - P[b] - the terminals of layer i
+void rgf_assemble_diag(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* E, const cplx* P, cplx* D)
+{
+    ProfScope ps(c, "rgf");
+    RgfTermArgs ta;
+    if (i == 0) ta = rgf_term_args(ls, 0, m0);
+    else if (i == ls->L - 1) ta = rgf_term_args(ls, 1, m0);
+    else ta = rgf_term_args(ls, -1, m0);
+    launch_rgf_diag(c->stream, ls->n[i], nb, E + m0, ls->dSd + ls->doff[i], ls->dFd + ls->doff[i], P, ls->stride, ta, D, ls->stride);
+}
+
+// the negated couplings of the pair (i, i+1): CU = C_{i,i+1} (n_i x n_{i+1}), CL = C_{i+1,i}
+void rgf_couplings(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* E, cplx* CU, cplx* CL)
+{
+    ProfScope ps(c, "rgf");
+    const int cnt = ls->n[i] * ls->n[i + 1];
+    launch_rgf_coupling(c->stream, cnt, nb, E + m0, ls->dSu + ls->uoff[i], ls->dFu + ls->uoff[i], CU, ls->stride);
+    launch_rgf_coupling(c->stream, cnt, nb, E + m0, ls->dSl + ls->uoff[i], ls->dFl + ls->uoff[i], CL, ls->stride);
+}
+
+// C[b] (M x N) = A[b] (M x K) B[b] (K x N), all compact at the system's stride
+void rgf_mm(negf_ctx* c, LayeredSystem* ls, int M, int N, int K, int nb, const cplx* A, const cplx* B, cplx* C)
+{
+    ProfScope ps(c, "zgemm");
+    launch_zgemm(c->stream, M, N, K, nb, A, K, ls->stride, B, N, ls->stride, 0, C, N, ls->stride);
+}
+
+// In-place inverse of the n x n matrices in A with B as the blocked kernels' second area: *res = where the inverses
+// lie.  A zero pivot of layer i is reported as column off_i + k of the whole system.
+int rgf_inverse(negf_ctx* c, LayeredSystem* ls, int i, int nb, cplx* A, cplx* B, int* info, cplx** res)
+{
+    const int n = ls->n[i];
+    {
+        ProfScope ps(c, "inverse");
+        int algo = c->inverse_algo;
+        if (algo == 0) algo = inverse_blocked_supported(n) ? 2 : 1;
+        const int win_mode = algo == 3 ? 1 : algo == 4 ? 2 : 0;
+        if (algo > 2) algo = 2;
+        bool in_b = false;
+        if (algo == 2) {
+            in_b = launch_inverse_blocked(c->stream, n, nb, A, B, ls->stride, ls->d_piv, ls->d_linfo, &c->gj_side, win_mode, nullptr);
+            if (!in_b) algo = 1;
+        }
+        if (algo == 1 && !launch_inverse_unblocked(c->stream, n, nb, A, ls->d_linfo, ls->stride)) return NEGF_EINVAL;
+        NEGF_HIP_CHECK(hipGetLastError());
+        const double dn = n, np = (double)((n + 15) & ~15), k4 = (double)((n + 3) & ~3);
+        negf_count_flops(8.0 * dn * dn * dn * nb, algo == 2 ? 6.0 * np * np * k4 * nb - inverse_blocked_vector_flops() : 0.0);
+        *res = in_b ? B : A;
+    }
+    launch_rgf_merge_info(c->stream, nb, ls->off[i], ls->d_linfo, info);
+    return NEGF_OK;
+}
+
+// Forward sweep of the batch [m0, m0 + nb).  keep: the g_i go to d_gstore (a backward sweep follows); otherwise only
+// g_{i-1} is alive, and the corner block X_i (corner = 1: G_{i,0}) or Y_i (corner = 2: G_{0,i}) is carried along --
+// *corner_out = the block of the last layer.  Work areas: buf[0..8].
+int rgf_forward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, bool keep, int corner, cplx** corner_out)
+{
+    LayeredSystem* ls = r.ls;
+    const size_t s = ls->stride;
+    const size_t layer_bytes = (size_t)nb * s * sizeof(cplx);
+    cplx *CU = r.buf[0], *CL = r.buf[1], *T = r.buf[2], *P = r.buf[3];
+    cplx* R[3] = {r.buf[4], r.buf[5], r.buf[6]};           // rotating: g_{i-1} | matrix to invert | second area
+    cplx *Xa = r.buf[7], *Xb = r.buf[8];
+    int* info = c->d_info + m0;
+    NEGF_HIP_CHECK(hipMemsetAsync(info, 0, (size_t)nb * sizeof(int), c->stream));
+    int rc;
+    if ((rc = rgf_chain_sigmas(c, ls, m0, nb, E))) return rc;
+    cplx* gprev = nullptr;
+    for (int i = 0; i < ls->L; ++i) {
+        const int ni = ls->n[i];
+        cplx *D, *B;
+        if (keep) { D = ls->d_gstore + (size_t)i * r.nb_max * s; B = R[0]; }
+        else {
+            cplx* fr[3]; int k = 0;
+            for (cplx* q : R) if (q != gprev) fr[k++] = q;             // the two areas g_{i-1} does not occupy
+            D = fr[0]; B = fr[1];
+        }
+        if (i > 0) {
+            const int np = ls->n[i - 1];
+            rgf_couplings(c, ls, i - 1, m0, nb, E, CU, CL);
+            rgf_mm(c, ls, ni, np, np, nb, CL, gprev, T);               // C_{i,i-1} g_{i-1}
+            rgf_mm(c, ls, ni, ni, np, nb, T, CU, P);                   // ... C_{i-1,i}
+        }
+        rgf_assemble_diag(c, ls, i, m0, nb, E, i > 0 ? P : nullptr, D);
+        cplx* g = nullptr;
+        if ((rc = rgf_inverse(c, ls, i, nb, D, B, info, &g))) return rc;
+        if (keep && g != D) { NEGF_HIP_CHECK(hipMemcpyAsync(D, g, layer_bytes, hipMemcpyDeviceToDevice, c->stream)); g = D; }
+        if (!keep && corner) {
+            const int n0 = ls->n[0];
+            if (i == 0) { NEGF_HIP_CHECK(hipMemcpyAsync(Xa, g, layer_bytes, hipMemcpyDeviceToDevice, c->stream)); }
+            else if (corner == 1) {
+                rgf_mm(c, ls, ni, n0, ls->n[i - 1], nb, CL, Xa, T);    // C_{i,i-1} X_{i-1}
+                rgf_mm(c, ls, ni, n0, ni, nb, g, T, Xb);               // X_i = g_i ...
+                std::swap(Xa, Xb);
+            } else {
+                rgf_mm(c, ls, n0, ni, ls->n[i - 1], nb, Xa, CU, T);    // Y_{i-1} C_{i-1,i}
+                rgf_mm(c, ls, n0, ni, ni, nb, T, g, Xb);               // Y_i = ... g_i
+                std::swap(Xa, Xb);
+            }
+        }
+        gprev = g;
+    }
+    if (corner_out) *corner_out = Xa;
+    return NEGF_OK;
+}
+
+// what a backward sweep hands to its consumer, layer by layer from the last one down: G_ii, and for i < L - 1 the
+// blocks G_{i,i+1}, G_{i+1,i} (null for the last layer)
+typedef void (*RgfConsume)(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* Gii, const cplx* Gup, const cplx* Glo, void* arg);
+
+int rgf_backward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, RgfConsume consume, void* arg)
+{
+    LayeredSystem* ls = r.ls;
+    const size_t s = ls->stride;
+    cplx *CU = r.buf[0], *CL = r.buf[1], *U = r.buf[2], *V = r.buf[3], *Wm = r.buf[4], *Gup = r.buf[5], *Glo = r.buf[6];
+    cplx *Gcur = r.buf[7], *Galt = r.buf[8];
+    auto g_of = [&](int i) { return ls->d_gstore + (size_t)i * r.nb_max * s; };
+    const cplx* Gnext = g_of(ls->L - 1);
+    consume(c, ls, ls->L - 1, m0, nb, Gnext, nullptr, nullptr, arg);
+    for (int i = ls->L - 2; i >= 0; --i) {
+        const int ni = ls->n[i], nn = ls->n[i + 1];
+        const cplx* g = g_of(i);
+        rgf_couplings(c, ls, i, m0, nb, E, CU, CL);
+        rgf_mm(c, ls, ni, nn, ni, nb, g, CU, U);                       // U = g_i C_{i,i+1}
+        rgf_mm(c, ls, ni, nn, nn, nb, U, Gnext, Gup);                  // G_{i,i+1}
+        rgf_mm(c, ls, nn, ni, ni, nb, CL, g, V);                       // V = C_{i+1,i} g_i
+        rgf_mm(c, ls, nn, ni, nn, nb, Gnext, V, Glo);                  // G_{i+1,i}
+        rgf_mm(c, ls, ni, ni, nn, nb, Gup, V, Wm);                     // g_i C G_{i+1,i+1} C g_i
+        { ProfScope ps(c, "rgf"); launch_rgf_add(c->stream, ni * ni, nb, g, s, Wm, s, Gcur, s); }
+        consume(c, ls, i, m0, nb, Gcur, Gup, Glo, arg);
+        Gnext = Gcur;
+        std::swap(Gcur, Galt);
+    }
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+struct RgfDosArg { int form; double* site; };      // site: [m][N] on the device
+
+void rgf_consume_dos(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* Gii, const cplx* Gup, const cplx* Glo, void* arg)
+{
+    ProfScope ps(c, "rgf");
+    const RgfDosArg* a = static_cast<const RgfDosArg*>(arg);
+    const size_t s = ls->stride;
+    double* site = a->site + (size_t)m0 * ls->N;
+    if (a->form == 0) { launch_rgf_dos_diag(c->stream, ls->n[i], nb, Gii, s, site + ls->off[i], (size_t)ls->N); return; }
+    // -Im (G S)_rr / pi, S_kr read as conj(S_rk): the diagonal block, then the two neighbours
+    launch_rgf_dos_rows(c->stream, ls->n[i], ls->n[i], nb, Gii, s, ls->dSd + ls->doff[i], site + ls->off[i], (size_t)ls->N, false);
+    if (Gup) {
+        launch_rgf_dos_rows(c->stream, ls->n[i], ls->n[i + 1], nb, Gup, s, ls->dSu + ls->uoff[i], site + ls->off[i], (size_t)ls->N, true);
+        launch_rgf_dos_rows(c->stream, ls->n[i + 1], ls->n[i], nb, Glo, s, ls->dSl + ls->uoff[i], site + ls->off[i + 1], (size_t)ls->N, true);
+    }
+}
+
+struct RgfSumArg { const cplx* w; cplx* out; };
+
+void rgf_consume_sum(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* Gii, const cplx* Gup, const cplx* Glo, void* arg)
+{
+    ProfScope ps(c, "accumulate");
+    const RgfSumArg* a = static_cast<const RgfSumArg*>(arg);
+    const size_t s = ls->stride;
+    launch_rgf_accumulate(c->stream, ls->n[i] * ls->n[i], nb, a->w + m0, Gii, s, a->out + ls->doff[i]);
+    if (Gup) {
+        const int cnt = ls->n[i] * ls->n[i + 1];
+        launch_rgf_accumulate(c->stream, cnt, nb, a->w + m0, Gup, s, a->out + ls->dtot + ls->uoff[i]);
+        launch_rgf_accumulate(c->stream, cnt, nb, a->w + m0, Glo, s, a->out + ls->dtot + ls->utot + ls->uoff[i]);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int negf_layered_create(negf_ctx* c, int n_layers, const int* sizes, const double* F_diag, const double* F_up,
+                        const double* S_diag, const double* S_up, int* handle)
+{
+    if (!c || !sizes || !F_diag || !F_up || !S_diag || !S_up || !handle) return NEGF_EINVAL;
+    if (n_layers < 2) return NEGF_EINVAL;
+    long long N = 0;
+    for (int i = 0; i < n_layers; ++i) {
+        if (sizes[i] < 1 || sizes[i] > 8192) return NEGF_EINVAL;        // what the inverse kernels serve
+        N += sizes[i];
+    }
+    if (N > (1LL << 30)) return NEGF_EINVAL;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    LayeredSystem* ls = new LayeredSystem();
+    ls->L = n_layers; ls->N = (int)N;
+    ls->n.assign(sizes, sizes + n_layers);
+    ls->off.resize(n_layers); ls->doff.resize(n_layers); ls->uoff.resize(n_layers - 1);
+    for (int i = 0, o = 0; i < n_layers; ++i) {
+        ls->off[i] = o; o += sizes[i];
+        ls->doff[i] = ls->dtot; ls->dtot += (size_t)sizes[i] * sizes[i];
+        if (i + 1 < n_layers) { ls->uoff[i] = ls->utot; ls->utot += (size_t)sizes[i] * sizes[i + 1]; }
+        ls->nmax = std::max(ls->nmax, sizes[i]);
+    }
+    ls->stride = (size_t)ls->nmax * ls->nmax;
+    // the lower blocks are the conjugate transposes of the upper ones: formed once on the host, so that every
+    // per-energy pass reads its block row-major
+    const cplx* Fu = reinterpret_cast<const cplx*>(F_up);
+    const cplx* Su = reinterpret_cast<const cplx*>(S_up);
+    std::vector<cplx> Fl(ls->utot), Sl(ls->utot);
+    for (int i = 0; i + 1 < n_layers; ++i) {
+        const int a = sizes[i], b = sizes[i + 1];
+        const size_t o = ls->uoff[i];
+        for (int r = 0; r < b; ++r)
+            for (int q = 0; q < a; ++q) {
+                Fl[o + (size_t)r * a + q] = cconj(Fu[o + (size_t)q * b + r]);
+                Sl[o + (size_t)r * a + q] = cconj(Su[o + (size_t)q * b + r]);
+            }
+    }
+    int rc;
+    if ((rc = dev_alloc(&ls->dFd, ls->dtot)) || (rc = dev_alloc(&ls->dSd, ls->dtot)) ||
+        (rc = dev_alloc(&ls->dFu, ls->utot)) || (rc = dev_alloc(&ls->dSu, ls->utot)) ||
+        (rc = dev_alloc(&ls->dFl, ls->utot)) || (rc = dev_alloc(&ls->dSl, ls->utot)) ||
+        (rc = upload(c, ls->dFd, reinterpret_cast<const cplx*>(F_diag), ls->dtot)) ||
+        (rc = upload(c, ls->dSd, reinterpret_cast<const cplx*>(S_diag), ls->dtot)) ||
+        (rc = upload(c, ls->dFu, Fu, ls->utot)) || (rc = upload(c, ls->dSu, Su, ls->utot)) ||
+        (rc = upload(c, ls->dFl, Fl.data(), ls->utot)) || (rc = upload(c, ls->dSl, Sl.data(), ls->utot))) { free_layered(ls); return rc; }
+    c->layered.push_back(ls);
+    *handle = (int)c->layered.size() - 1;
+    return NEGF_OK;
+}
+
+int negf_layered_free(negf_ctx* c, int h)
+{
+    LayeredSystem* ls = get_layered(c, h);
+    if (!ls) return NEGF_EINVAL;
+    (void)hipStreamSynchronize(c->stream);
+    free_layered(ls);
+    c->layered[h] = nullptr;
+    return NEGF_OK;
+}
+
+int negf_layered_terminal_const(negf_ctx* c, int h, int layer, int K, const int* inds, const double* sigma, int* terminal)
+{
+    if (!sigma) return NEGF_EINVAL;
+    LayeredSystem* ls; RgfTerminal* t;
+    int rc = rgf_new_terminal(c, h, layer, K, inds, terminal, &ls, &t);
+    if (rc) return rc;
+    t->kind = 0;
+    const size_t kk = (size_t)K * K;
+    if ((rc = dev_alloc(&t->d_sig, kk)) || (rc = upload(c, t->d_sig, reinterpret_cast<const cplx*>(sigma), kk))) { free_terminal(t); return rc; }
+    *terminal = rgf_add_terminal(ls, t);
+    return NEGF_OK;
+}
+
+int negf_layered_terminal_blocks(negf_ctx* c, int h, int layer, int K, const int* inds, int m, const double* sigma, int* terminal)
+{
+    if (!sigma || m < 1) return NEGF_EINVAL;
+    LayeredSystem* ls; RgfTerminal* t;
+    int rc = rgf_new_terminal(c, h, layer, K, inds, terminal, &ls, &t);
+    if (rc) return rc;
+    t->kind = 2; t->m_blk = m;
+    const size_t cnt = (size_t)K * K * m;
+    if ((rc = dev_alloc(&t->d_sig, cnt)) || (rc = upload(c, t->d_sig, reinterpret_cast<const cplx*>(sigma), cnt))) { free_terminal(t); return rc; }
+    *terminal = rgf_add_terminal(ls, t);
+    return NEGF_OK;
+}
+
+int negf_layered_terminal_chain(negf_ctx* c, int h, int layer, int K, const int* inds,
+                                const double* alpha, const double* Salpha, const double* beta, const double* Sbeta,
+                                const double* tau, const double* Stau, double eta, double conv, double relFactor,
+                                int max_iter, int force_iters, int solver, int* terminal)
+{
+    if (solver != 0 && solver != 1) return NEGF_EINVAL;
+    if (solver == 1 && (!(conv >= 0.0) || max_iter < 0)) return NEGF_EINVAL;
+    LayeredSystem* ls; RgfTerminal* t;
+    int rc = rgf_new_terminal(c, h, layer, K, inds, terminal, &ls, &t);
+    if (rc) return rc;
+    t->kind = 1;
+    // one CHAIN1D provider with one contact, its index list inside the layer: the chain kernels, the job order and the
+    // g(E) cache serve it as they serve a dense system's lead
+    if ((rc = make_chain1d(c, ls->n[layer], 1, &K, inds, alpha, Salpha, beta, Sbeta, tau, Stau, eta, conv,
+                           solver == 1 ? 1.0 : relFactor, max_iter, force_iters, &t->chain))) { free_terminal(t); return rc; }
+    t->chain->solver = solver;
+    *terminal = rgf_add_terminal(ls, t);
+    return NEGF_OK;
+}
+
+int negf_layered_terminal_sigma(negf_ctx* c, int h, int terminal, int m, const double* E, double* sigma_out)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (terminal < 0 || terminal >= (int)ls->terms.size() || (m > 0 && (!E || !sigma_out))) return NEGF_EINVAL;
+    RgfTerminal* t = ls->terms[terminal];
+    const size_t kk = (size_t)t->K * t->K;
+    cplx* out = reinterpret_cast<cplx*>(sigma_out);
+    if (t->kind == 0) { for (int b = 0; b < m; ++b) if ((rc = download(c, out + kk * b, t->d_sig, kk))) return rc; return NEGF_OK; }
+    if (t->kind == 2) return download(c, out, t->d_sig, kk * m);
+    if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
+    RgfRun r;
+    if ((rc = rgf_workspace(c, ls, m, false, &r))) return rc;
+    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
+        const int nb = std::min(r.nb_max, m - m0);
+        if ((rc = run_sigma_blocks(c, t->chain, nb, c->d_E + m0, ls->d_iters, ls->d_conv, m0, t->d_blk.p))) return rc;
+        if ((rc = download(c, out + kk * m0, t->d_blk.p, kk * nb))) return rc;
+    }
+    return NEGF_OK;
+}
+
+int negf_layered_transmission_dev(negf_ctx* c, int h, int term_a, int term_b, int m, const double* E_dev, double* T_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    const int nt = (int)ls->terms.size();
+    if (term_a < 0 || term_a >= nt || term_b < 0 || term_b >= nt) return NEGF_EINVAL;
+    RgfTerminal *ta = ls->terms[term_a], *tb = ls->terms[term_b];
+    if (ta->end == tb->end) return NEGF_EINVAL;                     // the corner blocks connect opposite end layers only
+    if (!T_dev || (m > 0 && !E_dev)) return NEGF_EINVAL;
+    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
+    RgfRun r;
+    if ((rc = rgf_workspace(c, ls, m, false, &r))) return rc;
+    const int Ka = ta->K, Kb = tb->K;
+    const size_t kab = (size_t)Ka * Kb, sa = (size_t)Ka * Ka, sb = (size_t)Kb * Kb;
+    const size_t per = sa + sb + 3 * kab;
+    if ((rc = ensure_cap(c, ls->d_small, per * r.nb_max))) return rc;
+    cplx* gamA = ls->d_small;
+    cplx* gamB = gamA + sa * r.nb_max;
+    cplx* Gab = gamB + sb * r.nb_max;
+    cplx* Xs = Gab + kab * r.nb_max;
+    cplx* Ys = Xs + kab * r.nb_max;
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    // a on the last layer: G_ab is cut from G_{L-1,0} (X); a on layer 0: from G_{0,L-1} (Y)
+    const int corner = ta->end == 1 ? 1 : 2;
+    const int ld = corner == 1 ? ls->n[0] : ls->n[ls->L - 1];
+    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
+        const int nb = std::min(r.nb_max, m - m0);
+        cplx* Gc = nullptr;
+        if ((rc = rgf_forward(c, r, m0, nb, E, false, corner, &Gc))) return rc;
+        const cplx *sA, *sB; size_t stA, stB;
+        rgf_sigma_of(ta, m0, &sA, &stA); rgf_sigma_of(tb, m0, &sB, &stB);
+        {
+            ProfScope ps(c, "gamma");
+            launch_rgf_gamma(c->stream, Ka, nb, sA, stA, gamA, sa);
+            launch_rgf_gamma(c->stream, Kb, nb, sB, stB, gamB, sb);
+        }
+        {
+            ProfScope ps(c, "zgemm");
+            launch_gather_block(c->stream, ld, Ka, Kb, nb, Gc, ls->stride, ta->d_idx, tb->d_idx, Gab, kab);
+            launch_zgemm(c->stream, Ka, Kb, Ka, nb, gamA, Ka, sa, Gab, Kb, kab, 0, Xs, Kb, kab);
+            launch_zgemm(c->stream, Ka, Kb, Kb, nb, Xs, Kb, kab, gamB, Kb, sb, 0, Ys, Kb, kab);
+        }
+        ProfScope ps(c, "trace");
+        launch_trace_dot(c->stream, Ka, Kb, nb, Ys, Kb, kab, Gab, Kb, kab, T_dev + m0, 1);
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_layered_transmission(negf_ctx* c, int h, int term_a, int term_b, int m, const double* E, double* T, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (m > 0 && (!E || !T)) return NEGF_EINVAL;
+    const int nt = (int)ls->terms.size();
+    if (term_a < 0 || term_a >= nt || term_b < 0 || term_b >= nt || ls->terms[term_a]->end == ls->terms[term_b]->end) return NEGF_EINVAL;
+    if (m == 0) return NEGF_OK;
+    if ((rc = stage_grid(c, m, 1, E, nullptr, (size_t)m * sizeof(double)))) return rc;
+    if ((rc = negf_layered_transmission_dev(c, h, term_a, term_b, m, reinterpret_cast<double*>(c->d_E), c->d_scal))) return rc;
+    return fetch_result_and_info(c, m, c->d_scal, (size_t)m * sizeof(double), T, info);
+}
+
+int negf_layered_dos_dev(negf_ctx* c, int h, int form, int m, const double* E_dev, double* dos_total_dev, double* dos_site_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if ((form != 0 && form != 1) || (m > 0 && (!E_dev || !dos_total_dev || !dos_site_dev))) return NEGF_EINVAL;
+    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
+    RgfRun r;
+    if ((rc = rgf_workspace(c, ls, m, true, &r))) return rc;
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    RgfDosArg arg{form, dos_site_dev};
+    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
+        const int nb = std::min(r.nb_max, m - m0);
+        if ((rc = rgf_forward(c, r, m0, nb, E, true, 0, nullptr))) return rc;
+        if ((rc = rgf_backward(c, r, m0, nb, E, rgf_consume_dos, &arg))) return rc;
+        ProfScope ps(c, "rgf");
+        launch_rgf_dos_total(c->stream, ls->N, nb, dos_site_dev + (size_t)m0 * ls->N, (size_t)ls->N, dos_total_dev + m0);
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_layered_dos(negf_ctx* c, int h, int form, int m, const double* E, double* dos_total, double* dos_site, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if ((form != 0 && form != 1) || (m > 0 && (!E || !dos_total))) return NEGF_EINVAL;
+    if (m == 0) return NEGF_OK;
+    if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
+    if ((rc = ensure_cap(c, ls->d_site, (size_t)m * ls->N))) return rc;
+    if ((rc = negf_layered_dos_dev(c, h, form, m, reinterpret_cast<double*>(c->d_E), c->d_scal, ls->d_site))) return rc;
+    if (dos_site && (rc = download(c, dos_site, ls->d_site.p, (size_t)m * ls->N))) return rc;
+    if ((rc = download(c, dos_total, c->d_scal, (size_t)m))) return rc;
+    return reduce_info(c, m, info);
+}
+
+int negf_layered_gr_int_dev(negf_ctx* c, int h, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
+    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
+    RgfRun r;
+    if ((rc = rgf_workspace(c, ls, m, true, &r))) return rc;
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    RgfSumArg arg{reinterpret_cast<const cplx*>(w_dev), reinterpret_cast<cplx*>(out_dev)};
+    NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, (ls->dtot + 2 * ls->utot) * sizeof(cplx), c->stream));
+    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
+        const int nb = std::min(r.nb_max, m - m0);
+        if ((rc = rgf_forward(c, r, m0, nb, E, true, 0, nullptr))) return rc;
+        if ((rc = rgf_backward(c, r, m0, nb, E, rgf_consume_sum, &arg))) return rc;
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_layered_gr_int(negf_ctx* c, int h, int m, const double* E, const double* w, double* out, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
+    const size_t tot = ls->dtot + 2 * ls->utot;
+    if ((rc = stage_grid(c, m, 1, E, w, tot * sizeof(cplx)))) return rc;
+    if ((rc = ensure_cap(c, ls->d_out, tot))) return rc;
+    if ((rc = negf_layered_gr_int_dev(c, h, m, reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
+                                      reinterpret_cast<double*>(ls->d_out.p)))) return rc;
+    return fetch_result_and_info(c, m, ls->d_out.p, tot * sizeof(cplx), out, info);
+}
+
+int negf_layered_workspace_bytes(negf_ctx* c, int h, long long* work)
+{
+    LayeredSystem* ls = get_layered(c, h);
+    if (!ls || !work) return NEGF_EINVAL;
+    *work = ls->work_bytes;
+    return NEGF_OK;
+}
+
+}  // extern "C"

@@ -900,6 +900,171 @@ class Engine:
         self.last_converged = conv[:E.size]
         return out
 
+    # ------------------------------------------------------ layered devices
+    # The recursive Green's function path (negf_layered_*): a layered system is an object of its own inside the context;
+    # nothing here touches the dense system, its providers or ``self.n``.
+    def _lcheck(self, rc, where):
+        """Invalid arguments of the layered calls are the caller's: ValueError, before anything was launched."""
+        if rc == _lib.NEGF_EINVAL:
+            raise ValueError(f"{where}: invalid argument (layer sizes, index lists, terminal layers or the number of "
+                             "energies of a 'blocks' terminal)")
+        return check(rc, where)
+
+    def layered_create(self, F_diag, F_up, S_diag, S_up):
+        """Blocks of a layered system: L diagonal blocks n_i x n_i and L - 1 upper blocks n_i x n_{i+1} of F and S."""
+        Fd = [_c128(b) for b in F_diag]; Sd = [_c128(b) for b in S_diag]
+        Fu = [_c128(b) for b in F_up]; Su = [_c128(b) for b in S_up]
+        L = len(Fd)
+        if L < 2 or len(Sd) != L or len(Fu) != L - 1 or len(Su) != L - 1:
+            raise ValueError("a layered system has L >= 2 diagonal blocks and L - 1 upper blocks of F and of S")
+        sizes = []
+        for i, b in enumerate(Fd):
+            if b.ndim != 2 or b.shape[0] != b.shape[1] or b.shape[0] < 1 or Sd[i].shape != b.shape:
+                raise ValueError(f"diagonal block {i}: F {b.shape}, S {Sd[i].shape}")
+            sizes.append(b.shape[0])
+        for i in range(L - 1):
+            if Fu[i].shape != (sizes[i], sizes[i + 1]) or Su[i].shape != Fu[i].shape:
+                raise ValueError(f"upper block {i}: expected {(sizes[i], sizes[i + 1])}, got F {Fu[i].shape}, S {Su[i].shape}")
+
+        def cat(bl):
+            return np.ascontiguousarray(np.concatenate([b.ravel() for b in bl])) if bl else np.zeros(0, np.complex128)
+        sz = np.ascontiguousarray(sizes, dtype=np.int32)
+        fd, fu, sd, su = cat(Fd), cat(Fu), cat(Sd), cat(Su)
+        h = C.c_int(-1)
+        self._lcheck(self._lib.negf_layered_create(self._ctx, L, _ptr(sz), _ptr(fd), _ptr(fu), _ptr(sd), _ptr(su),
+                                                   C.byref(h)), "negf_layered_create")
+        self.__dict__.setdefault("_layered_sizes", {})[h.value] = tuple(sizes)
+        return h.value
+
+    def layered_free(self, handle):
+        if getattr(self, "_ctx", None):
+            self._lib.negf_layered_free(self._ctx, int(handle))
+            self.__dict__.get("_layered_sizes", {}).pop(int(handle), None)
+
+    def _lsizes(self, handle):
+        try:
+            return self.__dict__["_layered_sizes"][int(handle)]
+        except KeyError:
+            raise ValueError(f"no layered system with handle {handle}") from None
+
+    @staticmethod
+    def _linds(inds):
+        return np.ascontiguousarray(np.asarray(inds).ravel(), dtype=np.int32)
+
+    def layered_terminal_const(self, handle, layer, inds, sigma):
+        inds = self._linds(inds)
+        sig = _c128(sigma, (inds.size, inds.size))
+        t = C.c_int(-1)
+        self._lcheck(self._lib.negf_layered_terminal_const(self._ctx, int(handle), int(layer), inds.size, _ptr(inds),
+                                                           _ptr(sig), C.byref(t)), "negf_layered_terminal_const")
+        return t.value
+
+    def layered_terminal_chain(self, handle, layer, inds, alpha, Salpha, beta, Sbeta, tau, Stau, eta, conv=1e-5,
+                               relFactor=0.1, max_iter=2000, force_iters=-1, solver='fixed-point',
+                               tol=SURFACE_DOUBLING_TOL, max_steps=SURFACE_DOUBLING_MAX_STEPS):
+        """A 1-D chain lead on ``inds`` of an end layer; arguments as sigma_chain1d's for one contact."""
+        if solver not in ('fixed-point', 'doubling'):
+            raise ValueError(f"solver must be 'fixed-point' or 'doubling', got {solver!r}")
+        inds = self._linds(inds)
+        k = inds.size
+        mats = [_c128(x, (k, k)) for x in (alpha, Salpha, beta, Sbeta, tau, Stau)]
+        rd = solver == 'doubling'
+        t = C.c_int(-1)
+        self._lcheck(self._lib.negf_layered_terminal_chain(
+            self._ctx, int(handle), int(layer), k, _ptr(inds), *[_ptr(x) for x in mats], float(eta),
+            float(tol if rd else conv), float(relFactor), int(max_steps if rd else max_iter), int(force_iters),
+            1 if rd else 0, C.byref(t)), "negf_layered_terminal_chain")
+        return t.value
+
+    def layered_terminal_blocks(self, handle, layer, inds, sigma):
+        """Self-energy blocks [m, K, K] supplied per energy: block k serves energy k of every later call."""
+        inds = self._linds(inds)
+        sig = _c128(sigma)
+        if sig.ndim != 3 or sig.shape[1:] != (inds.size, inds.size) or sig.shape[0] < 1:
+            raise ValueError(f"expected [m, {inds.size}, {inds.size}] blocks, got {sig.shape}")
+        t = C.c_int(-1)
+        self._lcheck(self._lib.negf_layered_terminal_blocks(self._ctx, int(handle), int(layer), inds.size, _ptr(inds),
+                                                            sig.shape[0], _ptr(sig), C.byref(t)),
+                     "negf_layered_terminal_blocks")
+        return t.value
+
+    def layered_terminal_sigma(self, handle, terminal, E, K):
+        """Sigma_t(E) [m, K, K] of a terminal with K orbitals."""
+        E, _ = self._grid(E)
+        out = np.zeros((E.size, int(K), int(K)), dtype=np.complex128)
+        self._lcheck(self._lib.negf_layered_terminal_sigma(self._ctx, int(handle), int(terminal), E.size, _ptr(E),
+                                                           _ptr(out)), "negf_layered_terminal_sigma")
+        return out
+
+    def layered_transmission(self, handle, term_a, term_b, E):
+        """T_ab(E) [m] between terminals on opposite end layers (the transmission from b into a)."""
+        E, _ = self._grid(E)
+        T = np.zeros(E.size, dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_transmission(self._ctx, int(handle), int(term_a), int(term_b), E.size,
+                                                              _ptr(E), _ptr(T), _ptr(info)), "negf_layered_transmission")
+        self._numerical(rc, info[:E.size], "layered_transmission")
+        return T
+
+    def layered_dos(self, handle, E, mulliken=False, per_site=True):
+        """(dos_total [m], dos_site [m, N]): -Im diag G / pi, or with ``mulliken`` -Im diag(G S) / pi."""
+        E, _ = self._grid(E)
+        N = sum(self._lsizes(handle))
+        tot = np.zeros(E.size, dtype=np.float64)
+        site = np.zeros((E.size, N), dtype=np.float64) if per_site else None
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_dos(self._ctx, int(handle), 1 if mulliken else 0, E.size, _ptr(E),
+                                                     _ptr(tot), _ptr(site), _ptr(info)), "negf_layered_dos")
+        self._numerical(rc, info[:E.size], "layered_dos")
+        return (tot, site) if per_site else tot
+
+    def _lsplit(self, handle, flat):
+        sizes = self._lsizes(handle)
+        diag, up, low, o = [], [], [], 0
+        for n in sizes:
+            diag.append(flat[o:o + n * n].reshape(n, n)); o += n * n
+        for a, b in zip(sizes[:-1], sizes[1:]):
+            up.append(flat[o:o + a * b].reshape(a, b)); o += a * b
+        for a, b in zip(sizes[:-1], sizes[1:]):
+            low.append(flat[o:o + a * b].reshape(b, a)); o += a * b
+        return diag, up, low
+
+    def layered_pattern_size(self, handle):
+        sizes = self._lsizes(handle)
+        return sum(n * n for n in sizes) + 2 * sum(a * b for a, b in zip(sizes[:-1], sizes[1:]))
+
+    def layered_gr_int(self, handle, E, w):
+        """sum_m w_m G(E_m) on the pattern of S: (diagonal blocks, upper blocks G_{i,i+1}, lower blocks G_{i+1,i})."""
+        E, w = self._grid(E, w)
+        flat = np.zeros(self.layered_pattern_size(handle), dtype=np.complex128)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_gr_int(self._ctx, int(handle), E.size, _ptr(E), _ptr(w), _ptr(flat),
+                                                        _ptr(info)), "negf_layered_gr_int")
+        self._numerical(rc, info[:E.size], "layered_gr_int")
+        return self._lsplit(handle, flat)
+
+    def layered_transmission_dev(self, handle, term_a, term_b, m, E_ptr, T_ptr):
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_transmission_dev(self._ctx, int(handle), int(term_a), int(term_b), int(m),
+                                                             C.c_void_p(E_ptr), C.c_void_p(T_ptr)),
+                     "negf_layered_transmission_dev")
+
+    def layered_dos_dev(self, handle, m, E_ptr, tot_ptr, site_ptr, mulliken=False):
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_dos_dev(self._ctx, int(handle), 1 if mulliken else 0, int(m), C.c_void_p(E_ptr),
+                                                    C.c_void_p(tot_ptr), C.c_void_p(site_ptr)), "negf_layered_dos_dev")
+
+    def layered_gr_int_dev(self, handle, m, E_ptr, w_ptr, out_ptr):
+        """out: layered_pattern_size(handle) complex values, diagonal | upper | lower blocks."""
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_gr_int_dev(self._ctx, int(handle), int(m), C.c_void_p(E_ptr), C.c_void_p(w_ptr),
+                                                       C.c_void_p(out_ptr)), "negf_layered_gr_int_dev")
+
+    def layered_workspace_bytes(self, handle):
+        v = C.c_longlong(0)
+        self._lcheck(self._lib.negf_layered_workspace_bytes(self._ctx, int(handle), C.byref(v)), "negf_layered_workspace_bytes")
+        return int(v.value)
+
     # -------------------------------------------------- device-resident calls
     def gr_int_dev(self, handle, m, E_ptr, w_ptr, out_ptr):
         self.counters["calls"] += 1; self.counters["points"] += int(m)

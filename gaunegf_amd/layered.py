@@ -1,0 +1,295 @@
+"""
+Layered (block-tridiagonal) devices on the recursive Green's function path of the engine.
+
+A long wire, an oligomer between two chain leads or a molecule with several principal layers of electrode attached
+couples only neighbouring layers; only the two end layers carry a self-energy.  ``LayeredSystem`` holds the blocks,
+``partition`` finds a layering of a dense (F, S), ``Lead`` describes a terminal, and the front ends follow their dense
+namesakes in transport.py / integrate.py:
+
+    calculate_transmission_layered(system, leads, energy_list)      -> T [m]
+    calculate_dos_layered(system, leads, energy_list)               -> (dos_total [m], dos_per_site [m, N])
+    calculate_pdos_layered(system, leads, energy_list, groups=None) -> [m, n_g]      (Mulliken, -Im (G S)_ii / pi)
+    GrIntLayered(system, leads, Elist, weights)                     -> (diag, up, low) block lists of sum_m w_m G(E_m)
+
+Per energy the work is L inverses and a handful of products of layer size instead of one N x N inverse.
+Everything that needs more of G than its blocks on the pattern of S and its two corner blocks raises instead of
+guessing: G Gamma G^H / GrLessInt, eigenchannels, probes, bond currents, spin layouts other than 'r', sharding over
+ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``) is host-side numpy.
+"""
+import numpy as np
+
+from .config import (ETA, SURFACE_DOUBLING_MAX_STEPS, SURFACE_DOUBLING_TOL, SURFACE_GREEN_CONVERGENCE,
+                     SURFACE_GREEN_MAX_ITER, SURFACE_GREEN_SOLVER, SURFACE_RELAXATION_FACTOR)
+
+
+def _worst_outside(M, offs, atol):
+    """(|value|, i, j) of the largest entry of M outside the block-tridiagonal pattern given by the layer offsets that
+    exceeds atol, or None."""
+    L = len(offs) - 1
+    layer = np.repeat(np.arange(L), np.diff(offs))
+    out = np.abs(layer[:, None] - layer[None, :]) > 1
+    A = np.where(out, np.abs(M), 0.0)
+    k = int(np.argmax(A))
+    i, j = divmod(k, M.shape[1])
+    return (float(A[i, j]), i, j) if A[i, j] > atol else None
+
+
+class LayeredSystem:
+    """L >= 2 diagonal blocks F_ii, S_ii (n_i x n_i) and L - 1 upper blocks F_{i,i+1}, S_{i,i+1} (n_i x n_{i+1}); the
+    lower blocks are their conjugate transposes (F, S Hermitian, real or complex).  The sizes are arbitrary."""
+
+    def __init__(self, F_diag, F_up, S_diag, S_up):
+        self.F_diag = [np.array(b) for b in F_diag]
+        self.F_up = [np.array(b) for b in F_up]
+        self.S_diag = [np.array(b) for b in S_diag]
+        self.S_up = [np.array(b) for b in S_up]
+        L = len(self.F_diag)
+        if L < 2:
+            raise ValueError(f"a layered system needs at least two layers, got {L}")
+        if len(self.S_diag) != L or len(self.F_up) != L - 1 or len(self.S_up) != L - 1:
+            raise ValueError("expected L diagonal blocks and L - 1 upper blocks of F and of S")
+        self.sizes = tuple(int(b.shape[0]) for b in self.F_diag)
+        for i in range(L):
+            n = self.sizes[i]
+            if n < 1 or self.F_diag[i].shape != (n, n) or self.S_diag[i].shape != (n, n):
+                raise ValueError(f"diagonal block {i}: F {self.F_diag[i].shape}, S {self.S_diag[i].shape}")
+        for i in range(L - 1):
+            want = (self.sizes[i], self.sizes[i + 1])
+            if self.F_up[i].shape != want or self.S_up[i].shape != want:
+                raise ValueError(f"upper block {i}: expected {want}, got F {self.F_up[i].shape}, S {self.S_up[i].shape}")
+
+    @property
+    def n_layers(self):
+        return len(self.sizes)
+
+    @property
+    def n(self):
+        return int(sum(self.sizes))
+
+    @property
+    def offsets(self):
+        return np.concatenate([[0], np.cumsum(self.sizes)]).astype(int)
+
+    @classmethod
+    def from_dense(cls, F, S, sizes, atol=0.0):
+        """Cut (F, S) into layers of the given sizes.  Raises ValueError, naming the largest entry it would drop, when F
+        or S exceeds ``atol`` outside the block-tridiagonal pattern."""
+        F = np.asarray(F); S = np.asarray(S)
+        sizes = [int(s) for s in sizes]
+        if F.ndim != 2 or F.shape[0] != F.shape[1] or S.shape != F.shape:
+            raise ValueError(f"F and S must be square matrices of one shape, got {F.shape} and {S.shape}")
+        if len(sizes) < 2 or min(sizes) < 1 or sum(sizes) != F.shape[0]:
+            raise ValueError(f"layer sizes {sizes} do not split {F.shape[0]} orbitals into at least two layers")
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        for name, M in (("F", F), ("S", S)):
+            bad = _worst_outside(M, offs, atol)
+            if bad is not None:
+                raise ValueError(f"{name}[{bad[1]}, {bad[2]}] = {M[bad[1], bad[2]]!r} (|.| = {bad[0]:.3g} > atol = {atol:g}) "
+                                 f"lies outside the layer pattern {tuple(sizes)}: it would be dropped")
+        L = len(sizes)
+        sl = [slice(offs[i], offs[i + 1]) for i in range(L)]
+        return cls([F[sl[i], sl[i]] for i in range(L)], [F[sl[i], sl[i + 1]] for i in range(L - 1)],
+                   [S[sl[i], sl[i]] for i in range(L)], [S[sl[i], sl[i + 1]] for i in range(L - 1)])
+
+    def to_dense(self):
+        """(F, S) as N x N matrices, lower blocks = conjugate transposes of the upper ones."""
+        offs = self.offsets
+        out = []
+        for diag, up in ((self.F_diag, self.F_up), (self.S_diag, self.S_up)):
+            M = np.zeros((self.n, self.n), dtype=np.result_type(*diag, *up))
+            for i, b in enumerate(diag):
+                M[offs[i]:offs[i + 1], offs[i]:offs[i + 1]] = b
+            for i, b in enumerate(up):
+                M[offs[i]:offs[i + 1], offs[i + 1]:offs[i + 2]] = b
+                M[offs[i + 1]:offs[i + 2], offs[i]:offs[i + 1]] = b.conj().T
+            out.append(M)
+        return out[0], out[1]
+
+    def locate(self, orbitals):
+        """(layer, indices inside it) of a list of orbitals that must all lie in one layer."""
+        orb = np.asarray(orbitals, dtype=int).ravel()
+        offs = self.offsets
+        if orb.size == 0 or orb.min() < 0 or orb.max() >= self.n:
+            raise ValueError(f"orbital list outside 0 .. {self.n - 1}")
+        layer = np.searchsorted(offs, orb, side='right') - 1
+        if np.any(layer != layer[0]):
+            raise ValueError("the orbitals of a lead must lie in one layer")
+        return int(layer[0]), orb - offs[layer[0]]
+
+
+def partition(F, S, left, right, atol=0.0):
+    """The finest layering of (F, S): a breadth-first walk of the graph of |F| + |S| > atol that starts from the orbitals
+    ``left`` -- layer k holds the orbitals k steps away.  Trailing layers are merged until the last one contains all of
+    ``right``.  Returns (system, perm): the LayeredSystem of the permuted matrices and the permutation, layer by layer
+    (``F[np.ix_(perm, perm)]`` is ``system.to_dense()[0]``).  Raises ValueError when no layering exists: part of the system
+    is not connected to ``left``, or ``right`` is reached in fewer than two steps -- the only split left is then
+    {left | everything else}, which puts the device and the right lead into one layer with the leads touching (a fully
+    coupled matrix is the extreme case)."""
+    F = np.asarray(F); S = np.asarray(S)
+    n = F.shape[0]
+    left = np.unique(np.asarray(left, dtype=int)); right = np.unique(np.asarray(right, dtype=int))
+    if left.size == 0 or right.size == 0 or left.min() < 0 or right.min() < 0 or max(left.max(), right.max()) >= n:
+        raise ValueError("left and right must be non-empty orbital lists inside the system")
+    adj = (np.abs(F) + np.abs(S)) > atol
+    adj = adj | adj.T
+    dist = np.full(n, -1)
+    dist[left] = 0
+    frontier, d = left, 0
+    while frontier.size:
+        d += 1
+        reach = np.any(adj[frontier], axis=0) & (dist < 0)
+        frontier = np.nonzero(reach)[0]
+        dist[frontier] = d
+    if np.any(dist < 0):
+        raise ValueError(f"no layering: {int(np.sum(dist < 0))} orbitals are not connected to the left lead "
+                         f"(first: {int(np.nonzero(dist < 0)[0][0])})")
+    last = int(dist[right].min())              # every layer from here on is merged into the last one
+    if last < 2:
+        # (the split {left | everything else} always exists, and is no layering: the device and the right lead share a
+        # layer, the two leads touch, and the sweep costs more than the dense inverse)
+        raise ValueError("no layering with two or more layers exists that keeps the leads apart: orbitals of the right "
+                         "lead couple directly to, or are among, the left lead's (a fully coupled system belongs on "
+                         "the dense engine)")
+    dist = np.minimum(dist, last)
+    perm = np.argsort(dist, kind='stable')
+    sizes = np.bincount(dist, minlength=last + 1)
+    system = LayeredSystem.from_dense(F[np.ix_(perm, perm)], S[np.ix_(perm, perm)], sizes, atol=atol)
+    return system, perm
+
+
+class Lead:
+    """A terminal of a layered system: a self-energy block on the orbitals ``inds`` (numbered in the whole system, all
+    inside layer 0 or the last layer)."""
+
+    def __init__(self, kind, inds, **kw):
+        self.kind = kind
+        self.inds = np.asarray(inds, dtype=int).ravel()
+        self.kw = kw
+
+    @classmethod
+    def const(cls, inds, sigma):
+        """An energy-independent K x K block."""
+        return cls('const', inds, sigma=np.asarray(sigma))
+
+    @classmethod
+    def chain(cls, inds, alpha, Salpha, beta, Sbeta, tau=None, Stau=None, eta=ETA, solver=SURFACE_GREEN_SOLVER,
+              conv=SURFACE_GREEN_CONVERGENCE, relFactor=SURFACE_RELAXATION_FACTOR, max_iter=SURFACE_GREEN_MAX_ITER,
+              tol=SURFACE_DOUBLING_TOL, max_steps=SURFACE_DOUBLING_MAX_STEPS):
+        """A 1-D chain lead with unit cell (alpha, Salpha), hopping (beta, Sbeta) and coupling (tau, Stau) to the device
+        (default: the lead's own hopping); ``solver`` 'fixed-point' or 'doubling'."""
+        return cls('chain', inds, alpha=alpha, Salpha=Salpha, beta=beta, Sbeta=Sbeta,
+                   tau=beta if tau is None else tau, Stau=Sbeta if Stau is None else Stau, eta=eta, solver=solver,
+                   conv=conv, relFactor=relFactor, max_iter=max_iter, tol=tol, max_steps=max_steps)
+
+    @classmethod
+    def blocks(cls, inds, sigma):
+        """Blocks [m, K, K] evaluated by the caller for exactly the energies of the calls that follow (Bethe lattices,
+        foreign self-energies); a call with more energies is refused."""
+        return cls('blocks', inds, sigma=np.asarray(sigma))
+
+
+class _Bound:
+    """A system with its leads on the engine, freed when the call is over."""
+
+    def __init__(self, system, leads, engine=None):
+        from .engine import get_engine
+        if not isinstance(system, LayeredSystem):
+            raise TypeError("expected a LayeredSystem (LayeredSystem.from_dense / partition make one)")
+        self.eng = engine if engine is not None else get_engine()
+        self.system = system
+        placed = []
+        for lead in leads:
+            layer, local = system.locate(lead.inds)
+            if layer not in (0, system.n_layers - 1):
+                raise ValueError(f"a lead on layer {layer}: terminals sit on the first or the last layer only")
+            placed.append((lead, layer, local))
+        self.h = self.eng.layered_create(system.F_diag, system.F_up, system.S_diag, system.S_up)
+        self.terms = []
+        try:
+            for lead, layer, local in placed:
+                if lead.kind == 'const':
+                    t = self.eng.layered_terminal_const(self.h, layer, local, lead.kw['sigma'])
+                elif lead.kind == 'blocks':
+                    t = self.eng.layered_terminal_blocks(self.h, layer, local, lead.kw['sigma'])
+                else:
+                    t = self.eng.layered_terminal_chain(self.h, layer, local, **lead.kw)
+                self.terms.append(t)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        if self.h is not None:
+            self.eng.layered_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _only_restricted(spin):
+    if spin not in (None, 'r'):
+        raise NotImplementedError(f"layered systems serve spin='r' only, got {spin!r}")
+
+
+def _no_checkpoint(checkpoint_file):
+    if checkpoint_file:
+        raise NotImplementedError("checkpoint files are not written for layered systems")
+
+
+def calculate_transmission_layered(system, leads, energy_list, spin=None, checkpoint_file=None, pair=(0, 1),
+                                   engine=None):
+    """T(E) [m] = Re Tr[Gamma_a G_ab Gamma_b G_ab^H] for ``pair`` = (a, b), indices into ``leads`` that sit on opposite
+    end layers (calculate_transmission's contacts 0 and 1)."""
+    _only_restricted(spin); _no_checkpoint(checkpoint_file)
+    with _Bound(system, leads, engine) as b:
+        return b.eng.layered_transmission(b.h, b.terms[pair[0]], b.terms[pair[1]], np.asarray(energy_list))
+
+
+def calculate_dos_layered(system, leads, energy_list, spin=None, checkpoint_file=None, engine=None):
+    """(dos_total [m], dos_per_site [m, N]): the reference's -Im diag G / pi, as calculate_dos; orbitals in layer order."""
+    _only_restricted(spin); _no_checkpoint(checkpoint_file)
+    with _Bound(system, leads, engine) as b:
+        return b.eng.layered_dos(b.h, np.asarray(energy_list), mulliken=False)
+
+
+def calculate_pdos_layered(system, leads, energy_list, groups=None, contact=None, spin=None, engine=None):
+    """Mulliken projected DOS [m, n_g], row a = sum_{i in a} -Im (G S)_ii / pi, as calculate_pdos with contact=None;
+    ``groups`` maps the N orbitals (layer order) to groups, None: every orbital its own."""
+    _only_restricted(spin)
+    if contact is not None:
+        raise NotImplementedError("the contact-resolved populations need G Gamma G^H, which the layered path does not form")
+    with _Bound(system, leads, engine) as b:
+        _, site = b.eng.layered_dos(b.h, np.asarray(energy_list), mulliken=True)
+    if groups is None:
+        return site
+    groups = np.asarray(groups, dtype=int).ravel()
+    if groups.size != system.n or groups.min() < 0:
+        raise ValueError(f"groups must map the {system.n} orbitals to non-negative group numbers")
+    out = np.zeros((site.shape[0], int(groups.max()) + 1))
+    for g in range(out.shape[1]):                 # orbitals of a group in ascending order
+        out[:, g] = site[:, groups == g].sum(axis=1)
+    return out
+
+
+def GrIntLayered(system, leads, Elist, weights, engine=None):
+    """sum_m w_m G(E_m) on the pattern of S, as GrInt: (diagonal blocks, upper blocks G_{i,i+1}, lower blocks G_{i+1,i})."""
+    with _Bound(system, leads, engine) as b:
+        return b.eng.layered_gr_int(b.h, np.asarray(Elist), np.asarray(weights))
+
+
+def _not_served(name):
+    def fn(*args, **kwargs):
+        raise NotImplementedError(f"{name} is not served on layered systems: it needs blocks of G outside the pattern of S "
+                                  "and the two corner blocks (use the dense engine on system.to_dense())")
+    fn.__name__ = name
+    return fn
+
+
+GrLessIntLayered = _not_served("GrLessIntLayered")
+calculate_transmission_channels_layered = _not_served("calculate_transmission_channels_layered")
+calculate_local_transmission_layered = _not_served("calculate_local_transmission_layered")
+calculate_transmission_matrix_layered = _not_served("calculate_transmission_matrix_layered")

@@ -496,6 +496,81 @@ int negf_gr_int_probes_dev(negf_ctx* ctx, int handle, int n_probes, const int* p
                            const double* probe_sigma_c128, int m, const double* E_dev, const double* w_dev,
                            double* out_dev);
 
+/* --------------------------------------------- layered devices: the recursive Green's function
+ * Wires, oligomers between chain leads, molecules with several principal layers of electrode: systems whose orbitals
+ * fall into L >= 2 layers that couple to their neighbours only.  Every entry point above inverts the full N x N matrix
+ * E S - F - Sigma(E) per energy (8 N^3 flops, 16 N^2 bytes); these do L inverses and a handful of products of LAYER size
+ * per energy (the recursive Green's function; the reference has no such path -- each call names the reference function
+ * whose dense form it replaces).
+ * A layered system is an object of its own inside the context, with its own handle, terminals and workspace; nothing
+ * here reads or changes the dense system of negf_set_system, its providers or their results.
+ *   blocks   F_ii, S_ii (n_i x n_i) and the upper couplings F_{i,i+1}, S_{i,i+1} (n_i x n_{i+1}), row-major, concatenated
+ *            in layer order; the lower blocks are their conjugate transposes (F, S Hermitian, real or complex); the
+ *            sizes n_i are arbitrary, 1 .. 8192 each.
+ *   per energy, A_ij = E S_ij - F_ij:
+ *            g_0 = (A_00 - Sigma_left)^-1,  g_i = (A_ii - A_{i,i-1} g_{i-1} A_{i-1,i} - [i = L-1] Sigma_right)^-1
+ *            X_0 = g_0, X_i = -g_i A_{i,i-1} X_{i-1} = G_{i,0};   Y_i = -Y_{i-1} A_{i-1,i} g_i = G_{0,i}
+ *            G_{L-1,L-1} = g_{L-1},  G_ii = g_i + g_i A_{i,i+1} G_{i+1,i+1} A_{i+1,i} g_i,
+ *            G_{i,i+1} = -g_i A_{i,i+1} G_{i+1,i+1},  G_{i+1,i} = -G_{i+1,i+1} A_{i+1,i} g_i
+ * NEGF_EINVAL before anything is launched: fewer than two layers, a layer size outside 1 .. 8192, an index list that
+ * leaves its layer or names an orbital twice, a terminal on an interior layer, more than 8 terminals on one end, a
+ * transmission between terminals of the same end, more energies than a `blocks` terminal was given.
+ * A singular layer sets info[k] = the 1-based column of the zero pivot counted over the whole system and returns
+ * NEGF_ESINGULAR, as the dense calls do.  negf_set_batch and negf_set_inverse_algo apply.  Every sum has a fixed order:
+ * results are bitwise equal from run to run, do not depend on negf_set_batch, and permuting the energies permutes them.
+ * Not served: G Gamma G^H / GrLessInt, eigenchannels, probes and bond currents on a layered system,
+ * terminals on interior layers, spin layouts other than 'r', sharding, checkpoints. */
+int negf_layered_create(negf_ctx* ctx, int n_layers, const int* sizes, const double* F_diag_c128, const double* F_up_c128,
+                        const double* S_diag_c128, const double* S_up_c128, int* handle);
+int negf_layered_free(negf_ctx* ctx, int handle);
+/* Terminals: a self-energy block Sigma_t on K distinct orbitals `inds` (counted inside the layer) of layer 0 or layer
+ * L - 1; several may share an end layer and orbitals (they are subtracted in the order they were made).  *terminal
+ * numbers them from 0.
+ *   const:  one K x K block for all energies -- surfGTester.py:94-132 restricted to its support.
+ *   chain:  the 1-D chain lead of negf_sigma_chain1d (surfG1D.py:223-399) with one contact; solver 0 = the reference's
+ *           relaxed fixed point (conv, relFactor, max_iter), 1 = renormalisation-decimation (conv = tol, max_iter =
+ *           max_steps, force_iters = force_steps; negf_sigma_chain1d_rd).  It runs through the same kernels and the same
+ *           g(E) cache: its Sigma is bitwise what negf_sigma_eval gives for that lead and energy on a dense system.
+ *   blocks: [m][K][K] blocks supplied per energy (Bethe lattices, foreign self-energies: negf_sigma_precomputed's role,
+ *           integrate.py:169,203-204); block k serves energy k of every later call. */
+int negf_layered_terminal_const(negf_ctx* ctx, int handle, int layer, int K, const int* inds, const double* sigma_c128,
+                                int* terminal);
+int negf_layered_terminal_chain(negf_ctx* ctx, int handle, int layer, int K, const int* inds,
+                                const double* alpha, const double* Salpha, const double* beta, const double* Sbeta,
+                                const double* tau, const double* Stau, double eta, double conv, double relFactor,
+                                int max_iter, int force_iters, int solver, int* terminal);
+int negf_layered_terminal_blocks(negf_ctx* ctx, int handle, int layer, int K, const int* inds, int m,
+                                 const double* sigma_c128, int* terminal);
+/* Sigma_t(E) itself, [m][K][K] -- g.sigma(E, i) on the terminal's orbitals (surfG1D.py:344-399) */
+int negf_layered_terminal_sigma(negf_ctx* ctx, int handle, int terminal, int m, const double* E_c128,
+                                double* sigma_out_c128);
+/* T_ab(E) = Re Tr[Gamma_a G_ab Gamma_b G_ab^H], G_ab = G[I_a, I_b] cut from the corner block G_{L-1,0} (a on the last
+ * layer) or G_{0,L-1} (a on layer 0) -- _transmission_kernel_restricted, transport.py:150-157; T [m].  T_ab is the
+ * transmission from b into a, what negf_transmission(L = a, R = b) returns on the dense system; G is not symmetric for
+ * complex F, so T_ab != T_ba in general.  One forward sweep, no g_i kept: 10 matrices of the largest layer per energy in
+ * flight, whatever L. */
+int negf_layered_transmission(negf_ctx* ctx, int handle, int term_a, int term_b, int m, const double* E_c128,
+                              double* T, int* info);
+int negf_layered_transmission_dev(negf_ctx* ctx, int handle, int term_a, int term_b, int m, const double* E_dev,
+                                  double* T_dev);
+/* form 0: -Im diag G / pi -- _dos_kernel, transport.py:183-190; form 1: the Mulliken form -Im diag(G S) / pi, which
+ * reads the blocks G_{i,i+-1} as well (the rows of negf_population's overlap table).  dos_total [m], dos_site [m][N]
+ * (N = sum n_i, orbitals in layer order; may be NULL in the host form only). */
+int negf_layered_dos(negf_ctx* ctx, int handle, int form, int m, const double* E_c128, double* dos_total,
+                     double* dos_site, int* info);
+int negf_layered_dos_dev(negf_ctx* ctx, int handle, int form, int m, const double* E_dev, double* dos_total_dev,
+                         double* dos_site_dev);
+/* sum_m w_m G(E_m) on the pattern of S -- GrInt, integrate.py:146-173.  out = the diagonal blocks G_ii, then the upper
+ * blocks G_{i,i+1}, then the lower blocks G_{i+1,i} (n_{i+1} x n_i), each row-major, concatenated in layer order:
+ * sum n_i^2 + 2 sum n_i n_{i+1} complex values.  Energy k enters every element's sum after energy k - 1. */
+int negf_layered_gr_int(negf_ctx* ctx, int handle, int m, const double* E_c128, const double* w_c128,
+                        double* out_c128, int* info);
+int negf_layered_gr_int_dev(negf_ctx* ctx, int handle, int m, const double* E_dev, const double* w_dev,
+                            double* out_dev);
+/* device bytes of the work areas of the system's last call: (10 + L for a backward sweep) matrices of the largest layer
+ * per energy in flight */
+int negf_layered_workspace_bytes(negf_ctx* ctx, int handle, long long* work);
+
 /* ------------------------------------------------------------- diagnostics */
 /* hipEvent timing of the library's own kernels, per kernel family
  * ("inverse", "assemble", "accumulate", "zgemm", "trace", "chain1d", "bethe", "eig", "bond", "pop", "tmat", "deph";

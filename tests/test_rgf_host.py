@@ -1,0 +1,124 @@
+"""CPU checks of the recursive Green's function references (rgf_ref.py) and of the host-side layering code
+(gaunegf_amd/layered.py): calibration of the accuracy bar, agreement of the restatements, from_dense / to_dense, partition."""
+import numpy as np
+import pytest
+
+import rgf_ref as rr
+from gaunegf_amd.layered import LayeredSystem, partition
+
+
+def test_inputs_are_meaningful():
+    """T of every case and energy lies between 0.2 and 1.05, so relative errors mean something"""
+    tab = rr.truth_table()
+    for tag, ent in tab.items():
+        if "T" in ent["keys"]:
+            T = np.asarray(ent["truth"]["T"], dtype=float)
+            print(tag, T)
+            assert T.min() > 0.2 and T.max() < 1.05, (tag, T)
+
+
+def test_calibration():
+    """R = the worst ratio between the two float64 sweep forms' errors against the truth over all inputs and quantities
+    (each error floored at 2^-52); C_RGF is the smallest power of two >= 2 R, written into rgf_ref.py with R."""
+    tab = rr.truth_table()
+    R = 1.0
+    for tag, ent in tab.items():
+        for k in ent["keys"]:
+            a, b = ent["err_lr"][k], ent["err_rl"][k]
+            print(f"{tag:8s} {k:6s} lr {a:.3g} rl {b:.3g} dense {ent['err_dense'][k]:.3g}")
+            R = max(R, a / b, b / a)
+    C = 2.0 ** np.ceil(np.log2(2 * R))
+    print(f"R = {R:.3f} -> C_RGF = {C:g}")
+    assert rr.C_RGF == C, f"rgf_ref.C_RGF = {rr.C_RGF} but the measured R = {R:.3f} asks for {C:g}"
+    assert abs(rr.R_MEASURED - R) <= 0.05 * R, f"rgf_ref.R_MEASURED = {rr.R_MEASURED}, measured {R:.3f}"
+
+
+def test_restatements_agree_at_the_project_bar():
+    tab = rr.truth_table()
+    for tag, ent in tab.items():
+        for k in ent["keys"]:
+            for form in ("lr", "rl"):
+                assert rr.rel_err(ent[form][k], ent["dense"][k]) <= rr.PROJECT_BAR, (tag, k, form)
+                assert ent["err_" + form][k] <= rr.PROJECT_BAR, (tag, k, form)
+            assert ent["err_dense"][k] <= rr.PROJECT_BAR, (tag, k)
+
+
+def test_mirrored_case_is_the_same_device():
+    c = rr.cases()[1]
+    m = c.mirrored()
+    F, S = c.to_dense()
+    Fm, Sm = m.to_dense()
+    flip = np.concatenate([np.arange(c.offsets[i], c.offsets[i + 1]) for i in range(len(c.sizes) - 1, -1, -1)])
+    assert np.array_equal(Fm, F[np.ix_(flip, flip)]) and np.array_equal(Sm, S[np.ix_(flip, flip)])
+    # the transmission from the left terminal into the right one is, on the mirror, the one from its right into its left
+    E = c.energies[1]
+    Gd, Gu, Gl, Grl = rr.dense(c, E)
+    G = np.linalg.inv(rr.assembled(m, E))
+    Glr_m = G[np.ix_(m.left_global, m.right_global)]
+    assert np.allclose(Glr_m, Grl, rtol=0, atol=1e-12)
+
+
+@pytest.mark.parametrize("idx", range(4))
+def test_from_dense_to_dense_round_trip_bitwise(idx):
+    c = rr.cases()[idx]
+    F, S = c.to_dense()
+    ls = LayeredSystem.from_dense(F, S, c.sizes)
+    assert ls.sizes == c.sizes and ls.n == c.N
+    F2, S2 = ls.to_dense()
+    assert F2.dtype == F.dtype and np.array_equal(F2, F) and np.array_equal(S2, S)
+    for i, b in enumerate(ls.F_up):
+        assert np.array_equal(b, c.F_up[i])
+
+
+def test_from_dense_names_the_entry_it_would_drop():
+    c = rr.cases()[1]
+    F, S = c.to_dense()
+    F = F.copy()
+    F[1, 20] = 3e-3; F[20, 1] = 3e-3           # layer 0 <-> layer 2
+    F[2, 30] = 1e-4; F[30, 2] = 1e-4           # a smaller one: not the one named
+    with pytest.raises(ValueError, match=r"F\[1, 20\]"):
+        LayeredSystem.from_dense(F, S, c.sizes)
+    with pytest.raises(ValueError, match=r"F\[1, 20\]"):
+        LayeredSystem.from_dense(F, S, c.sizes, atol=1e-3)
+    LayeredSystem.from_dense(F, S, c.sizes, atol=1e-2)      # below atol: dropped knowingly
+    S2 = S.copy()
+    S2[0, 32] = 0.5
+    with pytest.raises(ValueError, match=r"S\[0, 32\]"):
+        LayeredSystem.from_dense(c.to_dense()[0], S2, c.sizes)
+    with pytest.raises(ValueError):
+        LayeredSystem.from_dense(c.to_dense()[0], S, (33,))
+    with pytest.raises(ValueError):
+        LayeredSystem([F[:3, :3]], [], [S[:3, :3]], [])
+
+
+def test_partition_recovers_a_layering_of_a_permuted_system():
+    c = rr.cases()[1]
+    F, S = c.to_dense()
+    rng = np.random.default_rng(5)
+    p = rng.permutation(c.N)
+    Fp, Sp = F[np.ix_(p, p)], S[np.ix_(p, p)]
+    inv = np.argsort(p)                                      # orbital i of the case sits at inv[i] of the permuted system
+    left = inv[np.arange(c.sizes[0])]                        # the whole first layer as the left lead
+    right = inv[c.right_global]
+    ls, perm = partition(Fp, Sp, left, right)
+    assert ls.n_layers >= 2 and sum(ls.sizes) == c.N
+    assert sorted(perm.tolist()) == list(range(c.N))
+    F2, S2 = ls.to_dense()
+    assert np.array_equal(F2, Fp[np.ix_(perm, perm)]) and np.array_equal(S2, Sp[np.ix_(perm, perm)])
+    assert set(perm[:ls.sizes[0]].tolist()) == set(left.tolist())          # layer 0 holds the left lead
+    assert set(right.tolist()) <= set(perm[c.N - ls.sizes[-1]:].tolist())  # the last layer holds the right lead
+    # the walk finds the case's own four layers: they are fully coupled to their neighbours
+    assert ls.sizes == c.sizes
+
+
+def test_partition_refuses_what_has_no_layering():
+    rng = np.random.default_rng(6)
+    A = rng.standard_normal((12, 12))
+    F = A + A.T
+    S = np.eye(12)
+    with pytest.raises(ValueError, match="no layering"):
+        partition(F, S, [0, 1], [10, 11])
+    # two disconnected halves
+    F2 = np.zeros((8, 8)); F2[:4, :4] = 1.0; F2[4:, 4:] = 1.0
+    with pytest.raises(ValueError, match="not connected"):
+        partition(F2, np.eye(8), [0], [7])
