@@ -5,6 +5,7 @@
 #pragma once
 #include "negf_common.h"
 #include "wave_utils.h"
+#include "chain_rs_sched.h"
 
 namespace {
 
@@ -48,6 +49,17 @@ constexpr int RS_NB = RS_PANEL;           // panel width of the small inverse: h
 #ifndef RS_ABLATE
 #define RS_ABLATE 0                   // diagnostic builds only (wrong results; timing with force_iters): 1 = no panel factoring (the chain
 #endif                                //    wave's pivot steps), 2 = no trailing / look-ahead updates, 4 = no products, 8 = no mixing phase
+#ifndef RS_STAGE_SCHED
+#define RS_STAGE_SCHED 1              // remainder-strip classes with the roles by SIMD: 1 = the stages of the inverse follow the compile-time
+#endif                                //    schedule of chain_rs_sched.h (rs_inverse_sched: full panels without selects, jobs from a table,
+                                      //    full tiles stored unguarded), 0 = the generic loop (rs_inverse) everywhere
+#ifndef RS_SCHED_FACTOR
+#define RS_SCHED_FACTOR 0             // the factoring wave under the stage schedule: 0 = rs_factor as the generic loop instantiates it, 1 = a
+#endif                                //    full-panel instantiation without column tests and load selects and a 4-column one for the last panel.
+                                      //    Built and measured: 1 does NOT reproduce the generic loop's bits (Sigma differs in the last digits,
+                                      //    1e-15 .. 1e-13 relative, in most units at n = 33 .. 35 and 49 .. 51; sweep counts unchanged): with the
+                                      //    column steps no longer in conditional blocks of their own the compiler contracts the complex
+                                      //    multiply-adds of a step differently.  The jobs, the look-ahead and the last stage are bit for bit.
 #ifndef RS_STAMPS
 #define RS_STAMPS 0                   // 1: diagnostic build -- the phase / cycle stamps of NEGF_CHAIN_STAMPS=1 are compiled in
 #endif                                //    (NEGF_EXTRA_HIPCC_FLAGS=-DRS_STAMPS=1 python -m gaunegf_amd.build --force); the production
@@ -159,24 +171,30 @@ __device__ __forceinline__ double rs_readlane_f64(double v, int srclane)
 //     overflow / denormal range the IEEE division sequence guards).
 // A pivot row is not scaled at its column step (multiplier 0, a one in the pivot column) but once at
 // the end of the panel: the later steps act linearly on it, and every lane runs the same select-free update.
-template <int P>
+// NBW: columns the code is written for (pw <= NBW).  FULL: pw == NBW is known -- no column tests, and where the work matrix
+// has 64 rows no row select on the loads either: a lane r >= n is never `avail` and never stores, what it computes from the
+// spare rows is dead.
+template <int P, int NBW = RS_NB, bool FULL = false>
 __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colof, cplx* rowline /*[16] LDS*/,
                                           int p0, int pw, int lane, unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */)
 {
     const int r = rs_opaque(lane);                      // (see rs_opaque: nothing derived from the lane index is
-    cplx a[RS_NB];                                      //  hoisted out of the fixed-point loop and kept alive)
+    cplx a[NBW];                                        //  hoisted out of the fixed-point loop and kept alive)
+    constexpr bool ROWSEL = !FULL || 16 * ((P - 1 + 15) / 16) < 64;   // lanes beyond the rows of the work matrix read nothing
     bool avail = r < n && colof[r] < 0;
     cplx myip = cmake(1.0, 0.0);
     cplx* wrow = W + r * P + p0;                        // rows >= n are zero padding
 #pragma unroll
-    for (int s = 0; s < RS_NB; ++s) {
-        const cplx v = wrow[s];
-        const bool ok = (r < n) & (s < pw);
-        a[s] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
+    for (int s = 0; s < NBW; ++s) {
+        if (ROWSEL) {
+            const cplx v = wrow[s];
+            const bool ok = (r < n) & (FULL || s < pw);
+            a[s] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
+        } else a[s] = wrow[s];
     }
 #pragma unroll
-    for (int j = 0; j < RS_NB; ++j) {
-        if (j < pw) {
+    for (int j = 0; j < NBW; ++j) {
+        if (FULL || j < pw) {
             const bool stamp_here = fst && j == 4;
             unsigned long long tq0 = 0, tq1 = 0, tq2 = 0, tq3 = 0, tq4 = 0;
             if (stamp_here) tq0 = __builtin_amdgcn_s_memtime();
@@ -193,7 +211,7 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             pphys = __builtin_amdgcn_readfirstlane(pphys);
             if (stamp_here) tq1 = __builtin_amdgcn_s_memtime();
             const bool is_piv = r == pphys;
-            cplx rb[RS_NB];
+            cplx rb[NBW];
 #if RS_ROW_MODE == 0
             // through a 256-byte LDS line: one lane writes its 16 values, all lanes read them back.  The wave-level
             // barriers keep the compiler from ordering the two sides of the divergent branch the other way round
@@ -202,18 +220,18 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             if (is_piv) {
                 pivrow[p0 + j] = pphys; colof[pphys] = p0 + j;
 #pragma unroll
-                for (int s = 0; s < RS_NB; ++s) rowline[s] = a[s];
+                for (int s = 0; s < NBW; ++s) rowline[s] = a[s];
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-            for (int s = 0; s < RS_NB; ++s) rb[s] = rowline[s];
+            for (int s = 0; s < NBW; ++s) rb[s] = rowline[s];
 #elif RS_ROW_MODE == 1
             // through v_readlane (wave-uniform results, scalar operands of the FMAs): measured 10 cycles each
             if (is_piv) { pivrow[p0 + j] = pphys; colof[pphys] = p0 + j; }
 #pragma unroll
-            for (int s = 0; s < RS_NB; ++s)
+            for (int s = 0; s < NBW; ++s)
                 rb[s] = cmake(rs_readlane_f64(a[s].x, pphys), rs_readlane_f64(a[s].y, pphys));
 #else
             // through ds_bpermute_b32: every lane reads the pivot lane's register over the LDS crossbar -- no memory,
@@ -221,7 +239,7 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             if (is_piv) { pivrow[p0 + j] = pphys; colof[pphys] = p0 + j; }
             const int baddr = pphys << 2;
 #pragma unroll
-            for (int s = 0; s < RS_NB; ++s) {
+            for (int s = 0; s < NBW; ++s) {
                 rb[s].x = __hiloint2double(__builtin_amdgcn_ds_bpermute(baddr, __double2hiint(a[s].x)),
                                            __builtin_amdgcn_ds_bpermute(baddr, __double2loint(a[s].x)));
                 rb[s].y = __hiloint2double(__builtin_amdgcn_ds_bpermute(baddr, __double2hiint(a[s].y)),
@@ -239,10 +257,10 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             const cplx coef = cmake(is_piv ? 0.0 : mf.x, is_piv ? 0.0 : mf.y);
             if (stamp_here) { asm volatile("" :: "v"(coef.x), "v"(coef.y)); tq3 = __builtin_amdgcn_s_memtime(); }
 #pragma unroll
-            for (int s = 0; s < RS_NB; ++s) a[s] = cfma(a[s], coef, rb[s]);
+            for (int s = 0; s < NBW; ++s) a[s] = cfma(a[s], coef, rb[s]);
             if (stamp_here) {
 #pragma unroll
-                for (int s = 0; s < RS_NB; ++s) asm volatile("" :: "v"(a[s].x), "v"(a[s].y));
+                for (int s = 0; s < NBW; ++s) asm volatile("" :: "v"(a[s].x), "v"(a[s].y));
                 tq4 = __builtin_amdgcn_s_memtime();
                 if (lane == 0) { fst[0] = tq0; fst[1] = tq1; fst[2] = tq2; fst[3] = tq3; fst[4] = tq4; }
             }
@@ -253,8 +271,8 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
     }
     if (r < n) {
 #pragma unroll
-        for (int s = 0; s < RS_NB; ++s)
-            if (s < pw) {
+        for (int s = 0; s < NBW; ++s)
+            if (FULL || s < pw) {
                 wrow[s] = cmul(a[s], myip);                 // the deferred pivot-row scaling
             }
     }
@@ -265,7 +283,7 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
 // (the 0 by a mask of the seed, MASK, or because the pivot rows were zeroed after Q was read: rs_zero_pivot_rows)
 // A Q fragment holds the panel's pivot rows in the columns of one column tile (B operand); for the
 // column-strip tile TR every 4-column block holds the same columns TR*16 + (l&3) (see mfma3s).
-template <int P, int NKS, int TR /* last tile when it is a remainder strip, else -1 */>
+template <int P, int NKS, int TR /* last tile when it is a remainder strip, else -1 */, bool FULL = false /* pw == 4 NKS is known */>
 __device__ __forceinline__ void rs_load_qf(const cplx* W, const int* pivrow, int tj, int p0, int pw, int fi, int fk,
                                            cplx (&qf)[NKS])
 {
@@ -274,7 +292,7 @@ __device__ __forceinline__ void rs_load_qf(const cplx* W, const int* pivrow, int
     for (int ks = 0; ks < NKS; ++ks) {
         const int k = ks * 4 + fk;
         const cplx v = W[pivrow[p0 + k] * P + col];          // k >= pw: some valid row, zeroed below
-        const bool ok = k < pw;
+        const bool ok = FULL || k < pw;
         qf[ks] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
     }
 }
@@ -366,7 +384,7 @@ __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof,
 // (ti*16 + 4 (fi>>2) + fk, c0 + 4 s + (fi&3)): half the C loads, seeds, recombinations and stores as well.
 constexpr bool rs_half_strips(int nks) { return RS_HALF_STRIPS && RS_NB == 8 && nks == RS_NB / 4; }
 
-template <int P, int NKS>
+template <int P, int NKS, bool FULL = false>
 __device__ __forceinline__ void rs_load_qh(const cplx* W, const int* pivrow, int c0, int p0, int pw, int fi, int fk,
                                            cplx (&qh)[2][NKS])
 {
@@ -376,7 +394,7 @@ __device__ __forceinline__ void rs_load_qh(const cplx* W, const int* pivrow, int
         const int k = ks * 4 + fk;
         const cplx* q = W + pivrow[p0 + k] * P + col;        // k >= pw: some valid row, zeroed below
         const cplx v0 = q[0], v1 = q[4];
-        const bool ok = k < pw;
+        const bool ok = FULL || k < pw;
         qh[0][ks] = cmake(ok ? v0.x : 0.0, ok ? v0.y : 0.0);
         qh[1][ks] = cmake(ok ? v1.x : 0.0, ok ? v1.y : 0.0);
     }
@@ -613,6 +631,217 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
         stamp();
         __syncthreads();                 // panel sgi+1 (columns of W, pivrow/colof) and the update complete
     }
+}
+
+// ---- the compile-time stage schedule of the remainder-strip classes (RS_STAGE_SCHED, chain_rs_sched.h).  In such a class
+// (TR full tiles and a strip, every contact of the launch with 16 TR < n <= 16 TR + 4) with the roles by SIMD the generic
+// loop above derives, in every stage of every sweep, what never changes: 2 TR panels that are exactly 8 wide and lie inside
+// full tiles, then one narrow panel; role 3 factors; the column-tile jobs of a stage and their owners.  rs_inverse_sched
+// runs the same operations on the same operands in the same order with all of that fixed: the jobs of a role come out of one
+// 64-bit constant, the kind of a job selects one of three bodies (whole tile, half tile, column strip) that take the tile
+// index and the panel's first column as scalars -- one copy of each in the instruction stream --, a full panel's Q
+// fragments carry no selects, and full tiles are stored without tests (the factoring wave: RS_SCHED_FACTOR).
+// (TR = 1, class 19, keeps the generic loop: with the schedule its kernels need 128 VGPRs and 20 - 48 bytes of scratch
+//  instead of 110 and none, and the two-per-CU ones fall from four waves per SIMD to three)
+constexpr bool rs_stage_sched(int TR) { return RS_STAGE_SCHED && TR >= 2 && TR <= 3 && RS_NB == 8 && RS_HALF_STRIPS && !RS_LA_FLAGS && !RS_ABLATE; }
+
+// row strip of column tile tj < TR (rs_update_tile's strip form with the tile inside the matrix): rows 16 TR + fk < n are
+// stored; RANGE: only the columns [clo, clo + 8) of the tile; MASK: the panel's pivot rows are seeded with 0
+template <int P, int NKS, int TR, bool MASK, bool RANGE>
+__device__ __forceinline__ void rs_rowstrip_tile(int n, cplx* W, const int* colof, int tj, int p0, int fi, int fk,
+                                                 const cplx (&qf)[NKS], int clo)
+{
+    const int row = TR * 16 + fk, col = tj * 16 + fi;
+    const cplx* prow = W + (TR * 16 + (fi & 3)) * P + p0 + fk;
+    cplx* cptr = W + row * P + col;
+    const int cf = MASK ? colof[row] : -1;
+    const cplx cv = *cptr;
+    cplx pa[NKS];
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) pa[ks] = prow[ks * 4];
+    const bool keep = !MASK || !(cf >= p0 && cf < p0 + 4 * NKS);
+    double ua = keep ? cv.x : 0.0, ub = 0.0, uc = keep ? cv.x + cv.y : 0.0;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks)
+        mfma3s(ua, ub, uc, pa[ks].x, pa[ks].y, pa[ks].x + pa[ks].y, qf[ks].x, qf[ks].y, qf[ks].x + qf[ks].y);
+    if (row < n && (!RANGE || (unsigned)(col - clo) < 8u)) *cptr = cmake(ua - ub, uc - ua - ub);
+}
+
+// the pivot rows of a full panel in this lane's column
+template <int P, int NKS>
+__device__ __forceinline__ void rs_zero_pivot_rows_full(cplx* W, const int* pivrow, int p0, int fk, int col)
+{
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) W[pivrow[p0 + ks * 4 + fk] * P + col] = cmake(0.0, 0.0);
+}
+// ... and of the narrow last panel (one k-step, once a sweep).  Its zero is made here: the 16-byte zero of the full panels
+// stays in registers across the sweep only as long as every store that uses it sits on the hot path
+template <int P>
+__device__ __forceinline__ void rs_zero_pivot_rows_narrow(cplx* W, const int* pivrow, int p0, int pw, int fk, int col)
+{
+    double z = 0.0;
+    asm volatile("" : "+v"(z));
+    if (fk < pw) W[pivrow[p0 + fk] * P + col] = cmake(z, z);
+}
+
+// job kind WHOLE: full column tile tj under a full panel (FULL, NKS = 2) or under the narrow last one (pw <= 4, NKS = 1) --
+// rs_update_col's whole-tile form without a test on the stores
+template <int P, int TR, int NKS, bool FULL>
+__device__ __forceinline__ void rs_job_whole(int n, cplx* W, const int* pivrow, const int* colof, int tj, int p0, int pw, int lane)
+{
+    const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
+    const int col = tj * 16 + fi;
+    cplx qf[NKS];
+    rs_load_qf<P, NKS, -1, FULL>(W, pivrow, tj, p0, pw, fi, fk, qf);
+    if (FULL) rs_zero_pivot_rows_full<P, NKS>(W, pivrow, p0, fk, col);
+    else rs_zero_pivot_rows_narrow<P>(W, pivrow, p0, pw, fk, col);
+    constexpr bool M3 = RS_UPD_3M && P > 35;
+    double qs[NKS];
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) qs[ks] = qf[ks].x + qf[ks].y;
+    cplx* cbase = W + fk * P + col;
+    const cplx* pbase = W + fi * P + p0 + fk;
+    cplx cv[2][4], pa[2][NKS];
+    auto fetch = [&](int ti, int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cv[s][r] = cbase[(ti * 16 + 4 * r) * P];
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) pa[s][ks] = pbase[ti * 16 * P + ks * 4];
+    };
+    fetch(0, 0);
+#pragma unroll
+    for (int ti = 0; ti < TR; ++ti) {
+        const int s = ti & 1;
+        if (ti + 1 < TR) fetch(ti + 1, s ^ 1);
+        d4 ua, ub = {0, 0, 0, 0}, uc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { ua[r] = cv[s][r].x; uc[r] = M3 ? cv[s][r].x + cv[s][r].y : cv[s][r].y; }
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            if (M3) mfma3(ua, ub, uc, pa[s][ks].x, pa[s][ks].y, pa[s][ks].x + pa[s][ks].y, qf[ks].x, qf[ks].y, qs[ks]);
+            else zmfma(ua, uc, pa[s][ks], qf[ks]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cbase[(ti * 16 + 4 * r) * P] = M3 ? cmake(ua[r] - ub[r], uc[r] - ua[r] - ub[r]) : cmake(ua[r], uc[r]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    rs_rowstrip_tile<P, NKS, TR, false, false>(n, W, colof, tj, p0, fi, fk, qf, 0);
+}
+
+// job kind HALF: columns [clo, clo + 8) of full tile tj under a full panel -- rs_update_col's half-tile form
+template <int P, int TR>
+__device__ __forceinline__ void rs_job_half(int n, cplx* W, const int* pivrow, const int* colof, int tj, int clo, int p0, int lane)
+{
+    constexpr int NKS = RS_NB / 4;
+    const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
+    cplx qf[NKS], qh[2][NKS];
+    double qs[2][NKS];
+    rs_load_qf<P, NKS, -1, true>(W, pivrow, tj, p0, RS_NB, fi, fk, qf);           // the row strip's 16-column fragment
+    rs_load_qh<P, NKS, true>(W, pivrow, clo, p0, RS_NB, fi, fk, qh);
+    if ((unsigned)(tj * 16 + fi - clo) < 8u) rs_zero_pivot_rows_full<P, NKS>(W, pivrow, p0, fk, tj * 16 + fi);
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) { qs[0][ks] = qh[0][ks].x + qh[0][ks].y; qs[1][ks] = qh[1][ks].x + qh[1][ks].y; }
+    const int row = 4 * (fi >> 2) + fk;
+    cplx* cbase = W + row * P + clo + (fi & 3);
+    const cplx* pbase = W + fi * P + p0 + fk;
+    cplx cv[2][2], pa[2][NKS];
+    auto fetch = [&](int ti, int s) __attribute__((always_inline)) {
+        cv[s][0] = cbase[ti * 16 * P]; cv[s][1] = cbase[ti * 16 * P + 4];
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) pa[s][ks] = pbase[ti * 16 * P + ks * 4];
+    };
+    fetch(0, 0);
+#pragma unroll
+    for (int ti = 0; ti < TR; ++ti) {
+        const int s = ti & 1;
+        if (ti + 1 < TR) fetch(ti + 1, s ^ 1);
+        rs_half_mma<P, NKS>(cv[s], pa[s], qh, qs);
+        cbase[ti * 16 * P] = cv[s][0]; cbase[ti * 16 * P + 4] = cv[s][1];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    rs_rowstrip_tile<P, NKS, TR, false, true>(n, W, colof, tj, p0, fi, fk, qf, clo);
+}
+
+// job kind STRIP: the column strip (tile TR) under a full panel, every row tile on the 4x4x4 instruction
+template <int T16, int P, int TR>
+__device__ __forceinline__ void rs_job_strip(int n, cplx* W, const int* pivrow, const int* colof, int p0, int lane)
+{
+    constexpr int NKS = RS_NB / 4;
+    const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
+    const int col = TR * 16 + (fi & 3);
+    cplx qf[NKS];
+    rs_load_qf<P, NKS, TR, true>(W, pivrow, TR, p0, RS_NB, fi, fk, qf);
+    if (col < n) rs_zero_pivot_rows_full<P, NKS>(W, pivrow, p0, fk, col);
+#pragma unroll
+    for (int ti = 0; ti < T16; ++ti) {
+        rs_update_tile<P, NKS, TR, false>(n, W, colof, ti, TR, p0, RS_NB, fi, fk, qf, TR * 16, TR * 16 + 16);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// rs_inverse for a remainder-strip class with the roles by SIMD (wave = role; role 3 factors every panel)
+template <int T16, int P, int TR>
+__device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, int* colof, cplx* rowline, int tid, int wave,
+                                                 unsigned long long* st = nullptr)
+{
+    static_assert(TR == T16 - 1 && rs_sched_fits(TR), "a remainder-strip class");
+    constexpr int NKS = RS_NB / 4;
+    const int lane = tid & 63;
+    int sti = 0;
+    auto stamp = [&]() __attribute__((always_inline)) { if (st && tid == 0) st[sti] = __builtin_amdgcn_s_memrealtime(); ++sti; };
+    // this role's jobs of the full stages (roles 0 .. 2; role 3 factors)
+    wave = __builtin_amdgcn_readfirstlane(wave);                // (the same in every lane: the table stays in scalar registers)
+    const unsigned long long jobs = wave == 0 ? rs_sched_word(TR, 0) : wave == 1 ? rs_sched_word(TR, 1) : wave == 2 ? rs_sched_word(TR, 2) : 0ull;
+#pragma unroll 1
+    for (int sgi = -1; sgi < 2 * TR; ++sgi) {
+        // stage sgi: the full panel [p0, p0 + 8) is applied, panel [n0, n0 + 8) -- the narrow last one after stage 2 TR - 1 -- factored
+        const int p0 = sgi * RS_NB, n0 = p0 + RS_NB;
+        const bool full_next = sgi + 1 < 2 * TR;
+        if (sgi >= 0) {
+            // look-ahead: the next panel's columns, one row tile per wave.  A full next panel is half of a full tile (two column
+            // strips per row tile, the row strip in its own form), the last one the column strip
+            const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
+            const int tl = n0 >> 4;
+            cplx qh[2][NKS];
+            cplx (&qf)[NKS] = qh[0];                            // (one or the other)
+            if (full_next) {
+                if (wave < TR) rs_load_qh<P, NKS, true>(W, pivrow, n0, p0, RS_NB, fi, fk, qh);
+                else if (wave == TR) rs_load_qf<P, NKS, -1, true>(W, pivrow, tl, p0, RS_NB, fi, fk, qf);
+            } else if (wave < T16) rs_load_qf<P, NKS, TR, true>(W, pivrow, TR, p0, RS_NB, fi, fk, qf);
+            __syncthreads();
+            if (full_next) {
+                if (wave < TR) rs_update_half<P, NKS, true, true>(n, W, colof, wave, p0, RS_NB, fi, fk, qh, n0);
+                else if (wave == TR) rs_rowstrip_tile<P, NKS, TR, true, true>(n, W, colof, tl, p0, fi, fk, qf, n0);
+            } else if (wave < T16) rs_update_tile<P, NKS, TR, true>(n, W, colof, wave, TR, p0, RS_NB, fi, fk, qf, n0, n0 + RS_NB);
+            __syncthreads();
+            // the other columns: this role's jobs of the stage
+            unsigned c = (unsigned)(jobs >> (RS_STAGE_BITS * sgi)) & ((1u << RS_STAGE_BITS) - 1u);
+#pragma unroll 1
+            while (c) {
+                const unsigned kind = c & 3u;
+                const int tj = (int)(c >> 2) & 3;
+                if (kind == RS_JOB_WHOLE) rs_job_whole<P, TR, NKS, true>(n, W, pivrow, colof, tj, p0, RS_NB, lane);
+                else if (kind == RS_JOB_HALF) rs_job_half<P, TR>(n, W, pivrow, colof, tj, tj * 16 + (int)((c >> 4) & 1u) * 8, p0, lane);
+                else rs_job_strip<T16, P, TR>(n, W, pivrow, colof, p0, lane);
+                c >>= RS_JOB_BITS;
+            }
+        }
+        if (wave == RS_WAVES - 1) {
+            if (st && lane == 0) st[16 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
+            if (RS_PRIO) __builtin_amdgcn_s_setprio(3);         // (see rs_inverse)
+            if (!RS_SCHED_FACTOR) rs_factor<P>(n, W, pivrow, colof, rowline, n0, full_next ? RS_NB : n - n0, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
+            else if (full_next) rs_factor<P, RS_NB, true>(n, W, pivrow, colof, rowline, n0, RS_NB, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
+            else rs_factor<P, 4, false>(n, W, pivrow, colof, rowline, n0, n - n0, lane);
+            if (RS_PRIO) __builtin_amdgcn_s_setprio(0);
+            if (st && lane == 0) st[17 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
+        }
+        stamp();
+        __syncthreads();
+    }
+    // the last stage: the narrow panel [16 TR, n) (one k-step, guarded code) on the full tiles, tile tj by role tj
+    if (wave < TR) rs_job_whole<P, TR, 1, false>(n, W, pivrow, colof, wave, TR * 16, n - TR * 16, lane);
+    stamp();
+    __syncthreads();
 }
 
 }  // namespace

@@ -177,9 +177,12 @@ __device__ __forceinline__ void rs_gstore(unsigned long long base, unsigned cons
     *reinterpret_cast<__attribute__((address_space(1))) rs_d2*>(p + lane_bytes) = w;
 }
 
-template <int P, int OCC, bool GOLD_GLOBAL, bool RR>
-__global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
-    ChainRsArgs a, const cplx* __restrict__ E, cplx* __restrict__ blk, int* __restrict__ iters,
+// SCHED: the inverse of a remainder-strip class follows the compile-time stage schedule (RS_STAGE_SCHED, rs_inverse_sched) --
+// chain1d_rs_kernel; without it the generic loop -- chain1d_rs_wn_kernel, the launches with the roles by wave number.  Two
+// kernels, not one with both loops: the second copy of the inverse is 14 KB of code that a launch never runs.
+template <int P, int OCC, bool GOLD_GLOBAL, bool RR, bool SCHED>
+__device__ __forceinline__ void chain1d_rs_body(
+    const ChainRsArgs& a, const cplx* __restrict__ E, cplx* __restrict__ blk, int* __restrict__ iters,
     int* __restrict__ converged)
 {
     constexpr int T16 = (P - 1 + 15) / 16;              // 16-row tiles per dimension
@@ -682,6 +685,10 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
         unsigned long long* st = (RS_STAMPS && a.stamps && job == 0 && count == a.stamp_sweep) ? a.stamps : nullptr;
         if (st && tid == 0) st[0] = __builtin_amdgcn_s_memrealtime();
         if (!gc_hit && !skip) {
+            // a remainder-strip class: the compile-time stage schedule (RS_STAGE_SCHED); else, and with the roles by wave number, the generic loop
+            // (role 3 factors whether the roles follow the SIMDs or, two waves having reported the same one, the wave numbers)
+            if constexpr (SCHED && REM && rs_stage_sched(REM ? TR : -1)) rs_inverse_sched<T16, P, TR>(n, Ws, pivrow, colof, rowline, tid, wave, st ? st + 8 : nullptr);
+            else
             rs_inverse<T16, P, REM ? TR : -1>(n, Ws, pivrow, colof, rowline, tid, wave, chain_roles, la_cnt, la_epoch, st ? st + 8 : nullptr);   // st + 8: stage stamps, st + 24: factor
             if (st && tid == 0) st[1] = __builtin_amdgcn_s_memrealtime();
             if (!(RS_ABLATE & 8) || first) { if (RS_DENSE_MIX) gather_mix_dense(first, st); else gather_mix(first, st); }
@@ -826,6 +833,23 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
     }
 }
 
+template <int P, int OCC, bool GOLD_GLOBAL, bool RR>
+__global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_kernel(
+    ChainRsArgs a, const cplx* __restrict__ E, cplx* __restrict__ blk, int* __restrict__ iters,
+    int* __restrict__ converged)
+{
+    chain1d_rs_body<P, OCC, GOLD_GLOBAL, RR, true>(a, E, blk, iters, converged);
+}
+
+// the generic loop in the remainder-strip classes (launched with the roles by wave number; the other classes have one kernel)
+template <int P, int OCC, bool GOLD_GLOBAL, bool RR>
+__global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_wn_kernel(
+    ChainRsArgs a, const cplx* __restrict__ E, cplx* __restrict__ blk, int* __restrict__ iters,
+    int* __restrict__ converged)
+{
+    chain1d_rs_body<P, OCC, GOLD_GLOBAL, RR, false>(a, E, blk, iters, converged);
+}
+
 }  // namespace
 
 bool chain1d_lds_supported(int nc_max) { return nc_max <= 64; }
@@ -912,6 +936,17 @@ void chain1d_rs_launch(hipStream_t st, ChainRsArgs a, int n_max, int n_contacts,
         if (rr) go(kern_rr); else go(kern);
     };
     constexpr int OCC_MAX = T16 <= 2 ? 4 : 3;          // register budget: 128 VGPRs (T16 <= 2), 168 above
+    // a strip class launched with the roles by wave number runs the kernels with the generic inverse (RS_STAGE_SCHED)
+    constexpr bool STRIPS = RS_REMAINDER && T16 >= 2 && P - 16 * (T16 - 1) <= 4;
+    if constexpr (STRIPS && rs_stage_sched(T16 - 1)) {
+        if (!a.simd_roles) {
+            if (occ_env != 2 && fits(wmat + gold_lds, OCC_MAX)) launch(chain1d_rs_wn_kernel<P, OCC_MAX, false, false>, chain1d_rs_wn_kernel<P, OCC_MAX, false, true>, wmat + gold_lds, OCC_MAX);
+            else if (occ_env != 2 && gold_scratch && fits(wmat, OCC_MAX)) launch(chain1d_rs_wn_kernel<P, OCC_MAX, true, false>, chain1d_rs_wn_kernel<P, OCC_MAX, true, true>, wmat, OCC_MAX);
+            else if (fits(wmat + gold_lds, 2) || !gold_scratch) launch(chain1d_rs_wn_kernel<P, 2, false, false>, chain1d_rs_wn_kernel<P, 2, false, true>, wmat + gold_lds, 2);
+            else launch(chain1d_rs_wn_kernel<P, 2, true, false>, chain1d_rs_wn_kernel<P, 2, true, true>, wmat, 2);
+            return;
+        }
+    }
     if (occ_env != 2 && fits(wmat + gold_lds, OCC_MAX)) launch(chain1d_rs_kernel<P, OCC_MAX, false, false>, chain1d_rs_kernel<P, OCC_MAX, false, true>, wmat + gold_lds, OCC_MAX);
     else if (occ_env != 2 && gold_scratch && fits(wmat, OCC_MAX)) launch(chain1d_rs_kernel<P, OCC_MAX, true, false>, chain1d_rs_kernel<P, OCC_MAX, true, true>, wmat, OCC_MAX);
     else if (fits(wmat + gold_lds, 2) || !gold_scratch) launch(chain1d_rs_kernel<P, 2, false, false>, chain1d_rs_kernel<P, 2, false, true>, wmat + gold_lds, 2);
