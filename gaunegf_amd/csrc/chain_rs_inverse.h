@@ -54,12 +54,13 @@ constexpr int RS_NB = RS_PANEL;           // panel width of the small inverse: h
 #endif                                //    schedule of chain_rs_sched.h (rs_inverse_sched: full panels without selects, jobs from a table,
                                       //    full tiles stored unguarded), 0 = the generic loop (rs_inverse) everywhere
 #ifndef RS_SCHED_FACTOR
-#define RS_SCHED_FACTOR 0             // the factoring wave under the stage schedule: 0 = rs_factor as the generic loop instantiates it, 1 = a
-#endif                                //    full-panel instantiation without column tests and load selects and a 4-column one for the last panel.
-                                      //    Built and measured: 1 does NOT reproduce the generic loop's bits (Sigma differs in the last digits,
-                                      //    1e-15 .. 1e-13 relative, in most units at n = 33 .. 35 and 49 .. 51; sweep counts unchanged): with the
-                                      //    column steps no longer in conditional blocks of their own the compiler contracts the complex
-                                      //    multiply-adds of a step differently.  The jobs, the look-ahead and the last stage are bit for bit.
+#define RS_SCHED_FACTOR 2             // the factoring wave under the stage schedule (rs_factor_sched, arithmetic pinned to the generic loop's), a
+#endif                                //    bit mask: 2 = the narrow last panel in a 4-column instantiation -- bit for bit the generic loop, ON;
+                                      //    1 = the full panels in an instantiation without column tests and load selects -- OFF: Sigma still
+                                      //    differs from the generic loop's in the last digits (n = 33 .. 35 and 49 .. 51, sweep counts unchanged)
+                                      //    although the FP64 instructions of every column step now have the generic loop's form, operand by
+                                      //    operand (LAB_NOTES.md: the cause is not contraction alone and was not found); 0 = rs_factor as the
+                                      //    generic loop instantiates it
 #ifndef RS_STAMPS
 #define RS_STAMPS 0                   // 1: diagnostic build -- the phase / cycle stamps of NEGF_CHAIN_STAMPS=1 are compiled in
 #endif                                //    (NEGF_EXTRA_HIPCC_FLAGS=-DRS_STAMPS=1 python -m gaunegf_amd.build --force); the production
@@ -156,6 +157,32 @@ __device__ __forceinline__ double rs_readlane_f64(double v, int srclane)
 {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), srclane),
                             __builtin_amdgcn_readlane(__double2loint(v), srclane));
+}
+
+// ---- pinned arithmetic.  The compiler contracts a * b + c * d into one product and one fused multiply-add, and WHICH
+// product is fused is its choice per basic block: code that moves such an expression into another block (a branch
+// around it, a loop split in two, an instantiation without the column tests) may change the last bit of every result.
+// Where the chain kernel restructures such code the expressions are therefore written out -- the fused operation as
+// __builtin_fma, the rounded product as a product -- in the form the compiler chose for the generic code (read from its
+// ISA; scripts/isa_fp64_compare.py holds a build to it), inside functions with contraction switched off, so that
+// nothing is fused or unfused behind them.
+// the stopping test of one element: |g_new - g|^2 > conv^2 max(|g_new|^2, 1e-24) (over) / <= (ok); an element that does
+// not exist (!v) is neither over nor not ok, a NaN element is neither over nor ok
+__device__ __forceinline__ void rs_stop_test(cplx gn, cplx go, double conv2, bool v, bool& over, bool& ok)
+{
+#pragma clang fp contract(off)
+    const double dx = gn.x - go.x, dy = gn.y - go.y;
+    const double num2 = __builtin_fma(dx, dx, dy * dy);
+    const double den2 = fmax(__builtin_fma(gn.x, gn.x, gn.y * gn.y), 1e-24);
+    const double thr = conv2 * den2;
+    over |= v && num2 > thr;
+    ok &= !v || num2 <= thr;
+}
+// the mixing of one element: r g_new + (1 - r) g
+__device__ __forceinline__ cplx rs_mix(cplx gn, cplx go, double rf, double rf1)
+{
+#pragma clang fp contract(off)
+    return cmake(__builtin_fma(go.x, rf1, gn.x * rf), __builtin_fma(go.y, rf1, gn.y * rf));
 }
 
 // ---- panel [p0, p0+pw) factored by ONE wave: lane = row, 16 complex per lane, no barrier inside.  A wave
@@ -275,6 +302,112 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             if (FULL || s < pw) {
                 wrow[s] = cmul(a[s], myip);                 // the deferred pivot-row scaling
             }
+    }
+}
+
+// ---- the factoring of the stage schedule (RS_SCHED_FACTOR): rs_factor for a panel whose width is known -- the narrow last
+// panel in NBW = 4 columns instead of 8 (on); FULL, pw == NBW: no column tests, and where the work matrix has 64 rows no row
+// select on the loads (off, see RS_SCHED_FACTOR) -- with its arithmetic pinned to what the compiler makes of rs_factor in the
+// generic loop of the same class (read from the ISA of chain1d_rs_kernel<35 | 51, ...>, every column step, the plain and
+// the round-robin instantiations):
+//     a b          = ( fma(ax, bx, -(ay by)),  fma(ay, bx, ax by) )                       pivot-row scaling, a[j] ip
+//     a + coef rb  = ( fma(-rby, cy, fma(rbx, cx, ax)),  fma(rbx, cy, fma(rby, cx, ay)) )
+//     |pv|^2       = fma(pvy, pvy, pvx pvx) -- but fma(pvx, pvx, pvy pvy) in the LAST of rs_factor's eight column steps, the one
+//                    place where the compiler's choice differs from step to step (in every instantiation the same way);
+//     Newton: sc = fma(sc, fma(-d, sc, 1), sc);   ip = (pvx sc, -pvy sc)
+__device__ __forceinline__ cplx rs_cmul_pinned(cplx a, cplx b)
+{
+#pragma clang fp contract(off)
+    return cmake(__builtin_fma(a.x, b.x, -(a.y * b.y)), __builtin_fma(a.y, b.x, a.x * b.y));
+}
+__device__ __forceinline__ cplx rs_cfma_pinned(cplx a, cplx coef, cplx rb)
+{
+#pragma clang fp contract(off)
+    return cmake(__builtin_fma(-rb.y, coef.y, __builtin_fma(rb.x, coef.x, a.x)), __builtin_fma(rb.x, coef.y, __builtin_fma(rb.y, coef.x, a.y)));
+}
+__device__ __forceinline__ cplx rs_pivot_recip_pinned(cplx pv, bool last /* column step 7 of rs_factor's eight */)
+{
+#pragma clang fp contract(off)
+    const double d = last ? __builtin_fma(pv.x, pv.x, pv.y * pv.y) : __builtin_fma(pv.y, pv.y, pv.x * pv.x);
+    double sc = __builtin_amdgcn_rcp(d);
+    sc = __builtin_fma(sc, __builtin_fma(-d, sc, 1.0), sc);
+    sc = __builtin_fma(sc, __builtin_fma(-d, sc, 1.0), sc);
+    return cmake(pv.x * sc, -pv.y * sc);
+}
+constexpr bool rs_sched_factor(int which /* 1: the full panels, 2: the narrow last panel */) { return (RS_SCHED_FACTOR & which) && RS_ROW_MODE == 0; }
+
+template <int P, int NBW, bool FULL>
+__device__ __forceinline__ void rs_factor_sched(int n, cplx* W, int* pivrow, int* colof, cplx* rowline /*[16] LDS*/,
+                                                int p0, int pw, int lane, unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */)
+{
+    const int r = rs_opaque(lane);
+    cplx a[NBW];
+    constexpr bool ROWSEL = !FULL || 16 * ((P - 1 + 15) / 16) < 64;   // lanes beyond the rows of the work matrix read nothing
+    bool avail = r < n && colof[r] < 0;
+    cplx myip = cmake(1.0, 0.0);
+    cplx* wrow = W + r * P + p0;                        // rows >= n are zero padding
+#pragma unroll
+    for (int s = 0; s < NBW; ++s) {
+        if (ROWSEL) {
+            const cplx v = wrow[s];
+            const bool ok = (r < n) & (FULL || s < pw);
+            a[s] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
+        } else a[s] = wrow[s];
+    }
+#pragma unroll
+    for (int j = 0; j < NBW; ++j) {
+        if (FULL || j < pw) {
+            const bool stamp_here = fst && j == 4;
+            unsigned long long tq0 = 0, tq1 = 0, tq2 = 0, tq3 = 0, tq4 = 0;
+            if (stamp_here) tq0 = __builtin_amdgcn_s_memtime();
+            const double v = cabs1(a[j]);
+            const unsigned hi = (avail && v == v) ? (unsigned)__double2hiint(v) : 0u;
+            const unsigned m = rs_wave_max_u32(hi);
+            int pphys;
+            if (m != 0) {
+                pphys = (int)__ffsll((unsigned long long)__ballot(hi == m)) - 1;
+            } else {                                    // no usable candidate (zero / NaN column): lowest available row
+                const unsigned long long av = __ballot(avail);
+                pphys = av ? (int)__ffsll(av) - 1 : 0x7fffffff;
+            }
+            pphys = __builtin_amdgcn_readfirstlane(pphys);
+            if (stamp_here) tq1 = __builtin_amdgcn_s_memtime();
+            const bool is_piv = r == pphys;
+            cplx rb[NBW];
+            // the pivot row through the LDS line (rs_factor, RS_ROW_MODE 0)
+            __builtin_amdgcn_wave_barrier();
+            if (is_piv) {
+                pivrow[p0 + j] = pphys; colof[pphys] = p0 + j;
+#pragma unroll
+                for (int s = 0; s < NBW; ++s) rowline[s] = a[s];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+            for (int s = 0; s < NBW; ++s) rb[s] = rowline[s];
+            if (stamp_here) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tq2 = __builtin_amdgcn_s_memtime(); }
+            const cplx ip = rs_pivot_recip_pinned(rb[j], j == RS_NB - 1);
+            const cplx mf = cneg(rs_cmul_pinned(a[j], ip));
+            const cplx coef = cmake(is_piv ? 0.0 : mf.x, is_piv ? 0.0 : mf.y);
+            if (stamp_here) { asm volatile("" :: "v"(coef.x), "v"(coef.y)); tq3 = __builtin_amdgcn_s_memtime(); }
+#pragma unroll
+            for (int s = 0; s < NBW; ++s) a[s] = rs_cfma_pinned(a[s], coef, rb[s]);
+            if (stamp_here) {
+#pragma unroll
+                for (int s = 0; s < NBW; ++s) asm volatile("" :: "v"(a[s].x), "v"(a[s].y));
+                tq4 = __builtin_amdgcn_s_memtime();
+                if (lane == 0) { fst[0] = tq0; fst[1] = tq1; fst[2] = tq2; fst[3] = tq3; fst[4] = tq4; }
+            }
+            a[j] = is_piv ? cmake(1.0, 0.0) : coef;
+            myip = cmake(is_piv ? ip.x : myip.x, is_piv ? ip.y : myip.y);
+            avail = avail && !is_piv;
+        }
+    }
+    if (r < n) {
+#pragma unroll
+        for (int s = 0; s < NBW; ++s)
+            if (FULL || s < pw) wrow[s] = rs_cmul_pinned(a[s], myip);       // the deferred pivot-row scaling
     }
 }
 
@@ -829,9 +962,9 @@ __device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, in
         if (wave == RS_WAVES - 1) {
             if (st && lane == 0) st[16 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
             if (RS_PRIO) __builtin_amdgcn_s_setprio(3);         // (see rs_inverse)
-            if (!RS_SCHED_FACTOR) rs_factor<P>(n, W, pivrow, colof, rowline, n0, full_next ? RS_NB : n - n0, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
-            else if (full_next) rs_factor<P, RS_NB, true>(n, W, pivrow, colof, rowline, n0, RS_NB, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
-            else rs_factor<P, 4, false>(n, W, pivrow, colof, rowline, n0, n - n0, lane);
+            if (rs_sched_factor(1) && full_next) rs_factor_sched<P, RS_NB, true>(n, W, pivrow, colof, rowline, n0, RS_NB, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
+            else if (rs_sched_factor(2) && !full_next) rs_factor_sched<P, 4, false>(n, W, pivrow, colof, rowline, n0, n - n0, lane);
+            else rs_factor<P>(n, W, pivrow, colof, rowline, n0, full_next ? RS_NB : n - n0, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
             if (RS_PRIO) __builtin_amdgcn_s_setprio(0);
             if (st && lane == 0) st[17 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
         }

@@ -58,6 +58,9 @@
 #ifndef RS_DENSE_MIX
 #define RS_DENSE_MIX 1                // mixing on the dense lane map of chain_mix_map.h (10 slots at n_c = 50, not 13), the LDS slots and
 #endif                                //    the global slots of the old iterate as separate loops in their own address spaces
+#ifndef RS_LAZY_STOP
+#define RS_LAZY_STOP 1                // the stopping test of the dense mixing step by wave: slot 0 first, the other slots only when no lane of
+#endif                                //    the wave is over on it (see gather_mix_dense); 0 = every slot of every lane in every sweep
 
 namespace {
 
@@ -519,6 +522,9 @@ __device__ __forceinline__ void chain1d_rs_body(
         return rs_scalar_base(a.gold + (size_t)slot * KS * RS_THREADS);
     };
     constexpr unsigned GSLOT = RS_THREADS * sizeof(cplx);       // bytes of a slot of the record
+    // (RS_LAZY_STOP; the three-per-CU instantiations of the four-tile classes 57 and 65 keep the full test: their work matrix never
+    //  fits a CU three times, so they are never launched, and with the branch their 64 - 84 bytes of scratch grow by 4 - 8)
+    constexpr bool LAZY = RS_LAZY_STOP && !(T16 == 4 && OCC == 3);
     auto gather_mix_dense = [&](bool first, unsigned long long* st) __attribute__((always_inline)) {
         const int t = rs_opaque(tid);
         const int rg0 = (int)(((unsigned)t * mm.rcp) >> 16);
@@ -547,18 +553,23 @@ __device__ __forceinline__ void chain1d_rs_body(
         if (st && tid == 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st[5] = __builtin_amdgcn_s_memrealtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st[6] = __builtin_amdgcn_s_memrealtime(); }
         bool lane_over = false, lane_ok = true;
         if (!first) {
+            // The stopping test by wave (RS_LAZY_STOP).  All it feeds are the wave's two flags: over = any element over, ok = every
+            // element ok.  A lane that is over on its slot 0 (an LDS slot, valid in every active lane) settles both -- its
+            // element is valid and not ok --, so the wave then skips the test of its other slots: the common case, a fixed
+            // point is over in every sweep but its last few.  No lane over on slot 0 (NaN elements are neither over nor
+            // ok): the other slots are tested as before.  The mixing runs for every slot either way, in its own loop.
+            auto test = [&](int s) __attribute__((always_inline)) { rs_stop_test(gm[s], go[s], conv2, valid(s), lane_over, lane_ok); };
+            if (LAZY) {
+                test(0);
+                if (__ballot(lane_over) == 0ull) {
 #pragma unroll
-            for (int s = 0; s < MS; ++s) {
-                if (on(s)) {
-                    const cplx gn = gm[s];
-                    const double dx = gn.x - go[s].x, dy = gn.y - go[s].y;
-                    const double num2 = dx * dx + dy * dy;
-                    const double den2 = fmax(gn.x * gn.x + gn.y * gn.y, 1e-24);
-                    const bool v = valid(s);
-                    lane_over |= v && num2 > conv2 * den2;
-                    lane_ok &= !v || num2 <= conv2 * den2;
-                    gm[s] = cmake(gn.x * rf + go[s].x * rf1, gn.y * rf + go[s].y * rf1);
+                    for (int s = 1; s < MS; ++s) if (on(s)) test(s);
                 }
+#pragma unroll
+                for (int s = 0; s < MS; ++s) if (on(s)) gm[s] = rs_mix(gm[s], go[s], rf, rf1);
+            } else {                                    // (0, for A/B timing: every slot tested and mixed in turn)
+#pragma unroll
+                for (int s = 0; s < MS; ++s) if (on(s)) { test(s); gm[s] = rs_mix(gm[s], go[s], rf, rf1); }
             }
         }
 #pragma unroll
