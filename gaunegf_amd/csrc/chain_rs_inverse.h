@@ -11,27 +11,7 @@ namespace {
 
 constexpr int RS_THREADS = 256;
 constexpr int RS_WAVES = 4;
-#ifndef RS_PANEL
-#define RS_PANEL 8
-#endif
-constexpr int RS_NB = RS_PANEL;           // panel width of the small inverse: half a column tile (8) or a whole one (16)
-#ifndef RS_PRIO
-#define RS_PRIO 1
-#endif
-#ifndef RS_REMAINDER
-#define RS_REMAINDER 1
-#endif
-#ifndef RS_ROW_MODE
-#define RS_ROW_MODE 0                 // pivot row of the factoring wave: 0 LDS line (round 2), 1 v_readlane, 2 ds_bpermute
-#endif
-#ifndef RS_LA_FLAGS
-#define RS_LA_FLAGS 0                 // look-ahead of the small inverse synchronised by two workgroup barriers (0) or by LDS counters
-                                      // (1: built and measured in round 4 -- parity green, the C3 launch 666 ms against 668: with
-                                      // three workgroups per CU a barrier's wait is another workgroup's issue slot, not idle time)
-#endif
-#ifndef RS_RR
-#define RS_RR 1
-#endif
+constexpr int RS_NB = 8;                  // panel width of the small inverse: half a column tile
 // The pivot rows of a panel are replaced, not updated: W[pivot row][col] = 0 + P[pivot row][:] Q[:][col].  The trailing
 // update needs no per-tile mask for that: the owner of a column tile has the panel's pivot rows of its columns (the Q
 // fragment) in registers before it writes, so it zeroes them in LDS first and every tile is then a pure accumulation
@@ -39,28 +19,9 @@ constexpr int RS_NB = RS_PANEL;           // panel width of the small inverse: h
 // (rs_update_tile<.., true>).  Storing P - E instead (a one short at every (pivot row, its column), added back where
 // the inverse is read) saves the zeroing but forms the pivot row as q + (1/p - 1) q: 1/p - 1 is rounded to an
 // absolute u, so the row loses log2 |p| bits, all of them for |p| >= 2^53, and the read-back (x - 1) + 1 loses u / |x|.
-#ifndef RS_UPD_3M
-#define RS_UPD_3M 1                   // trailing / look-ahead updates (K = 8): 1 = three real products per tile and k-step (3M: operand
-#endif                                //    sums and a 12-instruction recombination per tile), 0 = four (no vector work per tile at all)
-#ifndef RS_HALF_STRIPS
-#define RS_HALF_STRIPS 1              // panels of 8: an update that may write only 8 columns of a full column tile (look-ahead, the
-#endif                                //    other half of the panel's tile / of the next tile) runs as two 16 x 4 column strips on the
-                                      //    4x4x4 instruction (half the matrix-pipe time, half the C traffic); 0 = whole tile, store masked
 #ifndef RS_ABLATE
 #define RS_ABLATE 0                   // diagnostic builds only (wrong results; timing with force_iters): 1 = no panel factoring (the chain
 #endif                                //    wave's pivot steps), 2 = no trailing / look-ahead updates, 4 = no products, 8 = no mixing phase
-#ifndef RS_STAGE_SCHED
-#define RS_STAGE_SCHED 1              // remainder-strip classes with the roles by SIMD: 1 = the stages of the inverse follow the compile-time
-#endif                                //    schedule of chain_rs_sched.h (rs_inverse_sched: full panels without selects, jobs from a table,
-                                      //    full tiles stored unguarded), 0 = the generic loop (rs_inverse) everywhere
-#ifndef RS_SCHED_FACTOR
-#define RS_SCHED_FACTOR 2             // the factoring wave under the stage schedule (rs_factor_sched, arithmetic pinned to the generic loop's), a
-#endif                                //    bit mask: 2 = the narrow last panel in a 4-column instantiation -- bit for bit the generic loop, ON;
-                                      //    1 = the full panels in an instantiation without column tests and load selects -- OFF: Sigma still
-                                      //    differs from the generic loop's in the last digits (n = 33 .. 35 and 49 .. 51, sweep counts unchanged)
-                                      //    although the FP64 instructions of every column step now have the generic loop's form, operand by
-                                      //    operand (LAB_NOTES.md: the cause is not contraction alone and was not found); 0 = rs_factor as the
-                                      //    generic loop instantiates it
 #ifndef RS_STAMPS
 #define RS_STAMPS 0                   // 1: diagnostic build -- the phase / cycle stamps of NEGF_CHAIN_STAMPS=1 are compiled in
 #endif                                //    (NEGF_EXTRA_HIPCC_FLAGS=-DRS_STAMPS=1 python -m gaunegf_amd.build --force); the production
@@ -132,9 +93,9 @@ __device__ __forceinline__ void mfma3(d4& a, d4& b, d4& c, double pr, double pi,
     b = __builtin_amdgcn_mfma_f64_16x16x4f64(pi, qi, b, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f64_16x16x4f64(ps, qs, c, 0, 0, 0);
 }
-#ifndef RS_3M_GEMM
-#define RS_3M_GEMM 1
-#endif
+// the trailing / look-ahead updates (K = 8) run in 3M form in the 168-VGPR kernels: operand sums and a 12-instruction
+// recombination per tile; below that pitch four products per tile and k-step, no vector work per tile at all
+constexpr bool rs_upd_3m(int P) { return P > 35; }
 // the same on the 4x4x4 instruction (remainder strips, one value per lane)
 __device__ __forceinline__ void mfma3s(double& a, double& b, double& c, double pr, double pi, double ps, double qr, double qi, double qs)
 {
@@ -151,12 +112,6 @@ __device__ __forceinline__ T rs_opaque(T v)
 {
     asm volatile("" : "+v"(v));
     return v;
-}
-
-__device__ __forceinline__ double rs_readlane_f64(double v, int srclane)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), srclane),
-                            __builtin_amdgcn_readlane(__double2loint(v), srclane));
 }
 
 // ---- pinned arithmetic.  The compiler contracts a * b + c * d into one product and one fused multiply-add, and WHICH
@@ -198,121 +153,14 @@ __device__ __forceinline__ cplx rs_mix(cplx gn, cplx go, double rf, double rf1)
 //     overflow / denormal range the IEEE division sequence guards).
 // A pivot row is not scaled at its column step (multiplier 0, a one in the pivot column) but once at
 // the end of the panel: the later steps act linearly on it, and every lane runs the same select-free update.
-// NBW: columns the code is written for (pw <= NBW).  FULL: pw == NBW is known -- no column tests, and where the work matrix
-// has 64 rows no row select on the loads either: a lane r >= n is never `avail` and never stores, what it computes from the
-// spare rows is dead.
-template <int P, int NBW = RS_NB, bool FULL = false>
-__device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colof, cplx* rowline /*[16] LDS*/,
-                                          int p0, int pw, int lane, unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */)
-{
-    const int r = rs_opaque(lane);                      // (see rs_opaque: nothing derived from the lane index is
-    cplx a[NBW];                                        //  hoisted out of the fixed-point loop and kept alive)
-    constexpr bool ROWSEL = !FULL || 16 * ((P - 1 + 15) / 16) < 64;   // lanes beyond the rows of the work matrix read nothing
-    bool avail = r < n && colof[r] < 0;
-    cplx myip = cmake(1.0, 0.0);
-    cplx* wrow = W + r * P + p0;                        // rows >= n are zero padding
-#pragma unroll
-    for (int s = 0; s < NBW; ++s) {
-        if (ROWSEL) {
-            const cplx v = wrow[s];
-            const bool ok = (r < n) & (FULL || s < pw);
-            a[s] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
-        } else a[s] = wrow[s];
-    }
-#pragma unroll
-    for (int j = 0; j < NBW; ++j) {
-        if (FULL || j < pw) {
-            const bool stamp_here = fst && j == 4;
-            unsigned long long tq0 = 0, tq1 = 0, tq2 = 0, tq3 = 0, tq4 = 0;
-            if (stamp_here) tq0 = __builtin_amdgcn_s_memtime();
-            const double v = cabs1(a[j]);
-            const unsigned hi = (avail && v == v) ? (unsigned)__double2hiint(v) : 0u;
-            const unsigned m = rs_wave_max_u32(hi);
-            int pphys;
-            if (m != 0) {
-                pphys = (int)__ffsll((unsigned long long)__ballot(hi == m)) - 1;
-            } else {                                    // no usable candidate (zero / NaN column): lowest available row
-                const unsigned long long av = __ballot(avail);
-                pphys = av ? (int)__ffsll(av) - 1 : 0x7fffffff;
-            }
-            pphys = __builtin_amdgcn_readfirstlane(pphys);
-            if (stamp_here) tq1 = __builtin_amdgcn_s_memtime();
-            const bool is_piv = r == pphys;
-            cplx rb[NBW];
-#if RS_ROW_MODE == 0
-            // through a 256-byte LDS line: one lane writes its 16 values, all lanes read them back.  The wave-level
-            // barriers keep the compiler from ordering the two sides of the divergent branch the other way round
-            // (it does, without them), the LDS then executes the wave's instructions in order
-            __builtin_amdgcn_wave_barrier();            // the reads of the previous column step are issued
-            if (is_piv) {
-                pivrow[p0 + j] = pphys; colof[pphys] = p0 + j;
-#pragma unroll
-                for (int s = 0; s < NBW; ++s) rowline[s] = a[s];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int s = 0; s < NBW; ++s) rb[s] = rowline[s];
-#elif RS_ROW_MODE == 1
-            // through v_readlane (wave-uniform results, scalar operands of the FMAs): measured 10 cycles each
-            if (is_piv) { pivrow[p0 + j] = pphys; colof[pphys] = p0 + j; }
-#pragma unroll
-            for (int s = 0; s < NBW; ++s)
-                rb[s] = cmake(rs_readlane_f64(a[s].x, pphys), rs_readlane_f64(a[s].y, pphys));
-#else
-            // through ds_bpermute_b32: every lane reads the pivot lane's register over the LDS crossbar -- no memory,
-            // no write -> wait -> read round trip, no wave barriers: one pass of 64 pipelined LDS instructions
-            if (is_piv) { pivrow[p0 + j] = pphys; colof[pphys] = p0 + j; }
-            const int baddr = pphys << 2;
-#pragma unroll
-            for (int s = 0; s < NBW; ++s) {
-                rb[s].x = __hiloint2double(__builtin_amdgcn_ds_bpermute(baddr, __double2hiint(a[s].x)),
-                                           __builtin_amdgcn_ds_bpermute(baddr, __double2loint(a[s].x)));
-                rb[s].y = __hiloint2double(__builtin_amdgcn_ds_bpermute(baddr, __double2hiint(a[s].y)),
-                                           __builtin_amdgcn_ds_bpermute(baddr, __double2loint(a[s].y)));
-            }
-#endif
-            if (stamp_here) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tq2 = __builtin_amdgcn_s_memtime(); }
-            const cplx pv = rb[j];
-            const double d = pv.x * pv.x + pv.y * pv.y;
-            double sc = __builtin_amdgcn_rcp(d);
-            sc = fma(sc, fma(-d, sc, 1.0), sc);
-            sc = fma(sc, fma(-d, sc, 1.0), sc);
-            const cplx ip = cmake(pv.x * sc, -pv.y * sc);
-            const cplx mf = cneg(cmul(a[j], ip));
-            const cplx coef = cmake(is_piv ? 0.0 : mf.x, is_piv ? 0.0 : mf.y);
-            if (stamp_here) { asm volatile("" :: "v"(coef.x), "v"(coef.y)); tq3 = __builtin_amdgcn_s_memtime(); }
-#pragma unroll
-            for (int s = 0; s < NBW; ++s) a[s] = cfma(a[s], coef, rb[s]);
-            if (stamp_here) {
-#pragma unroll
-                for (int s = 0; s < NBW; ++s) asm volatile("" :: "v"(a[s].x), "v"(a[s].y));
-                tq4 = __builtin_amdgcn_s_memtime();
-                if (lane == 0) { fst[0] = tq0; fst[1] = tq1; fst[2] = tq2; fst[3] = tq3; fst[4] = tq4; }
-            }
-            a[j] = is_piv ? cmake(1.0, 0.0) : coef;
-            myip = cmake(is_piv ? ip.x : myip.x, is_piv ? ip.y : myip.y);
-            avail = avail && !is_piv;
-        }
-    }
-    if (r < n) {
-#pragma unroll
-        for (int s = 0; s < NBW; ++s)
-            if (FULL || s < pw) {
-                wrow[s] = cmul(a[s], myip);                 // the deferred pivot-row scaling
-            }
-    }
-}
-
-// ---- the factoring of the stage schedule (RS_SCHED_FACTOR): rs_factor for a panel whose width is known -- the narrow last
-// panel in NBW = 4 columns instead of 8 (on); FULL, pw == NBW: no column tests, and where the work matrix has 64 rows no row
-// select on the loads (off, see RS_SCHED_FACTOR) -- with its arithmetic pinned to what the compiler makes of rs_factor in the
-// generic loop of the same class (read from the ISA of chain1d_rs_kernel<35 | 51, ...>, every column step, the plain and
-// the round-robin instantiations):
+//
+// ---- pinned factoring.  The stage schedule (rs_inverse_sched) factors its narrow last panel in an instantiation of NBW = 4
+// columns instead of 8, with the arithmetic pinned to what the compiler makes of the 8-column instantiation in the generic
+// loop of the same class (read from the ISA of chain1d_rs_kernel<35 | 51, ...>, every column step, the plain and the
+// round-robin instantiations):
 //     a b          = ( fma(ax, bx, -(ay by)),  fma(ay, bx, ax by) )                       pivot-row scaling, a[j] ip
 //     a + coef rb  = ( fma(-rby, cy, fma(rbx, cx, ax)),  fma(rbx, cy, fma(rby, cx, ay)) )
-//     |pv|^2       = fma(pvy, pvy, pvx pvx) -- but fma(pvx, pvx, pvy pvy) in the LAST of rs_factor's eight column steps, the one
+//     |pv|^2       = fma(pvy, pvy, pvx pvx) -- but fma(pvx, pvx, pvy pvy) in the LAST of the eight column steps, the one
 //                    place where the compiler's choice differs from step to step (in every instantiation the same way);
 //     Newton: sc = fma(sc, fma(-d, sc, 1), sc);   ip = (pvx sc, -pvy sc)
 __device__ __forceinline__ cplx rs_cmul_pinned(cplx a, cplx b)
@@ -334,29 +182,49 @@ __device__ __forceinline__ cplx rs_pivot_recip_pinned(cplx pv, bool last /* colu
     sc = __builtin_fma(sc, __builtin_fma(-d, sc, 1.0), sc);
     return cmake(pv.x * sc, -pv.y * sc);
 }
-constexpr bool rs_sched_factor(int which /* 1: the full panels, 2: the narrow last panel */) { return (RS_SCHED_FACTOR & which) && RS_ROW_MODE == 0; }
-
-template <int P, int NBW, bool FULL>
-__device__ __forceinline__ void rs_factor_sched(int n, cplx* W, int* pivrow, int* colof, cplx* rowline /*[16] LDS*/,
-                                                int p0, int pw, int lane, unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */)
+// the three arithmetic sites of rs_factor: the compiler's contraction (the generic loop) or the pinned form
+template <bool PINNED>
+__device__ __forceinline__ cplx rs_factor_recip(cplx pv, bool last)
 {
-    const int r = rs_opaque(lane);
-    cplx a[NBW];
-    constexpr bool ROWSEL = !FULL || 16 * ((P - 1 + 15) / 16) < 64;   // lanes beyond the rows of the work matrix read nothing
+    if constexpr (PINNED) return rs_pivot_recip_pinned(pv, last);
+    else {
+        const double d = pv.x * pv.x + pv.y * pv.y;
+        double sc = __builtin_amdgcn_rcp(d);
+        sc = fma(sc, fma(-d, sc, 1.0), sc);
+        sc = fma(sc, fma(-d, sc, 1.0), sc);
+        return cmake(pv.x * sc, -pv.y * sc);
+    }
+}
+template <bool PINNED>
+__device__ __forceinline__ cplx rs_factor_cmul(cplx a, cplx b)
+{
+    if constexpr (PINNED) return rs_cmul_pinned(a, b); else return cmul(a, b);
+}
+template <bool PINNED>
+__device__ __forceinline__ cplx rs_factor_cfma(cplx a, cplx coef, cplx rb)
+{
+    if constexpr (PINNED) return rs_cfma_pinned(a, coef, rb); else return cfma(a, coef, rb);
+}
+
+// NBW: columns the code is written for (pw <= NBW).  PINNED: the arithmetic in the written-out form above (rs_*_pinned).
+template <int P, int NBW = RS_NB, bool PINNED = false>
+__device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colof, cplx* rowline /*[16] LDS*/,
+                                          int p0, int pw, int lane, unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */)
+{
+    const int r = rs_opaque(lane);                      // (see rs_opaque: nothing derived from the lane index is
+    cplx a[NBW];                                        //  hoisted out of the fixed-point loop and kept alive)
     bool avail = r < n && colof[r] < 0;
     cplx myip = cmake(1.0, 0.0);
     cplx* wrow = W + r * P + p0;                        // rows >= n are zero padding
 #pragma unroll
     for (int s = 0; s < NBW; ++s) {
-        if (ROWSEL) {
-            const cplx v = wrow[s];
-            const bool ok = (r < n) & (FULL || s < pw);
-            a[s] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
-        } else a[s] = wrow[s];
+        const cplx v = wrow[s];
+        const bool ok = (r < n) & (s < pw);
+        a[s] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
     }
 #pragma unroll
     for (int j = 0; j < NBW; ++j) {
-        if (FULL || j < pw) {
+        if (j < pw) {
             const bool stamp_here = fst && j == 4;
             unsigned long long tq0 = 0, tq1 = 0, tq2 = 0, tq3 = 0, tq4 = 0;
             if (stamp_here) tq0 = __builtin_amdgcn_s_memtime();
@@ -374,8 +242,10 @@ __device__ __forceinline__ void rs_factor_sched(int n, cplx* W, int* pivrow, int
             if (stamp_here) tq1 = __builtin_amdgcn_s_memtime();
             const bool is_piv = r == pphys;
             cplx rb[NBW];
-            // the pivot row through the LDS line (rs_factor, RS_ROW_MODE 0)
-            __builtin_amdgcn_wave_barrier();
+            // through a 256-byte LDS line: one lane writes its 16 values, all lanes read them back.  The wave-level
+            // barriers keep the compiler from ordering the two sides of the divergent branch the other way round
+            // (it does, without them), the LDS then executes the wave's instructions in order
+            __builtin_amdgcn_wave_barrier();            // the reads of the previous column step are issued
             if (is_piv) {
                 pivrow[p0 + j] = pphys; colof[pphys] = p0 + j;
 #pragma unroll
@@ -387,12 +257,12 @@ __device__ __forceinline__ void rs_factor_sched(int n, cplx* W, int* pivrow, int
 #pragma unroll
             for (int s = 0; s < NBW; ++s) rb[s] = rowline[s];
             if (stamp_here) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tq2 = __builtin_amdgcn_s_memtime(); }
-            const cplx ip = rs_pivot_recip_pinned(rb[j], j == RS_NB - 1);
-            const cplx mf = cneg(rs_cmul_pinned(a[j], ip));
+            const cplx ip = rs_factor_recip<PINNED>(rb[j], j == RS_NB - 1);
+            const cplx mf = cneg(rs_factor_cmul<PINNED>(a[j], ip));
             const cplx coef = cmake(is_piv ? 0.0 : mf.x, is_piv ? 0.0 : mf.y);
             if (stamp_here) { asm volatile("" :: "v"(coef.x), "v"(coef.y)); tq3 = __builtin_amdgcn_s_memtime(); }
 #pragma unroll
-            for (int s = 0; s < NBW; ++s) a[s] = rs_cfma_pinned(a[s], coef, rb[s]);
+            for (int s = 0; s < NBW; ++s) a[s] = rs_factor_cfma<PINNED>(a[s], coef, rb[s]);
             if (stamp_here) {
 #pragma unroll
                 for (int s = 0; s < NBW; ++s) asm volatile("" :: "v"(a[s].x), "v"(a[s].y));
@@ -407,7 +277,7 @@ __device__ __forceinline__ void rs_factor_sched(int n, cplx* W, int* pivrow, int
     if (r < n) {
 #pragma unroll
         for (int s = 0; s < NBW; ++s)
-            if (FULL || s < pw) wrow[s] = rs_cmul_pinned(a[s], myip);       // the deferred pivot-row scaling
+            if (s < pw) wrow[s] = rs_factor_cmul<PINNED>(a[s], myip);     // the deferred pivot-row scaling
     }
 }
 
@@ -430,13 +300,6 @@ __device__ __forceinline__ void rs_load_qf(const cplx* W, const int* pivrow, int
     }
 }
 
-// one tile (ti, tj): a full 16 x 16 tile, or a row / column strip (one value per lane, corner: one block)
-__device__ __forceinline__ void rs_wait_count(const unsigned* cnt, unsigned target)
-{
-    // (LDS counter of the look-ahead, see rs_inverse: spins only while another wave of the workgroup is behind)
-    while (*reinterpret_cast<const volatile unsigned*>(cnt) < target) __builtin_amdgcn_s_sleep(1);
-}
-
 // the panel's pivot rows in the columns of this lane's Q fragment (rs_load_qf) that are to be updated, [clo, chi) inside
 // the matrix, are set to zero: the owner of those columns calls it after its Q fragment is loaded (a wave's LDS
 // operations execute in order, and the stores may alias the loads, so neither the compiler nor the LDS reorders them)
@@ -454,10 +317,10 @@ __device__ __forceinline__ void rs_zero_pivot_rows(int n, cplx* W, const int* pi
     }
 }
 
+// one tile (ti, tj): a full 16 x 16 tile, or a row / column strip (one value per lane, corner: one block)
 template <int P, int NKS, int TR, bool MASK /* seed the pivot rows of the panel with 0 (else they already are 0) */>
 __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof, int ti, int tj, int p0, int pw,
-                                               int fi, int fk, const cplx (&qf)[NKS], int clo, int chi /* columns [clo, chi) are stored */,
-                                               const unsigned* wait_cnt = nullptr, unsigned wait_target = 0 /* stores wait for *wait_cnt >= wait_target */)
+                                               int fi, int fk, const cplx (&qf)[NKS], int clo, int chi /* columns [clo, chi) are stored */)
 {
     const bool rowstrip = TR >= 0 && ti == TR, colstrip = TR >= 0 && tj == TR;
     if (!rowstrip && !colstrip) {
@@ -469,7 +332,7 @@ __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof,
         for (int r = 0; r < 4; ++r) { if (MASK) cf[r] = colof[ti * 16 + fk + 4 * r]; cv[r] = cbase[4 * r * P]; }
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) pa[ks] = pbase[ks * 4];
-        constexpr bool M3 = RS_UPD_3M && P > 35;            // 3M (mfma3) in the 168-VGPR kernels
+        constexpr bool M3 = rs_upd_3m(P);
         d4 ua, ub = {0, 0, 0, 0}, uc;                       // accumulators, seeded with the old tile
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -481,7 +344,6 @@ __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof,
             if (M3) mfma3(ua, ub, uc, pa[ks].x, pa[ks].y, pa[ks].x + pa[ks].y, qf[ks].x, qf[ks].y, qf[ks].x + qf[ks].y);
             else zmfma(ua, uc, pa[ks], qf[ks]);
         }
-        if (wait_cnt) rs_wait_count(wait_cnt, wait_target);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = ti * 16 + fk + 4 * r;
@@ -504,7 +366,6 @@ __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof,
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks)
             mfma3s(ua, ub, uc, pa[ks].x, pa[ks].y, pa[ks].x + pa[ks].y, qf[ks].x, qf[ks].y, qf[ks].x + qf[ks].y);
-        if (wait_cnt) rs_wait_count(wait_cnt, wait_target);
         if (mine && row < n && col < n && col >= clo && col < chi) *cptr = cmake(ua - ub, uc - ua - ub);
     }
 }
@@ -515,7 +376,7 @@ __device__ __forceinline__ void rs_update_tile(int n, cplx* W, const int* colof,
 // (every 4-column block of the B operand holds the strip's columns c0 + 4 s + (l&3)), 2 x NKS x 3 4x4x4 instructions
 // -- half the matrix-pipe time of the whole tile -- and TWO values per lane, elements
 // (ti*16 + 4 (fi>>2) + fk, c0 + 4 s + (fi&3)): half the C loads, seeds, recombinations and stores as well.
-constexpr bool rs_half_strips(int nks) { return RS_HALF_STRIPS && RS_NB == 8 && nks == RS_NB / 4; }
+constexpr bool rs_half_strips(int nks) { return nks == RS_NB / 4; }
 
 template <int P, int NKS, bool FULL = false>
 __device__ __forceinline__ void rs_load_qh(const cplx* W, const int* pivrow, int c0, int p0, int pw, int fi, int fk,
@@ -537,7 +398,7 @@ __device__ __forceinline__ void rs_load_qh(const cplx* W, const int* pivrow, int
 template <int P, int NKS>
 __device__ __forceinline__ void rs_half_mma(cplx (&cv)[2], const cplx (&pa)[NKS], const cplx (&qh)[2][NKS], const double (&qs)[2][NKS])
 {
-    constexpr bool M3 = RS_UPD_3M && P > 35;                 // 3M (mfma3s) in the 168-VGPR kernels
+    constexpr bool M3 = rs_upd_3m(P);
     if (M3) {
         double ua[2], ub[2] = {0.0, 0.0}, uc[2];
 #pragma unroll
@@ -628,7 +489,7 @@ __device__ __forceinline__ void rs_update_col(int n, cplx* W, const int* pivrow,
     }
     const int col = tj * 16 + fi;
     const bool colin = col >= clo && col < chi;             // this lane's column is one of those to be updated
-    constexpr bool M3 = RS_UPD_3M && P > 35;                 // 3M (mfma3) in the 168-VGPR kernels
+    constexpr bool M3 = rs_upd_3m(P);
     double qs[NKS];                                          // 3M: re + im of the Q fragment, once per column tile
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) qs[ks] = qf[ks].x + qf[ks].y;
@@ -675,7 +536,6 @@ __device__ __forceinline__ void rs_update_col(int n, cplx* W, const int* pivrow,
 template <int T16, int P, int TR>
 __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* colof, cplx* rowline, int tid,
                                            int wave /* role number of this wave, see rs_wave_role */, bool fixed_fw,
-                                           unsigned* la_cnt /* [2] LDS */, unsigned& la_epoch,
                                            unsigned long long* st = nullptr)
 {
     const int lane = tid & 63;
@@ -696,31 +556,17 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
             const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
             // the next panel is half of a full column tile: this wave's row tile is a half tile, two column strips with a Q
             // fragment each (the row strip keeps its own form: one 4x4x4 instruction per k-step covers 16 columns already)
-            const bool half = !RS_LA_FLAGS && rs_half_strips(RS_NB / 4) && n0 + RS_NB <= n && !(TR >= 0 && (tl == TR || wave == TR));
+            const bool half = n0 + RS_NB <= n && !(TR >= 0 && (tl == TR || wave == TR));
             cplx qh[2][RS_NB / 4];
             cplx (&qf)[RS_NB / 4] = qh[0];                      // (one or the other)
             if (half) rs_load_qh<P, RS_NB / 4>(W, pivrow, n0, p0, pw, fi, fk, qh);
             else rs_load_qf<P, RS_NB / 4, TR>(W, pivrow, tl, p0, pw, fi, fk, qf);
-#if RS_LA_FLAGS
-            // No workgroup barrier in the look-ahead (there were two, seven times a sweep): two LDS counters instead.
-            // la_cnt[0] counts the waves whose Q fragment -- the panel's pivot rows in the next panel's columns, rows that
-            // other waves are about to overwrite -- is on its way (a wave's LDS operations execute in order, so its
-            // counter increment is behind its reads); a wave stores its look-ahead tile only when all four are.
-            // la_cnt[1] counts the waves that have stored; only the FACTORING wave waits for it -- the others go straight
-            // on to the trailing update, which touches neither the next panel's columns nor anybody else's pivot rows.
-            la_epoch += RS_WAVES;
-            if (lane == 0) atomicAdd(&la_cnt[0], 1u);
-            if (wave < T16 && wave * 16 < n) rs_update_tile<P, RS_NB / 4, TR, true>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB, &la_cnt[0], la_epoch);
-            if (lane == 0) atomicAdd(&la_cnt[1], 1u);
-            if (wave == fw) rs_wait_count(&la_cnt[1], la_epoch);
-#else
             __syncthreads();
             if (!(RS_ABLATE & 2) && wave < T16 && wave * 16 < n) {
                 if (half) rs_update_half<P, RS_NB / 4, TR >= 0, true>(n, W, colof, wave, p0, pw, fi, fk, qh, n0);
                 else rs_update_tile<P, RS_NB / 4, TR, true>(n, W, colof, wave, tl, p0, pw, fi, fk, qf, n0, n0 + RS_NB);
             }
             __syncthreads();
-#endif
         }
         if (has_cur) {
             // the other columns, tile by tile, one owner per tile (the owner reads its Q fragment before it writes):
@@ -733,14 +579,8 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
 #pragma unroll 1
             for (int tj = 0; tj < ntiles; ++tj) {
                 int clo = tj * 16, chi = tj * 16 + 16;
-                if (tj == tp) {
-                    if (RS_NB == 16) continue;
-                    if (p0 & 8) chi = p0; else clo = p0 + RS_NB;
-                }
-                if (has_next && tj == tl) {
-                    if (RS_NB == 16) continue;
-                    if (n0 & 8) chi = min(chi, n0); else clo = max(clo, n0 + RS_NB);
-                }
+                if (tj == tp) { if (p0 & 8) chi = p0; else clo = p0 + RS_NB; }
+                if (has_next && tj == tl) { if (n0 & 8) chi = min(chi, n0); else clo = max(clo, n0 + RS_NB); }
                 if (clo >= chi || clo >= n) continue;
                 const bool mine = (!has_next || wave != fw) && (cnt % team == me);
                 ++cnt;
@@ -755,10 +595,10 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
             if (st && lane == 0) st[16 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
             // the factoring wave is its workgroup's critical path (the others wait for it at the barrier):
             // it goes first when it shares its SIMD's issue slots with waves of the other workgroups
-            if (RS_PRIO) __builtin_amdgcn_s_setprio(3);
+            __builtin_amdgcn_s_setprio(3);
             if (!(RS_ABLATE & 1)) rs_factor<P>(n, W, pivrow, colof, rowline, n0, nw, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
             else if (lane < nw) { pivrow[n0 + lane] = n0 + lane; colof[n0 + lane] = n0 + lane; }
-            if (RS_PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             if (st && lane == 0) st[17 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
         }
         stamp();
@@ -766,17 +606,17 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
     }
 }
 
-// ---- the compile-time stage schedule of the remainder-strip classes (RS_STAGE_SCHED, chain_rs_sched.h).  In such a class
+// ---- the compile-time stage schedule of the remainder-strip classes (chain_rs_sched.h).  In such a class
 // (TR full tiles and a strip, every contact of the launch with 16 TR < n <= 16 TR + 4) with the roles by SIMD the generic
 // loop above derives, in every stage of every sweep, what never changes: 2 TR panels that are exactly 8 wide and lie inside
 // full tiles, then one narrow panel; role 3 factors; the column-tile jobs of a stage and their owners.  rs_inverse_sched
 // runs the same operations on the same operands in the same order with all of that fixed: the jobs of a role come out of one
 // 64-bit constant, the kind of a job selects one of three bodies (whole tile, half tile, column strip) that take the tile
 // index and the panel's first column as scalars -- one copy of each in the instruction stream --, a full panel's Q
-// fragments carry no selects, and full tiles are stored without tests (the factoring wave: RS_SCHED_FACTOR).
+// fragments carry no selects, and full tiles are stored without tests (the factoring wave: rs_factor, pinned factoring).
 // (TR = 1, class 19, keeps the generic loop: with the schedule its kernels need 128 VGPRs and 20 - 48 bytes of scratch
 //  instead of 110 and none, and the two-per-CU ones fall from four waves per SIMD to three)
-constexpr bool rs_stage_sched(int TR) { return RS_STAGE_SCHED && TR >= 2 && TR <= 3 && RS_NB == 8 && RS_HALF_STRIPS && !RS_LA_FLAGS && !RS_ABLATE; }
+constexpr bool rs_stage_sched(int TR) { return TR >= 2 && TR <= 3 && !RS_ABLATE; }     // (an ablation build runs the generic loop, which carries the ablations)
 
 // row strip of column tile tj < TR (rs_update_tile's strip form with the tile inside the matrix): rows 16 TR + fk < n are
 // stored; RANGE: only the columns [clo, clo + 8) of the tile; MASK: the panel's pivot rows are seeded with 0
@@ -828,7 +668,7 @@ __device__ __forceinline__ void rs_job_whole(int n, cplx* W, const int* pivrow, 
     rs_load_qf<P, NKS, -1, FULL>(W, pivrow, tj, p0, pw, fi, fk, qf);
     if (FULL) rs_zero_pivot_rows_full<P, NKS>(W, pivrow, p0, fk, col);
     else rs_zero_pivot_rows_narrow<P>(W, pivrow, p0, pw, fk, col);
-    constexpr bool M3 = RS_UPD_3M && P > 35;
+    constexpr bool M3 = rs_upd_3m(P);
     double qs[NKS];
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) qs[ks] = qf[ks].x + qf[ks].y;
@@ -961,11 +801,11 @@ __device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, in
         }
         if (wave == RS_WAVES - 1) {
             if (st && lane == 0) st[16 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
-            if (RS_PRIO) __builtin_amdgcn_s_setprio(3);         // (see rs_inverse)
-            if (rs_sched_factor(1) && full_next) rs_factor_sched<P, RS_NB, true>(n, W, pivrow, colof, rowline, n0, RS_NB, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
-            else if (rs_sched_factor(2) && !full_next) rs_factor_sched<P, 4, false>(n, W, pivrow, colof, rowline, n0, n - n0, lane);
-            else rs_factor<P>(n, W, pivrow, colof, rowline, n0, full_next ? RS_NB : n - n0, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
-            if (RS_PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(3);                      // (see rs_inverse)
+            // the narrow last panel in a 4-column instantiation with the arithmetic pinned: bit for bit the generic loop
+            if (!full_next) rs_factor<P, 4, true>(n, W, pivrow, colof, rowline, n0, n - n0, lane);
+            else rs_factor<P>(n, W, pivrow, colof, rowline, n0, RS_NB, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
+            __builtin_amdgcn_s_setprio(0);
             if (st && lane == 0) st[17 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
         }
         stamp();

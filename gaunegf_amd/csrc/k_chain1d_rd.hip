@@ -121,12 +121,9 @@ __global__ __launch_bounds__(RS_THREADS, 2) void chain1d_rd_kernel(
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ int pivrow[64], colof[64];
     __shared__ cplx rowline[RS_NB];
-    __shared__ unsigned la_cnt[2];
     __shared__ double red[2 * RS_WAVES];
-    unsigned la_epoch = 0;
     cplx* Ws = reinterpret_cast<cplx*>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) { la_cnt[0] = 0u; la_cnt[1] = 0u; }
 
     cplx* base = a.ws + (size_t)blockIdx.x * a.ws_per_slot;
     cplx* ES = base;
@@ -141,7 +138,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void chain1d_rd_kernel(
     auto invert = [&](int n, const cplx* src) __attribute__((always_inline)) {
         for (int t = tid; t < n * n; t += RS_THREADS) { const int i = t / n, j = t - i * n; Ws[i * P + j] = src[i * NP + j]; }
         __syncthreads();
-        rs_inverse<T16, P, -1>(n, Ws, pivrow, colof, rowline, tid, wave, false, la_cnt, la_epoch);
+        rs_inverse<T16, P, -1>(n, Ws, pivrow, colof, rowline, tid, wave, false);
         for (int t = tid; t < n * n; t += RS_THREADS) { const int i = t / n, j = t - i * n; Gm[i * NP + j] = Ws[pivrow[i] * P + colof[j]]; }
         __syncthreads();
         if (tid < 64) colof[tid] = -1;

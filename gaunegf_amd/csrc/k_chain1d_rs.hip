@@ -18,7 +18,7 @@
 //     reads back for its own elements only (chain_mix_map.h: 10 slots per lane at n_c = 50): in a second LDS
 //     matrix when two workgroups share the CU; when three do, the first slots in the unused rows of the work
 //     matrix and the rest in a lane-private global scratch record (L2-resident).
-//   * the in-place Gauss-Jordan inverse of M works on panels of 8 columns (RS_PANEL).  The wave on SIMD 0 -- the
+//   * the in-place Gauss-Jordan inverse of M works on panels of 8 columns (RS_NB).  The wave on SIMD 0 -- the
 //     CHAIN wave (rs_wave_role: the roles follow the SIMD a wave runs on, because an FP64 matrix instruction holds
 //     its SIMD's vector issue) -- factors every panel: lane = row, DPP arg-max on the high word of |re| + |im|, the
 //     pivot row through a 128-byte LDS line, no workgroup barrier inside.  The other three waves apply the previous
@@ -44,36 +44,21 @@
 #include <algorithm>
 #include <type_traits>
 
-// The three phases around the inverse, each with a switch for A/B timing (1 = on, the default):
-#ifndef RS_PAD_LEADS
-#define RS_PAD_LEADS 1                // the streamed operands of both products and the A of M = A - T B^H are read from the zero-padded
-#endif                                //    lead matrices (ChainRsArgs::pad): one lane base + compile-time offsets, no clamp, no select
-#ifndef RS_BATCH_MSTORE
-#define RS_BATCH_MSTORE 1             // M = A - T B^H: the A loads of a row tile go out as one batch, then the tile is stored: one round trip
-#endif                                //    per row tile; full tiles of a remainder-strip class are stored unguarded (needs RS_PAD_LEADS)
-#ifndef RS_MSTORE_AHEAD
-#define RS_MSTORE_AHEAD 0             // 1: A of row tile ti + 1 requested BEFORE tile ti is stored.  Default 0: the loads of tile ti + 1 go out
-                                      //    AFTER the stores of tile ti (with 1: 39 spilled VGPRs in <51,3,true,false>)
-#endif
-#ifndef RS_DENSE_MIX
-#define RS_DENSE_MIX 1                // mixing on the dense lane map of chain_mix_map.h (10 slots at n_c = 50, not 13), the LDS slots and
-#endif                                //    the global slots of the old iterate as separate loops in their own address spaces
-#ifndef RS_LAZY_STOP
-#define RS_LAZY_STOP 1                // the stopping test of the dense mixing step by wave: slot 0 first, the other slots only when no lane of
-#endif                                //    the wave is over on it (see gather_mix_dense); 0 = every slot of every lane in every sweep
-
 namespace {
 
 struct ChainRsArgs {
-    const cplx *alpha, *Salpha, *beta, *Sbeta, *tau, *Stau;   // concatenated per contact
-    const cplx* pad;                 // the same six, zero-padded: [matrix][contact][CHAIN_PAD][CHAIN_PAD] (SigmaProvider::d_lead_pad)
+    // concatenated per contact.  The kernel reads alpha, Salpha (the start matrix A) and streams everything else from `pad`;
+    // the other four keep the layout of the kernel arguments: without them the compiler loads the arguments in other
+    // groups and every instantiation gains 10 - 40 reloads of spilled scalars (LAB_NOTES.md, "retired variants")
+    const cplx *alpha, *Salpha, *beta, *Sbeta, *tau, *Stau;
+    const cplx* pad;                 // the six lead matrices, zero-padded: [matrix][contact][CHAIN_PAD][CHAIN_PAD] (SigmaProvider::d_lead_pad)
     const int* nc;
     const int* blk_off;
     int n_contacts, blk_stride;
     double eta, conv, relFactor;
     int max_iter, force_iters;
     cplx* gold;                      // [workgroups][KS][256] lane-private copies of the iterate (GOLD_GLOBAL kernels)
-    int gold_lds_off, gold_lds_slots; // the first slots of a lane's copy live in LDS at this element offset
+    int gold_lds_off;                // the first slots of a lane's copy live in LDS at this element offset
     const int* order;                // launch slot -> job (energy * n_contacts + contact), longest jobs first; or null
     // surface Green's function cache (negf_set_chain_cache): gc_mode 1 = this launch is a miss, every job stores its
     // final iterate g into gcache [energy][blk_stride] (the layout of blk); 2 = a hit, every job loads g from there and
@@ -180,7 +165,7 @@ __device__ __forceinline__ void rs_gstore(unsigned long long base, unsigned cons
     *reinterpret_cast<__attribute__((address_space(1))) rs_d2*>(p + lane_bytes) = w;
 }
 
-// SCHED: the inverse of a remainder-strip class follows the compile-time stage schedule (RS_STAGE_SCHED, rs_inverse_sched) --
+// SCHED: the inverse of a remainder-strip class follows the compile-time stage schedule (rs_inverse_sched) --
 // chain1d_rs_kernel; without it the generic loop -- chain1d_rs_wn_kernel, the launches with the roles by wave number.  Two
 // kernels, not one with both loops: the second copy of the inverse is 14 KB of code that a launch never runs.
 template <int P, int OCC, bool GOLD_GLOBAL, bool RR, bool SCHED>
@@ -192,23 +177,19 @@ __device__ __forceinline__ void chain1d_rs_body(
     constexpr int KS = (P + 3) / 4 < 4 * T16 ? (P + 3) / 4 : 4 * T16;   // k-steps of a full-width product (n <= P)
     constexpr int WELEMS = 16 * T16 * P + 16;           // 16*T16 rows and a few elements of slack behind the last one
     constexpr int TR = T16 - 1;                         // the last tile
-    constexpr bool REM = RS_REMAINDER && T16 >= 2 && P - 16 * TR <= 4;   // ... holds <= 4 rows / columns: strips
+    constexpr bool REM = T16 >= 2 && P - 16 * TR <= 4;   // ... holds <= 4 rows / columns: strips
     constexpr int FT = REM ? TR : T16;                  // full 16 x 16 tiles per dimension
-    constexpr bool M3G = T16 >= 3;                      // products in 3M form (mfma3): the 168-VGPR kernels
+    constexpr bool M3G = T16 >= 3;                      // products in 3M form (mfma3): the 168-VGPR kernels (the updates: rs_upd_3m)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ int flags[2 * RS_WAVES];                 // per wave: any(diff > conv), all(diff <= conv)
     __shared__ int pivrow[64], colof[64];
     __shared__ cplx rowline[RS_NB];                     // pivot row of the column step being factored
-    __shared__ unsigned la_cnt[2];                      // look-ahead counters of rs_inverse
-    unsigned la_epoch = 0;
-    if (threadIdx.x == 0) { la_cnt[0] = 0u; la_cnt[1] = 0u; }
 
     // job of this launch slot: in launch order, or -- when the provider has seen this grid before -- in
     // the order of decreasing sweep counts of the previous evaluation (the jobs differ by up to 20x in
     // length; started longest first, the last workgroups of the grid do not leave the chip idle).
     // Round robin (a.rr_quantum > 0): the slot is a persistent workgroup and takes its jobs from the queue.
     const int slot = blockIdx.y * gridDim.x + blockIdx.x;
-    constexpr bool rr = RS_RR && RR;
     __shared__ long long rr_msg;
     cplx* Ws = reinterpret_cast<cplx*>(smem_raw);       // [16*T16][P] (+ slack): g (start of a sweep), T, M, the reduced M
     const int tid = threadIdx.x, lane = tid & 63;
@@ -240,28 +221,16 @@ __device__ __forceinline__ void chain1d_rs_body(
     // ---- the job: set by next_job() below -- once, or (round robin) whenever this workgroup takes another one
     int job = 0, count = 0, c = 0, b = 0, n = 1, off = 0, ksteps = 1;
     bool resume = false;                                // a job that was set aside after `count` sweeps: its iterate waits in blk
-    const int fi = lane & 15, fk = lane >> 4;
-    // ---- the old iterate of the mixing step.  LIVE layout (RS_DENSE_MIX = 1): the dense lane map of chain_mix_map.h, see
-    // gather_mix_dense below; of the names that follow it uses a.gold and a.gold_lds_off only.  Both layouts keep their LDS
-    // part at element gold_lds_off of the dynamic LDS -- behind the work matrix when two workgroups share the CU; when
-    // three do, in the rows n_max+2 .. 16*T16-1 of the work matrix itself, which only feed discarded output rows of the
-    // padded tiles and may hold any finite values -- and the rest in global scratch [slot][thread] (coalesced); with the
-    // LDS part taken off, the scratch of the workgroups of an XCD fits its 4 MB L2 and is rewritten there sweep after sweep.
-    // LEGACY layout (RS_DENSE_MIX = 0, kept for A/B timing: gather_mix, gold_g, gold_l, LS_CT, lds_slots, and
-    // a.gold_lds_slots of the launcher): element (ks*4 + fk, wave*16 + fi) of g at slot ks of this lane; slot
-    // ks < gold_lds_slots in LDS as a compact matrix (pitch n), the other slots in global scratch.
-    cplx* gold_g = GOLD_GLOBAL ? a.gold + ((size_t)slot * KS) * RS_THREADS + tid : nullptr;
-    cplx* gold_l = Ws;
-    // (legacy layout) LDS slots of the old iterate: LS_CT (what fits when n = P, a compile-time number) or one more
-    constexpr int LS_FIT = (16 * T16 * P + 16 - (P + 2) * P) / (4 * P);
-    constexpr int LS_CT = GOLD_GLOBAL ? (LS_FIT > 0 ? LS_FIT : 0) : KS;
-    const int lds_slots = GOLD_GLOBAL ? a.gold_lds_slots : KS;
-
-    const cplx *alpha = a.alpha, *Salpha = a.Salpha, *beta = a.beta, *Sbeta = a.Sbeta, *tau = a.tau, *Stau = a.Stau;
-    // RS_PAD_LEADS: matrix k (0 alpha, 1 Salpha, 2 beta, 3 Sbeta, 4 tau, 5 Stau) of the job's contact, padded.  One base and
+    // ---- the old iterate of the mixing step lives on the dense lane map of chain_mix_map.h (gather_mix below).  Its LDS part
+    // sits at element a.gold_lds_off of the dynamic LDS -- behind the work matrix when two workgroups share the CU; when three
+    // do, in the rows n_max+2 .. 16*T16-1 of the work matrix itself, which only feed discarded output rows of the padded tiles
+    // and may hold any finite values -- and the rest in global scratch a.gold [slot][thread] (coalesced); with the LDS part
+    // taken off, the scratch of the workgroups of an XCD fits its 4 MB L2 and is rewritten there sweep after sweep.
+    const cplx *alpha = a.alpha, *Salpha = a.Salpha;    // (at pitch n: the start matrix A)
+    // the padded lead matrices: matrix k (0 alpha, 1 Salpha, 2 beta, 3 Sbeta, 4 tau, 5 Stau) of the job's contact, padded.  One base and
     // one stride stay live across the sweep, not six pointers
     const cplx* pad_c = a.pad; unsigned pad_ps = 0;
-    RsMixMap mm = rs_mix_map(1);                        // the job's lane map of the mixing step (RS_DENSE_MIX): scalars
+    RsMixMap mm = rs_mix_map(1);                        // the job's lane map of the mixing step: scalars
     bool final_pass = false;                            // the pass that runs Sigma = t g t^H through the two products
     auto lead_p = [&](int k) __attribute__((always_inline)) { return pad_c + (size_t)k * pad_ps; };
     cplx e = cmake(0.0, 0.0), z = e;
@@ -278,27 +247,24 @@ __device__ __forceinline__ void chain1d_rs_body(
     // (52-64 VGPRs that the three-workgroups-per-CU budget does not have): each product streams it from the
     // lead matrices, which every workgroup of the contact shares (L2 / L1 resident), PF k-steps ahead.
     // Rows >= n give garbage in output rows / columns >= n only (never stored); k >= n is zeroed.
-    // Padded lead matrices (PADL): a lane's element of k-step ks sits ks * 64 bytes behind its first one -- an immediate
+    // In the padded lead matrices a lane's element of k-step ks sits ks * 64 bytes behind its first one -- an immediate
     // offset, no clamp; rows and k >= n read zeros, and z * 0 - 0 is a zero of either sign, which multiplies finite
     // values and is added to an accumulator that starts at +0: no stored value depends on the sign.
-    constexpr bool PADL = RS_PAD_LEADS;
     constexpr int PF = 1;                           // k-steps the streamed operand is requested ahead: two named buffers
-    const cplx* opS = Sbeta; const cplx* opM = beta; cplx opz = z;     // (set per job and per pass; PADL: the padded matrices)
+    cplx opz = z;                                   // z of the sweeps, E (no eta) of the final pass
     struct Stream { cplx s[2], m[2]; };
     auto stream_row = [&](const cplx* op, int irow, int fk) __attribute__((always_inline)) {
-        return PADL ? op + (unsigned)(irow * CHAIN_PAD + fk) : op + min(irow, n - 1) * n;
+        return op + (unsigned)(irow * CHAIN_PAD + fk);
     };
-    auto stream_fetch = [&](Stream& q, const cplx* sS, const cplx* sM, int ks, int fk) __attribute__((always_inline)) {
-        const int kc = PADL ? ks * 4 : min(ks * 4 + fk, n - 1);
-        q.s[ks & 1] = sS[kc]; q.m[ks & 1] = sM[kc];
+    auto stream_fetch = [&](Stream& q, const cplx* sS, const cplx* sM, int ks) __attribute__((always_inline)) {
+        q.s[ks & 1] = sS[ks * 4]; q.m[ks & 1] = sM[ks * 4];
     };
-    auto stream_elem = [&](const Stream& q, int ks, int fk) __attribute__((always_inline)) {
-        const cplx v = csub(cmul(opz, q.s[ks & 1]), q.m[ks & 1]);
-        return PADL ? v : sel(ks * 4 + fk < n, v);
+    auto stream_elem = [&](const Stream& q, int ks) __attribute__((always_inline)) {
+        return csub(cmul(opz, q.s[ks & 1]), q.m[ks & 1]);
     };
     // k-steps of this job's products: in a remainder-strip class every contact reaches into the strip (the launcher's
     // class rule), n > 16 TR, so all KS k-steps run and the loops below carry no branch
-    const auto ksteps_of = [&]() __attribute__((always_inline)) { return (REM && PADL) ? KS : ksteps; };
+    const auto ksteps_of = [&]() __attribute__((always_inline)) { return REM ? KS : ksteps; };
 
     // wave w: acc[tj] = sum_k Op[w*16 + fi][k] * Ws[k][tj*16 + fi]  (row tile w of  Op Ws).  The padding of
     // Ws is zero / finite, output columns >= n are never stored.
@@ -308,12 +274,12 @@ __device__ __forceinline__ void chain1d_rs_body(
         const cplx* bb = Ws + fk * P + fi;
         const cplx* bb4 = Ws + fk * P + (fi & 3);       // column-strip B operand: column TR*16 + (l&3) in every block
         const int irow = strip_wave ? TR * 16 + (fi & 3) : wave * 16 + fi;
-        const cplx* sS = stream_row(PADL ? lead_p(final_pass ? 5 : 3) : opS, irow, fk);
-        const cplx* sM = stream_row(PADL ? lead_p(final_pass ? 4 : 2) : opM, irow, fk);
+        const cplx* sS = stream_row(lead_p(final_pass ? 5 : 3), irow, fk);
+        const cplx* sM = stream_row(lead_p(final_pass ? 4 : 2), irow, fk);
         const int ksteps = ksteps_of();
         Stream q;
 #pragma unroll
-        for (int ks = 0; ks < PF; ++ks) stream_fetch(q, sS, sM, ks, fk);
+        for (int ks = 0; ks < PF; ++ks) stream_fetch(q, sS, sM, ks);
 #pragma unroll
         for (int tj = 0; tj < T16; ++tj) { accr[tj] = (d4){0, 0, 0, 0}; acci[tj] = (d4){0, 0, 0, 0}; accc[tj] = (d4){0, 0, 0, 0}; }
         // the LDS operands (B fragments of the work matrix) of k-step ks+1 are requested in front of the matrix
@@ -328,9 +294,9 @@ __device__ __forceinline__ void chain1d_rs_body(
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             if (ks < ksteps) {
-                const cplx pa = stream_elem(q, ks, fk);
+                const cplx pa = stream_elem(q, ks);
                 const double ps = pa.x + pa.y;
-                if (ks + PF < KS) stream_fetch(q, sS, sM, ks + PF, fk);
+                if (ks + PF < KS) stream_fetch(q, sS, sM, ks + PF);
                 cplx (&qb)[T16] = qbuf[ks & 1];
                 if (ks + 1 < KS && ks + 1 < ksteps) load_qb(ks + 1, qbuf[(ks + 1) & 1]);
                 if (strip_wave) {
@@ -352,12 +318,12 @@ __device__ __forceinline__ void chain1d_rs_body(
         const cplx* ab = Ws + fi * P + fk;
         const cplx* ab4 = Ws + (fi & 3) * P + fk;       // row-strip A operand: row TR*16 + (l&3) in every block
         const int irow = strip_wave ? TR * 16 + (fi & 3) : wave * 16 + fi;
-        const cplx* sS = stream_row(PADL ? lead_p(final_pass ? 5 : 3) : opS, irow, fk);
-        const cplx* sM = stream_row(PADL ? lead_p(final_pass ? 4 : 2) : opM, irow, fk);
+        const cplx* sS = stream_row(lead_p(final_pass ? 5 : 3), irow, fk);
+        const cplx* sM = stream_row(lead_p(final_pass ? 4 : 2), irow, fk);
         const int ksteps = ksteps_of();
         Stream q;
 #pragma unroll
-        for (int ks = 0; ks < PF; ++ks) stream_fetch(q, sS, sM, ks, fk);
+        for (int ks = 0; ks < PF; ++ks) stream_fetch(q, sS, sM, ks);
 #pragma unroll
         for (int ti = 0; ti < T16; ++ti) { accr[ti] = (d4){0, 0, 0, 0}; acci[ti] = (d4){0, 0, 0, 0}; accc[ti] = (d4){0, 0, 0, 0}; }
         cplx pbuf[2][T16];                               // A fragments of the work matrix, double buffered (see gemm_rowtile)
@@ -370,9 +336,9 @@ __device__ __forceinline__ void chain1d_rs_body(
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             if (ks < ksteps) {
-                const cplx br = stream_elem(q, ks, fk);
+                const cplx br = stream_elem(q, ks);
                 const double bd = br.x - br.y;
-                if (ks + PF < KS) stream_fetch(q, sS, sM, ks + PF, fk);
+                if (ks + PF < KS) stream_fetch(q, sS, sM, ks + PF);
                 cplx (&pa)[T16] = pbuf[ks & 1];
                 if (ks + 1 < KS && ks + 1 < ksteps) load_pa(ks + 1, pbuf[(ks + 1) & 1]);
                 // pa * conj(b)
@@ -420,7 +386,7 @@ __device__ __forceinline__ void chain1d_rs_body(
         const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
         // a full tile of a remainder-strip class lies inside every contact of the launch (the launcher's class rule, as
         // rs_update_col assumes): stored without the test
-        const bool inside = RS_BATCH_MSTORE && REM && wave < TR;
+        const bool inside = REM && wave < TR;
 #pragma unroll
         for (int tj = 0; tj < T16; ++tj) {
             if (inside && tj < TR)
@@ -432,79 +398,9 @@ __device__ __forceinline__ void chain1d_rs_body(
         }
     };
     // g_new[k][col] = W[pivrow[k]][colof[col]] for this lane's elements; first: g = g_new, else the
-    // reference's mixing and stopping test (surfG1D.py:276-284).  Leaves g in Ws and in gold.
-    // (RS_DENSE_MIX = 0: the lane map of the tiles, element (ks*4 + fk, wave*16 + fi) at slot ks; the default is
-    //  gather_mix_dense below)
+    // reference's mixing and stopping test (surfG1D.py:276-284).  Leaves g in Ws and in the old iterate.
     int over = 1, allok = 0;
-    auto gather_mix = [&](bool first, unsigned long long* st) __attribute__((always_inline)) {
-        const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
-        const int col = wave * 16 + fi;
-        const bool colok = col < n;
-        const int colc = min(col, n - 1);               // every load below is unconditional, at a clamped (valid) address
-        const int* pvr = pivrow + fk;
-        cplx* gdst = Ws + fk * P + col;
-        cplx* gl = rs_opaque(gold_l) - col + colc;
-        cplx* gg = GOLD_GLOBAL ? rs_opaque(gold_g) : nullptr;
-        // slot ks of the old iterate lives in LDS?  compile-time below / above LS_CT, wave-uniform at LS_CT
-        auto in_lds = [&](int ks) { return !GOLD_GLOBAL || ks < LS_CT || (ks == LS_CT && lds_slots > LS_CT); };
-        // element (ks*4 + fk, col) exists?  with a remainder strip all k-steps below 4 TR hold rows < 16 TR < n
-        auto valid = [&](int ks) { return colok && ((REM && ks * 4 + 3 < 16 * TR) || ks * 4 + fk < n); };
-        // All requests of the phase go out in three batches -- pivot indices, old iterate (global scratch: the
-        // longest latency, requested before the gathers), gathered new iterate -- instead of slot by slot: the
-        // phase is three dependent round trips long, not thirteen.
-        int pr[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) pr[ks] = ks < ksteps ? pvr[ks * 4] : 0;
-        const int cfc = colof[colc];
-        const cplx* gsrc = Ws + cfc;
-        cplx go[KS], gm[KS];
-        if (!first) {
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-                if (ks < ksteps) go[ks] = in_lds(ks) ? gl[ks * 4 * n] : gg[ks * RS_THREADS];
-        }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) gm[ks] = ks < ksteps ? gsrc[pr[ks] * P] : cmake(0.0, 0.0);
-        if (st && tid == 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st[5] = __builtin_amdgcn_s_memrealtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st[6] = __builtin_amdgcn_s_memrealtime(); }
-        bool lane_over = false, lane_ok = true;
-        if (!first) {
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                if (ks < ksteps) {
-                    const cplx gn = gm[ks];
-                    const double dx = gn.x - go[ks].x, dy = gn.y - go[ks].y;
-                    const double num2 = dx * dx + dy * dy;
-                    const double den2 = fmax(gn.x * gn.x + gn.y * gn.y, 1e-24);
-                    const bool v = valid(ks);
-                    lane_over |= v && num2 > conv2 * den2;
-                    lane_ok &= !v || num2 <= conv2 * den2;
-                    gm[ks] = cmake(gn.x * rf + go[ks].x * rf1, gn.y * rf + go[ks].y * rf1);
-                }
-            }
-        }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-            if (ks < ksteps && valid(ks)) { if (in_lds(ks)) gl[ks * 4 * n] = gm[ks]; else gg[ks * RS_THREADS] = gm[ks]; }
-        if (!first) {
-            const bool w_over = __ballot(lane_over) != 0ull;
-            const bool w_ok = __ballot(!lane_ok) == 0ull;
-            if (lane == 0) { flags[wave] = w_over ? 1 : 0; flags[RS_WAVES + wave] = w_ok ? 1 : 0; }
-        }
-        if (st && tid == 0) st[7] = __builtin_amdgcn_s_memrealtime();
-        __syncthreads();                                // all gathers done: Ws may be overwritten
-        if (st && tid == 0) st[40] = __builtin_amdgcn_s_memrealtime();
-        if (tid < 64) colof[tid] = -1;                  // for the next inverse (every lane has read its colof)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-            if (ks < ksteps && valid(ks)) gdst[ks * 4 * P] = gm[ks];
-        if (!first) {
-            over = flags[0] | flags[1] | flags[2] | flags[3];
-            allok = flags[4] & flags[5] & flags[6] & flags[7];
-        }
-        __syncthreads();
-    };
-
-    // ---- the same on the dense lane map (chain_mix_map.h): lane t < RG n holds column t mod n of the rows t / n + RG s.
+    // The dense lane map (chain_mix_map.h): lane t < RG n holds column t mod n of the rows t / n + RG s.
     // Slot s of the old iterate lives at [s][t]: the first MLS slots in LDS (the spare rows of the work matrix, 256 lanes
     // per slot; every slot as the compact n x n matrix behind the work matrix when two workgroups share the CU), the others
     // in the global scratch record.  Two loops in two address spaces -- no generic pointer --, the global requests first,
@@ -522,10 +418,10 @@ __device__ __forceinline__ void chain1d_rs_body(
         return rs_scalar_base(a.gold + (size_t)slot * KS * RS_THREADS);
     };
     constexpr unsigned GSLOT = RS_THREADS * sizeof(cplx);       // bytes of a slot of the record
-    // (RS_LAZY_STOP; the three-per-CU instantiations of the four-tile classes 57 and 65 keep the full test: their work matrix never
+    // the lazy stopping test (see gather_mix; the three-per-CU instantiations of the four-tile classes 57 and 65 keep the full test: their work matrix never
     //  fits a CU three times, so they are never launched, and with the branch their 64 - 84 bytes of scratch grow by 4 - 8)
-    constexpr bool LAZY = RS_LAZY_STOP && !(T16 == 4 && OCC == 3);
-    auto gather_mix_dense = [&](bool first, unsigned long long* st) __attribute__((always_inline)) {
+    constexpr bool LAZY = !(T16 == 4 && OCC == 3);
+    auto gather_mix = [&](bool first, unsigned long long* st) __attribute__((always_inline)) {
         const int t = rs_opaque(tid);
         const int rg0 = (int)(((unsigned)t * mm.rcp) >> 16);
         const bool active = rg0 < mm.rg;
@@ -553,7 +449,7 @@ __device__ __forceinline__ void chain1d_rs_body(
         if (st && tid == 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st[5] = __builtin_amdgcn_s_memrealtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st[6] = __builtin_amdgcn_s_memrealtime(); }
         bool lane_over = false, lane_ok = true;
         if (!first) {
-            // The stopping test by wave (RS_LAZY_STOP).  All it feeds are the wave's two flags: over = any element over, ok = every
+            // The stopping test by wave (LAZY).  All it feeds are the wave's two flags: over = any element over, ok = every
             // element ok.  A lane that is over on its slot 0 (an LDS slot, valid in every active lane) settles both -- its
             // element is valid and not ok --, so the wave then skips the test of its other slots: the common case, a fixed
             // point is over in every sweep but its last few.  No lane over on slot 0 (NaN elements are neither over nor
@@ -567,7 +463,7 @@ __device__ __forceinline__ void chain1d_rs_body(
                 }
 #pragma unroll
                 for (int s = 0; s < MS; ++s) if (on(s)) gm[s] = rs_mix(gm[s], go[s], rf, rf1);
-            } else {                                    // (0, for A/B timing: every slot tested and mixed in turn)
+            } else {                                    // (every slot tested and mixed in turn)
 #pragma unroll
                 for (int s = 0; s < MS; ++s) if (on(s)) { test(s); gm[s] = rs_mix(gm[s], go[s], rf, rf1); }
             }
@@ -598,7 +494,7 @@ __device__ __forceinline__ void chain1d_rs_body(
         __syncthreads();
     };
     // a job that was set aside continues: its old iterate is the iterate itself (gather_mix leaves the mixed g in both places)
-    auto resume_old_dense = [&]() __attribute__((always_inline)) {
+    auto resume_old = [&]() __attribute__((always_inline)) {
         const int t = rs_opaque(tid);
         const int rg0 = (int)(((unsigned)t * mm.rcp) >> 16);
         const bool active = rg0 < mm.rg;
@@ -620,7 +516,7 @@ __device__ __forceinline__ void chain1d_rs_body(
     bool first = true, skip = false;
     int q_end = 0;
     auto next_job = [&]() __attribute__((always_inline)) -> bool {
-        if (rr) {
+        if (RR) {
             if (tid == 0) rr_msg = rs_rr_pop(a.rr_q, a.order);
             __syncthreads();                            // (also: every wave is done with the LDS of the previous job)
             const long long ent = rr_msg;
@@ -633,16 +529,12 @@ __device__ __forceinline__ void chain1d_rs_body(
         resume = count > 0;
         c = job % a.n_contacts; b = job / a.n_contacts;
         n = a.nc[c]; off = a.blk_off[c]; ksteps = (n + 3) >> 2;
-        if (!RS_DENSE_MIX) gold_l = Ws + a.gold_lds_off + fk * n + wave * 16 + fi;     // (legacy layout)
-        alpha = a.alpha + off; Salpha = a.Salpha + off; beta = a.beta + off; Sbeta = a.Sbeta + off;
-        tau = a.tau + off; Stau = a.Stau + off;
-        if (RS_DENSE_MIX) mm = rs_mix_map(n);
-        if (RS_PAD_LEADS) {                             // (alpha, Salpha at pitch n still give the start A below)
-            pad_c = a.pad + (size_t)c * (CHAIN_PAD * CHAIN_PAD); pad_ps = (unsigned)a.n_contacts * (CHAIN_PAD * CHAIN_PAD);
-        }
+        alpha = a.alpha + off; Salpha = a.Salpha + off;
+        mm = rs_mix_map(n);
+        pad_c = a.pad + (size_t)c * (CHAIN_PAD * CHAIN_PAD); pad_ps = (unsigned)a.n_contacts * (CHAIN_PAD * CHAIN_PAD);
         e = E[b]; z = cmake(e.x, e.y + a.eta);
-        if (RS_PAD_LEADS) { e = cmake(rs_uniform(e.x), rs_uniform(e.y)); z = cmake(rs_uniform(z.x), rs_uniform(z.y)); }   // (the same for every lane: scalar registers)
-        opS = Sbeta; opM = beta; opz = z;
+        e = cmake(rs_uniform(e.x), rs_uniform(e.y)); z = cmake(rs_uniform(z.x), rs_uniform(z.y));   // (the same for every lane: scalar registers)
+        opz = z;
         over = 1; allok = 0;
         first = !resume; skip = resume; final_pass = false;
         q_end = count + a.rr_quantum;
@@ -663,20 +555,7 @@ __device__ __forceinline__ void chain1d_rs_body(
         if (resume) {
             // the old iterate of the mixing step is the iterate itself (gather_mix leaves the mixed g in both places)
             __syncthreads();
-            if (RS_DENSE_MIX) resume_old_dense();
-            else {                                      // (legacy layout)
-                const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
-                const int col = wave * 16 + fi;
-                cplx* gl = rs_opaque(gold_l);
-                cplx* gg = GOLD_GLOBAL ? rs_opaque(gold_g) : nullptr;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    if (ks < ksteps && col < n && ks * 4 + fk < n) {
-                        const cplx v = Ws[(ks * 4 + fk) * P + col];
-                        if (!GOLD_GLOBAL || ks < LS_CT || (ks == LS_CT && lds_slots > LS_CT)) gl[ks * 4 * n] = v; else gg[ks * RS_THREADS] = v;
-                    }
-                }
-            }
+            resume_old();
         }
         if (tid < 64) { colof[tid] = -1; pivrow[tid] = 0; }
         __syncthreads();
@@ -696,13 +575,13 @@ __device__ __forceinline__ void chain1d_rs_body(
         unsigned long long* st = (RS_STAMPS && a.stamps && job == 0 && count == a.stamp_sweep) ? a.stamps : nullptr;
         if (st && tid == 0) st[0] = __builtin_amdgcn_s_memrealtime();
         if (!gc_hit && !skip) {
-            // a remainder-strip class: the compile-time stage schedule (RS_STAGE_SCHED); else, and with the roles by wave number, the generic loop
+            // a remainder-strip class: the compile-time stage schedule; else, and with the roles by wave number, the generic loop
             // (role 3 factors whether the roles follow the SIMDs or, two waves having reported the same one, the wave numbers)
             if constexpr (SCHED && REM && rs_stage_sched(REM ? TR : -1)) rs_inverse_sched<T16, P, TR>(n, Ws, pivrow, colof, rowline, tid, wave, st ? st + 8 : nullptr);
             else
-            rs_inverse<T16, P, REM ? TR : -1>(n, Ws, pivrow, colof, rowline, tid, wave, chain_roles, la_cnt, la_epoch, st ? st + 8 : nullptr);   // st + 8: stage stamps, st + 24: factor
+            rs_inverse<T16, P, REM ? TR : -1>(n, Ws, pivrow, colof, rowline, tid, wave, chain_roles, st ? st + 8 : nullptr);   // st + 8: stage stamps, st + 24: factor
             if (st && tid == 0) st[1] = __builtin_amdgcn_s_memrealtime();
-            if (!(RS_ABLATE & 8) || first) { if (RS_DENSE_MIX) gather_mix_dense(first, st); else gather_mix(first, st); }
+            if (!(RS_ABLATE & 8) || first) gather_mix(first, st);
             else { if (tid < 64) colof[tid] = -1; __syncthreads(); }
             if (st && tid == 0) st[2] = __builtin_amdgcn_s_memrealtime();
             if (!first) ++count;
@@ -712,12 +591,12 @@ __device__ __forceinline__ void chain1d_rs_body(
             skip = false;
         } else if (gc_hit || (a.force_iters >= 0 ? count >= a.force_iters : !(over && count < a.max_iter))) {
             final_pass = true;
-            opS = Stau; opM = tau; opz = e;
+            opz = e;
             if (a.gc_mode == 1) {                       // a miss leaves its final iterate in the cache (g sits in Ws, complete
                 cplx* gcj = a.gcache + (size_t)b * a.blk_stride + off;                              //  since the barrier that ends gather_mix)
                 for (int t = tid; t < n * n; t += RS_THREADS) { const int i = t / n; gcj[t] = Ws[i * P + (t - i * n)]; }
             }
-        } else if (__builtin_expect(rr && count >= q_end, 0)) {
+        } else if (__builtin_expect(RR && count >= q_end, 0)) {
             // the quantum is over.  Nobody waiting: carry on.  Otherwise the iterate goes to the job's output block (g sits in
             // Ws, complete since the barrier that ends gather_mix), the job to the back of the queue, and this workgroup
             // takes the job at the front
@@ -760,85 +639,71 @@ __device__ __forceinline__ void chain1d_rs_body(
                 if (iters) iters[(size_t)b * a.n_contacts + c] = count;
                 if (converged) converged[(size_t)b * a.n_contacts + c] = (count > 0 && allok) ? 1 : 0;
             }
-            if (!rr) break;
+            if (!RR) break;
             need_job = true;
             continue;
         }
         __syncthreads();
         // M = A - T B^H.  With the padded alpha, Salpha no load needs the store's guard: the (up to) eight loads of a
         // row tile go out together and are consumed in order as they arrive (a ladder of vmcnt waits, one round trip per
-        // tile); those of tile ti + 1 go out after tile ti is stored (before it with RS_MSTORE_AHEAD = 1, which spills)
-        if (RS_BATCH_MSTORE && RS_PAD_LEADS) {
-            // SC: this wave's column tile is the column strip (its tiles ti < TR use the strip's lane map, see for_tile).
-            // Every element is a compile-time row offset from one lane base, in the padded alpha / Salpha and in Ws.
-            // Tests: none for a full tile of a remainder-strip class (inside every contact of the launch by the launcher's
-            // class rule), the strip's own rows / columns against n; every element in the other classes.
-            auto mstore = [&](auto sc) __attribute__((always_inline)) {
-                constexpr bool SC = decltype(sc)::value;
-                const int ljn = wave * 16 + fis, lis = 4 * (fis >> 2) + fks, ljs = TR * 16 + (fis & 3);
-                const unsigned lon = (unsigned)(fks * CHAIN_PAD + ljn), los = (unsigned)(lis * CHAIN_PAD + ljs);
-                cplx* wn = Ws + fks * P + ljn;
-                cplx* wsc = Ws + lis * P + ljs;
-                auto smap = [](int ti) { return SC && ti < TR; };
-                auto nel = [&](int ti) { return smap(ti) || (REM && ti == TR) ? 1 : 4; };
-                auto rowc = [&](int ti, int r) { return ti * 16 + (smap(ti) ? 0 : 4 * r); };
-                cplx as[2][4], aa[2][4];
-                const unsigned long long bS = rs_scalar_base(lead_p(1)), bA = rs_scalar_base(lead_p(0));
-                const unsigned lbn = lon * (unsigned)sizeof(cplx), lbs = los * (unsigned)sizeof(cplx);
-                unsigned long long curS = bS, curA = bA;        // the bases at row cur_row
-                int cur_row = 0;
-                auto load_a = [&](int ti, cplx (&s)[4], cplx (&m)[4]) __attribute__((always_inline)) {
+        // tile); those of tile ti + 1 go out after tile ti is stored (requested before it they spill: 39 VGPRs in <51,3,true,false>)
+        // SC: this wave's column tile is the column strip (its tiles ti < TR use the strip's lane map, see for_tile).
+        // Every element is a compile-time row offset from one lane base, in the padded alpha / Salpha and in Ws.
+        // Tests: none for a full tile of a remainder-strip class (inside every contact of the launch by the launcher's
+        // class rule), the strip's own rows / columns against n; every element in the other classes.
+        auto mstore = [&](auto sc) __attribute__((always_inline)) {
+            constexpr bool SC = decltype(sc)::value;
+            const int ljn = wave * 16 + fis, lis = 4 * (fis >> 2) + fks, ljs = TR * 16 + (fis & 3);
+            const unsigned lon = (unsigned)(fks * CHAIN_PAD + ljn), los = (unsigned)(lis * CHAIN_PAD + ljs);
+            cplx* wn = Ws + fks * P + ljn;
+            cplx* wsc = Ws + lis * P + ljs;
+            auto smap = [](int ti) { return SC && ti < TR; };
+            auto nel = [&](int ti) { return smap(ti) || (REM && ti == TR) ? 1 : 4; };
+            auto rowc = [&](int ti, int r) { return ti * 16 + (smap(ti) ? 0 : 4 * r); };
+            cplx as[4], aa[4];
+            const unsigned long long bS = rs_scalar_base(lead_p(1)), bA = rs_scalar_base(lead_p(0));
+            const unsigned lbn = lon * (unsigned)sizeof(cplx), lbs = los * (unsigned)sizeof(cplx);
+            unsigned long long curS = bS, curA = bA;        // the bases at row cur_row
+            int cur_row = 0;
+            auto load_a = [&](int ti, cplx (&s)[4], cplx (&m)[4]) __attribute__((always_inline)) {
 #pragma unroll
-                    for (int r = 0; r < nel(ti); ++r) {
-                        const unsigned lb = smap(ti) ? lbs : lbn;
-                        const long long adv = (long long)(rowc(ti, r) - cur_row) * CHAIN_PAD * (long long)sizeof(cplx);
-                        if (adv) { curS = rs_scalar_advance(curS, adv); curA = rs_scalar_advance(curA, adv); cur_row = rowc(ti, r); }
-                        s[r] = rs_gload(curS, 0, lb); m[r] = rs_gload(curA, 0, lb);
-                    }
-                };
-                load_a(0, as[0], aa[0]);
-                // T B^H out of the 3M sums first, in place: two values per element are live beside the A buffers, not three
-                if (M3G) {
-#pragma unroll
-                    for (int ti = 0; ti < T16; ++ti)
-#pragma unroll
-                        for (int r = 0; r < nel(ti); ++r) {
-                            const double va = mr[ti][r], vb = mi[ti][r], vc = mc[ti][r];
-                            mr[ti][r] = va + vb; mi[ti][r] = vc - va + vb;
-                        }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int ti = 0; ti < T16; ++ti) {
-                    if (RS_MSTORE_AHEAD && ti + 1 < T16) load_a(ti + 1, as[(ti + 1) & 1], aa[(ti + 1) & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    const cplx (&s)[4] = as[RS_MSTORE_AHEAD ? ti & 1 : 0];
-                    const cplx (&m)[4] = aa[RS_MSTORE_AHEAD ? ti & 1 : 0];
-#pragma unroll
-                    for (int r = 0; r < nel(ti); ++r) {
-                        const double re = mr[ti][r], im = mi[ti][r];
-                        const cplx av = csub(cmul(z, s[r]), m[r]);
-                        const int i = rowc(ti, r) + (smap(ti) ? lis : fks), j = smap(ti) ? ljs : ljn;
-                        const bool ok = !REM ? (i < n && j < n) : ((ti < TR || i < n) && (!SC || j < n));
-                        if (ok) (smap(ti) ? wsc : wn)[rowc(ti, r) * P] = cmake(av.x - re, av.y - im);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (!RS_MSTORE_AHEAD && ti + 1 < T16) load_a(ti + 1, as[0], aa[0]);
+                for (int r = 0; r < nel(ti); ++r) {
+                    const unsigned lb = smap(ti) ? lbs : lbn;
+                    const long long adv = (long long)(rowc(ti, r) - cur_row) * CHAIN_PAD * (long long)sizeof(cplx);
+                    if (adv) { curS = rs_scalar_advance(curS, adv); curA = rs_scalar_advance(curA, adv); cur_row = rowc(ti, r); }
+                    s[r] = rs_gload(curS, 0, lb); m[r] = rs_gload(curA, 0, lb);
                 }
             };
-            if (!REM || wave < TR) mstore(std::false_type{});
-            else if (wave == TR) mstore(std::true_type{});
-            // (a remainder-strip class's wave > TR owns no column of the matrix)
-        } else {
+            load_a(0, as, aa);
+            // T B^H out of the 3M sums first, in place: two values per element are live beside the A buffers, not three
+            if (M3G) {
+#pragma unroll
+                for (int ti = 0; ti < T16; ++ti)
+#pragma unroll
+                    for (int r = 0; r < nel(ti); ++r) {
+                        const double va = mr[ti][r], vb = mi[ti][r], vc = mc[ti][r];
+                        mr[ti][r] = va + vb; mi[ti][r] = vc - va + vb;
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int ti = 0; ti < T16; ++ti) {
-                for_tile(ti, wave, mr[ti], mi[ti], mc[ti], true, fis, fks, [&](int r, int i, int j, double re, double im) {
-                    const cplx av = Aat(i, j);
-                    if (i < n && j < n) Ws[i * P + j] = cmake(av.x - re, av.y - im);
-                });
-                __builtin_amdgcn_sched_barrier(0);      // the A elements of one tile in flight, not of all
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int r = 0; r < nel(ti); ++r) {
+                    const double re = mr[ti][r], im = mi[ti][r];
+                    const cplx av = csub(cmul(z, as[r]), aa[r]);
+                    const int i = rowc(ti, r) + (smap(ti) ? lis : fks), j = smap(ti) ? ljs : ljn;
+                    const bool ok = !REM ? (i < n && j < n) : ((ti < TR || i < n) && (!SC || j < n));
+                    if (ok) (smap(ti) ? wsc : wn)[rowc(ti, r) * P] = cmake(av.x - re, av.y - im);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (ti + 1 < T16) load_a(ti + 1, as, aa);
             }
-        }
+        };
+        if (!REM || wave < TR) mstore(std::false_type{});
+        else if (wave == TR) mstore(std::true_type{});
+        // (a remainder-strip class's wave > TR owns no column of the matrix)
         __syncthreads();
         if (st && tid == 0) st[4] = __builtin_amdgcn_s_memrealtime();
     }
@@ -909,13 +774,9 @@ void chain1d_rs_launch(hipStream_t st, ChainRsArgs a, int n_max, int n_contacts,
     // (allocated in granules of 1280 bytes: 53.8 KB per workgroup is the most that still fits three times)
     auto fits = [](size_t smem, int per_cu) { return ((smem + 832 + 1279) / 1280) * 1280 * per_cu <= 160 * 1024; };
     // old iterate behind the work matrix (all slots in LDS) ...
-    ChainRsArgs al = a; al.gold_lds_off = 16 * T16 * P + 16; al.gold_lds_slots = 1 << 20;
+    ChainRsArgs al = a; al.gold_lds_off = 16 * T16 * P + 16;
     // ... or its first slots in the unused rows n_max+2 .. of the work matrix, the rest in global scratch
     ChainRsArgs ag = a; ag.gold_lds_off = (n_max + 2) * P;
-    // (gold_lds_slots serves the legacy layout of RS_DENSE_MIX = 0 only: the dense map fixes its LDS slots at compile time)
-    constexpr int LS_FIT = (16 * T16 * P + 16 - (P + 2) * P) / (4 * P);      // the kernel's LS_CT
-    ag.gold_lds_slots = std::min(std::max(0, (16 * T16 * P + 16 - ag.gold_lds_off) / (4 * n_max)), std::max(LS_FIT, 0) + 1);
-    if (ag.gold_lds_slots < std::max(LS_FIT, 0)) ag.gold_lds_slots = 0;       // (cannot happen: n_max <= P)
     static int n_cus = 0;
     if (!n_cus) {
         int dev = 0; hipDeviceProp_t prop;
@@ -931,7 +792,7 @@ void chain1d_rs_launch(hipStream_t st, ChainRsArgs a, int n_max, int n_contacts,
         // an order or with one predicted from too few points (order_trusted) -- unless the caller set the quantum
         // himself (negf_set_chain_round_robin: tests, A/B).
         const int jobs = n_contacts * nb, slots = rr_slots > 0 ? std::min(rr_slots, occ * n_cus) : occ * n_cus;
-        const bool rr = RS_RR && aa.rr_quantum > 0 && jobs > slots && (aa.order == nullptr || rr_forced);
+        const bool rr = aa.rr_quantum > 0 && jobs > slots && (aa.order == nullptr || rr_forced);
         if (rr) {
             hipLaunchKernelGGL(rs_rr_init_kernel, dim3((rr_cap + 255) / 256), dim3(256), 0, st, aa.rr_q, rr_cap, (unsigned)jobs);
             grid = dim3(slots, 1);
@@ -947,8 +808,8 @@ void chain1d_rs_launch(hipStream_t st, ChainRsArgs a, int n_max, int n_contacts,
         if (rr) go(kern_rr); else go(kern);
     };
     constexpr int OCC_MAX = T16 <= 2 ? 4 : 3;          // register budget: 128 VGPRs (T16 <= 2), 168 above
-    // a strip class launched with the roles by wave number runs the kernels with the generic inverse (RS_STAGE_SCHED)
-    constexpr bool STRIPS = RS_REMAINDER && T16 >= 2 && P - 16 * (T16 - 1) <= 4;
+    // a strip class launched with the roles by wave number runs the kernels with the generic inverse
+    constexpr bool STRIPS = T16 >= 2 && P - 16 * (T16 - 1) <= 4;
     if constexpr (STRIPS && rs_stage_sched(T16 - 1)) {
         if (!a.simd_roles) {
             if (occ_env != 2 && fits(wmat + gold_lds, OCC_MAX)) launch(chain1d_rs_wn_kernel<P, OCC_MAX, false, false>, chain1d_rs_wn_kernel<P, OCC_MAX, false, true>, wmat + gold_lds, OCC_MAX);

@@ -7,7 +7,12 @@ they were: a product that is fused into another multiply-add shows as a changed 
 Blocks without such an instruction are left out, the others are compared in order, each as a sorted list (the scheduler
 may order independent instructions of a block differently).  Verdict per kernel: `same` (block by block), `same multiset`
 (the blocks are cut differently, the kernel's instructions together are the same) or `DIFFERENT` with the difference.
-Exit status 1 when a kernel is DIFFERENT or missing on one side."""
+Exit status 1 when a kernel is DIFFERENT or missing on one side.
+    python scripts/isa_fp64_compare.py --census old.s new.s
+prints instead what a refactoring must also leave alone: per kernel the resources of its descriptor (next_free_vgpr, accum_offset,
+private_segment_fixed_size, group_segment_fixed_size) and the instruction counts by class -- matrix, LDS, vector memory, which
+must not move; vector and scalar ALU, which spill placement may move --, the kernels that differ with old -> new per figure.
+Exit status 1 when a resource or a matrix / LDS / vector-memory count differs."""
 import collections
 import re
 import sys
@@ -62,7 +67,54 @@ def kernels(path):
     return out
 
 
+RESOURCES = ("next_free_vgpr", "accum_offset", "private_segment_fixed_size", "group_segment_fixed_size")
+CLASSES = (("matrix", ("v_mfma",)), ("lds", ("ds_",)), ("vmem", ("global_", "scratch_", "buffer_", "flat_")), ("valu", ("v_",)),
+           ("salu", ("s_",)))
+FIXED = RESOURCES + ("matrix", "lds", "vmem")
+
+
+def census(path):
+    """{kernel name: {resource or instruction class: number}}"""
+    out, name, desc = {}, None, None
+    for line in open(path):
+        t = line.strip()
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            name = m.group(1)
+            out[name] = collections.Counter()
+        elif t.startswith(".Lfunc_end"):
+            name = None
+        elif t.startswith(".amdhsa_kernel "):
+            desc = t.split()[1]
+        elif t.startswith(".end_amdhsa_kernel"):
+            desc = None
+        elif desc and t.startswith(".amdhsa_") and t.split()[0][8:] in RESOURCES:
+            out[desc][t.split()[0][8:]] = int(t.split()[1])
+        elif name and t and t[0] not in ";." and not t.endswith(":"):
+            op = t.split()[0]
+            out[name][next((c for c, pre in CLASSES if op.startswith(pre)), "other")] += 1
+    return out
+
+
+def main_census(old, new):
+    bad = moved = 0
+    for k in sorted(set(old) | set(new)):
+        if k not in old or k not in new:
+            print("MISSING", "in old:" if k not in old else "in new:", k)
+            bad += 1
+            continue
+        diff = [f for f in FIXED + ("valu", "salu", "other") if old[k][f] != new[k][f]]
+        if diff:
+            moved += 1
+            print(k + ":", ", ".join(f"{f} {old[k][f]} -> {new[k][f]}" for f in diff))
+            bad += any(f in FIXED for f in diff)
+    print(f"kernels: {len(new)}, equal in every figure: {len(new) - moved}, moved: {moved}, resources or fixed classes differ: {bad}")
+    return 1 if bad else 0
+
+
 def main():
+    if sys.argv[1] == "--census":
+        return main_census(census(sys.argv[2]), census(sys.argv[3]))
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
     bad = 0
     tally = collections.Counter()

@@ -1,5 +1,5 @@
 """
-The half-tile updates of the chain kernels' small inverse (chain_rs_inverse.h, RS_HALF_STRIPS): with panels of 8 columns
+The half-tile updates of the chain kernels' small inverse (chain_rs_inverse.h, rs_half_strips): with panels of 8 columns
 the look-ahead, the other half of the panel's own column tile and the other half of the next tile update 8 columns of
 a 16-column tile, as two 16 x 4 column strips on the 4x4x4 matrix instruction.  Which of them a sweep runs, and where
 the ragged last panel falls back to the whole tile, depends on n_c alone, so the sizes are swept one by one:

@@ -1,5 +1,5 @@
 """
-The stopping test of the chain fixed-point kernel (k_chain1d_rs.hip, gather_mix_dense) run by wave -- slot 0 of every
+The stopping test of the chain fixed-point kernel (k_chain1d_rs.hip, gather_mix) run by wave -- slot 0 of every
 lane first, the other slots only when no lane of the wave is over on it -- and the pinned arithmetic of the mixing step
 and of the stage schedule's factoring, against what the commit before them computed:
 tests/golden/chain_lazy_stop_parent.npz, recorded on the GPU by scripts/gen_chain_lazy_stop_fixture.py from a build of

@@ -1,5 +1,5 @@
 """
-The compile-time stage schedule of the chain kernel's small inverse (chain_rs_inverse.h: rs_inverse_sched, RS_STAGE_SCHED;
+The compile-time stage schedule of the chain kernel's small inverse (chain_rs_inverse.h: rs_inverse_sched, rs_stage_sched;
 the job table of chain_rs_sched.h) against the generic loop of the same build.  The schedule changes control flow, guards
 and addressing only -- every stored element comes from the same operations on the same operands in the same order -- so
 Sigma blocks, sweep counts and flags are compared with np.array_equal.  The generic loop runs in the launches with the
