@@ -6,6 +6,9 @@
 //   rgf_gamma     : Gamma = i (Sigma - Sigma^H) on a terminal's K x K block
 //   rgf_dos_*     : -Im G_rr / pi, and the rows of -Im (G S) / pi block by block
 //   rgf_accumulate: acc += sum_b w_b X_b, b ascending in ONE chain per element (bitwise independent of the batch cut)
+//   rgf_gather_cols / rgf_gamma_union / rgf_accumulate_ct / rgf_pop_*: the passes of G Gamma G^H on the pattern of S
+//                   (negf_layered_gless_int, negf_layered_contact_dos): the columns G[:, J] of a terminal set, its Gamma
+//                   on the union list J, the conjugate-transposed sum of the lower blocks, the contact Mulliken rows
 // Every matrix of a batch is compact row-major (leading dimension = its own column count) at a batch stride the
 // caller gives; consecutive lanes touch consecutive 16-byte elements.  No atomics.
 #include "negf_common.h"
@@ -205,6 +208,143 @@ void launch_rgf_accumulate(hipStream_t st, int count, int nb, const cplx* w, con
     if (count <= 0 || nb <= 0) return;
     hipLaunchKernelGGL(rgf_accumulate_kernel, dim3((count + RGF_THREADS - 1) / RGF_THREADS), dim3(RGF_THREADS), 0, st,
                        count, nb, w, X, strideX, acc);
+}
+
+// out[b][r][a] = G[b][r][idx[a]]: the K columns `idx` of an n x n matrix, compact n x K
+__global__ __launch_bounds__(RGF_THREADS) void rgf_gather_cols_kernel(
+    int n, int K, const cplx* __restrict__ G, size_t strideG, const int* __restrict__ idx, cplx* __restrict__ out,
+    size_t stride_out)
+{
+    const int b = blockIdx.y;
+    const cplx* g = G + (size_t)b * strideG;
+    cplx* o = out + (size_t)b * stride_out;
+    const int cnt = n * K;
+    for (int t = blockIdx.x * RGF_THREADS + threadIdx.x; t < cnt; t += gridDim.x * RGF_THREADS) {
+        const int r = t / K, a = t - r * K;
+        o[t] = g[(size_t)r * n + idx[a]];
+    }
+}
+
+void launch_rgf_gather_cols(hipStream_t st, int n, int K, int nb, const cplx* G, size_t strideG, const int* idx, cplx* out,
+                            size_t stride_out)
+{
+    hipLaunchKernelGGL(rgf_gather_cols_kernel, dim3(rgf_grid((size_t)n * K), nb), dim3(RGF_THREADS), 0, st, n, K, G,
+                       strideG, idx, out, stride_out);
+}
+
+// out[b][p][q] = sum over the terminals k, in their order, of Gamma_k[pos_k[J[p]]][pos_k[J[q]]] where both lie in terminal
+// k's list; Gamma_k = i (Sigma_k - Sigma_k^H) element by element as rgf_gamma forms it
+__global__ __launch_bounds__(RGF_THREADS) void rgf_gamma_union_kernel(
+    int KJ, const int* __restrict__ J, RgfTermArgs t, cplx* __restrict__ out, size_t stride_out)
+{
+    const int b = blockIdx.y;
+    cplx* o = out + (size_t)b * stride_out;
+    for (int e = blockIdx.x * RGF_THREADS + threadIdx.x; e < KJ * KJ; e += gridDim.x * RGF_THREADS) {
+        const int p = e / KJ, q = e - p * KJ;
+        const int jp = J[p], jq = J[q];
+        cplx v = cmake(0.0, 0.0);
+        for (int k = 0; k < t.count; ++k) {
+            const int i = t.pos[k][jp], j = t.pos[k][jq];
+            if (i < 0 || j < 0) continue;
+            const cplx* s = t.sig[k] + (size_t)b * t.stride[k];
+            const cplx a = s[(size_t)i * t.K[k] + j], c = s[(size_t)j * t.K[k] + i];
+            v = cadd(v, cmake(-(a.y + c.y), a.x - c.x));
+        }
+        o[e] = v;
+    }
+}
+
+void launch_rgf_gamma_union(hipStream_t st, int KJ, int nb, const int* J, const RgfTermArgs& t, cplx* out, size_t stride_out)
+{
+    hipLaunchKernelGGL(rgf_gamma_union_kernel, dim3(rgf_grid((size_t)KJ * KJ), nb), dim3(RGF_THREADS), 0, st, KJ, J, t, out,
+                       stride_out);
+}
+
+// acc[c][r] += sum_b w_b conj(X_b[r][c]) (X nr x nc, acc nc x nr), b ascending in one chain per element.  A 16 x 16 tile
+// goes through LDS so that the read of X and the write of acc both run along rows; the tile's rows are padded by one
+// double against bank conflicts of the transposed read.
+static constexpr int RGF_CT_TILE = 16;
+
+__global__ __launch_bounds__(RGF_CT_TILE * RGF_CT_TILE) void rgf_accumulate_ct_kernel(
+    int nr, int nc, int nb, const cplx* __restrict__ w, const cplx* __restrict__ X, size_t strideX, cplx* __restrict__ acc)
+{
+    __shared__ double tre[RGF_CT_TILE][RGF_CT_TILE + 1], tim[RGF_CT_TILE][RGF_CT_TILE + 1];
+    const int tx = threadIdx.x & (RGF_CT_TILE - 1), ty = threadIdx.x / RGF_CT_TILE;
+    const int r0 = blockIdx.y * RGF_CT_TILE, c0 = blockIdx.x * RGF_CT_TILE;
+    const bool in_ok = r0 + ty < nr && c0 + tx < nc;        // X[r0 + ty][c0 + tx]
+    const bool out_ok = c0 + ty < nc && r0 + tx < nr;       // acc[c0 + ty][r0 + tx]
+    const size_t in_at = (size_t)(r0 + ty) * nc + c0 + tx, out_at = (size_t)(c0 + ty) * nr + r0 + tx;
+    cplx v = out_ok ? acc[out_at] : cmake(0.0, 0.0);
+    for (int b = 0; b < nb; ++b) {
+        if (in_ok) { const cplx x = X[(size_t)b * strideX + in_at]; tre[ty][tx] = x.x; tim[ty][tx] = x.y; }
+        __syncthreads();
+        if (out_ok) v = cfma(v, w[b], cmake(tre[tx][ty], -tim[tx][ty]));
+        __syncthreads();
+    }
+    if (out_ok) acc[out_at] = v;
+}
+
+void launch_rgf_accumulate_ct(hipStream_t st, int nr, int nc, int nb, const cplx* w, const cplx* X, size_t strideX, cplx* acc)
+{
+    if (nr <= 0 || nc <= 0 || nb <= 0) return;
+    hipLaunchKernelGGL(rgf_accumulate_ct_kernel, dim3((nc + RGF_CT_TILE - 1) / RGF_CT_TILE, (nr + RGF_CT_TILE - 1) / RGF_CT_TILE),
+                       dim3(RGF_CT_TILE * RGF_CT_TILE), 0, st, nr, nc, nb, w, X, strideX, acc);
+}
+
+// contact Mulliken rows of one block A (nr x nk) against its S block X:
+//   rows: site[b][r] (+)= sum_k Re[A_b[r][k] conj(X[r][k])] / 2 pi, one wave per (energy, row), rgf_dos_rows's tree
+//   cols: site[b][k]  += sum_r Re[A_b[r][k] conj(X[r][k])] / 2 pi, one thread per column, r ascending
+__global__ __launch_bounds__(RGF_THREADS) void rgf_pop_rows_kernel(
+    int nr, int nk, const cplx* __restrict__ A, size_t strideA, const cplx* __restrict__ X,
+    double* __restrict__ site, size_t site_stride, int accumulate)
+{
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (RGF_THREADS / 64) + (threadIdx.x >> 6);
+    if (r >= nr) return;                                    // whole waves leave together
+    const cplx* a = A + (size_t)b * strideA + (size_t)r * nk;
+    const cplx* x = X + (size_t)r * nk;
+    double s = 0.0;
+    for (int k = lane; k < nk; k += 64) {
+        const cplx p = a[k], c = x[k];
+        s += p.x * c.x + p.y * c.y;                         // Re[p conj(c)]
+    }
+    s = rgf_wave_sum(s);
+    if (lane == 0) {
+        const double two_pi = 6.28318530717958647692;
+        double* o = site + (size_t)b * site_stride + r;
+        const double v = s / two_pi;
+        *o = accumulate ? *o + v : v;
+    }
+}
+
+__global__ __launch_bounds__(RGF_THREADS) void rgf_pop_cols_kernel(
+    int nr, int nk, const cplx* __restrict__ A, size_t strideA, const cplx* __restrict__ X,
+    double* __restrict__ site, size_t site_stride)
+{
+    const int b = blockIdx.y;
+    const int k = blockIdx.x * RGF_THREADS + threadIdx.x;
+    if (k >= nk) return;
+    const cplx* a = A + (size_t)b * strideA;
+    double s = 0.0;
+    for (int r = 0; r < nr; ++r) {
+        const cplx p = a[(size_t)r * nk + k], c = X[(size_t)r * nk + k];
+        s += p.x * c.x + p.y * c.y;
+    }
+    const double two_pi = 6.28318530717958647692;
+    site[(size_t)b * site_stride + k] += s / two_pi;
+}
+
+void launch_rgf_pop_block(hipStream_t st, int nr, int nk, int nb, const cplx* A, size_t strideA, const cplx* X,
+                          double* row_site, bool accumulate_rows, double* col_site, size_t site_stride)
+{
+    if (nr <= 0 || nk <= 0 || nb <= 0) return;
+    const int rows_per = RGF_THREADS / 64;
+    hipLaunchKernelGGL(rgf_pop_rows_kernel, dim3((nr + rows_per - 1) / rows_per, nb), dim3(RGF_THREADS), 0, st, nr, nk, A,
+                       strideA, X, row_site, site_stride, accumulate_rows ? 1 : 0);
+    if (col_site)
+        hipLaunchKernelGGL(rgf_pop_cols_kernel, dim3((nk + RGF_THREADS - 1) / RGF_THREADS, nb), dim3(RGF_THREADS), 0, st, nr,
+                           nk, A, strideA, X, col_site, site_stride);
 }
 
 // info[b] = offset + linfo[b] for the first layer that reported a zero pivot

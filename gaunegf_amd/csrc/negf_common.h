@@ -558,6 +558,19 @@ void launch_rgf_dos_rows(hipStream_t st, int nr, int nk, int nb, const cplx* G, 
 void launch_rgf_dos_total(hipStream_t st, int N, int nb, const double* site, size_t site_stride, double* tot);
 // acc[i] += sum_b w[b] X[b][i], one chain per element with b ascending
 void launch_rgf_accumulate(hipStream_t st, int count, int nb, const cplx* w, const cplx* X, size_t strideX, cplx* acc);
+// G Gamma G^H on the pattern of S (negf_layered_gless_int, negf_layered_contact_dos):
+// out[b][r][a] = G[b][r][idx[a]]   (G n x n, out n x K compact)
+void launch_rgf_gather_cols(hipStream_t st, int n, int K, int nb, const cplx* G, size_t strideG, const int* idx, cplx* out,
+                            size_t stride_out);
+// out[b] (KJ x KJ) = sum_k of i (Sigma_k - Sigma_k^H) scattered into the union list J (layer orbitals, ascending), k in
+// the order of `t`
+void launch_rgf_gamma_union(hipStream_t st, int KJ, int nb, const int* J, const RgfTermArgs& t, cplx* out, size_t stride_out);
+// acc[c][r] += sum_b w[b] conj(X[b][r][c])   (X nr x nc, acc nc x nr), one chain per element with b ascending
+void launch_rgf_accumulate_ct(hipStream_t st, int nr, int nc, int nb, const cplx* w, const cplx* X, size_t strideX, cplx* acc);
+// row_site[b * site_stride + r] (+)= sum_k Re[A[b][r][k] conj(X[r][k])] / 2 pi, and, col_site given,
+// col_site[b * site_stride + k] += sum_r of the same terms   (A, X nr x nk)
+void launch_rgf_pop_block(hipStream_t st, int nr, int nk, int nb, const cplx* A, size_t strideA, const cplx* X,
+                          double* row_site, bool accumulate_rows, double* col_site, size_t site_stride);
 void launch_rgf_merge_info(hipStream_t st, int nb, int offset, const int* linfo, int* info);
 
 bool small_fused_supported(int n);

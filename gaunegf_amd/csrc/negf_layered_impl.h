@@ -12,6 +12,11 @@
 //   corner     X_0 = g_0,  X_i = g_i C_{i,i-1} X_{i-1}  -> G_{L-1,0};    Y_i = Y_{i-1} C_{i-1,i} g_i  -> G_{0,L-1}
 //   backward   G_{L-1,L-1} = g_{L-1};  U = g_i C_{i,i+1},  V = C_{i+1,i} g_i:
 //              G_{i,i+1} = U G_{i+1,i+1},   G_{i+1,i} = G_{i+1,i+1} V,   G_ii = g_i + G_{i,i+1} V
+//   columns    of a terminal set on the union J of its orbitals (G Gamma G^H on the pattern of S), W_i = G_{i,end}[:, J]:
+//              last layer:  W_{L-1} = G_{L-1,L-1}[:, J],  W_i = U_i W_{i+1}                    (backward sweep)
+//              layer 0:     x_0 = g_0[:, J],  z_i = C_{i,i-1} x_{i-1},  x_i = g_i z_i          (forward sweep, the z_i kept)
+//                           W_0 = G_00[:, J],  W_i = G_ii z_i                                  (backward sweep)
+//              A_ii = (W_i Gamma) W_i^H,   A_{i,i+1} = (W_i Gamma) W_{i+1}^H,   A_{i+1,i} = A_{i,i+1}^H never formed
 // Every layer matrix of a batch is compact row-major at ONE batch stride (the largest layer's n^2): the inverses and
 // products are the dense path's launchers, batched over the energies.
 
@@ -20,6 +25,7 @@ struct RgfTerminal {
     int kind = 0;                  // 0 const, 1 chain, 2 blocks
     int K = 0;
     int* d_idx = nullptr;          // [K] orbitals inside the layer
+    std::vector<int> idx;          // the same list on the host
     int* d_pos = nullptr;          // [n_layer] position in the list, -1 outside
     cplx* d_sig = nullptr;         // const: [K*K]; blocks: [m_blk][K*K]
     int m_blk = 0;
@@ -40,11 +46,13 @@ struct LayeredSystem {
     DevBuf<cplx> d_pool;                        // [RGF_NBUF][batch][stride] work areas
     DevBuf<cplx> d_gstore;                      // [L][batch][stride] the g_i of a backward sweep
     DevBuf<cplx> d_small;                       // Gamma_a | Gamma_b | G_ab | X | Y of the transmission
+    DevBuf<cplx> d_cols;                        // column sets of G Gamma G^H: z_i | x | W | Y | Gamma, per energy in flight
+    DevBuf<int> d_J;                            // [2][nmax] their union lists, layer 0's then the last layer's
     DevBuf<cplx> d_out;                         // gr_int: the block lists, host-pointer entry point
     DevBuf<double> d_site;                      // dos: [m][N] staging of the host-pointer entry point
     DevBuf<int> d_piv, d_linfo, d_iters, d_conv;
     int batch = 0;                              // energies the work areas are laid out for
-    long long work_bytes = 0;                   // of the last call: pool + stored g
+    long long work_bytes = 0;                   // of the last call: pool + stored g + column sets
 };
 
 constexpr int RGF_NBUF = 10;
@@ -63,8 +71,9 @@ void free_layered(LayeredSystem* ls)
     if (!ls) return;
     for (auto* t : ls->terms) free_terminal(t);
     dev_free(ls->dFd); dev_free(ls->dSd); dev_free(ls->dFu); dev_free(ls->dSu); dev_free(ls->dFl); dev_free(ls->dSl);
-    release_bufs(ls->d_pool, ls->d_gstore, ls->d_small, ls->d_out);
+    release_bufs(ls->d_pool, ls->d_gstore, ls->d_small, ls->d_out, ls->d_cols);
     release_bufs(ls->d_site);
+    release_bufs(ls->d_J);
     release_bufs(ls->d_piv, ls->d_linfo, ls->d_iters, ls->d_conv);
     delete ls;
 }
@@ -104,6 +113,7 @@ int rgf_new_terminal(negf_ctx* c, int h, int layer, int K, const int* inds, int*
     NEGF_HIP_CHECK(hipSetDevice(c->device));
     RgfTerminal* t = new RgfTerminal();
     t->end = end; t->K = K;
+    t->idx.assign(inds, inds + K);
     std::vector<int> pos((size_t)nl, -1);
     for (int a = 0; a < K; ++a) pos[inds[a]] = a;
     int rc;
@@ -115,6 +125,19 @@ int rgf_new_terminal(negf_ctx* c, int h, int layer, int K, const int* inds, int*
 
 int rgf_add_terminal(LayeredSystem* ls, RgfTerminal* t) { ls->terms.push_back(t); return (int)ls->terms.size() - 1; }
 
+// A G Gamma G^H call: the terminals it selects, per end (0: layer 0, 1: layer L - 1) the union J of their orbitals, and
+// the column areas of the batch in flight (all compact n_i x K at the stride cs)
+typedef void (*RgfConsumeA)(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* A, bool up, void* arg);
+struct RgfLess {
+    int K[2] = {0, 0};                          // |J|, 0: no terminal of that end selected
+    const int* J[2] = {nullptr, nullptr};       // device, ascending
+    const RgfTerminal* only = nullptr;          // the one terminal selected, null: all
+    size_t cs = 0, per_energy = 0;
+    cplx *z = nullptr, *x[2] = {nullptr, nullptr};          // layer-0 set: z_1 .. z_{L-1} [L-1][batch][cs], x_{i-1} | x_i
+    cplx *W[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *Y[2] = {nullptr, nullptr}, *gam[2] = {nullptr, nullptr};
+    RgfConsumeA consume = nullptr; void* arg = nullptr;
+};
+
 struct RgfRun {
     LayeredSystem* ls;
     int nb_max;                 // energies per sweep
@@ -122,19 +145,20 @@ struct RgfRun {
 };
 
 // Energies per sweep and the work areas for them.  A sweep holds RGF_NBUF matrices of the largest layer per energy, a
-// backward sweep L more (the g_i); the budget is the dense path's (auto_batch): a quarter of the free HBM, at most 64 GB.
-int rgf_workspace(negf_ctx* c, LayeredSystem* ls, int m, bool backward, RgfRun* r)
+// backward sweep L more (the g_i), a G Gamma G^H call `extra` elements more (its column sets, rgf_less_layout); the budget
+// is the dense path's (auto_batch): a quarter of the free HBM, at most 64 GB.
+int rgf_workspace(negf_ctx* c, LayeredSystem* ls, int m, bool backward, RgfRun* r, size_t extra = 0)
 {
     const size_t s = ls->stride;
     const int nbufs = RGF_NBUF + (backward ? ls->L : 0);
     int want;
     if (c->batch_user > 0) want = std::min(c->batch_user, std::max(m, 1));
     else {
-        const double per = 16.0 * (double)s * nbufs;
+        const double per = 16.0 * ((double)s * nbufs + (double)extra);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)24e9;
         // (what this system already holds counts as free: it is reused)
-        const double held = 16.0 * (double)(ls->d_pool.cap + ls->d_gstore.cap);
+        const double held = 16.0 * (double)(ls->d_pool.cap + ls->d_gstore.cap + ls->d_cols.cap);
         const double budget = std::min(64.0e9, std::max(2.0e9, 0.25 * ((double)free_b + held)));
         long b = (long)(budget / per);
         b = std::max(1L, std::min(b, 4096L));
@@ -143,12 +167,13 @@ int rgf_workspace(negf_ctx* c, LayeredSystem* ls, int m, bool backward, RgfRun* 
     int rc;
     if ((rc = ensure_cap(c, ls->d_pool, (size_t)RGF_NBUF * want * s + 64))) return rc;
     if (backward && (rc = ensure_cap(c, ls->d_gstore, (size_t)ls->L * want * s + 64))) return rc;
+    if (extra && (rc = ensure_cap(c, ls->d_cols, extra * want + 64))) return rc;
     if ((rc = ensure_cap(c, ls->d_piv, (size_t)2 * ls->nmax * want)) || (rc = ensure_cap(c, ls->d_linfo, (size_t)want)) ||
         (rc = ensure_cap(c, ls->d_iters, (size_t)want)) || (rc = ensure_cap(c, ls->d_conv, (size_t)want))) return rc;
     for (auto* t : ls->terms)
         if (t->kind == 1 && (rc = ensure_cap(c, t->d_blk, (size_t)want * t->K * t->K))) return rc;
     ls->batch = want;
-    ls->work_bytes = 16LL * (long long)s * want * nbufs;
+    ls->work_bytes = 16LL * ((long long)s * nbufs + (long long)extra) * want;
     r->ls = ls; r->nb_max = want;
     for (int k = 0; k < RGF_NBUF; ++k) r->buf[k] = ls->d_pool + (size_t)k * want * s;
     return NEGF_OK;
@@ -185,12 +210,13 @@ void rgf_sigma_of(const RgfTerminal* t, int m0, const cplx** sig, size_t* stride
     else { *sig = t->d_blk.p; *stride = kk; }
 }
 
-RgfTermArgs rgf_term_args(const LayeredSystem* ls, int end, int m0)
+// (only: the one terminal that counts, null: all of that end)
+RgfTermArgs rgf_term_args(const LayeredSystem* ls, int end, int m0, const RgfTerminal* only = nullptr)
 {
     RgfTermArgs a;
     for (int k = 0; k < RGF_MAX_TERM; ++k) { a.pos[k] = nullptr; a.sig[k] = nullptr; a.stride[k] = 0; a.K[k] = 0; }
     for (auto* t : ls->terms) {
-        if (t->end != end) continue;
+        if (t->end != end || (only && t != only)) continue;
         const int k = a.count++;
         a.pos[k] = t->d_pos; a.K[k] = t->K;
         rgf_sigma_of(t, m0, &a.sig[k], &a.stride[k]);
@@ -253,8 +279,10 @@ int rgf_inverse(negf_ctx* c, LayeredSystem* ls, int i, int nb, cplx* A, cplx* B,
 
 // Forward sweep of the batch [m0, m0 + nb).  keep: the g_i go to d_gstore (a backward sweep follows); otherwise only
 // g_{i-1} is alive, and the corner block X_i (corner = 1: G_{i,0}) or Y_i (corner = 2: G_{0,i}) is carried along --
-// *corner_out = the block of the last layer.  Work areas: buf[0..8].
-int rgf_forward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, bool keep, int corner, cplx** corner_out)
+// *corner_out = the block of the last layer.  less (with keep): the z_i chain of a column set on layer 0.  Work areas:
+// buf[0..8].
+int rgf_forward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, bool keep, int corner, cplx** corner_out,
+                RgfLess* less = nullptr)
 {
     LayeredSystem* ls = r.ls;
     const size_t s = ls->stride;
@@ -286,6 +314,19 @@ int rgf_forward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, boo
         cplx* g = nullptr;
         if ((rc = rgf_inverse(c, ls, i, nb, D, B, info, &g))) return rc;
         if (keep && g != D) { NEGF_HIP_CHECK(hipMemcpyAsync(D, g, layer_bytes, hipMemcpyDeviceToDevice, c->stream)); g = D; }
+        if (keep && less && less->K[0] > 0) {
+            const int K = less->K[0];
+            if (i == 0) { ProfScope ps(c, "rgf"); launch_rgf_gather_cols(c->stream, ni, K, nb, g, s, less->J[0], less->x[0], less->cs); }
+            else {
+                cplx* z = less->z + (size_t)(i - 1) * r.nb_max * less->cs;
+                ProfScope ps(c, "zgemm");
+                launch_zgemm(c->stream, ni, K, ls->n[i - 1], nb, CL, ls->n[i - 1], s, less->x[0], K, less->cs, 0, z, K, less->cs);   // z_i = C_{i,i-1} x_{i-1}
+                if (i + 1 < ls->L) {
+                    launch_zgemm(c->stream, ni, K, ni, nb, g, ni, s, z, K, less->cs, 0, less->x[1], K, less->cs);                 // x_i = g_i z_i
+                    std::swap(less->x[0], less->x[1]);
+                }
+            }
+        }
         if (!keep && corner) {
             const int n0 = ls->n[0];
             if (i == 0) { NEGF_HIP_CHECK(hipMemcpyAsync(Xa, g, layer_bytes, hipMemcpyDeviceToDevice, c->stream)); }
@@ -309,7 +350,53 @@ int rgf_forward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, boo
 // blocks G_{i,i+1}, G_{i+1,i} (null for the last layer)
 typedef void (*RgfConsume)(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* Gii, const cplx* Gup, const cplx* Glo, void* arg);
 
-int rgf_backward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, RgfConsume consume, void* arg)
+// Layer i of a G Gamma G^H sweep: the columns W_i of each selected end from G_ii, U_i and W_{i+1}, then the blocks A_ii and
+// A_{i,i+1} (the layer-0 set's contribution first, the last layer's added to it) handed to the consumer one after the other.
+// Work areas: buf[9], buf[4], buf[3] -- free once G_ii stands.
+void rgf_less_layer(negf_ctx* c, const RgfRun& r, RgfLess* less, int i, int m0, int nb, const cplx* Gii, const cplx* U)
+{
+    LayeredSystem* ls = r.ls;
+    const size_t s = ls->stride, cs = less->cs;
+    const int ni = ls->n[i], L = ls->L;
+    for (int e = 0; e < 2; ++e) {
+        const int K = less->K[e];
+        if (K == 0) continue;
+        cplx* W = less->W[e][1];
+        if ((e == 0 && i == 0) || (e == 1 && i == L - 1)) {
+            ProfScope ps(c, "rgf");
+            launch_rgf_gather_cols(c->stream, ni, K, nb, Gii, s, less->J[e], W, cs);
+        } else if (e == 0) {
+            ProfScope ps(c, "zgemm");
+            launch_zgemm(c->stream, ni, K, ni, nb, Gii, ni, s, less->z + (size_t)(i - 1) * r.nb_max * cs, K, cs, 0, W, K, cs);    // G_ii z_i
+        } else {
+            const int nn = ls->n[i + 1];
+            ProfScope ps(c, "zgemm");
+            launch_zgemm(c->stream, ni, K, nn, nb, U, nn, s, less->W[e][0], K, cs, 0, W, K, cs);                                 // U_i W_{i+1}
+        }
+        ProfScope ps(c, "zgemm");
+        launch_zgemm(c->stream, ni, K, K, nb, W, K, cs, less->gam[e], K, (size_t)K * K, 0, less->Y[e], K, cs);                   // Y_i = W_i Gamma
+    }
+    cplx* Ab[2] = {r.buf[9], r.buf[4]};
+    const bool both = less->K[0] > 0 && less->K[1] > 0;
+    for (int up = 0; up < 2; ++up) {
+        if (up && i == L - 1) break;
+        const int nc = up ? ls->n[i + 1] : ni;
+        for (int e = 0; e < 2; ++e) {
+            const int K = less->K[e];
+            if (K == 0) continue;
+            ProfScope ps(c, "zgemm");
+            // op(B) = W^H; the diagonal block is a Hermitian product
+            launch_zgemm(c->stream, ni, nc, K, nb, less->Y[e], K, cs, less->W[e][up ? 0 : 1], K, cs, up ? 1 : 3, Ab[e], nc, s);
+        }
+        const cplx* A = less->K[0] > 0 ? Ab[0] : Ab[1];
+        if (both) { ProfScope ps(c, "rgf"); launch_rgf_add(c->stream, ni * nc, nb, Ab[0], s, Ab[1], s, r.buf[3], s); A = r.buf[3]; }
+        less->consume(c, ls, i, m0, nb, A, up != 0, less->arg);
+    }
+    for (int e = 0; e < 2; ++e) std::swap(less->W[e][0], less->W[e][1]);       // W_i is the next layer's W_{i+1}
+}
+
+// less: a G Gamma G^H sweep -- the consumer is less->consume (consume is null), G_{i+1,i} is not formed
+int rgf_backward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, RgfConsume consume, void* arg, RgfLess* less = nullptr)
 {
     LayeredSystem* ls = r.ls;
     const size_t s = ls->stride;
@@ -317,7 +404,8 @@ int rgf_backward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, Rg
     cplx *Gcur = r.buf[7], *Galt = r.buf[8];
     auto g_of = [&](int i) { return ls->d_gstore + (size_t)i * r.nb_max * s; };
     const cplx* Gnext = g_of(ls->L - 1);
-    consume(c, ls, ls->L - 1, m0, nb, Gnext, nullptr, nullptr, arg);
+    if (less) rgf_less_layer(c, r, less, ls->L - 1, m0, nb, Gnext, nullptr);
+    else consume(c, ls, ls->L - 1, m0, nb, Gnext, nullptr, nullptr, arg);
     for (int i = ls->L - 2; i >= 0; --i) {
         const int ni = ls->n[i], nn = ls->n[i + 1];
         const cplx* g = g_of(i);
@@ -325,10 +413,11 @@ int rgf_backward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, Rg
         rgf_mm(c, ls, ni, nn, ni, nb, g, CU, U);                       // U = g_i C_{i,i+1}
         rgf_mm(c, ls, ni, nn, nn, nb, U, Gnext, Gup);                  // G_{i,i+1}
         rgf_mm(c, ls, nn, ni, ni, nb, CL, g, V);                       // V = C_{i+1,i} g_i
-        rgf_mm(c, ls, nn, ni, nn, nb, Gnext, V, Glo);                  // G_{i+1,i}
+        if (!less) rgf_mm(c, ls, nn, ni, nn, nb, Gnext, V, Glo);       // G_{i+1,i}
         rgf_mm(c, ls, ni, ni, nn, nb, Gup, V, Wm);                     // g_i C G_{i+1,i+1} C g_i
         { ProfScope ps(c, "rgf"); launch_rgf_add(c->stream, ni * ni, nb, g, s, Wm, s, Gcur, s); }
-        consume(c, ls, i, m0, nb, Gcur, Gup, Glo, arg);
+        if (less) rgf_less_layer(c, r, less, i, m0, nb, Gcur, U);
+        else consume(c, ls, i, m0, nb, Gcur, Gup, Glo, arg);
         Gnext = Gcur;
         std::swap(Gcur, Galt);
     }
@@ -366,6 +455,95 @@ void rgf_consume_sum(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, cons
         launch_rgf_accumulate(c->stream, cnt, nb, a->w + m0, Gup, s, a->out + ls->dtot + ls->uoff[i]);
         launch_rgf_accumulate(c->stream, cnt, nb, a->w + m0, Glo, s, a->out + ls->dtot + ls->utot + ls->uoff[i]);
     }
+}
+
+bool rgf_less_ind_ok(const LayeredSystem* ls, int ind)
+{
+    const int nt = (int)ls->terms.size();
+    return ind == NEGF_IND_TOTAL ? nt > 0 : (ind >= -nt && ind < nt);
+}
+
+// Which terminals `ind` names (negf_gless_int's reading: -n_t .. n_t - 1, NEGF_IND_TOTAL = all), their union lists on
+// the device, and the size of the column areas per energy.  NEGF_EINVAL before anything is launched.
+int rgf_less_select(negf_ctx* c, LayeredSystem* ls, int ind, RgfLess* less)
+{
+    if (!rgf_less_ind_ok(ls, ind)) return NEGF_EINVAL;
+    if (ind != NEGF_IND_TOTAL) less->only = ls->terms[ind < 0 ? ind + (int)ls->terms.size() : ind];
+    std::vector<int> J[2];
+    for (int e = 0; e < 2; ++e) {
+        const int nl = ls->n[e == 0 ? 0 : ls->L - 1];
+        std::vector<char> in((size_t)nl, 0);
+        for (auto* t : ls->terms)
+            if (t->end == e && (!less->only || t == less->only)) for (int o : t->idx) in[o] = 1;
+        for (int o = 0; o < nl; ++o) if (in[o]) J[e].push_back(o);
+        less->K[e] = (int)J[e].size();
+    }
+    int rc;
+    if ((rc = ensure_cap(c, ls->d_J, (size_t)2 * ls->nmax))) return rc;
+    for (int e = 0; e < 2; ++e) {
+        less->J[e] = ls->d_J + (size_t)e * ls->nmax;
+        if ((rc = upload(c, ls->d_J + (size_t)e * ls->nmax, J[e].data(), J[e].size()))) return rc;
+    }
+    const size_t Kmax = (size_t)std::max(less->K[0], less->K[1]);
+    less->cs = (size_t)ls->nmax * Kmax;
+    // layer-0 set: z_1 .. z_{L-1}, x | x, W | W, Y;  last layer's: W | W, Y;  and the two Gamma
+    less->per_energy = (less->K[0] > 0 ? (size_t)(ls->L - 1) + 5 : 0) * less->cs + (less->K[1] > 0 ? 3 : 0) * less->cs +
+                       (size_t)less->K[0] * less->K[0] + (size_t)less->K[1] * less->K[1];
+    return NEGF_OK;
+}
+
+// carve the column areas out of d_cols for the batch size of this run
+void rgf_less_layout(const RgfRun& r, RgfLess* less)
+{
+    const size_t cb = less->cs * r.nb_max;
+    cplx* p = r.ls->d_cols.p;
+    auto take = [&](size_t count) { cplx* q = p; p += count; return q; };
+    if (less->K[0] > 0) {
+        less->z = take((size_t)(r.ls->L - 1) * cb);
+        less->x[0] = take(cb); less->x[1] = take(cb);
+    }
+    for (int e = 0; e < 2; ++e) {
+        if (less->K[e] == 0) continue;
+        less->W[e][0] = take(cb); less->W[e][1] = take(cb); less->Y[e] = take(cb);
+        less->gam[e] = take((size_t)less->K[e] * less->K[e] * r.nb_max);
+    }
+}
+
+// forward sweep, the Gamma of the selected terminals on their union lists, backward sweep of one batch
+int rgf_less_batch(negf_ctx* c, const RgfRun& r, RgfLess* less, int m0, int nb, const cplx* E)
+{
+    int rc;
+    if ((rc = rgf_forward(c, r, m0, nb, E, true, 0, nullptr, less))) return rc;
+    {
+        ProfScope ps(c, "gamma");
+        for (int e = 0; e < 2; ++e)
+            if (less->K[e] > 0)
+                launch_rgf_gamma_union(c->stream, less->K[e], nb, less->J[e], rgf_term_args(r.ls, e, m0, less->only), less->gam[e],
+                                       (size_t)less->K[e] * less->K[e]);
+    }
+    return rgf_backward(c, r, m0, nb, E, nullptr, nullptr, less);
+}
+
+void rgf_consume_less_sum(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* A, bool up, void* arg)
+{
+    ProfScope ps(c, "accumulate");
+    const RgfSumArg* a = static_cast<const RgfSumArg*>(arg);
+    const size_t s = ls->stride;
+    if (!up) { launch_rgf_accumulate(c->stream, ls->n[i] * ls->n[i], nb, a->w + m0, A, s, a->out + ls->doff[i]); return; }
+    launch_rgf_accumulate(c->stream, ls->n[i] * ls->n[i + 1], nb, a->w + m0, A, s, a->out + ls->dtot + ls->uoff[i]);
+    // the lower block (i+1, i): sum_k w_k conj(A_{i,i+1}(E_k))^T
+    launch_rgf_accumulate_ct(c->stream, ls->n[i], ls->n[i + 1], nb, a->w + m0, A, s, a->out + ls->dtot + ls->utot + ls->uoff[i]);
+}
+
+void rgf_consume_less_dos(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* A, bool up, void* arg)
+{
+    ProfScope ps(c, "rgf");
+    double* site = static_cast<double*>(arg) + (size_t)m0 * ls->N;
+    const size_t s = ls->stride;
+    if (!up) launch_rgf_pop_block(c->stream, ls->n[i], ls->n[i], nb, A, s, ls->dSd + ls->doff[i], site + ls->off[i], false, nullptr, (size_t)ls->N);
+    // the rows of layer i, and through A_{i+1,i} = A_{i,i+1}^H the rows of layer i + 1 as the block's column sums
+    else launch_rgf_pop_block(c->stream, ls->n[i], ls->n[i + 1], nb, A, s, ls->dSu + ls->uoff[i], site + ls->off[i], true,
+                              site + ls->off[i + 1], (size_t)ls->N);
 }
 
 }  // namespace
@@ -637,6 +815,85 @@ int negf_layered_gr_int(negf_ctx* c, int h, int m, const double* E, const double
     if ((rc = negf_layered_gr_int_dev(c, h, m, reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
                                       reinterpret_cast<double*>(ls->d_out.p)))) return rc;
     return fetch_result_and_info(c, m, ls->d_out.p, tot * sizeof(cplx), out, info);
+}
+
+int negf_layered_gless_int_dev(negf_ctx* c, int h, int ind, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
+    RgfLess less;
+    if ((rc = rgf_less_select(c, ls, ind, &less))) return rc;
+    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
+    RgfRun r;
+    if ((rc = rgf_workspace(c, ls, m, true, &r, less.per_energy))) return rc;
+    rgf_less_layout(r, &less);
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    RgfSumArg arg{reinterpret_cast<const cplx*>(w_dev), reinterpret_cast<cplx*>(out_dev)};
+    less.consume = rgf_consume_less_sum; less.arg = &arg;
+    NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, (ls->dtot + 2 * ls->utot) * sizeof(cplx), c->stream));
+    for (int m0 = 0; m0 < m; m0 += r.nb_max)
+        if ((rc = rgf_less_batch(c, r, &less, m0, std::min(r.nb_max, m - m0), E))) return rc;
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_layered_gless_int(negf_ctx* c, int h, int ind, int m, const double* E, const double* w, double* out, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
+    if (!rgf_less_ind_ok(ls, ind)) return NEGF_EINVAL;
+    const size_t tot = ls->dtot + 2 * ls->utot;
+    if ((rc = stage_grid(c, m, 1, E, w, tot * sizeof(cplx)))) return rc;
+    if ((rc = ensure_cap(c, ls->d_out, tot))) return rc;
+    if ((rc = negf_layered_gless_int_dev(c, h, ind, m, reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
+                                         reinterpret_cast<double*>(ls->d_out.p)))) return rc;
+    return fetch_result_and_info(c, m, ls->d_out.p, tot * sizeof(cplx), out, info);
+}
+
+int negf_layered_contact_dos_dev(negf_ctx* c, int h, int ind, int m, const double* E_dev, double* dos_total_dev, double* dos_site_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (m > 0 && (!E_dev || !dos_total_dev || !dos_site_dev)) return NEGF_EINVAL;
+    RgfLess less;
+    if ((rc = rgf_less_select(c, ls, ind, &less))) return rc;
+    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
+    RgfRun r;
+    if ((rc = rgf_workspace(c, ls, m, true, &r, less.per_energy))) return rc;
+    rgf_less_layout(r, &less);
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    less.consume = rgf_consume_less_dos; less.arg = dos_site_dev;
+    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
+        const int nb = std::min(r.nb_max, m - m0);
+        if ((rc = rgf_less_batch(c, r, &less, m0, nb, E))) return rc;
+        ProfScope ps(c, "rgf");
+        launch_rgf_dos_total(c->stream, ls->N, nb, dos_site_dev + (size_t)m0 * ls->N, (size_t)ls->N, dos_total_dev + m0);
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_layered_contact_dos(negf_ctx* c, int h, int ind, int m, const double* E, double* dos_total, double* dos_site, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (m > 0 && (!E || !dos_total)) return NEGF_EINVAL;
+    if (!rgf_less_ind_ok(ls, ind)) return NEGF_EINVAL;
+    if (m == 0) return NEGF_OK;
+    if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
+    if ((rc = ensure_cap(c, ls->d_site, (size_t)m * ls->N))) return rc;
+    if ((rc = negf_layered_contact_dos_dev(c, h, ind, m, reinterpret_cast<double*>(c->d_E), c->d_scal, ls->d_site))) return rc;
+    if (dos_site && (rc = download(c, dos_site, ls->d_site.p, (size_t)m * ls->N))) return rc;
+    if ((rc = download(c, dos_total, c->d_scal, (size_t)m))) return rc;
+    return reduce_info(c, m, info);
 }
 
 int negf_layered_workspace_bytes(negf_ctx* c, int h, long long* work)

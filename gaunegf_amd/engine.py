@@ -906,8 +906,8 @@ class Engine:
     def _lcheck(self, rc, where):
         """Invalid arguments of the layered calls are the caller's: ValueError, before anything was launched."""
         if rc == _lib.NEGF_EINVAL:
-            raise ValueError(f"{where}: invalid argument (layer sizes, index lists, terminal layers or the number of "
-                             "energies of a 'blocks' terminal)")
+            raise ValueError(f"{where}: invalid argument (layer sizes, index lists, terminal layers and numbers or the "
+                             "number of energies of a 'blocks' terminal)")
         return check(rc, where)
 
     def layered_create(self, F_diag, F_up, S_diag, S_up):
@@ -1042,6 +1042,42 @@ class Engine:
                                                         _ptr(info)), "negf_layered_gr_int")
         self._numerical(rc, info[:E.size], "layered_gr_int")
         return self._lsplit(handle, flat)
+
+    def layered_gless_int(self, handle, ind, E, w):
+        """sum_m w_m G Gamma G^H on the pattern of S for terminal ``ind`` (None: all terminals), as gless_int: (diagonal
+        blocks, upper blocks A_{i,i+1}, lower blocks sum_m w_m A_{i,i+1}(E_m)^H)."""
+        E, w = self._grid(E, w)
+        flat = np.zeros(self.layered_pattern_size(handle), dtype=np.complex128)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_gless_int(self._ctx, int(handle), _ind(ind), E.size, _ptr(E), _ptr(w),
+                                                           _ptr(flat), _ptr(info)), "negf_layered_gless_int")
+        self._numerical(rc, info[:E.size], "layered_gless_int")
+        return self._lsplit(handle, flat)
+
+    def layered_contact_dos(self, handle, ind, E, per_site=True):
+        """(total [m], site [m, N]): terminal ``ind``'s share of the Mulliken DOS, (1/2pi) Re sum_j (G Gamma G^H)_ij conj(S_ij)
+        (None: all terminals) -- population(h, ind, E, rows=True) of the dense engine."""
+        E, _ = self._grid(E)
+        N = sum(self._lsizes(handle))
+        tot = np.zeros(E.size, dtype=np.float64)
+        site = np.zeros((E.size, N), dtype=np.float64) if per_site else None
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_contact_dos(self._ctx, int(handle), _ind(ind), E.size, _ptr(E), _ptr(tot),
+                                                             _ptr(site), _ptr(info)), "negf_layered_contact_dos")
+        self._numerical(rc, info[:E.size], "layered_contact_dos")
+        return (tot, site) if per_site else tot
+
+    def layered_gless_int_dev(self, handle, ind, m, E_ptr, w_ptr, out_ptr):
+        """out: layered_pattern_size(handle) complex values, diagonal | upper | lower blocks."""
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_gless_int_dev(self._ctx, int(handle), _ind(ind), int(m), C.c_void_p(E_ptr),
+                                                          C.c_void_p(w_ptr), C.c_void_p(out_ptr)), "negf_layered_gless_int_dev")
+
+    def layered_contact_dos_dev(self, handle, ind, m, E_ptr, tot_ptr, site_ptr):
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_contact_dos_dev(self._ctx, int(handle), _ind(ind), int(m), C.c_void_p(E_ptr),
+                                                            C.c_void_p(tot_ptr), C.c_void_p(site_ptr)),
+                     "negf_layered_contact_dos_dev")
 
     def layered_transmission_dev(self, handle, term_a, term_b, m, E_ptr, T_ptr):
         self.counters["calls"] += 1; self.counters["points"] += int(m)

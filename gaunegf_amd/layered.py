@@ -10,11 +10,15 @@ namesakes in transport.py / integrate.py:
     calculate_dos_layered(system, leads, energy_list)               -> (dos_total [m], dos_per_site [m, N])
     calculate_pdos_layered(system, leads, energy_list, groups=None) -> [m, n_g]      (Mulliken, -Im (G S)_ii / pi)
     GrIntLayered(system, leads, Elist, weights)                     -> (diag, up, low) block lists of sum_m w_m G(E_m)
+    GrLessIntLayered(system, leads, Elist, weights, ind=None)       -> the same lists of sum_m w_m G Gamma G^H (E_m)
+    calculate_contact_pdos_layered(system, leads, energy_list, contact, groups=None) -> [m, n_g]   (a lead's share)
 
 Per energy the work is L inverses and a handful of products of layer size instead of one N x N inverse.
-Everything that needs more of G than its blocks on the pattern of S and its two corner blocks raises instead of
-guessing: G Gamma G^H / GrLessInt, eigenchannels, probes, bond currents, spin layouts other than 'r', sharding over
-ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``) is host-side numpy.
+G Gamma_c G^H is formed on the pattern of S only -- what Tr[P S], a tight-binding Fock builder and the Mulliken populations
+read -- from the columns of G on the lead's orbitals, which the two sweeps yield at a few n^2 K products per layer.
+Everything that needs more of G than that raises instead of guessing: eigenchannels, probes, bond currents, spin
+layouts other than 'r', sharding over ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``)
+is host-side numpy.
 """
 import numpy as np
 
@@ -218,6 +222,14 @@ class _Bound:
             self.close()
             raise
 
+    def term_of(self, ind):
+        """the engine's terminal number of lead ``ind`` (negative: from the end), None: all"""
+        if ind is None:
+            return None
+        if not -len(self.terms) <= int(ind) < len(self.terms):
+            raise ValueError(f"lead {ind} of {len(self.terms)}")
+        return self.terms[int(ind)]
+
     def close(self):
         if self.h is not None:
             self.eng.layered_free(self.h)
@@ -261,9 +273,13 @@ def calculate_pdos_layered(system, leads, energy_list, groups=None, contact=None
     ``groups`` maps the N orbitals (layer order) to groups, None: every orbital its own."""
     _only_restricted(spin)
     if contact is not None:
-        raise NotImplementedError("the contact-resolved populations need G Gamma G^H, which the layered path does not form")
+        raise NotImplementedError("the contact-resolved populations are calculate_contact_pdos_layered's")
     with _Bound(system, leads, engine) as b:
         _, site = b.eng.layered_dos(b.h, np.asarray(energy_list), mulliken=True)
+    return _grouped(system, site, groups)
+
+
+def _grouped(system, site, groups):
     if groups is None:
         return site
     groups = np.asarray(groups, dtype=int).ravel()
@@ -275,21 +291,37 @@ def calculate_pdos_layered(system, leads, energy_list, groups=None, contact=None
     return out
 
 
+def calculate_contact_pdos_layered(system, leads, energy_list, contact, groups=None, spin=None, engine=None):
+    """The share of lead ``contact`` (an index into ``leads``, None: all of them) in the Mulliken projected DOS [m, n_g],
+    row a = sum_{i in a} (1/2pi) Re sum_j (G Gamma_c G^H)_ij conj(S_ij), as calculate_pdos with a contact; ``groups`` as
+    calculate_pdos_layered's."""
+    _only_restricted(spin)
+    with _Bound(system, leads, engine) as b:
+        _, site = b.eng.layered_contact_dos(b.h, b.term_of(contact), np.asarray(energy_list))
+    return _grouped(system, site, groups)
+
+
 def GrIntLayered(system, leads, Elist, weights, engine=None):
     """sum_m w_m G(E_m) on the pattern of S, as GrInt: (diagonal blocks, upper blocks G_{i,i+1}, lower blocks G_{i+1,i})."""
     with _Bound(system, leads, engine) as b:
         return b.eng.layered_gr_int(b.h, np.asarray(Elist), np.asarray(weights))
 
 
+def GrLessIntLayered(system, leads, Elist, weights, ind=None, engine=None):
+    """sum_m w_m G Gamma G^H (E_m) on the pattern of S, as GrLessInt: (diagonal blocks, upper blocks (i, i+1), lower blocks
+    (i+1, i)); ``ind`` indexes ``leads``, None: Gamma of all of them."""
+    with _Bound(system, leads, engine) as b:
+        return b.eng.layered_gless_int(b.h, b.term_of(ind), np.asarray(Elist), np.asarray(weights))
+
+
 def _not_served(name):
     def fn(*args, **kwargs):
-        raise NotImplementedError(f"{name} is not served on layered systems: it needs blocks of G outside the pattern of S "
-                                  "and the two corner blocks (use the dense engine on system.to_dense())")
+        raise NotImplementedError(f"{name} is not served on layered systems: it needs blocks of G outside the pattern of S, "
+                                  "the two corner blocks and the leads' columns (use the dense engine on system.to_dense())")
     fn.__name__ = name
     return fn
 
 
-GrLessIntLayered = _not_served("GrLessIntLayered")
 calculate_transmission_channels_layered = _not_served("calculate_transmission_channels_layered")
 calculate_local_transmission_layered = _not_served("calculate_local_transmission_layered")
 calculate_transmission_matrix_layered = _not_served("calculate_transmission_matrix_layered")

@@ -518,8 +518,8 @@ int negf_gr_int_probes_dev(negf_ctx* ctx, int handle, int n_probes, const int* p
  * A singular layer sets info[k] = the 1-based column of the zero pivot counted over the whole system and returns
  * NEGF_ESINGULAR, as the dense calls do.  negf_set_batch and negf_set_inverse_algo apply.  Every sum has a fixed order:
  * results are bitwise equal from run to run, do not depend on negf_set_batch, and permuting the energies permutes them.
- * Not served: G Gamma G^H / GrLessInt, eigenchannels, probes and bond currents on a layered system,
- * terminals on interior layers, spin layouts other than 'r', sharding, checkpoints. */
+ * Not served: eigenchannels, probes and bond currents on a layered system, terminals on interior layers,
+ * spin layouts other than 'r', sharding, checkpoints. */
 int negf_layered_create(negf_ctx* ctx, int n_layers, const int* sizes, const double* F_diag_c128, const double* F_up_c128,
                         const double* S_diag_c128, const double* S_up_c128, int* handle);
 int negf_layered_free(negf_ctx* ctx, int handle);
@@ -567,8 +567,36 @@ int negf_layered_gr_int(negf_ctx* ctx, int handle, int m, const double* E_c128, 
                         double* out_c128, int* info);
 int negf_layered_gr_int_dev(negf_ctx* ctx, int handle, int m, const double* E_dev, const double* w_dev,
                             double* out_dev);
+/* A_c = G Gamma_c G^H on the pattern of S, Gamma_c = i (Sigma_c - Sigma_c^H).  A terminal touches K orbitals J of its end
+ * layer, so only the columns W_i = G_{i,end}[:, J] (n_i x K) are formed, from what the two sweeps hold anyway:
+ *   terminal on the last layer:  W_{L-1} = G_{L-1,L-1}[:, J],  W_i = g_i C_{i,i+1} W_{i+1}                  (C = -A)
+ *   terminal on layer 0:         x_0 = g_0[:, J],  z_i = C_{i,i-1} x_{i-1},  x_i = g_i z_i  (forward, the z_i kept);
+ *                                W_0 = G_00[:, J],  W_i = G_ii z_i                          (backward)
+ *   A_ii = (W_i Gamma) W_i^H,  A_{i,i+1} = (W_i Gamma) W_{i+1}^H;  A_{i+1,i} = A_{i,i+1}^H is never formed.
+ * `ind`: a terminal number in [-n_t, n_t), negative values counted from the end as negf_gless_int reads them, or
+ * NEGF_IND_TOTAL = all terminals of both ends.  Each end has ONE column set on the union of the selected terminals'
+ * orbitals (ascending); its Gamma is the sum of theirs in the order the terminals were made, and the contribution of
+ * layer 0's set to an element is added before the last layer's.  NEGF_EINVAL before anything is launched: an unknown
+ * handle, `ind` outside the range, NEGF_IND_TOTAL on a system without terminals, more energies than a `blocks` terminal
+ * holds, null pointers.  A singular layer reports as negf_layered_gr_int's does.
+ *
+ * negf_layered_gless_int: sum_k w_k A(E_k) -- GrLessInt, integrate.py:177-208 (densityGrid, density.py:605-658), in
+ * negf_layered_gr_int's layout.  The weights are complex: the lower blocks are sum_k w_k conj(A_{i,i+1}(E_k))^T, which is
+ * the conjugate transpose of the upper sum only for real weights.  Energy k enters every element's sum after k - 1. */
+int negf_layered_gless_int(negf_ctx* ctx, int handle, int ind, int m, const double* E_c128, const double* w_c128,
+                           double* out_c128, int* info);
+int negf_layered_gless_int_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, const double* w_dev,
+                               double* out_dev);
+/* The contact-resolved Mulliken PDOS, dos_site[k][i] = (1/2pi) Re sum_j A_ij(E_k) conj(S_ij) over the pattern -- the rows
+ * of negf_population's contact form with X = S, rows_only = 1 (calculate_pdos with a contact); dos_total[k] = their sum.
+ * dos_total [m], dos_site [m][N] (may be NULL in the host form only). */
+int negf_layered_contact_dos(negf_ctx* ctx, int handle, int ind, int m, const double* E_c128, double* dos_total,
+                             double* dos_site, int* info);
+int negf_layered_contact_dos_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, double* dos_total_dev,
+                                 double* dos_site_dev);
 /* device bytes of the work areas of the system's last call: (10 + L for a backward sweep) matrices of the largest layer
- * per energy in flight */
+ * per energy in flight, and for a G Gamma G^H call its column sets -- with cs = n_max K_max: (L + 4) cs + K^2 for the set of
+ * layer 0 (the z_i, x twice, W twice, Y, Gamma), 3 cs + K^2 for the last layer's */
 int negf_layered_workspace_bytes(negf_ctx* ctx, int handle, long long* work);
 
 /* ------------------------------------------------------------- diagnostics */
