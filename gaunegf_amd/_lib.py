@@ -106,6 +106,8 @@ SIGNATURES = {
     "negf_layered_gless_int_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "negf_layered_contact_dos": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "negf_layered_contact_dos_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "negf_layered_transmission_matrix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "negf_layered_transmission_matrix_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     "negf_layered_workspace_bytes": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_longlong)]),
     "negf_sync": (C.c_int, [_vp]),
     "negf_last_info": (C.c_int, [_vp, C.c_int, _vp]),

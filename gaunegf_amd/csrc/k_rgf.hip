@@ -9,6 +9,9 @@
 //   rgf_gather_cols / rgf_gamma_union / rgf_accumulate_ct / rgf_pop_*: the passes of G Gamma G^H on the pattern of S
 //                   (negf_layered_gless_int, negf_layered_contact_dos): the columns G[:, J] of a terminal set, its Gamma
 //                   on the union list J, the conjugate-transposed sum of the lower blocks, the contact Mulliken rows
+//   rgf_sub_probes / rgf_strip_pair: the transmission matrix with probes on any layer (negf_layered_transmission_matrix):
+//                   the probes' Sigma blocks subtracted from an assembled diagonal matrix, and T[a][b] of the terminal pairs
+//                   of one layer level from the column strip [G_ii[:, J_i] | G_{i,i+1}[:, J_{i+1}] | ...] of that level
 // Every matrix of a batch is compact row-major (leading dimension = its own column count) at a batch stride the
 // caller gives; consecutive lanes touch consecutive 16-byte elements.  No atomics.
 #include "negf_common.h"
@@ -211,8 +214,9 @@ void launch_rgf_accumulate(hipStream_t st, int count, int nb, const cplx* w, con
 }
 
 // out[b][r][a] = G[b][r][idx[a]]: the K columns `idx` of an n x n matrix, compact n x K
+// (ld: the leading dimension of out -- K for a compact set, the strip's width for the head of a column strip)
 __global__ __launch_bounds__(RGF_THREADS) void rgf_gather_cols_kernel(
-    int n, int K, const cplx* __restrict__ G, size_t strideG, const int* __restrict__ idx, cplx* __restrict__ out,
+    int n, int K, int ld, const cplx* __restrict__ G, size_t strideG, const int* __restrict__ idx, cplx* __restrict__ out,
     size_t stride_out)
 {
     const int b = blockIdx.y;
@@ -221,14 +225,22 @@ __global__ __launch_bounds__(RGF_THREADS) void rgf_gather_cols_kernel(
     const int cnt = n * K;
     for (int t = blockIdx.x * RGF_THREADS + threadIdx.x; t < cnt; t += gridDim.x * RGF_THREADS) {
         const int r = t / K, a = t - r * K;
-        o[t] = g[(size_t)r * n + idx[a]];
+        o[(size_t)r * ld + a] = g[(size_t)r * n + idx[a]];
     }
 }
 
 void launch_rgf_gather_cols(hipStream_t st, int n, int K, int nb, const cplx* G, size_t strideG, const int* idx, cplx* out,
                             size_t stride_out)
 {
-    hipLaunchKernelGGL(rgf_gather_cols_kernel, dim3(rgf_grid((size_t)n * K), nb), dim3(RGF_THREADS), 0, st, n, K, G,
+    hipLaunchKernelGGL(rgf_gather_cols_kernel, dim3(rgf_grid((size_t)n * K), nb), dim3(RGF_THREADS), 0, st, n, K, K, G,
+                       strideG, idx, out, stride_out);
+}
+
+void launch_rgf_strip_head(hipStream_t st, int n, int K, int ld, int nb, const cplx* G, size_t strideG, const int* idx,
+                           cplx* out, size_t stride_out)
+{
+    if (K <= 0 || nb <= 0) return;
+    hipLaunchKernelGGL(rgf_gather_cols_kernel, dim3(rgf_grid((size_t)n * K), nb), dim3(RGF_THREADS), 0, st, n, K, ld, G,
                        strideG, idx, out, stride_out);
 }
 
@@ -357,4 +369,112 @@ __global__ void rgf_merge_info_kernel(int nb, int offset, const int* __restrict_
 void launch_rgf_merge_info(hipStream_t st, int nb, int offset, const int* linfo, int* info)
 {
     hipLaunchKernelGGL(rgf_merge_info_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, nb, offset, linfo, info);
+}
+
+// ------------------------------------------------------------ probes of a layer into its assembled matrix
+// D[b][I_p, I_p] -= Sigma_p for the probes order[0 .. n_probes) (terminal numbers) of ONE layer, one after the other in
+// that order (the host sorts them by content: overlapping probes meet in an order the caller's listing does not change).
+// One workgroup per energy; inside a probe the indices are distinct, so every element is touched by one thread.
+// rows: the probes' orbitals counted inside the layer, at ioff[t]; sig: their blocks, at soff[t], the same for all energies.
+__global__ __launch_bounds__(RGF_THREADS) void rgf_sub_probes_kernel(
+    int n, int n_probes, const int* __restrict__ order, const int* __restrict__ tK, const int* __restrict__ ioff,
+    const int* __restrict__ soff, const int* __restrict__ rows, const cplx* __restrict__ sig, cplx* __restrict__ D,
+    size_t strideD)
+{
+    cplx* Db = D + (size_t)blockIdx.x * strideD;
+    for (int q = 0; q < n_probes; ++q) {
+        const int t = order[q];
+        const int K = tK[t];
+        const int* I = rows + ioff[t];
+        const cplx* s = sig + soff[t];
+        for (int e = threadIdx.x; e < K * K; e += RGF_THREADS) {
+            const int i = e / K, j = e - i * K;
+            const size_t at = (size_t)I[i] * n + I[j];
+            Db[at] = csub(Db[at], s[e]);
+        }
+        __syncthreads();
+    }
+}
+
+void launch_rgf_sub_probes(hipStream_t st, int n, int n_probes, int nb, const int* order, const int* tK, const int* ioff,
+                           const int* soff, const int* rows, const cplx* sig, cplx* D, size_t strideD)
+{
+    if (n_probes <= 0 || nb <= 0) return;
+    hipLaunchKernelGGL(rgf_sub_probes_kernel, dim3(nb), dim3(RGF_THREADS), 0, st, n, n_probes, order, tK, ioff, soff, rows,
+                       sig, D, strideD);
+}
+
+// ------------------------------------------------------------ one terminal pair per workgroup, G_ab read from a strip
+// T[b][a][b'] = Re sum_ij (Gamma_a G_ab Gamma_b')_ij conj(G_ab,ij) for the pairs (a * C + b') of one layer level and one
+// class (tmat_pair_class).  G_ab,ij = strip[b][rows_a[i]][tcol[b'] - col0 + cpos_b'[j]]: a's orbitals are rows of the
+// level's layer, b''s orbitals columns of the strip through their position in the union list of b''s layer (cpos) and
+// that list's first column (tcol[b'] - col0).  Gamma_t: gstat + goff[t] where gstride[t] = 0, gdyn + b gstride[t] + goff[t]
+// otherwise.  LDS and every summation order are tmat_pair_kernel's (k_tmatrix.hip): element t = i K_b + j belongs to thread
+// t mod THREADS, which adds its elements in ascending t, the k sums run in ascending k, and the threads' sums meet in a
+// binary tree over the thread index.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void rgf_strip_pair_kernel(
+    int C, const int* __restrict__ pairs, const int* __restrict__ tK, const int* __restrict__ ioff,
+    const int* __restrict__ goff, const int* __restrict__ gstride, const int* __restrict__ tcol, int col0,
+    const int* __restrict__ rows, const int* __restrict__ cpos, const cplx* __restrict__ strip, int ld, size_t strideS,
+    const cplx* __restrict__ gstat, const cplx* __restrict__ gdyn, double* __restrict__ T)
+{
+    extern __shared__ cplx rgf_pair_lds[];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int pr = pairs[blockIdx.x];
+    const int ta = pr / C, tb = pr - ta * C;
+    const int Ka = tK[ta], Kb = tK[tb], ne = Ka * Kb;
+    cplx* sG = rgf_pair_lds;
+    cplx* sX = sG + ne;
+    double* red = reinterpret_cast<double*>(sX + ne);
+    const int* Ia = rows + ioff[ta];
+    const int* Jb = cpos + ioff[tb];
+    const cplx* Sb = strip + (size_t)b * strideS + (tcol[tb] - col0);
+    const cplx* Ga = gstride[ta] ? gdyn + (size_t)b * gstride[ta] + goff[ta] : gstat + goff[ta];
+    const cplx* Gm = gstride[tb] ? gdyn + (size_t)b * gstride[tb] + goff[tb] : gstat + goff[tb];
+    for (int t = tid; t < ne; t += THREADS) {
+        const int i = t / Kb, j = t - i * Kb;
+        sG[t] = Sb[(size_t)Ia[i] * ld + Jb[j]];
+    }
+    __syncthreads();
+    for (int t = tid; t < ne; t += THREADS) {
+        const int i = t / Kb, j = t - i * Kb;
+        cplx acc = cmake(0.0, 0.0);
+        for (int k = 0; k < Ka; ++k) acc = cfma(acc, Ga[i * Ka + k], sG[k * Kb + j]);
+        sX[t] = acc;
+    }
+    __syncthreads();
+    double s = 0.0;
+    for (int t = tid; t < ne; t += THREADS) {
+        const int i = t / Kb, j = t - i * Kb;
+        cplx acc = cmake(0.0, 0.0);
+        for (int k = 0; k < Kb; ++k) acc = cfma(acc, sX[i * Kb + k], Gm[k * Kb + j]);
+        const cplx g = sG[t];
+        s += acc.x * g.x + acc.y * g.y;
+    }
+    red[tid] = s;
+    __syncthreads();
+#pragma unroll
+    for (int off = THREADS / 2; off > 0; off >>= 1) {
+        if (tid < off) red[tid] += red[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) T[((size_t)b * C + ta) * C + tb] = red[0];
+}
+
+void launch_rgf_strip_pairs(hipStream_t st, int cls, int C, int npairs, int max_elems, int nb, const int* pairs,
+                            const int* tK, const int* ioff, const int* goff, const int* gstride, const int* tcol, int col0,
+                            const int* rows, const int* cpos, const cplx* strip, int ld, size_t strideS, const cplx* gstat,
+                            const cplx* gdyn, double* T)
+{
+    if (npairs <= 0 || nb <= 0) return;
+    if (cls == 1) {
+        const size_t lds = (size_t)2 * max_elems * sizeof(cplx) + 64 * sizeof(double);
+        hipLaunchKernelGGL(rgf_strip_pair_kernel<64>, dim3(npairs, nb), dim3(64), lds, st, C, pairs, tK, ioff, goff, gstride,
+                           tcol, col0, rows, cpos, strip, ld, strideS, gstat, gdyn, T);
+    } else {
+        const size_t lds = (size_t)2 * max_elems * sizeof(cplx) + 256 * sizeof(double);
+        hipLaunchKernelGGL(rgf_strip_pair_kernel<256>, dim3(npairs, nb), dim3(256), lds, st, C, pairs, tK, ioff, goff,
+                           gstride, tcol, col0, rows, cpos, strip, ld, strideS, gstat, gdyn, T);
+    }
 }

@@ -572,6 +572,20 @@ void launch_rgf_accumulate_ct(hipStream_t st, int nr, int nc, int nb, const cplx
 void launch_rgf_pop_block(hipStream_t st, int nr, int nk, int nb, const cplx* A, size_t strideA, const cplx* X,
                           double* row_site, bool accumulate_rows, double* col_site, size_t site_stride);
 void launch_rgf_merge_info(hipStream_t st, int nb, int offset, const int* linfo, int* info);
+// Transmission matrix with probes on any layer (negf_layered_transmission_matrix):
+// the columns idx of G into the first K columns of a strip of width ld (out[b][r * ld + a] = G[b][r][idx[a]])
+void launch_rgf_strip_head(hipStream_t st, int n, int K, int ld, int nb, const cplx* G, size_t strideG, const int* idx,
+                           cplx* out, size_t stride_out);
+// D[b][I_p, I_p] -= Sigma_p for the probes order[0 .. n_probes) of one layer, one after the other (tables as k_tmatrix's,
+// rows = the orbitals counted inside the layer)
+void launch_rgf_sub_probes(hipStream_t st, int n, int n_probes, int nb, const int* order, const int* tK, const int* ioff,
+                           const int* soff, const int* rows, const cplx* sig, cplx* D, size_t strideD);
+// T[b][a][b'] for the pairs (a * C + b') of one layer level and one class (tmat_pair_class 1 / 2) from the level's column
+// strip (n_i x ld at strideS): row rows[ioff[a] + i], column tcol[b'] - col0 + cpos[ioff[b'] + j]; max_elems >= K_a K_b
+void launch_rgf_strip_pairs(hipStream_t st, int cls, int C, int npairs, int max_elems, int nb, const int* pairs,
+                            const int* tK, const int* ioff, const int* goff, const int* gstride, const int* tcol, int col0,
+                            const int* rows, const int* cpos, const cplx* strip, int ld, size_t strideS, const cplx* gstat,
+                            const cplx* gdyn, double* T);
 
 bool small_fused_supported(int n);
 int small_fused_grid(int n, int m);

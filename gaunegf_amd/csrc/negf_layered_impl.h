@@ -17,6 +17,11 @@
 //              layer 0:     x_0 = g_0[:, J],  z_i = C_{i,i-1} x_{i-1},  x_i = g_i z_i          (forward sweep, the z_i kept)
 //                           W_0 = G_00[:, J],  W_i = G_ii z_i                                  (backward sweep)
 //              A_ii = (W_i Gamma) W_i^H,   A_{i,i+1} = (W_i Gamma) W_{i+1}^H,   A_{i+1,i} = A_{i,i+1}^H never formed
+//   strips     of the transmission matrix between ALL terminals, probes on any layer included (rgf_tmat_*): with J_q the
+//              union of the orbitals of the terminals on layer q,
+//              strip_{L-1} = [G_{L-1,L-1}[:, J_{L-1}]],   strip_i = [G_ii[:, J_i] | U_i strip_{i+1}]   (backward sweep)
+//              holds G_{i,q}[:, J_q] for every q >= i: the pairs (a on layer i, b on a layer >= i) are read from it, the
+//              pairs with b on an earlier layer from the same pass over the layers in REVERSE order
 // Every layer matrix of a batch is compact row-major at ONE batch stride (the largest layer's n^2): the inverses and
 // products are the dense path's launchers, batched over the energies.
 
@@ -46,10 +51,13 @@ struct LayeredSystem {
     DevBuf<cplx> d_pool;                        // [RGF_NBUF][batch][stride] work areas
     DevBuf<cplx> d_gstore;                      // [L][batch][stride] the g_i of a backward sweep
     DevBuf<cplx> d_small;                       // Gamma_a | Gamma_b | G_ab | X | Y of the transmission
-    DevBuf<cplx> d_cols;                        // column sets of G Gamma G^H: z_i | x | W | Y | Gamma, per energy in flight
+    DevBuf<cplx> d_cols;                        // column sets of G Gamma G^H: z_i | x | W | Y | Gamma, per energy in flight;
+                                                // of a transmission matrix: strip | strip | Gamma(E) | G_ab | X | Y
     DevBuf<int> d_J;                            // [2][nmax] their union lists, layer 0's then the last layer's
     DevBuf<cplx> d_out;                         // gr_int: the block lists, host-pointer entry point
     DevBuf<double> d_site;                      // dos: [m][N] staging of the host-pointer entry point
+    DevBuf<int> d_tm_tab;                       // transmission matrix: the terminal tables, union lists and pair lists
+    DevBuf<cplx> d_tm_sig, d_tm_gam;            // ... the probes' Sigma blocks; the Gamma blocks that do not depend on E
     DevBuf<int> d_piv, d_linfo, d_iters, d_conv;
     int batch = 0;                              // energies the work areas are laid out for
     long long work_bytes = 0;                   // of the last call: pool + stored g + column sets
@@ -73,7 +81,8 @@ void free_layered(LayeredSystem* ls)
     dev_free(ls->dFd); dev_free(ls->dSd); dev_free(ls->dFu); dev_free(ls->dSu); dev_free(ls->dFl); dev_free(ls->dSl);
     release_bufs(ls->d_pool, ls->d_gstore, ls->d_small, ls->d_out, ls->d_cols);
     release_bufs(ls->d_site);
-    release_bufs(ls->d_J);
+    release_bufs(ls->d_J, ls->d_tm_tab);
+    release_bufs(ls->d_tm_sig, ls->d_tm_gam);
     release_bufs(ls->d_piv, ls->d_linfo, ls->d_iters, ls->d_conv);
     delete ls;
 }
@@ -546,6 +555,290 @@ void rgf_consume_less_dos(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb,
                               site + ls->off[i + 1], (size_t)ls->N);
 }
 
+// ------------------------------------------------- transmission matrix between all terminals, probes on any layer
+// Terminals: the system's end terminals in the order they were made, then the call's probes (orbital lists numbered in
+// the whole system, each inside ONE layer).  Two passes of forward sweep (g_i kept) and backward sweep with column strips:
+// pass 0 over the layers as they are serves the pairs (a, b) with layer(b) >= layer(a), pass 1 over the layers in reverse
+// order (view level i = layer L - 1 - i, C_{i,i+1} and C_{i+1,i} swapped -- a view, no block is copied) the others.
+struct RgfTmatPlan {
+    int C = 0, nt = 0, n_probes = 0, Ktot = 0;
+    std::vector<int> K, layer, ioff, goff, gstride, soff;      // per terminal
+    std::vector<int> tcol[2];                                  // first strip column of the terminal's layer, per pass
+    std::vector<int> rows, cpos;                               // per terminal orbital: index inside its layer, position in J
+    std::vector<int> nJ, Joff, J;                              // per layer: |J_q|, start in J; the union lists, ascending
+    std::vector<int> colbase[2];                               // per layer and pass: columns of the layers before it in view
+    std::vector<int> porder, poff;                             // the probes of layer q in content order: porder[poff[q] .. poff[q+1])
+    std::vector<int> pairs;                                    // a * C + b, grouped by (pass, level, class)
+    std::vector<int> pair_at, pair_n;                          // [(pass * L + level) * 3 + class]
+    int max_elems[3] = {0, 0, 0};
+    size_t psum = 0, stat = 0, dyn = 0, big_kk = 0;            // sum K_p^2 | static Gamma elements | per-energy ones | class 0
+    bool two_pass = false;
+    // device tables
+    const int *dK = nullptr, *d_ioff = nullptr, *d_goff = nullptr, *d_gstride = nullptr, *d_soff = nullptr;
+    const int *d_tcol[2] = {nullptr, nullptr}, *d_rows = nullptr, *d_cpos = nullptr, *d_J = nullptr, *d_porder = nullptr;
+    const int* d_pairs = nullptr;
+    // work areas of the batch in flight
+    size_t cs = 0, per_energy = 0;
+    cplx *strip[2] = {nullptr, nullptr}, *gdyn = nullptr, *Gab = nullptr, *Xs = nullptr, *Ys = nullptr;
+};
+
+// validation and the host tables; NEGF_EINVAL before anything is launched
+int rgf_tmat_plan(LayeredSystem* ls, int n_probes, const int* probe_nk, const int* probe_inds, const cplx* psig, RgfTmatPlan* pl)
+{
+    if (n_probes < 0 || (n_probes > 0 && (!probe_nk || !probe_inds || !psig))) return NEGF_EINVAL;
+    const int L = ls->L, nt = (int)ls->terms.size();
+    if ((long)nt + n_probes > TMAT_MAX_TERMINALS || nt + n_probes == 0) return NEGF_EINVAL;
+    const int C = nt + n_probes;
+    pl->C = C; pl->nt = nt; pl->n_probes = n_probes;
+    pl->K.resize(C); pl->layer.resize(C); pl->ioff.resize(C); pl->goff.resize(C); pl->gstride.resize(C); pl->soff.assign(C, 0);
+    for (int t = 0; t < nt; ++t) {
+        const RgfTerminal* T = ls->terms[t];
+        pl->K[t] = T->K; pl->layer[t] = T->end == 0 ? 0 : L - 1; pl->ioff[t] = (int)pl->rows.size();
+        pl->rows.insert(pl->rows.end(), T->idx.begin(), T->idx.end());
+    }
+    std::vector<char> seen((size_t)ls->N, 0);
+    size_t isum = 0, psum = 0;
+    for (int q = 0; q < n_probes; ++q) {
+        const int t = nt + q, k = probe_nk[q];
+        if (k < 1) return NEGF_EINVAL;
+        const int* I = probe_inds + isum;
+        int lay = -1;
+        for (int i = 0; i < k; ++i) {
+            const int v = I[i];
+            if (v < 0 || v >= ls->N || seen[v]) return NEGF_EINVAL;
+            seen[v] = 1;
+            const int l = (int)(std::upper_bound(ls->off.begin(), ls->off.end(), v) - ls->off.begin()) - 1;
+            if (lay >= 0 && l != lay) return NEGF_EINVAL;                  // a probe lives on one layer
+            lay = l;
+        }
+        for (int i = 0; i < k; ++i) seen[I[i]] = 0;
+        pl->K[t] = k; pl->layer[t] = lay; pl->ioff[t] = (int)pl->rows.size(); pl->soff[t] = (int)psum;
+        for (int i = 0; i < k; ++i) pl->rows.push_back(I[i] - ls->off[lay]);
+        isum += k; psum += (size_t)k * k;
+        if (psum > ((size_t)1 << 30)) return NEGF_EINVAL;
+    }
+    pl->psum = psum;
+    // Gamma blocks: the probes' (at their Sigma's offsets) and the const terminals' once per call, the others per energy
+    size_t stat = psum, dyn = 0;
+    for (int t = 0; t < nt; ++t) {
+        const size_t kk = (size_t)pl->K[t] * pl->K[t];
+        if (ls->terms[t]->kind == 0) { pl->goff[t] = (int)stat; stat += kk; }
+        else { pl->goff[t] = (int)dyn; dyn += kk; }
+    }
+    for (int t = 0; t < nt; ++t) pl->gstride[t] = ls->terms[t]->kind == 0 ? 0 : (int)dyn;
+    for (int t = nt; t < C; ++t) { pl->goff[t] = pl->soff[t]; pl->gstride[t] = 0; }
+    pl->stat = stat; pl->dyn = dyn;
+    // union lists J_q and every terminal orbital's position in its layer's list
+    pl->nJ.assign(L, 0); pl->Joff.assign(L, 0);
+    std::vector<std::vector<int>> on(L);
+    for (int t = 0; t < C; ++t) on[pl->layer[t]].push_back(t);
+    pl->cpos.assign(pl->rows.size(), 0);
+    int first = L, last = -1;
+    for (int q = 0; q < L; ++q) {
+        pl->Joff[q] = (int)pl->J.size();
+        if (on[q].empty()) continue;
+        first = std::min(first, q); last = std::max(last, q);
+        std::vector<int> pos((size_t)ls->n[q], -1);
+        for (int t : on[q]) for (int i = 0; i < pl->K[t]; ++i) pos[pl->rows[pl->ioff[t] + i]] = 0;
+        int cnt = 0;
+        for (int o = 0; o < ls->n[q]; ++o) if (pos[o] == 0) { pos[o] = cnt++; pl->J.push_back(o); }
+        pl->nJ[q] = cnt;
+        for (int t : on[q]) for (int i = 0; i < pl->K[t]; ++i) pl->cpos[pl->ioff[t] + i] = pos[pl->rows[pl->ioff[t] + i]];
+    }
+    pl->Ktot = (int)pl->J.size();
+    pl->two_pass = first != last;
+    for (int pass = 0; pass < 2; ++pass) {
+        pl->colbase[pass].assign(L, 0);
+        int acc = 0;
+        for (int i = 0; i < L; ++i) { const int p = pass ? L - 1 - i : i; pl->colbase[pass][p] = acc; acc += pl->nJ[p]; }
+        pl->tcol[pass].resize(C);
+        for (int t = 0; t < C; ++t) pl->tcol[pass][t] = pl->colbase[pass][pl->layer[t]];
+    }
+    // the probes of each layer in content order: tmat_plan's comparison (size, orbital list, the block's values as numbers)
+    pl->poff.assign(L + 1, 0);
+    const double* sg = reinterpret_cast<const double*>(psig);
+    for (int q = 0; q < L; ++q) {
+        pl->poff[q] = (int)pl->porder.size();
+        const size_t at = pl->porder.size();
+        for (int t : on[q]) if (t >= nt) pl->porder.push_back(t);
+        std::stable_sort(pl->porder.begin() + at, pl->porder.end(), [&](int a, int b) {
+            const int ka = pl->K[a], kb = pl->K[b];
+            if (ka != kb) return ka < kb;
+            const int* ia = pl->rows.data() + pl->ioff[a];
+            const int* ib = pl->rows.data() + pl->ioff[b];
+            for (int i = 0; i < ka; ++i) if (ia[i] != ib[i]) return ia[i] < ib[i];
+            const double* xa = sg + 2 * (size_t)pl->soff[a];
+            const double* xb = sg + 2 * (size_t)pl->soff[b];
+            for (int i = 0; i < 2 * ka * ka; ++i) if (xa[i] != xb[i]) return xa[i] < xb[i];
+            return false;
+        });
+    }
+    pl->poff[L] = (int)pl->porder.size();
+    // pair lists: pass 0 takes b on a's layer or a later one, pass 1 b on an earlier one
+    pl->pair_at.assign((size_t)2 * L * 3, 0); pl->pair_n.assign((size_t)2 * L * 3, 0);
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < L; ++i) {
+            const int p = pass ? L - 1 - i : i;
+            std::vector<int> byc[3];
+            for (int a : on[p])
+                for (int b = 0; b < C; ++b) {
+                    const int lb = pl->layer[b];
+                    if (pass == 0 ? lb < p : lb >= p) continue;
+                    const int cls = tmat_pair_class(pl->K[a], pl->K[b]);
+                    byc[cls].push_back(a * C + b);
+                    const int ne = pl->K[a] * pl->K[b];
+                    pl->max_elems[cls] = std::max(pl->max_elems[cls], ne);
+                    if (cls == 0) pl->big_kk = std::max(pl->big_kk, (size_t)ne);
+                }
+            for (int cls = 0; cls < 3; ++cls) {
+                const size_t k = ((size_t)pass * L + i) * 3 + cls;
+                pl->pair_at[k] = (int)pl->pairs.size(); pl->pair_n[k] = (int)byc[cls].size();
+                pl->pairs.insert(pl->pairs.end(), byc[cls].begin(), byc[cls].end());
+            }
+        }
+    // per energy in flight: two strips of n_max K_tot, the Gamma blocks that depend on E, G_ab | X | Y of the class-0 pairs
+    pl->cs = (size_t)ls->nmax * pl->Ktot;
+    pl->per_energy = 2 * pl->cs + pl->dyn + 3 * pl->big_kk;
+    return NEGF_OK;
+}
+
+// the tables, the probes' Sigma and the Gamma blocks that do not depend on E, on the device
+int rgf_tmat_setup(negf_ctx* c, LayeredSystem* ls, const cplx* psig, RgfTmatPlan* pl)
+{
+    std::vector<int> tab;
+    size_t at[12]; int k = 0;
+    for (const std::vector<int>* v : {&pl->K, &pl->ioff, &pl->goff, &pl->gstride, &pl->soff, &pl->tcol[0], &pl->tcol[1], &pl->rows,
+                                      &pl->cpos, &pl->J, &pl->porder, &pl->pairs}) {
+        at[k++] = tab.size();
+        tab.insert(tab.end(), v->begin(), v->end());
+    }
+    int rc;
+    if ((rc = ensure_cap(c, ls->d_tm_tab, tab.size() + 1)) || (rc = upload(c, ls->d_tm_tab.p, tab.data(), tab.size()))) return rc;
+    const int* d = ls->d_tm_tab;
+    pl->dK = d + at[0]; pl->d_ioff = d + at[1]; pl->d_goff = d + at[2]; pl->d_gstride = d + at[3]; pl->d_soff = d + at[4];
+    pl->d_tcol[0] = d + at[5]; pl->d_tcol[1] = d + at[6]; pl->d_rows = d + at[7]; pl->d_cpos = d + at[8]; pl->d_J = d + at[9];
+    pl->d_porder = d + at[10]; pl->d_pairs = d + at[11];
+    if ((rc = ensure_cap(c, ls->d_tm_gam, pl->stat + 1))) return rc;
+    if (pl->n_probes > 0 && ((rc = ensure_cap(c, ls->d_tm_sig, pl->psum)) || (rc = upload(c, ls->d_tm_sig.p, psig, pl->psum)))) return rc;
+    ProfScope ps(c, "tmat");
+    launch_tmat_gamma(c->stream, pl->nt, pl->n_probes, 1, pl->dK, pl->d_soff, pl->d_goff, pl->d_gstride, ls->d_tm_sig, 0, ls->d_tm_gam);
+    for (int t = 0; t < pl->nt; ++t)
+        if (ls->terms[t]->kind == 0) launch_rgf_gamma(c->stream, pl->K[t], 1, ls->terms[t]->d_sig, 0, ls->d_tm_gam + pl->goff[t], 0);
+    return NEGF_OK;
+}
+
+// the pairs of view level i of a pass, read from the level's strip (n x ld)
+void rgf_tmat_pairs(negf_ctx* c, LayeredSystem* ls, const RgfTmatPlan& pl, int pass, int i, int nb, const cplx* strip, int ld, double* T)
+{
+    const int L = ls->L, C = pl.C, p = pass ? L - 1 - i : i;
+    const int col0 = pl.colbase[pass][p];
+    const size_t k0 = ((size_t)pass * L + i) * 3;
+    if (pl.pair_n[k0] + pl.pair_n[k0 + 1] + pl.pair_n[k0 + 2] == 0) return;
+    ProfScope ps(c, "tmat");
+    double cmadds = 0;
+    for (int cls = 1; cls <= 2; ++cls) {
+        launch_rgf_strip_pairs(c->stream, cls, C, pl.pair_n[k0 + cls], pl.max_elems[cls], nb, pl.d_pairs + pl.pair_at[k0 + cls],
+                               pl.dK, pl.d_ioff, pl.d_goff, pl.d_gstride, pl.d_tcol[pass], col0, pl.d_rows, pl.d_cpos, strip, ld,
+                               pl.cs, ls->d_tm_gam, pl.gdyn, T);
+        for (int q = 0; q < pl.pair_n[k0 + cls]; ++q) {
+            const int pr = pl.pairs[pl.pair_at[k0 + cls] + q];
+            const double ka = pl.K[pr / C], kb = pl.K[pr % C];
+            cmadds += ka * kb * (ka + kb);
+        }
+    }
+    negf_count_flops(8.0 * cmadds * nb, 0.0);
+    // two lead-sized blocks, or blocks beyond the pair kernel's LDS: gather, two products on the matrix cores, trace
+    for (int q = 0; q < pl.pair_n[k0]; ++q) {
+        const int pr = pl.pairs[pl.pair_at[k0] + q];
+        const int a = pr / C, b = pr - a * C, Ka = pl.K[a], Kb = pl.K[b];
+        const size_t kk = (size_t)Ka * Kb;
+        const cplx* ga = pl.gstride[a] ? pl.gdyn + pl.goff[a] : ls->d_tm_gam + pl.goff[a];
+        const cplx* gb = pl.gstride[b] ? pl.gdyn + pl.goff[b] : ls->d_tm_gam + pl.goff[b];
+        launch_gather_block(c->stream, ld, Ka, Kb, nb, strip + (pl.tcol[pass][b] - col0), pl.cs, pl.d_rows + pl.ioff[a],
+                            pl.d_cpos + pl.ioff[b], pl.Gab, kk);
+        launch_zgemm(c->stream, Ka, Kb, Ka, nb, ga, Ka, (size_t)pl.gstride[a], pl.Gab, Kb, kk, 0, pl.Xs, Kb, kk);
+        launch_zgemm(c->stream, Ka, Kb, Kb, nb, pl.Xs, Kb, kk, gb, Kb, (size_t)pl.gstride[b], 0, pl.Ys, Kb, kk);
+        launch_trace_dot(c->stream, Ka, Kb, nb, pl.Ys, Kb, kk, pl.Gab, Kb, kk, T + (size_t)a * C + b, C * C);
+    }
+}
+
+// One pass of the batch [m0, m0 + nb): forward sweep with the g_i kept (the probes in the diagonal), backward sweep with
+// the column strips, the pairs of every level consumed from its strip.  Level i of the view is layer p(i) = i (pass 0) or
+// L - 1 - i (pass 1); the view's C_{i,i+1} is the lower block of the pair in pass 1.  Work areas: buf[0..8], d_gstore.
+int rgf_tmat_pass(negf_ctx* c, const RgfRun& r, const RgfTmatPlan& pl, int pass, int m0, int nb, const cplx* E, double* T)
+{
+    LayeredSystem* ls = r.ls;
+    const int L = ls->L;
+    const size_t s = ls->stride;
+    const size_t layer_bytes = (size_t)nb * s * sizeof(cplx);
+    cplx *CU = r.buf[0], *CL = r.buf[1], *U = r.buf[2], *V = r.buf[3], *Wm = r.buf[4], *Gup = r.buf[5], *B = r.buf[6];
+    cplx *Gcur = r.buf[7], *Galt = r.buf[8];
+    int* info = c->d_info + m0;
+    auto phys = [&](int i) { return pass ? L - 1 - i : i; };
+    auto g_of = [&](int i) { return ls->d_gstore + (size_t)i * r.nb_max * s; };
+    // the negated couplings between view levels i and i + 1: CU = C_{i,i+1}, CL = C_{i+1,i}
+    auto couplings = [&](int i) {
+        ProfScope ps(c, "rgf");
+        const int q = pass ? phys(i + 1) : i;                          // the pair (q, q + 1) of the system
+        const int cnt = ls->n[q] * ls->n[q + 1];
+        const cplx *Su = ls->dSu + ls->uoff[q], *Fu = ls->dFu + ls->uoff[q], *Sl = ls->dSl + ls->uoff[q], *Fl = ls->dFl + ls->uoff[q];
+        launch_rgf_coupling(c->stream, cnt, nb, E + m0, pass ? Sl : Su, pass ? Fl : Fu, CU, s);
+        launch_rgf_coupling(c->stream, cnt, nb, E + m0, pass ? Su : Sl, pass ? Fu : Fl, CL, s);
+    };
+    int rc;
+    for (int i = 0; i < L; ++i) {
+        const int p = phys(i), ni = ls->n[p];
+        cplx* D = g_of(i);
+        if (i > 0) {
+            const int np = ls->n[phys(i - 1)];
+            couplings(i - 1);
+            rgf_mm(c, ls, ni, np, np, nb, CL, g_of(i - 1), U);         // C_{i,i-1} g_{i-1}
+            rgf_mm(c, ls, ni, ni, np, nb, U, CU, V);                   // ... C_{i-1,i}
+        }
+        rgf_assemble_diag(c, ls, p, m0, nb, E, i > 0 ? V : nullptr, D);
+        if (pl.poff[p + 1] > pl.poff[p]) {
+            ProfScope ps(c, "rgf");
+            launch_rgf_sub_probes(c->stream, ni, pl.poff[p + 1] - pl.poff[p], nb, pl.d_porder + pl.poff[p], pl.dK, pl.d_ioff,
+                                  pl.d_soff, pl.d_rows, ls->d_tm_sig, D, s);
+        }
+        cplx* g = nullptr;
+        if ((rc = rgf_inverse(c, ls, p, nb, D, B, info, &g))) return rc;
+        if (g != D) NEGF_HIP_CHECK(hipMemcpyAsync(D, g, layer_bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    cplx *Scur = pl.strip[0], *Snext = pl.strip[1];
+    const cplx* Gnext = g_of(L - 1);
+    int wnext = 0;                                                     // width of the strip of level i + 1
+    for (int i = L - 1; i >= 0; --i) {
+        const int p = phys(i), ni = ls->n[p], nj = pl.nJ[p], w = nj + wnext;
+        const cplx* Gii = Gnext;
+        if (i < L - 1) {
+            const int nn = ls->n[phys(i + 1)];
+            const cplx* g = g_of(i);
+            couplings(i);
+            rgf_mm(c, ls, ni, nn, ni, nb, g, CU, U);                   // U = g_i C_{i,i+1}
+            rgf_mm(c, ls, ni, nn, nn, nb, U, Gnext, Gup);              // G_{i,i+1}
+            rgf_mm(c, ls, nn, ni, ni, nb, CL, g, V);                   // V = C_{i+1,i} g_i
+            rgf_mm(c, ls, ni, ni, nn, nb, Gup, V, Wm);
+            { ProfScope ps(c, "rgf"); launch_rgf_add(c->stream, ni * ni, nb, g, s, Wm, s, Gcur, s); }
+            Gii = Gcur;
+            if (wnext > 0) {
+                ProfScope ps(c, "zgemm");                              // U_i strip_{i+1} behind the head of strip_i
+                launch_zgemm(c->stream, ni, wnext, nn, nb, U, nn, s, Snext, wnext, pl.cs, 0, Scur + nj, w, pl.cs);
+            }
+        }
+        if (nj > 0) {
+            ProfScope ps(c, "rgf");
+            launch_rgf_strip_head(c->stream, ni, nj, w, nb, Gii, s, pl.d_J + pl.Joff[p], Scur, pl.cs);
+        }
+        rgf_tmat_pairs(c, ls, pl, pass, i, nb, Scur, w, T);
+        if (i < L - 1) { Gnext = Gcur; std::swap(Gcur, Galt); }
+        std::swap(Scur, Snext);
+        wnext = w;
+    }
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -893,6 +1186,75 @@ int negf_layered_contact_dos(negf_ctx* c, int h, int ind, int m, const double* E
     if ((rc = negf_layered_contact_dos_dev(c, h, ind, m, reinterpret_cast<double*>(c->d_E), c->d_scal, ls->d_site))) return rc;
     if (dos_site && (rc = download(c, dos_site, ls->d_site.p, (size_t)m * ls->N))) return rc;
     if ((rc = download(c, dos_total, c->d_scal, (size_t)m))) return rc;
+    return reduce_info(c, m, info);
+}
+
+int negf_layered_transmission_matrix_dev(negf_ctx* c, int h, int n_probes, const int* probe_nk, const int* probe_inds,
+                                         const double* probe_sigma, int m, const double* E_dev, double* T_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    RgfTmatPlan pl;
+    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
+    if ((rc = rgf_tmat_plan(ls, n_probes, probe_nk, probe_inds, psig, &pl))) return rc;
+    if (m > 0 && (!E_dev || !T_dev)) return NEGF_EINVAL;
+    if (m == 0) { c->last_m = 0; return NEGF_OK; }
+    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
+    RgfRun r;
+    if ((rc = rgf_workspace(c, ls, m, true, &r, pl.per_energy))) return rc;
+    ls->work_bytes += 16LL * (long long)pl.stat;
+    if ((rc = rgf_tmat_setup(c, ls, psig, &pl))) return rc;
+    {
+        const size_t nbm = (size_t)r.nb_max;
+        cplx* q = ls->d_cols.p;
+        pl.strip[0] = q; q += pl.cs * nbm;
+        pl.strip[1] = q; q += pl.cs * nbm;
+        pl.gdyn = q; q += pl.dyn * nbm;
+        pl.Gab = q; q += pl.big_kk * nbm;
+        pl.Xs = q; q += pl.big_kk * nbm;
+        pl.Ys = q;
+    }
+    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    const size_t C2 = (size_t)pl.C * pl.C;
+    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
+        const int nb = std::min(r.nb_max, m - m0);
+        double* T = T_dev + C2 * m0;
+        NEGF_HIP_CHECK(hipMemsetAsync(c->d_info + m0, 0, (size_t)nb * sizeof(int), c->stream));
+        if ((rc = rgf_chain_sigmas(c, ls, m0, nb, E))) return rc;
+        {
+            ProfScope ps(c, "tmat");
+            for (int t = 0; t < pl.nt; ++t) {
+                if (ls->terms[t]->kind == 0) continue;
+                const cplx* sig; size_t st;
+                rgf_sigma_of(ls->terms[t], m0, &sig, &st);
+                launch_rgf_gamma(c->stream, pl.K[t], nb, sig, st, pl.gdyn + pl.goff[t], pl.dyn);
+            }
+        }
+        for (int pass = 0; pass < (pl.two_pass ? 2 : 1); ++pass)
+            if ((rc = rgf_tmat_pass(c, r, pl, pass, m0, nb, E, T))) return rc;
+        ProfScope ps(c, "tmat");
+        launch_tmat_nan(c->stream, pl.C, nb, c->d_info + m0, T);
+    }
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+int negf_layered_transmission_matrix(negf_ctx* c, int h, int n_probes, const int* probe_nk, const int* probe_inds,
+                                     const double* probe_sigma, int m, const double* E, double* T, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    const long Cl = (long)ls->terms.size() + n_probes;
+    if (n_probes < 0 || Cl < 1 || Cl > TMAT_MAX_TERMINALS || (m > 0 && (!E || !T))) return NEGF_EINVAL;
+    if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
+    const size_t C = ls->terms.size() + (size_t)n_probes, cnt = (size_t)m * C * C;
+    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
+    if ((rc = negf_layered_transmission_matrix_dev(c, h, n_probes, probe_nk, probe_inds, probe_sigma, m,
+                                                   reinterpret_cast<double*>(c->d_E), c->d_bond_T))) return rc;
+    if ((rc = download(c, T, c->d_bond_T.p, cnt))) return rc;
     return reduce_info(c, m, info);
 }
 

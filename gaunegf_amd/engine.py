@@ -730,18 +730,19 @@ class Engine:
                      "lists (constant Sigma with a nonzero support per contact, 1-D chain leads, Bethe leads without the "
                      "Xi Sigma Xi transform) and at most 1024 terminals; this provider is not served")
 
-    def _probes(self, probes):
+    def _probes(self, probes, n=None):
         """(n_probes, sizes int32, concatenated indices int32, concatenated blocks complex128) of a list of
-        (indices, block); ValueError for an invalid list."""
+        (indices, block); ValueError for an invalid list.  ``n``: the number of orbitals (None: the dense system's)."""
         if not probes:
             return 0, None, None, None
+        n = self.n if n is None else n
         nk, inds, blocks = [], [], []
         for q, (idx, blk) in enumerate(probes):
             idx = np.asarray(idx).ravel()
             if idx.size < 1 or not np.issubdtype(idx.dtype, np.integer):
                 raise ValueError(f"probe {q}: the orbital list must be a non-empty list of integers")
-            if idx.min() < 0 or idx.max() >= self.n or np.unique(idx).size != idx.size:
-                raise ValueError(f"probe {q}: orbital indices must be distinct and lie in [0, {self.n})")
+            if idx.min() < 0 or idx.max() >= n or np.unique(idx).size != idx.size:
+                raise ValueError(f"probe {q}: orbital indices must be distinct and lie in [0, {n})")
             blk = np.asarray(blk)
             if blk.shape != (idx.size, idx.size):
                 raise ValueError(f"probe {q}: expected a {idx.size}x{idx.size} block, got {blk.shape}")
@@ -934,12 +935,14 @@ class Engine:
         self._lcheck(self._lib.negf_layered_create(self._ctx, L, _ptr(sz), _ptr(fd), _ptr(fu), _ptr(sd), _ptr(su),
                                                    C.byref(h)), "negf_layered_create")
         self.__dict__.setdefault("_layered_sizes", {})[h.value] = tuple(sizes)
+        self.__dict__.setdefault("_layered_nterm", {})[h.value] = 0
         return h.value
 
     def layered_free(self, handle):
         if getattr(self, "_ctx", None):
             self._lib.negf_layered_free(self._ctx, int(handle))
             self.__dict__.get("_layered_sizes", {}).pop(int(handle), None)
+            self.__dict__.get("_layered_nterm", {}).pop(int(handle), None)
 
     def _lsizes(self, handle):
         try:
@@ -957,6 +960,7 @@ class Engine:
         t = C.c_int(-1)
         self._lcheck(self._lib.negf_layered_terminal_const(self._ctx, int(handle), int(layer), inds.size, _ptr(inds),
                                                            _ptr(sig), C.byref(t)), "negf_layered_terminal_const")
+        self._layered_nterm[int(handle)] = t.value + 1
         return t.value
 
     def layered_terminal_chain(self, handle, layer, inds, alpha, Salpha, beta, Sbeta, tau, Stau, eta, conv=1e-5,
@@ -974,6 +978,7 @@ class Engine:
             self._ctx, int(handle), int(layer), k, _ptr(inds), *[_ptr(x) for x in mats], float(eta),
             float(tol if rd else conv), float(relFactor), int(max_steps if rd else max_iter), int(force_iters),
             1 if rd else 0, C.byref(t)), "negf_layered_terminal_chain")
+        self._layered_nterm[int(handle)] = t.value + 1
         return t.value
 
     def layered_terminal_blocks(self, handle, layer, inds, sigma):
@@ -986,6 +991,7 @@ class Engine:
         self._lcheck(self._lib.negf_layered_terminal_blocks(self._ctx, int(handle), int(layer), inds.size, _ptr(inds),
                                                             sig.shape[0], _ptr(sig), C.byref(t)),
                      "negf_layered_terminal_blocks")
+        self._layered_nterm[int(handle)] = t.value + 1
         return t.value
 
     def layered_terminal_sigma(self, handle, terminal, E, K):
@@ -1095,6 +1101,39 @@ class Engine:
         self.counters["calls"] += 1; self.counters["points"] += int(m)
         self._lcheck(self._lib.negf_layered_gr_int_dev(self._ctx, int(handle), int(m), C.c_void_p(E_ptr), C.c_void_p(w_ptr),
                                                        C.c_void_p(out_ptr)), "negf_layered_gr_int_dev")
+
+    def layered_terminal_count(self, handle, probes=None):
+        """C = the system's end terminals + the probes: the size of layered_transmission_matrix's result."""
+        self._lsizes(handle)
+        return self._layered_nterm[int(handle)] + (len(probes) if probes else 0)
+
+    def layered_transmission_matrix(self, handle, E, probes=None):
+        """T [m, C, C] between ALL terminals of a layered system (negf_layered_transmission_matrix): T[k, a, b] =
+        Re Tr[Gamma_a G Gamma_b G^H](E_k), the transmission from b into a, as transmission_matrix defines it.  The terminals
+        are the end terminals in the order they were made, then ``probes``: a list of (orbital indices, K x K complex block
+        Sigma_p) as transmission_matrix takes, the indices numbered in the whole system in layer order and each probe
+        inside ONE layer -- any layer.  Without probes: the matrix over the end terminals, same-end pairs included.
+        ValueError for a probe that spans layers, repeats or leaves the system, and for more than 1024 terminals; matrices
+        of singular energies are NaN (with a warning, as layered_transmission)."""
+        N = sum(self._lsizes(handle))
+        npr, nk, inds, sig = self._probes(probes, N)
+        Cn = self.layered_terminal_count(handle, probes)
+        E, _ = self._grid(E)
+        T = np.zeros((E.size, Cn, Cn), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_transmission_matrix(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds),
+                                                                     _ptr(sig), E.size, _ptr(E), _ptr(T), _ptr(info)),
+                          "negf_layered_transmission_matrix")
+        self._numerical(rc, info[:E.size], "layered_transmission_matrix")
+        return T
+
+    def layered_transmission_matrix_dev(self, handle, m, E_ptr, T_ptr, probes=None):
+        """negf_layered_transmission_matrix_dev: grid and the [m, C, C] result in HBM; ``probes`` stays a host list."""
+        npr, nk, inds, sig = self._probes(probes, sum(self._lsizes(handle)))
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_transmission_matrix_dev(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds),
+                                                                    _ptr(sig), int(m), C.c_void_p(E_ptr), C.c_void_p(T_ptr)),
+                     "negf_layered_transmission_matrix_dev")
 
     def layered_workspace_bytes(self, handle):
         v = C.c_longlong(0)

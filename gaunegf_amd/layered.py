@@ -12,12 +12,19 @@ namesakes in transport.py / integrate.py:
     GrIntLayered(system, leads, Elist, weights)                     -> (diag, up, low) block lists of sum_m w_m G(E_m)
     GrLessIntLayered(system, leads, Elist, weights, ind=None)       -> the same lists of sum_m w_m G Gamma G^H (E_m)
     calculate_contact_pdos_layered(system, leads, energy_list, contact, groups=None) -> [m, n_g]   (a lead's share)
+    calculate_transmission_matrix_layered(system, leads, energy_list, probes=None)   -> T [m, C, C], probes on any layer
+    dephasing_probes_layered(system, groups, gamma)                 -> the probes' (indices, block) list
+    calculate_effective_transmission_layered(system, leads, energy_list, probes)     -> (T_eff [m], T_coherent [m])
+    calculate_effective_current_layered(system, leads, fermi, qV, probes)            -> the current with floating probes
 
 Per energy the work is L inverses and a handful of products of layer size instead of one N x N inverse.
 G Gamma_c G^H is formed on the pattern of S only -- what Tr[P S], a tight-binding Fock builder and the Mulliken populations
 read -- from the columns of G on the lead's orbitals, which the two sweeps yield at a few n^2 K products per layer.
-Everything that needs more of G than that raises instead of guessing: eigenchannels, probes, bond currents, spin
-layouts other than 'r', sharding over ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``)
+The transmission matrix between all terminals, with Buettiker / D'Amato-Pastawski probes on ANY layer, comes from column
+strips of G on the terminals' orbitals that the backward sweep carries from layer to layer, one pass over the layers
+as they are and one in reverse order; no block of G between distant layers is formed.
+Everything that needs more of G than that raises instead of guessing: eigenchannels, bond currents, the floating
+probes' response and G^<, spin layouts other than 'r', sharding over ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``)
 is host-side numpy.
 """
 import numpy as np
@@ -314,6 +321,89 @@ def GrLessIntLayered(system, leads, Elist, weights, ind=None, engine=None):
         return b.eng.layered_gless_int(b.h, b.term_of(ind), np.asarray(Elist), np.asarray(weights))
 
 
+def calculate_transmission_matrix_layered(system, leads, energy_list, probes=None, spin=None, checkpoint_file=None,
+                                          engine=None):
+    """T [m, C, C] between all terminals: T[k, a, b] = Re Tr[Gamma_a G Gamma_b G^H](E_k), the transmission from b into a, as
+    calculate_transmission_matrix.  The terminals are ``leads`` in their order, then ``probes``: a list of (indices,
+    block) -- orbitals numbered in the whole system in layer order, each probe inside one layer, any layer (see
+    dephasing_probes_layered).  Without probes: the matrix over the leads, pairs on the same end included."""
+    _only_restricted(spin); _no_checkpoint(checkpoint_file)
+    with _Bound(system, leads, engine) as b:
+        return b.eng.layered_transmission_matrix(b.h, np.asarray(energy_list), probes)
+
+
+def dephasing_probes_layered(system, groups, gamma):
+    """Buettiker / D'Amato-Pastawski probes on a layered system, as transport.dephasing_probes: the list of (indices,
+    block) with Sigma_p = -(i gamma_p / 2) S[I_p, I_p], S taken from the system's own diagonal blocks.  ``groups``: an
+    orbital -> probe label map of length N (negative: no probe; labels without an orbital are skipped) or a list of index
+    lists, orbitals numbered in layer order; ``gamma``: a scalar or one value per probe.  Raises ValueError when a group
+    spans layers."""
+    if not isinstance(system, LayeredSystem):
+        raise TypeError("expected a LayeredSystem (LayeredSystem.from_dense / partition make one)")
+    n = system.n
+    if len(groups) > 0 and np.ndim(groups[0]) > 0:
+        lists = [np.asarray(g, dtype=int).ravel() for g in groups]
+    else:
+        g = np.asarray(groups).ravel()
+        if g.size != n or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError(f"groups must be an integer label per orbital (length {n}) or a list of index lists")
+        lists = [np.nonzero(g == lab)[0] for lab in range(int(g.max()) + 1 if g.size else 0)]
+        lists = [ix for ix in lists if ix.size]
+    gam = (np.broadcast_to(np.asarray(gamma, dtype=float), (len(lists),)) if np.ndim(gamma) == 0
+           else np.asarray(gamma, dtype=float).ravel())
+    if gam.size != len(lists):
+        raise ValueError(f"gamma must be a scalar or one value per probe ({len(lists)}), got {gam.size}")
+    offs = system.offsets
+    out = []
+    for q, (ix, gp) in enumerate(zip(lists, gam)):
+        if ix.size == 0 or ix.min() < 0 or ix.max() >= n or np.unique(ix).size != ix.size:
+            raise ValueError(f"a probe must be a non-empty list of distinct orbital indices in [0, {n})")
+        layer = np.searchsorted(offs, ix, side='right') - 1
+        if layer.min() != layer.max():
+            raise ValueError(f"probe group {q} spans layers {int(layer.min())} and {int(layer.max())}: a probe of a layered "
+                             "system lies inside one layer")
+        loc = ix - offs[layer[0]]
+        out.append((ix, -0.5j * gp * np.asarray(system.S_diag[layer[0]])[np.ix_(loc, loc)].astype(complex)))
+    return out
+
+
+def calculate_effective_transmission_layered(system, leads, energy_list, probes, source=0, drain=-1, spin=None, engine=None):
+    """(T_eff [m], T_coherent [m]) between the leads ``source`` and ``drain`` with the ``probes`` floating at every energy,
+    as calculate_effective_transmission: transport.effective_transmission on calculate_transmission_matrix_layered's
+    result (the solve runs on the host); T_coherent is the direct term T[drain][source] in the presence of the probes."""
+    from .transport import effective_transmission
+    T = calculate_transmission_matrix_layered(system, leads, energy_list, probes=probes, spin=spin, engine=engine)
+    n_real = len(leads)
+    eff = effective_transmission(T, n_real, source, drain)
+    d = drain + n_real if drain < 0 else drain
+    s_ = source + n_real if source < 0 else source
+    return eff, T[:, d, s_]
+
+
+def calculate_effective_current_layered(system, leads, fermi, qV, probes, T=None, spin=None, dE=None, engine=None):
+    """Current at bias qV with dephasing probes, as calculate_effective_current: transport.current_grid's energies, its
+    occupation factor, trapezoid rule, e/h and the factor 2 of spin 'r', applied to
+    calculate_effective_transmission_layered's T_eff."""
+    from . import transport as tp
+    _only_restricted(spin)
+    T = tp.TEMPERATURE if T is None else T
+    dE = tp.ENERGY_STEP if dE is None else dE
+    if fermi is None or qV is None:
+        raise ValueError("fermi and qV must be provided for current calculations")
+    if np.allclose(0, qV):
+        return 0.0
+    energies, muL, muR = tp.current_grid(fermi, qV, T, dE)
+    if len(energies) == 0:
+        raise ValueError("No energies in integration window. Check fermi, qV, and dE.")
+    t_eff, _ = calculate_effective_transmission_layered(system, leads, energies, probes, engine=engine)
+    if T == 0:
+        total = tp.eoverh * tp.trapezoid(t_eff, energies)
+    else:
+        occupation = np.abs(1 / (np.exp((energies - muR) / (tp.kB * T)) + 1) - 1 / (np.exp((energies - muL) / (tp.kB * T)) + 1))
+        total = tp.eoverh * tp.trapezoid(t_eff * occupation, energies)
+    return 2 * total
+
+
 def _not_served(name):
     def fn(*args, **kwargs):
         raise NotImplementedError(f"{name} is not served on layered systems: it needs blocks of G outside the pattern of S, "
@@ -324,4 +414,3 @@ def _not_served(name):
 
 calculate_transmission_channels_layered = _not_served("calculate_transmission_channels_layered")
 calculate_local_transmission_layered = _not_served("calculate_local_transmission_layered")
-calculate_transmission_matrix_layered = _not_served("calculate_transmission_matrix_layered")

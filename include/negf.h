@@ -518,8 +518,9 @@ int negf_gr_int_probes_dev(negf_ctx* ctx, int handle, int n_probes, const int* p
  * A singular layer sets info[k] = the 1-based column of the zero pivot counted over the whole system and returns
  * NEGF_ESINGULAR, as the dense calls do.  negf_set_batch and negf_set_inverse_algo apply.  Every sum has a fixed order:
  * results are bitwise equal from run to run, do not depend on negf_set_batch, and permuting the energies permutes them.
- * Not served: eigenchannels, probes and bond currents on a layered system, terminals on interior layers,
- * spin layouts other than 'r', sharding, checkpoints. */
+ * Not served: eigenchannels, bond currents, the floating probes' response and G^< on a layered system,
+ * TERMINALS (leads) on interior layers -- probes, which are arguments of negf_layered_transmission_matrix, may sit on any
+ * layer --, spin layouts other than 'r', sharding, checkpoints. */
 int negf_layered_create(negf_ctx* ctx, int n_layers, const int* sizes, const double* F_diag_c128, const double* F_up_c128,
                         const double* S_diag_c128, const double* S_up_c128, int* handle);
 int negf_layered_free(negf_ctx* ctx, int handle);
@@ -594,9 +595,35 @@ int negf_layered_contact_dos(negf_ctx* ctx, int handle, int ind, int m, const do
                              double* dos_site, int* info);
 int negf_layered_contact_dos_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, double* dos_total_dev,
                                  double* dos_site_dev);
+/* The transmission matrix T[k][a][b] = Re Tr[Gamma_a G Gamma_b G^H](E_k) between ALL terminals -- negf_transmission_matrix's
+ * definition and orientation (the transmission from b into a) on a layered system; T [m][C][C].  The terminals are the
+ * system's end terminals in the order they were made, then the call's n_probes probes, C = n_t + n_probes.  Probe p is
+ * probe_nk[p] distinct orbitals (probe_inds, concatenated; numbered in the WHOLE system in layer order) that all lie in
+ * ONE layer -- any layer -- and an energy-independent probe_nk[p] x probe_nk[p] block Sigma_p (probe_sigma, concatenated),
+ * subtracted from A_ll beside the terminals' blocks; probes may overlap each other and the leads, and overlapping probes
+ * enter A in an order derived from their content (size, orbital list, values), not from the caller's order.
+ * With J_q = the ascending union of the orbitals of the terminals on layer q and K_tot = sum |J_q|, a backward sweep carries
+ *   strip_{L-1} = [G_{L-1,L-1}[:, J_{L-1}]],   strip_i = [G_ii[:, J_i] | g_i C_{i,i+1} strip_{i+1}]      (n_i x sum_{q>=i} |J_q|)
+ * which holds G_{i,q}[:, J_q] for every q >= i: the pairs (a on layer i, b on a layer >= i) are read from it and the strip
+ * is dropped; the pairs with b on an earlier layer come from the same pass over the layers in reverse order.  No block
+ * G_iq of two distant layers is ever formed: O(L n^3 + L n^2 K_tot) flops and O(L n^2 + n K_tot) memory per energy.
+ * n_probes = 0 gives the matrix over the end terminals, pairs on the SAME end included.
+ * NEGF_EINVAL before anything is launched: an unknown handle, a probe that leaves [0, N), names an orbital twice or spans
+ * two layers, C > 1024, C = 0, more energies than a `blocks` terminal holds.  A singular layer gives a NaN matrix for
+ * that energy, its info (the whole-system column) and NEGF_ESINGULAR; other energies are unaffected.  No floating-point
+ * atomics; results are bitwise equal from run to run, independent of negf_set_batch, and permuting the probes permutes
+ * rows and columns of T bit for bit. */
+int negf_layered_transmission_matrix(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                                     const double* probe_sigma_c128, int m, const double* E_c128, double* T, int* info);
+int negf_layered_transmission_matrix_dev(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk,
+                                         const int* probe_inds, const double* probe_sigma_c128, int m, const double* E_dev,
+                                         double* T_dev);
 /* device bytes of the work areas of the system's last call: (10 + L for a backward sweep) matrices of the largest layer
  * per energy in flight, and for a G Gamma G^H call its column sets -- with cs = n_max K_max: (L + 4) cs + K^2 for the set of
- * layer 0 (the z_i, x twice, W twice, Y, Gamma), 3 cs + K^2 for the last layer's */
+ * layer 0 (the z_i, x twice, W twice, Y, Gamma), 3 cs + K^2 for the last layer's.  For a transmission-matrix call, per
+ * energy in flight: the 10 + L matrices, two strips of n_max K_tot, the Gamma blocks of the chain and blocks terminals and
+ * three K_a K_b areas of the largest pair that takes the matrix-core path; once per call: the Gamma blocks of the probes
+ * and const terminals (sum K^2).  The result [m][C][C] is the caller's. */
 int negf_layered_workspace_bytes(negf_ctx* ctx, int handle, long long* work);
 
 /* ------------------------------------------------------------- diagnostics */
