@@ -2704,6 +2704,24 @@ struct TmatPlan {
     bool per_energy = false;                               // the contacts' Gamma blocks depend on E (block providers)
 };
 
+// The content order of two probes a and b (terminal numbers): size, then orbital list (idx at ioff), then the block's
+// values (sigma at soff) compared as numbers.  The dense and the layered path add their probes to H in this one order,
+// which is what keeps the two bit for bit alike whatever order the caller names the probes in.
+bool tmat_probe_before(const std::vector<int>& K, const std::vector<int>& idx, const std::vector<int>& ioff, const cplx* sigma,
+                       const std::vector<int>& soff, int a, int b)
+{
+    const int ka = K[a], kb = K[b];
+    if (ka != kb) return ka < kb;
+    const int* ia = idx.data() + ioff[a];
+    const int* ib = idx.data() + ioff[b];
+    for (int i = 0; i < ka; ++i) if (ia[i] != ib[i]) return ia[i] < ib[i];
+    const double* sg = reinterpret_cast<const double*>(sigma);
+    const double* xa = sg + 2 * (size_t)soff[a];
+    const double* xb = sg + 2 * (size_t)soff[b];
+    for (int i = 0; i < 2 * ka * ka; ++i) if (xa[i] != xb[i]) return xa[i] < xb[i];
+    return false;
+}
+
 // providers whose Gamma_c is confined to a known orbital list, as for the eigenchannels; the probe lists are checked
 int tmat_plan(negf_ctx* c, SigmaProvider* p, int n_probes, const int* probe_nk, const int* probe_inds,
               const cplx* probe_sigma, TmatPlan* pl)
@@ -2751,18 +2769,8 @@ int tmat_plan(negf_ctx* c, SigmaProvider* p, int n_probes, const int* probe_nk, 
     // numbers, which a scaling by a power of two keeps), so that it does not follow the caller's order
     pl->order.resize(n_probes);
     for (int q = 0; q < n_probes; ++q) pl->order[q] = nc + q;
-    const double* sg = reinterpret_cast<const double*>(probe_sigma);
-    std::stable_sort(pl->order.begin(), pl->order.end(), [&](int a, int b) {
-        const int ka = pl->K[a], kb = pl->K[b];
-        if (ka != kb) return ka < kb;
-        const int* ia = pl->idx.data() + pl->ioff[a];
-        const int* ib = pl->idx.data() + pl->ioff[b];
-        for (int i = 0; i < ka; ++i) if (ia[i] != ib[i]) return ia[i] < ib[i];
-        const double* xa = sg + 2 * (size_t)pl->soff[a];
-        const double* xb = sg + 2 * (size_t)pl->soff[b];
-        for (int i = 0; i < 2 * ka * ka; ++i) if (xa[i] != xb[i]) return xa[i] < xb[i];
-        return false;
-    });
+    std::stable_sort(pl->order.begin(), pl->order.end(),
+                     [&](int a, int b) { return tmat_probe_before(pl->K, pl->idx, pl->ioff, probe_sigma, pl->soff, a, b); });
     for (int a = 0; a < C; ++a)
         for (int b = 0; b < C; ++b) {
             const int cls = tmat_pair_class(pl->K[a], pl->K[b]);

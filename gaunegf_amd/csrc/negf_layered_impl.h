@@ -8,22 +8,30 @@
 // buffer, the Sigma kernels' scratch and the g(E) cache of the chain leads.
 //
 // Per energy, with C_ij = F_ij - E S_ij (the NEGATED coupling -A_ij: every sign of the textbook recursion cancels):
-//   forward    g_0 = (A_00 - Sigma_left)^-1,   g_i = (A_ii - C_{i,i-1} g_{i-1} C_{i-1,i} - [i = L-1] Sigma_right)^-1
+//   factor     g_0 = (A_00 - Sigma_left)^-1,   g_i = (A_ii - C_{i,i-1} g_{i-1} C_{i-1,i} - [i = L-1] Sigma_right)^-1
 //   corner     X_0 = g_0,  X_i = g_i C_{i,i-1} X_{i-1}  -> G_{L-1,0};    Y_i = Y_{i-1} C_{i-1,i} g_i  -> G_{0,L-1}
-//   backward   G_{L-1,L-1} = g_{L-1};  U = g_i C_{i,i+1},  V = C_{i+1,i} g_i:
+//   solve      G_{L-1,L-1} = g_{L-1};  U = g_i C_{i,i+1},  V = C_{i+1,i} g_i:
 //              G_{i,i+1} = U G_{i+1,i+1},   G_{i+1,i} = G_{i+1,i+1} V,   G_ii = g_i + G_{i,i+1} V
 //   columns    of a terminal set on the union J of its orbitals (G Gamma G^H on the pattern of S), W_i = G_{i,end}[:, J]:
-//              last layer:  W_{L-1} = G_{L-1,L-1}[:, J],  W_i = U_i W_{i+1}                    (backward sweep)
-//              layer 0:     x_0 = g_0[:, J],  z_i = C_{i,i-1} x_{i-1},  x_i = g_i z_i          (forward sweep, the z_i kept)
-//                           W_0 = G_00[:, J],  W_i = G_ii z_i                                  (backward sweep)
+//              last layer:  W_{L-1} = G_{L-1,L-1}[:, J],  W_i = U_i W_{i+1}                    (solve sweep)
+//              layer 0:     x_0 = g_0[:, J],  z_i = C_{i,i-1} x_{i-1},  x_i = g_i z_i          (factor sweep, the z_i kept)
+//                           W_0 = G_00[:, J],  W_i = G_ii z_i                                  (solve sweep)
 //              A_ii = (W_i Gamma) W_i^H,   A_{i,i+1} = (W_i Gamma) W_{i+1}^H,   A_{i+1,i} = A_{i,i+1}^H never formed
 //   strips     of the transmission matrix between ALL terminals, probes on any layer included (rgf_tmat_*): with J_q the
 //              union of the orbitals of the terminals on layer q,
-//              strip_{L-1} = [G_{L-1,L-1}[:, J_{L-1}]],   strip_i = [G_ii[:, J_i] | U_i strip_{i+1}]   (backward sweep)
+//              strip_{L-1} = [G_{L-1,L-1}[:, J_{L-1}]],   strip_i = [G_ii[:, J_i] | U_i strip_{i+1}]   (solve sweep)
 //              holds G_{i,q}[:, J_q] for every q >= i: the pairs (a on layer i, b on a layer >= i) are read from it, the
 //              pairs with b on an earlier layer from the same pass over the layers in REVERSE order
 // Every layer matrix of a batch is compact row-major at ONE batch stride (the largest layer's n^2): the inverses and
 // products are the dense path's launchers, batched over the energies.
+//
+// The recursion stands once.  rgf_factor_sweep keeps every g_i in d_gstore and takes two callables, run before and after
+// the inverse of a level (the strips' probes; the columns' x / z chain); rgf_solve_sweep hands each level as it stands
+// (RgfLevel) to a visitor: the block visitors RgfSumBlocks / RgfDosBlocks, the column visitor RgfColumns, the strip
+// visitor RgfStrips.  Only a block visitor has G_{i+1,i} formed.  rgf_corner_sweep shares the level (rgf_factor_level) but
+// not the loop: it alone lets g_{i-2} go.  All of them walk the levels of an RgfView, which the strips' second pass reverses.
+// The ten work areas have names (RgfAreas says who writes each, and when); the two places that lend one out say so:
+// rgf_corner_sweep and RgfColumns::level.  Every device-resident call is its checks, its work areas, then rgf_batches.
 
 struct RgfTerminal {
     int end = 0;                   // 0: layer 0, 1: layer L - 1
@@ -136,7 +144,6 @@ int rgf_add_terminal(LayeredSystem* ls, RgfTerminal* t) { ls->terms.push_back(t)
 
 // A G Gamma G^H call: the terminals it selects, per end (0: layer 0, 1: layer L - 1) the union J of their orbitals, and
 // the column areas of the batch in flight (all compact n_i x K at the stride cs)
-typedef void (*RgfConsumeA)(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* A, bool up, void* arg);
 struct RgfLess {
     int K[2] = {0, 0};                          // |J|, 0: no terminal of that end selected
     const int* J[2] = {nullptr, nullptr};       // device, ascending
@@ -144,13 +151,37 @@ struct RgfLess {
     size_t cs = 0, per_energy = 0;
     cplx *z = nullptr, *x[2] = {nullptr, nullptr};          // layer-0 set: z_1 .. z_{L-1} [L-1][batch][cs], x_{i-1} | x_i
     cplx *W[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *Y[2] = {nullptr, nullptr}, *gam[2] = {nullptr, nullptr};
-    RgfConsumeA consume = nullptr; void* arg = nullptr;
+};
+
+// The RGF_NBUF work areas of a sweep, each [batch][stride], in the order they lie in the pool.  A factor sweep is over
+// before the solve sweep of the same batch starts, so the two name their own uses of one area.
+struct RgfAreas {
+    cplx *CU, *CL;              // the negated couplings of the level pair at hand
+    cplx *U, *V;                // solve: g_i C_{i,i+1}, C_{i+1,i} g_i;  factor: C_{i,i-1} g_{i-1}, then the Schur term
+    cplx *W;                    // solve: G_{i,i+1} V
+    cplx *Gup, *Glo;            // solve: G_{i,i+1}, G_{i+1,i};  factor: Glo is the inverse's second area
+    cplx* Gii[2];               // solve: G_ii of this level and of the level before it, alternating
+    cplx* spare;                // nobody's: a visitor may use it
 };
 
 struct RgfRun {
+    negf_ctx* c;
     LayeredSystem* ls;
     int nb_max;                 // energies per sweep
-    cplx* buf[RGF_NBUF];
+    RgfAreas a;
+    cplx* g(int i) const { return ls->d_gstore + (size_t)i * nb_max * ls->stride; }     // the kept g of level i
+};
+
+// one batch [m0, m0 + nb) of a run on its way through the sweeps; E: the whole grid, on the device
+struct RgfBatch : RgfRun {
+    int m0, nb;
+    const cplx* E;
+};
+
+// hands out consecutive areas of a buffer that holds a call's small per-batch areas
+struct RgfCarve {
+    cplx* p;
+    cplx* take(size_t count) { cplx* q = p; p += count; return q; }
 };
 
 // Energies per sweep and the work areas for them.  A sweep holds RGF_NBUF matrices of the largest layer per energy, a
@@ -183,8 +214,11 @@ int rgf_workspace(negf_ctx* c, LayeredSystem* ls, int m, bool backward, RgfRun* 
         if (t->kind == 1 && (rc = ensure_cap(c, t->d_blk, (size_t)want * t->K * t->K))) return rc;
     ls->batch = want;
     ls->work_bytes = 16LL * ((long long)s * nbufs + (long long)extra) * want;
-    r->ls = ls; r->nb_max = want;
-    for (int k = 0; k < RGF_NBUF; ++k) r->buf[k] = ls->d_pool + (size_t)k * want * s;
+    r->c = c; r->ls = ls; r->nb_max = want;
+    RgfCarve pool{ls->d_pool.p};
+    RgfAreas& a = r->a;
+    for (cplx** area : {&a.CU, &a.CL, &a.U, &a.V, &a.W, &a.Gup, &a.Glo, &a.Gii[0], &a.Gii[1], &a.spare}) *area = pool.take((size_t)want * s);
+    static_assert(sizeof(RgfAreas) == RGF_NBUF * sizeof(cplx*), "RGF_NBUF areas");
     return NEGF_OK;
 }
 
@@ -196,17 +230,6 @@ int rgf_open(negf_ctx* c, int h, int m, LayeredSystem** lsp)
     for (auto* t : ls->terms) if (t->kind == 2 && m > t->m_blk) return NEGF_EINVAL;   // more energies than Sigma blocks supplied
     NEGF_HIP_CHECK(hipSetDevice(c->device));
     *lsp = ls;
-    return NEGF_OK;
-}
-
-// Sigma blocks of the chain terminals for the energies [m0, m0 + nb) -> their d_blk
-int rgf_chain_sigmas(negf_ctx* c, LayeredSystem* ls, int m0, int nb, const cplx* E)
-{
-    for (auto* t : ls->terms) {
-        if (t->kind != 1) continue;
-        int rc = run_sigma_blocks(c, t->chain, nb, E + m0, ls->d_iters, ls->d_conv, m0, t->d_blk.p);
-        if (rc) return rc;
-    }
     return NEGF_OK;
 }
 
@@ -234,37 +257,49 @@ RgfTermArgs rgf_term_args(const LayeredSystem* ls, int end, int m0, const RgfTer
 }
 
 // D[b] = A_ii(E_b) - P[b] - the terminals of layer i
-void rgf_assemble_diag(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* E, const cplx* P, cplx* D)
+void rgf_assemble_diag(const RgfBatch& b, int i, const cplx* P, cplx* D)
 {
-    ProfScope ps(c, "rgf");
-    RgfTermArgs ta;
-    if (i == 0) ta = rgf_term_args(ls, 0, m0);
-    else if (i == ls->L - 1) ta = rgf_term_args(ls, 1, m0);
-    else ta = rgf_term_args(ls, -1, m0);
-    launch_rgf_diag(c->stream, ls->n[i], nb, E + m0, ls->dSd + ls->doff[i], ls->dFd + ls->doff[i], P, ls->stride, ta, D, ls->stride);
+    ProfScope ps(b.c, "rgf");
+    const LayeredSystem* ls = b.ls;
+    const RgfTermArgs ta = rgf_term_args(ls, i == 0 ? 0 : i == ls->L - 1 ? 1 : -1, b.m0);
+    launch_rgf_diag(b.c->stream, ls->n[i], b.nb, b.E + b.m0, ls->dSd + ls->doff[i], ls->dFd + ls->doff[i], P, ls->stride, ta, D, ls->stride);
 }
 
-// the negated couplings of the pair (i, i+1): CU = C_{i,i+1} (n_i x n_{i+1}), CL = C_{i+1,i}
-void rgf_couplings(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* E, cplx* CU, cplx* CL)
-{
-    ProfScope ps(c, "rgf");
-    const int cnt = ls->n[i] * ls->n[i + 1];
-    launch_rgf_coupling(c->stream, cnt, nb, E + m0, ls->dSu + ls->uoff[i], ls->dFu + ls->uoff[i], CU, ls->stride);
-    launch_rgf_coupling(c->stream, cnt, nb, E + m0, ls->dSl + ls->uoff[i], ls->dFl + ls->uoff[i], CL, ls->stride);
-}
+// The layers in the order a sweep visits them: level i is layer i, or layer L - 1 - i when reversed -- a view, no block
+// is copied.  The sweeps speak of levels only.
+struct RgfView {
+    const LayeredSystem* ls;
+    bool reversed;
+    int layer(int i) const { return reversed ? ls->L - 1 - i : i; }
+    int n(int i) const { return ls->n[layer(i)]; }
+    // the negated couplings of the levels (i, i+1): CU = C_{i,i+1} (n_i x n_{i+1}), CL = C_{i+1,i}; reversed, the
+    // upper block of the pair of layers is the view's lower one
+    void couplings(const RgfBatch& b, int i) const
+    {
+        ProfScope ps(b.c, "rgf");
+        const int q = std::min(layer(i), layer(i + 1));                  // the pair (q, q + 1) of the system
+        const int cnt = ls->n[q] * ls->n[q + 1];
+        const cplx *Su = ls->dSu + ls->uoff[q], *Fu = ls->dFu + ls->uoff[q], *Sl = ls->dSl + ls->uoff[q], *Fl = ls->dFl + ls->uoff[q];
+        launch_rgf_coupling(b.c->stream, cnt, b.nb, b.E + b.m0, reversed ? Sl : Su, reversed ? Fl : Fu, b.a.CU, ls->stride);
+        launch_rgf_coupling(b.c->stream, cnt, b.nb, b.E + b.m0, reversed ? Su : Sl, reversed ? Fu : Fl, b.a.CL, ls->stride);
+    }
+};
 
 // C[b] (M x N) = A[b] (M x K) B[b] (K x N), all compact at the system's stride
-void rgf_mm(negf_ctx* c, LayeredSystem* ls, int M, int N, int K, int nb, const cplx* A, const cplx* B, cplx* C)
+void rgf_mm(const RgfBatch& b, int M, int N, int K, const cplx* A, const cplx* B, cplx* C)
 {
-    ProfScope ps(c, "zgemm");
-    launch_zgemm(c->stream, M, N, K, nb, A, K, ls->stride, B, N, ls->stride, 0, C, N, ls->stride);
+    ProfScope ps(b.c, "zgemm");
+    const size_t s = b.ls->stride;
+    launch_zgemm(b.c->stream, M, N, K, b.nb, A, K, s, B, N, s, 0, C, N, s);
 }
 
 // In-place inverse of the n x n matrices in A with B as the blocked kernels' second area: *res = where the inverses
 // lie.  A zero pivot of layer i is reported as column off_i + k of the whole system.
-int rgf_inverse(negf_ctx* c, LayeredSystem* ls, int i, int nb, cplx* A, cplx* B, int* info, cplx** res)
+int rgf_inverse(const RgfBatch& b, int i, cplx* A, cplx* B, cplx** res)
 {
-    const int n = ls->n[i];
+    negf_ctx* c = b.c;
+    LayeredSystem* ls = b.ls;
+    const int n = ls->n[i], nb = b.nb;
     {
         ProfScope ps(c, "inverse");
         int algo = c->inverse_algo;
@@ -282,189 +317,181 @@ int rgf_inverse(negf_ctx* c, LayeredSystem* ls, int i, int nb, cplx* A, cplx* B,
         negf_count_flops(8.0 * dn * dn * dn * nb, algo == 2 ? 6.0 * np * np * k4 * nb - inverse_blocked_vector_flops() : 0.0);
         *res = in_b ? B : A;
     }
-    launch_rgf_merge_info(c->stream, nb, ls->off[i], ls->d_linfo, info);
+    launch_rgf_merge_info(c->stream, nb, ls->off[i], ls->d_linfo, c->d_info + b.m0);
     return NEGF_OK;
 }
 
-// Forward sweep of the batch [m0, m0 + nb).  keep: the g_i go to d_gstore (a backward sweep follows); otherwise only
-// g_{i-1} is alive, and the corner block X_i (corner = 1: G_{i,0}) or Y_i (corner = 2: G_{0,i}) is carried along --
-// *corner_out = the block of the last layer.  less (with keep): the z_i chain of a column set on layer 0.  Work areas:
-// buf[0..8].
-int rgf_forward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, bool keep, int corner, cplx** corner_out,
-                RgfLess* less = nullptr)
+// a step that a caller of a factor sweep does not need
+const auto rgf_no_step = [](int, const cplx*) {};
+
+// Level i of a factor sweep: D = A_ii - C_{i,i-1} g_{i-1} C_{i-1,i} - the layer's terminals (level 0: no Schur term),
+// the caller's step before(i, D) on it, the inverse in place with B as its second area: *g = D or B, where g_i lies.
+template <class Before>
+int rgf_factor_level(const RgfBatch& b, const RgfView& v, int i, const cplx* gprev, cplx* D, cplx* B, Before& before, cplx** g)
 {
-    LayeredSystem* ls = r.ls;
-    const size_t s = ls->stride;
-    const size_t layer_bytes = (size_t)nb * s * sizeof(cplx);
-    cplx *CU = r.buf[0], *CL = r.buf[1], *T = r.buf[2], *P = r.buf[3];
-    cplx* R[3] = {r.buf[4], r.buf[5], r.buf[6]};           // rotating: g_{i-1} | matrix to invert | second area
-    cplx *Xa = r.buf[7], *Xb = r.buf[8];
-    int* info = c->d_info + m0;
-    NEGF_HIP_CHECK(hipMemsetAsync(info, 0, (size_t)nb * sizeof(int), c->stream));
-    int rc;
-    if ((rc = rgf_chain_sigmas(c, ls, m0, nb, E))) return rc;
+    const RgfAreas& a = b.a;
+    if (i > 0) {
+        const int ni = v.n(i), np = v.n(i - 1);
+        v.couplings(b, i - 1);
+        rgf_mm(b, ni, np, np, a.CL, gprev, a.U);                       // C_{i,i-1} g_{i-1}
+        rgf_mm(b, ni, ni, np, a.U, a.CU, a.V);                         // ... C_{i-1,i}
+    }
+    rgf_assemble_diag(b, v.layer(i), i > 0 ? a.V : nullptr, D);
+    before(i, D);
+    return rgf_inverse(b, v.layer(i), D, B, g);
+}
+
+// Factor sweep with every g_i kept in d_gstore, for the solve sweep that follows.  after(i, g_i) runs with CU, CL of the
+// levels (i-1, i) still standing.
+template <class Before, class After>
+int rgf_factor_sweep(const RgfBatch& b, const RgfView& v, Before&& before, After&& after)
+{
+    const size_t layer_bytes = (size_t)b.nb * b.ls->stride * sizeof(cplx);
+    for (int i = 0; i < b.ls->L; ++i) {
+        cplx *D = b.g(i), *g = nullptr;
+        int rc = rgf_factor_level(b, v, i, i > 0 ? b.g(i - 1) : nullptr, D, b.a.Glo, before, &g);
+        if (rc) return rc;
+        if (g != D) NEGF_HIP_CHECK(hipMemcpyAsync(D, g, layer_bytes, hipMemcpyDeviceToDevice, b.c->stream));
+        after(i, D);
+    }
+    return NEGF_OK;
+}
+
+// Factor sweep that keeps only g_{i-1} alive and carries a corner block along: X_i = G_{i,0} (lower) or Y_i = G_{0,i}.
+// Returns the block of the last level in *corner.  No solve sweep follows, so the solve sweep's areas are lent out
+// here: W | Gup | Glo rotate as g_{i-1} | matrix to invert | second area, Gii[0] | Gii[1] alternate as the corner block.
+int rgf_corner_sweep(const RgfBatch& b, bool lower, cplx** corner)
+{
+    const RgfAreas& a = b.a;
+    const RgfView v{b.ls, false};
+    const size_t layer_bytes = (size_t)b.nb * b.ls->stride * sizeof(cplx);
+    cplx* const R[3] = {a.W, a.Gup, a.Glo};
+    cplx *Xa = a.Gii[0], *Xb = a.Gii[1];
     cplx* gprev = nullptr;
-    for (int i = 0; i < ls->L; ++i) {
-        const int ni = ls->n[i];
-        cplx *D, *B;
-        if (keep) { D = ls->d_gstore + (size_t)i * r.nb_max * s; B = R[0]; }
-        else {
-            cplx* fr[3]; int k = 0;
-            for (cplx* q : R) if (q != gprev) fr[k++] = q;             // the two areas g_{i-1} does not occupy
-            D = fr[0]; B = fr[1];
-        }
-        if (i > 0) {
-            const int np = ls->n[i - 1];
-            rgf_couplings(c, ls, i - 1, m0, nb, E, CU, CL);
-            rgf_mm(c, ls, ni, np, np, nb, CL, gprev, T);               // C_{i,i-1} g_{i-1}
-            rgf_mm(c, ls, ni, ni, np, nb, T, CU, P);                   // ... C_{i-1,i}
-        }
-        rgf_assemble_diag(c, ls, i, m0, nb, E, i > 0 ? P : nullptr, D);
+    const int n0 = v.n(0);
+    for (int i = 0; i < b.ls->L; ++i) {
+        cplx* fr[3]; int k = 0;
+        for (cplx* q : R) if (q != gprev) fr[k++] = q;                 // the areas g_{i-1} does not occupy
         cplx* g = nullptr;
-        if ((rc = rgf_inverse(c, ls, i, nb, D, B, info, &g))) return rc;
-        if (keep && g != D) { NEGF_HIP_CHECK(hipMemcpyAsync(D, g, layer_bytes, hipMemcpyDeviceToDevice, c->stream)); g = D; }
-        if (keep && less && less->K[0] > 0) {
-            const int K = less->K[0];
-            if (i == 0) { ProfScope ps(c, "rgf"); launch_rgf_gather_cols(c->stream, ni, K, nb, g, s, less->J[0], less->x[0], less->cs); }
-            else {
-                cplx* z = less->z + (size_t)(i - 1) * r.nb_max * less->cs;
-                ProfScope ps(c, "zgemm");
-                launch_zgemm(c->stream, ni, K, ls->n[i - 1], nb, CL, ls->n[i - 1], s, less->x[0], K, less->cs, 0, z, K, less->cs);   // z_i = C_{i,i-1} x_{i-1}
-                if (i + 1 < ls->L) {
-                    launch_zgemm(c->stream, ni, K, ni, nb, g, ni, s, z, K, less->cs, 0, less->x[1], K, less->cs);                 // x_i = g_i z_i
-                    std::swap(less->x[0], less->x[1]);
-                }
-            }
-        }
-        if (!keep && corner) {
-            const int n0 = ls->n[0];
-            if (i == 0) { NEGF_HIP_CHECK(hipMemcpyAsync(Xa, g, layer_bytes, hipMemcpyDeviceToDevice, c->stream)); }
-            else if (corner == 1) {
-                rgf_mm(c, ls, ni, n0, ls->n[i - 1], nb, CL, Xa, T);    // C_{i,i-1} X_{i-1}
-                rgf_mm(c, ls, ni, n0, ni, nb, g, T, Xb);               // X_i = g_i ...
-                std::swap(Xa, Xb);
+        int rc = rgf_factor_level(b, v, i, gprev, fr[0], fr[1], rgf_no_step, &g);
+        if (rc) return rc;
+        const int ni = v.n(i);
+        if (i == 0) { NEGF_HIP_CHECK(hipMemcpyAsync(Xa, g, layer_bytes, hipMemcpyDeviceToDevice, b.c->stream)); }
+        else {
+            if (lower) {
+                rgf_mm(b, ni, n0, v.n(i - 1), a.CL, Xa, a.U);          // C_{i,i-1} X_{i-1}
+                rgf_mm(b, ni, n0, ni, g, a.U, Xb);                     // X_i = g_i ...
             } else {
-                rgf_mm(c, ls, n0, ni, ls->n[i - 1], nb, Xa, CU, T);    // Y_{i-1} C_{i-1,i}
-                rgf_mm(c, ls, n0, ni, ni, nb, T, g, Xb);               // Y_i = ... g_i
-                std::swap(Xa, Xb);
+                rgf_mm(b, n0, ni, v.n(i - 1), Xa, a.CU, a.U);          // Y_{i-1} C_{i-1,i}
+                rgf_mm(b, n0, ni, ni, a.U, g, Xb);                     // Y_i = ... g_i
             }
+            std::swap(Xa, Xb);
         }
         gprev = g;
     }
-    if (corner_out) *corner_out = Xa;
+    *corner = Xa;
     return NEGF_OK;
 }
 
-// what a backward sweep hands to its consumer, layer by layer from the last one down: G_ii, and for i < L - 1 the
-// blocks G_{i,i+1}, G_{i+1,i} (null for the last layer)
-typedef void (*RgfConsume)(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* Gii, const cplx* Gup, const cplx* Glo, void* arg);
+// What stands when a solve sweep calls its visitor at level i: G_ii, and below the last level U_i = g_i C_{i,i+1},
+// G_{i,i+1} and -- for a visitor that wants_lower -- G_{i+1,i}.  The visitor may overwrite V, W and spare.
+struct RgfLevel {
+    int i;
+    const cplx *Gii, *U, *Gup, *Glo;
+};
 
-// Layer i of a G Gamma G^H sweep: the columns W_i of each selected end from G_ii, U_i and W_{i+1}, then the blocks A_ii and
-// A_{i,i+1} (the layer-0 set's contribution first, the last layer's added to it) handed to the consumer one after the other.
-// Work areas: buf[9], buf[4], buf[3] -- free once G_ii stands.
-void rgf_less_layer(negf_ctx* c, const RgfRun& r, RgfLess* less, int i, int m0, int nb, const cplx* Gii, const cplx* U)
+// Solve sweep over the kept g_i, from the last level down; visitor.level(batch, RgfLevel) consumes each level as it stands
+template <class Visitor>
+int rgf_solve_sweep(const RgfBatch& b, const RgfView& v, Visitor&& visitor)
 {
-    LayeredSystem* ls = r.ls;
-    const size_t s = ls->stride, cs = less->cs;
-    const int ni = ls->n[i], L = ls->L;
-    for (int e = 0; e < 2; ++e) {
-        const int K = less->K[e];
-        if (K == 0) continue;
-        cplx* W = less->W[e][1];
-        if ((e == 0 && i == 0) || (e == 1 && i == L - 1)) {
-            ProfScope ps(c, "rgf");
-            launch_rgf_gather_cols(c->stream, ni, K, nb, Gii, s, less->J[e], W, cs);
-        } else if (e == 0) {
-            ProfScope ps(c, "zgemm");
-            launch_zgemm(c->stream, ni, K, ni, nb, Gii, ni, s, less->z + (size_t)(i - 1) * r.nb_max * cs, K, cs, 0, W, K, cs);    // G_ii z_i
-        } else {
-            const int nn = ls->n[i + 1];
-            ProfScope ps(c, "zgemm");
-            launch_zgemm(c->stream, ni, K, nn, nb, U, nn, s, less->W[e][0], K, cs, 0, W, K, cs);                                 // U_i W_{i+1}
-        }
-        ProfScope ps(c, "zgemm");
-        launch_zgemm(c->stream, ni, K, K, nb, W, K, cs, less->gam[e], K, (size_t)K * K, 0, less->Y[e], K, cs);                   // Y_i = W_i Gamma
-    }
-    cplx* Ab[2] = {r.buf[9], r.buf[4]};
-    const bool both = less->K[0] > 0 && less->K[1] > 0;
-    for (int up = 0; up < 2; ++up) {
-        if (up && i == L - 1) break;
-        const int nc = up ? ls->n[i + 1] : ni;
-        for (int e = 0; e < 2; ++e) {
-            const int K = less->K[e];
-            if (K == 0) continue;
-            ProfScope ps(c, "zgemm");
-            // op(B) = W^H; the diagonal block is a Hermitian product
-            launch_zgemm(c->stream, ni, nc, K, nb, less->Y[e], K, cs, less->W[e][up ? 0 : 1], K, cs, up ? 1 : 3, Ab[e], nc, s);
-        }
-        const cplx* A = less->K[0] > 0 ? Ab[0] : Ab[1];
-        if (both) { ProfScope ps(c, "rgf"); launch_rgf_add(c->stream, ni * nc, nb, Ab[0], s, Ab[1], s, r.buf[3], s); A = r.buf[3]; }
-        less->consume(c, ls, i, m0, nb, A, up != 0, less->arg);
-    }
-    for (int e = 0; e < 2; ++e) std::swap(less->W[e][0], less->W[e][1]);       // W_i is the next layer's W_{i+1}
-}
-
-// less: a G Gamma G^H sweep -- the consumer is less->consume (consume is null), G_{i+1,i} is not formed
-int rgf_backward(negf_ctx* c, const RgfRun& r, int m0, int nb, const cplx* E, RgfConsume consume, void* arg, RgfLess* less = nullptr)
-{
-    LayeredSystem* ls = r.ls;
-    const size_t s = ls->stride;
-    cplx *CU = r.buf[0], *CL = r.buf[1], *U = r.buf[2], *V = r.buf[3], *Wm = r.buf[4], *Gup = r.buf[5], *Glo = r.buf[6];
-    cplx *Gcur = r.buf[7], *Galt = r.buf[8];
-    auto g_of = [&](int i) { return ls->d_gstore + (size_t)i * r.nb_max * s; };
-    const cplx* Gnext = g_of(ls->L - 1);
-    if (less) rgf_less_layer(c, r, less, ls->L - 1, m0, nb, Gnext, nullptr);
-    else consume(c, ls, ls->L - 1, m0, nb, Gnext, nullptr, nullptr, arg);
-    for (int i = ls->L - 2; i >= 0; --i) {
-        const int ni = ls->n[i], nn = ls->n[i + 1];
-        const cplx* g = g_of(i);
-        rgf_couplings(c, ls, i, m0, nb, E, CU, CL);
-        rgf_mm(c, ls, ni, nn, ni, nb, g, CU, U);                       // U = g_i C_{i,i+1}
-        rgf_mm(c, ls, ni, nn, nn, nb, U, Gnext, Gup);                  // G_{i,i+1}
-        rgf_mm(c, ls, nn, ni, ni, nb, CL, g, V);                       // V = C_{i+1,i} g_i
-        if (!less) rgf_mm(c, ls, nn, ni, nn, nb, Gnext, V, Glo);       // G_{i+1,i}
-        rgf_mm(c, ls, ni, ni, nn, nb, Gup, V, Wm);                     // g_i C G_{i+1,i+1} C g_i
-        { ProfScope ps(c, "rgf"); launch_rgf_add(c->stream, ni * ni, nb, g, s, Wm, s, Gcur, s); }
-        if (less) rgf_less_layer(c, r, less, i, m0, nb, Gcur, U);
-        else consume(c, ls, i, m0, nb, Gcur, Gup, Glo, arg);
-        Gnext = Gcur;
-        std::swap(Gcur, Galt);
+    constexpr bool lower = std::remove_reference<Visitor>::type::wants_lower;
+    const RgfAreas& a = b.a;
+    const int L = b.ls->L;
+    const size_t s = b.ls->stride;
+    const cplx* Gnext = b.g(L - 1);                                 // G of the last level is its g
+    visitor.level(b, RgfLevel{L - 1, Gnext, nullptr, nullptr, nullptr});
+    for (int i = L - 2; i >= 0; --i) {
+        const int ni = v.n(i), nn = v.n(i + 1);
+        const cplx* g = b.g(i);
+        cplx* Gii = a.Gii[(L - i) & 1];
+        v.couplings(b, i);
+        rgf_mm(b, ni, nn, ni, g, a.CU, a.U);                           // U = g_i C_{i,i+1}
+        rgf_mm(b, ni, nn, nn, a.U, Gnext, a.Gup);                      // G_{i,i+1}
+        rgf_mm(b, nn, ni, ni, a.CL, g, a.V);                           // V = C_{i+1,i} g_i
+        if (lower) rgf_mm(b, nn, ni, nn, Gnext, a.V, a.Glo);           // G_{i+1,i}
+        rgf_mm(b, ni, ni, nn, a.Gup, a.V, a.W);                        // g_i C G_{i+1,i+1} C g_i
+        { ProfScope ps(b.c, "rgf"); launch_rgf_add(b.c->stream, ni * ni, b.nb, g, s, a.W, s, Gii, s); }
+        visitor.level(b, RgfLevel{i, Gii, a.U, a.Gup, lower ? a.Glo : nullptr});
+        Gnext = Gii;
     }
     NEGF_HIP_CHECK(hipGetLastError());
     return NEGF_OK;
 }
 
-struct RgfDosArg { int form; double* site; };      // site: [m][N] on the device
-
-void rgf_consume_dos(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* Gii, const cplx* Gup, const cplx* Glo, void* arg)
-{
-    ProfScope ps(c, "rgf");
-    const RgfDosArg* a = static_cast<const RgfDosArg*>(arg);
-    const size_t s = ls->stride;
-    double* site = a->site + (size_t)m0 * ls->N;
-    if (a->form == 0) { launch_rgf_dos_diag(c->stream, ls->n[i], nb, Gii, s, site + ls->off[i], (size_t)ls->N); return; }
-    // -Im (G S)_rr / pi, S_kr read as conj(S_rk): the diagonal block, then the two neighbours
-    launch_rgf_dos_rows(c->stream, ls->n[i], ls->n[i], nb, Gii, s, ls->dSd + ls->doff[i], site + ls->off[i], (size_t)ls->N, false);
-    if (Gup) {
-        launch_rgf_dos_rows(c->stream, ls->n[i], ls->n[i + 1], nb, Gup, s, ls->dSu + ls->uoff[i], site + ls->off[i], (size_t)ls->N, true);
-        launch_rgf_dos_rows(c->stream, ls->n[i + 1], ls->n[i], nb, Glo, s, ls->dSl + ls->uoff[i], site + ls->off[i + 1], (size_t)ls->N, true);
+// The two block visitors: level() takes G_ii, G_{i,i+1}, G_{i+1,i} of a Green's function sweep, less() a block A_ii or
+// (up) A_{i,i+1} of G Gamma G^H from the column visitor.  This one sums them with the weights into the block lists on the
+// pattern of S (gr_int, gless_int) ...
+struct RgfSumBlocks {
+    static constexpr bool wants_lower = true;
+    const cplx* w;
+    cplx* out;                                                          // diagonal | upper | lower blocks
+    void level(const RgfBatch& b, const RgfLevel& lv) const
+    {
+        ProfScope ps(b.c, "accumulate");
+        const LayeredSystem* ls = b.ls;
+        const size_t s = ls->stride;
+        const int i = lv.i;
+        launch_rgf_accumulate(b.c->stream, ls->n[i] * ls->n[i], b.nb, w + b.m0, lv.Gii, s, out + ls->doff[i]);
+        if (lv.Gup) {
+            const int cnt = ls->n[i] * ls->n[i + 1];
+            launch_rgf_accumulate(b.c->stream, cnt, b.nb, w + b.m0, lv.Gup, s, out + ls->dtot + ls->uoff[i]);
+            launch_rgf_accumulate(b.c->stream, cnt, b.nb, w + b.m0, lv.Glo, s, out + ls->dtot + ls->utot + ls->uoff[i]);
+        }
     }
-}
-
-struct RgfSumArg { const cplx* w; cplx* out; };
-
-void rgf_consume_sum(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* Gii, const cplx* Gup, const cplx* Glo, void* arg)
-{
-    ProfScope ps(c, "accumulate");
-    const RgfSumArg* a = static_cast<const RgfSumArg*>(arg);
-    const size_t s = ls->stride;
-    launch_rgf_accumulate(c->stream, ls->n[i] * ls->n[i], nb, a->w + m0, Gii, s, a->out + ls->doff[i]);
-    if (Gup) {
-        const int cnt = ls->n[i] * ls->n[i + 1];
-        launch_rgf_accumulate(c->stream, cnt, nb, a->w + m0, Gup, s, a->out + ls->dtot + ls->uoff[i]);
-        launch_rgf_accumulate(c->stream, cnt, nb, a->w + m0, Glo, s, a->out + ls->dtot + ls->utot + ls->uoff[i]);
+    void less(const RgfBatch& b, int i, const cplx* A, bool up) const
+    {
+        ProfScope ps(b.c, "accumulate");
+        const LayeredSystem* ls = b.ls;
+        const size_t s = ls->stride;
+        if (!up) { launch_rgf_accumulate(b.c->stream, ls->n[i] * ls->n[i], b.nb, w + b.m0, A, s, out + ls->doff[i]); return; }
+        launch_rgf_accumulate(b.c->stream, ls->n[i] * ls->n[i + 1], b.nb, w + b.m0, A, s, out + ls->dtot + ls->uoff[i]);
+        // the lower block (i+1, i): sum_k w_k conj(A_{i,i+1}(E_k))^T
+        launch_rgf_accumulate_ct(b.c->stream, ls->n[i], ls->n[i + 1], b.nb, w + b.m0, A, s, out + ls->dtot + ls->utot + ls->uoff[i]);
     }
-}
+};
+
+// ... this one reduces them to the per-site densities [m][N] on the device (dos, contact_dos)
+struct RgfDosBlocks {
+    static constexpr bool wants_lower = true;
+    int form;                                                           // of level(): 0 diag G, 1 diag(G S)
+    double* site;
+    void level(const RgfBatch& b, const RgfLevel& lv) const
+    {
+        ProfScope ps(b.c, "rgf");
+        const LayeredSystem* ls = b.ls;
+        const size_t s = ls->stride, N = (size_t)ls->N;
+        const int i = lv.i;
+        double* row = site + (size_t)b.m0 * N;
+        if (form == 0) { launch_rgf_dos_diag(b.c->stream, ls->n[i], b.nb, lv.Gii, s, row + ls->off[i], N); return; }
+        // -Im (G S)_rr / pi, S_kr read as conj(S_rk): the diagonal block, then the two neighbours
+        launch_rgf_dos_rows(b.c->stream, ls->n[i], ls->n[i], b.nb, lv.Gii, s, ls->dSd + ls->doff[i], row + ls->off[i], N, false);
+        if (lv.Gup) {
+            launch_rgf_dos_rows(b.c->stream, ls->n[i], ls->n[i + 1], b.nb, lv.Gup, s, ls->dSu + ls->uoff[i], row + ls->off[i], N, true);
+            launch_rgf_dos_rows(b.c->stream, ls->n[i + 1], ls->n[i], b.nb, lv.Glo, s, ls->dSl + ls->uoff[i], row + ls->off[i + 1], N, true);
+        }
+    }
+    void less(const RgfBatch& b, int i, const cplx* A, bool up) const
+    {
+        ProfScope ps(b.c, "rgf");
+        const LayeredSystem* ls = b.ls;
+        const size_t s = ls->stride, N = (size_t)ls->N;
+        double* row = site + (size_t)b.m0 * N;
+        if (!up) launch_rgf_pop_block(b.c->stream, ls->n[i], ls->n[i], b.nb, A, s, ls->dSd + ls->doff[i], row + ls->off[i], false, nullptr, N);
+        // the rows of layer i, and through A_{i+1,i} = A_{i,i+1}^H the rows of layer i + 1 as the block's column sums
+        else launch_rgf_pop_block(b.c->stream, ls->n[i], ls->n[i + 1], b.nb, A, s, ls->dSu + ls->uoff[i], row + ls->off[i], true,
+                                  row + ls->off[i + 1], N);
+    }
+};
 
 bool rgf_less_ind_ok(const LayeredSystem* ls, int ind)
 {
@@ -505,54 +532,108 @@ int rgf_less_select(negf_ctx* c, LayeredSystem* ls, int ind, RgfLess* less)
 void rgf_less_layout(const RgfRun& r, RgfLess* less)
 {
     const size_t cb = less->cs * r.nb_max;
-    cplx* p = r.ls->d_cols.p;
-    auto take = [&](size_t count) { cplx* q = p; p += count; return q; };
+    RgfCarve cols{r.ls->d_cols.p};
     if (less->K[0] > 0) {
-        less->z = take((size_t)(r.ls->L - 1) * cb);
-        less->x[0] = take(cb); less->x[1] = take(cb);
+        less->z = cols.take((size_t)(r.ls->L - 1) * cb);
+        less->x[0] = cols.take(cb); less->x[1] = cols.take(cb);
     }
     for (int e = 0; e < 2; ++e) {
         if (less->K[e] == 0) continue;
-        less->W[e][0] = take(cb); less->W[e][1] = take(cb); less->Y[e] = take(cb);
-        less->gam[e] = take((size_t)less->K[e] * less->K[e] * r.nb_max);
+        less->W[e][0] = cols.take(cb); less->W[e][1] = cols.take(cb); less->Y[e] = cols.take(cb);
+        less->gam[e] = cols.take((size_t)less->K[e] * less->K[e] * r.nb_max);
     }
 }
 
-// forward sweep, the Gamma of the selected terminals on their union lists, backward sweep of one batch
-int rgf_less_batch(negf_ctx* c, const RgfRun& r, RgfLess* less, int m0, int nb, const cplx* E)
+// The factor sweep's part in G Gamma G^H, after the inverse of level i: the x / z chain of the column set on layer 0
+void rgf_less_chain(const RgfBatch& b, RgfLess* less, int i, const cplx* g)
 {
-    int rc;
-    if ((rc = rgf_forward(c, r, m0, nb, E, true, 0, nullptr, less))) return rc;
+    const int K = less->K[0];
+    if (K == 0) return;
+    const LayeredSystem* ls = b.ls;
+    const size_t s = ls->stride, cs = less->cs;
+    const int ni = ls->n[i];
+    if (i == 0) { ProfScope ps(b.c, "rgf"); launch_rgf_gather_cols(b.c->stream, ni, K, b.nb, g, s, less->J[0], less->x[0], cs); return; }
+    cplx* z = less->z + (size_t)(i - 1) * b.nb_max * cs;
+    ProfScope ps(b.c, "zgemm");
+    launch_zgemm(b.c->stream, ni, K, ls->n[i - 1], b.nb, b.a.CL, ls->n[i - 1], s, less->x[0], K, cs, 0, z, K, cs);   // z_i = C_{i,i-1} x_{i-1}
+    if (i + 1 < ls->L) {
+        launch_zgemm(b.c->stream, ni, K, ni, b.nb, g, ni, s, z, K, cs, 0, less->x[1], K, cs);                         // x_i = g_i z_i
+        std::swap(less->x[0], less->x[1]);
+    }
+}
+
+// The column visitor: the columns W_i of each selected end from G_ii, U_i and W_{i+1}, then the blocks A_ii and A_{i,i+1}
+// (the layer-0 set's contribution first, the last layer's added to it) handed to a block visitor's less() one after the other.
+template <class Blocks>
+struct RgfColumns {
+    static constexpr bool wants_lower = false;
+    RgfLess* less;
+    const Blocks& sink;
+    void level(const RgfBatch& b, const RgfLevel& lv)
     {
-        ProfScope ps(c, "gamma");
+        const LayeredSystem* ls = b.ls;
+        hipStream_t st = b.c->stream;
+        const size_t s = ls->stride, cs = less->cs;
+        const int i = lv.i, nb = b.nb, ni = ls->n[i], L = ls->L;
+        for (int e = 0; e < 2; ++e) {
+            const int K = less->K[e];
+            if (K == 0) continue;
+            cplx* W = less->W[e][1];
+            if ((e == 0 && i == 0) || (e == 1 && i == L - 1)) {
+                ProfScope ps(b.c, "rgf");
+                launch_rgf_gather_cols(st, ni, K, nb, lv.Gii, s, less->J[e], W, cs);
+            } else if (e == 0) {
+                ProfScope ps(b.c, "zgemm");
+                launch_zgemm(st, ni, K, ni, nb, lv.Gii, ni, s, less->z + (size_t)(i - 1) * b.nb_max * cs, K, cs, 0, W, K, cs);   // G_ii z_i
+            } else {
+                const int nn = ls->n[i + 1];
+                ProfScope ps(b.c, "zgemm");
+                launch_zgemm(st, ni, K, nn, nb, lv.U, nn, s, less->W[e][0], K, cs, 0, W, K, cs);                                  // U_i W_{i+1}
+            }
+            ProfScope ps(b.c, "zgemm");
+            launch_zgemm(st, ni, K, K, nb, W, K, cs, less->gam[e], K, (size_t)K * K, 0, less->Y[e], K, cs);                       // Y_i = W_i Gamma
+        }
+        // G_ii stands and U has been read: the two ends' block products go to spare and W, their sum to V
+        const RgfAreas& a = b.a;
+        cplx* const Ab[2] = {a.spare, a.W};
+        cplx* const Asum = a.V;
+        const bool both = less->K[0] > 0 && less->K[1] > 0;
+        for (int up = 0; up < 2; ++up) {
+            if (up && i == L - 1) break;
+            const int nc = up ? ls->n[i + 1] : ni;
+            for (int e = 0; e < 2; ++e) {
+                const int K = less->K[e];
+                if (K == 0) continue;
+                ProfScope ps(b.c, "zgemm");
+                // op(B) = W^H; the diagonal block is a Hermitian product
+                launch_zgemm(st, ni, nc, K, nb, less->Y[e], K, cs, less->W[e][up ? 0 : 1], K, cs, up ? 1 : 3, Ab[e], nc, s);
+            }
+            const cplx* A = less->K[0] > 0 ? Ab[0] : Ab[1];
+            if (both) { ProfScope ps(b.c, "rgf"); launch_rgf_add(st, ni * nc, nb, Ab[0], s, Ab[1], s, Asum, s); A = Asum; }
+            sink.less(b, i, A, up != 0);
+        }
+        for (int e = 0; e < 2; ++e) std::swap(less->W[e][0], less->W[e][1]);       // W_i is the next level's W_{i+1}
+    }
+};
+
+// One batch of a call on the pattern of S.  Without `less` the two sweeps of the Green's function, its blocks to the block
+// visitor; with it G Gamma G^H: factor sweep with the layer-0 chain, the Gamma of the selected terminals on their union
+// lists, solve sweep with the column visitor in front of the block visitor
+template <class Blocks>
+int rgf_pattern_batch(const RgfBatch& b, RgfLess* less, const Blocks& sink)
+{
+    const RgfView v{b.ls, false};
+    int rc;
+    if (!less) return (rc = rgf_factor_sweep(b, v, rgf_no_step, rgf_no_step)) ? rc : rgf_solve_sweep(b, v, sink);
+    if ((rc = rgf_factor_sweep(b, v, rgf_no_step, [&](int i, const cplx* g) { rgf_less_chain(b, less, i, g); }))) return rc;
+    {
+        ProfScope ps(b.c, "gamma");
         for (int e = 0; e < 2; ++e)
             if (less->K[e] > 0)
-                launch_rgf_gamma_union(c->stream, less->K[e], nb, less->J[e], rgf_term_args(r.ls, e, m0, less->only), less->gam[e],
+                launch_rgf_gamma_union(b.c->stream, less->K[e], b.nb, less->J[e], rgf_term_args(b.ls, e, b.m0, less->only), less->gam[e],
                                        (size_t)less->K[e] * less->K[e]);
     }
-    return rgf_backward(c, r, m0, nb, E, nullptr, nullptr, less);
-}
-
-void rgf_consume_less_sum(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* A, bool up, void* arg)
-{
-    ProfScope ps(c, "accumulate");
-    const RgfSumArg* a = static_cast<const RgfSumArg*>(arg);
-    const size_t s = ls->stride;
-    if (!up) { launch_rgf_accumulate(c->stream, ls->n[i] * ls->n[i], nb, a->w + m0, A, s, a->out + ls->doff[i]); return; }
-    launch_rgf_accumulate(c->stream, ls->n[i] * ls->n[i + 1], nb, a->w + m0, A, s, a->out + ls->dtot + ls->uoff[i]);
-    // the lower block (i+1, i): sum_k w_k conj(A_{i,i+1}(E_k))^T
-    launch_rgf_accumulate_ct(c->stream, ls->n[i], ls->n[i + 1], nb, a->w + m0, A, s, a->out + ls->dtot + ls->utot + ls->uoff[i]);
-}
-
-void rgf_consume_less_dos(negf_ctx* c, LayeredSystem* ls, int i, int m0, int nb, const cplx* A, bool up, void* arg)
-{
-    ProfScope ps(c, "rgf");
-    double* site = static_cast<double*>(arg) + (size_t)m0 * ls->N;
-    const size_t s = ls->stride;
-    if (!up) launch_rgf_pop_block(c->stream, ls->n[i], ls->n[i], nb, A, s, ls->dSd + ls->doff[i], site + ls->off[i], false, nullptr, (size_t)ls->N);
-    // the rows of layer i, and through A_{i+1,i} = A_{i,i+1}^H the rows of layer i + 1 as the block's column sums
-    else launch_rgf_pop_block(c->stream, ls->n[i], ls->n[i + 1], nb, A, s, ls->dSu + ls->uoff[i], site + ls->off[i], true,
-                              site + ls->off[i + 1], (size_t)ls->N);
+    return rgf_solve_sweep(b, v, RgfColumns<Blocks>{less, sink});
 }
 
 // ------------------------------------------------- transmission matrix between all terminals, probes on any layer
@@ -654,24 +735,14 @@ int rgf_tmat_plan(LayeredSystem* ls, int n_probes, const int* probe_nk, const in
         pl->tcol[pass].resize(C);
         for (int t = 0; t < C; ++t) pl->tcol[pass][t] = pl->colbase[pass][pl->layer[t]];
     }
-    // the probes of each layer in content order: tmat_plan's comparison (size, orbital list, the block's values as numbers)
+    // the probes of each layer in the dense path's content order (inside a layer, local and global orbital numbers order alike)
     pl->poff.assign(L + 1, 0);
-    const double* sg = reinterpret_cast<const double*>(psig);
     for (int q = 0; q < L; ++q) {
         pl->poff[q] = (int)pl->porder.size();
         const size_t at = pl->porder.size();
         for (int t : on[q]) if (t >= nt) pl->porder.push_back(t);
-        std::stable_sort(pl->porder.begin() + at, pl->porder.end(), [&](int a, int b) {
-            const int ka = pl->K[a], kb = pl->K[b];
-            if (ka != kb) return ka < kb;
-            const int* ia = pl->rows.data() + pl->ioff[a];
-            const int* ib = pl->rows.data() + pl->ioff[b];
-            for (int i = 0; i < ka; ++i) if (ia[i] != ib[i]) return ia[i] < ib[i];
-            const double* xa = sg + 2 * (size_t)pl->soff[a];
-            const double* xb = sg + 2 * (size_t)pl->soff[b];
-            for (int i = 0; i < 2 * ka * ka; ++i) if (xa[i] != xb[i]) return xa[i] < xb[i];
-            return false;
-        });
+        std::stable_sort(pl->porder.begin() + at, pl->porder.end(),
+                         [&](int a, int b) { return tmat_probe_before(pl->K, pl->rows, pl->ioff, psig, pl->soff, a, b); });
     }
     pl->poff[L] = (int)pl->porder.size();
     // pair lists: pass 0 takes b on a's layer or a later one, pass 1 b on an earlier one
@@ -762,79 +833,64 @@ void rgf_tmat_pairs(negf_ctx* c, LayeredSystem* ls, const RgfTmatPlan& pl, int p
     }
 }
 
-// One pass of the batch [m0, m0 + nb): forward sweep with the g_i kept (the probes in the diagonal), backward sweep with
-// the column strips, the pairs of every level consumed from its strip.  Level i of the view is layer p(i) = i (pass 0) or
-// L - 1 - i (pass 1); the view's C_{i,i+1} is the lower block of the pair in pass 1.  Work areas: buf[0..8], d_gstore.
-int rgf_tmat_pass(negf_ctx* c, const RgfRun& r, const RgfTmatPlan& pl, int pass, int m0, int nb, const cplx* E, double* T)
-{
-    LayeredSystem* ls = r.ls;
-    const int L = ls->L;
-    const size_t s = ls->stride;
-    const size_t layer_bytes = (size_t)nb * s * sizeof(cplx);
-    cplx *CU = r.buf[0], *CL = r.buf[1], *U = r.buf[2], *V = r.buf[3], *Wm = r.buf[4], *Gup = r.buf[5], *B = r.buf[6];
-    cplx *Gcur = r.buf[7], *Galt = r.buf[8];
-    int* info = c->d_info + m0;
-    auto phys = [&](int i) { return pass ? L - 1 - i : i; };
-    auto g_of = [&](int i) { return ls->d_gstore + (size_t)i * r.nb_max * s; };
-    // the negated couplings between view levels i and i + 1: CU = C_{i,i+1}, CL = C_{i+1,i}
-    auto couplings = [&](int i) {
-        ProfScope ps(c, "rgf");
-        const int q = pass ? phys(i + 1) : i;                          // the pair (q, q + 1) of the system
-        const int cnt = ls->n[q] * ls->n[q + 1];
-        const cplx *Su = ls->dSu + ls->uoff[q], *Fu = ls->dFu + ls->uoff[q], *Sl = ls->dSl + ls->uoff[q], *Fl = ls->dFl + ls->uoff[q];
-        launch_rgf_coupling(c->stream, cnt, nb, E + m0, pass ? Sl : Su, pass ? Fl : Fu, CU, s);
-        launch_rgf_coupling(c->stream, cnt, nb, E + m0, pass ? Su : Sl, pass ? Fu : Fl, CL, s);
-    };
-    int rc;
-    for (int i = 0; i < L; ++i) {
-        const int p = phys(i), ni = ls->n[p];
-        cplx* D = g_of(i);
-        if (i > 0) {
-            const int np = ls->n[phys(i - 1)];
-            couplings(i - 1);
-            rgf_mm(c, ls, ni, np, np, nb, CL, g_of(i - 1), U);         // C_{i,i-1} g_{i-1}
-            rgf_mm(c, ls, ni, ni, np, nb, U, CU, V);                   // ... C_{i-1,i}
-        }
-        rgf_assemble_diag(c, ls, p, m0, nb, E, i > 0 ? V : nullptr, D);
-        if (pl.poff[p + 1] > pl.poff[p]) {
-            ProfScope ps(c, "rgf");
-            launch_rgf_sub_probes(c->stream, ni, pl.poff[p + 1] - pl.poff[p], nb, pl.d_porder + pl.poff[p], pl.dK, pl.d_ioff,
-                                  pl.d_soff, pl.d_rows, ls->d_tm_sig, D, s);
-        }
-        cplx* g = nullptr;
-        if ((rc = rgf_inverse(c, ls, p, nb, D, B, info, &g))) return rc;
-        if (g != D) NEGF_HIP_CHECK(hipMemcpyAsync(D, g, layer_bytes, hipMemcpyDeviceToDevice, c->stream));
-    }
-    cplx *Scur = pl.strip[0], *Snext = pl.strip[1];
-    const cplx* Gnext = g_of(L - 1);
+// The strip visitor: strip_i = [G_ii[:, J_i] | U_i strip_{i+1}] in one of the two alternating strip areas, then the pairs
+// of the level read from it
+struct RgfStrips {
+    static constexpr bool wants_lower = false;
+    const RgfView& v;
+    const RgfTmatPlan& pl;
+    double* T;
+    cplx *Scur, *Snext;
     int wnext = 0;                                                     // width of the strip of level i + 1
-    for (int i = L - 1; i >= 0; --i) {
-        const int p = phys(i), ni = ls->n[p], nj = pl.nJ[p], w = nj + wnext;
-        const cplx* Gii = Gnext;
-        if (i < L - 1) {
-            const int nn = ls->n[phys(i + 1)];
-            const cplx* g = g_of(i);
-            couplings(i);
-            rgf_mm(c, ls, ni, nn, ni, nb, g, CU, U);                   // U = g_i C_{i,i+1}
-            rgf_mm(c, ls, ni, nn, nn, nb, U, Gnext, Gup);              // G_{i,i+1}
-            rgf_mm(c, ls, nn, ni, ni, nb, CL, g, V);                   // V = C_{i+1,i} g_i
-            rgf_mm(c, ls, ni, ni, nn, nb, Gup, V, Wm);
-            { ProfScope ps(c, "rgf"); launch_rgf_add(c->stream, ni * ni, nb, g, s, Wm, s, Gcur, s); }
-            Gii = Gcur;
-            if (wnext > 0) {
-                ProfScope ps(c, "zgemm");                              // U_i strip_{i+1} behind the head of strip_i
-                launch_zgemm(c->stream, ni, wnext, nn, nb, U, nn, s, Snext, wnext, pl.cs, 0, Scur + nj, w, pl.cs);
-            }
+    void level(const RgfBatch& b, const RgfLevel& lv)
+    {
+        const int i = lv.i, p = v.layer(i), ni = v.n(i), nj = pl.nJ[p], w = nj + wnext;
+        if (wnext > 0) {
+            const int nn = v.n(i + 1);
+            ProfScope ps(b.c, "zgemm");                                // U_i strip_{i+1} behind the head of strip_i
+            launch_zgemm(b.c->stream, ni, wnext, nn, b.nb, lv.U, nn, b.ls->stride, Snext, wnext, pl.cs, 0, Scur + nj, w, pl.cs);
         }
         if (nj > 0) {
-            ProfScope ps(c, "rgf");
-            launch_rgf_strip_head(c->stream, ni, nj, w, nb, Gii, s, pl.d_J + pl.Joff[p], Scur, pl.cs);
+            ProfScope ps(b.c, "rgf");
+            launch_rgf_strip_head(b.c->stream, ni, nj, w, b.nb, lv.Gii, b.ls->stride, pl.d_J + pl.Joff[p], Scur, pl.cs);
         }
-        rgf_tmat_pairs(c, ls, pl, pass, i, nb, Scur, w, T);
-        if (i < L - 1) { Gnext = Gcur; std::swap(Gcur, Galt); }
+        rgf_tmat_pairs(b.c, b.ls, pl, v.reversed, i, b.nb, Scur, w, T);
         std::swap(Scur, Snext);
         wnext = w;
     }
+};
+
+// One pass of a batch, the pairs (a, b) with b on a's level or a later one of the view: factor sweep with the probes of
+// each level's layer taken out of its diagonal before the inverse, solve sweep with the strips
+int rgf_tmat_pass(const RgfBatch& b, const RgfTmatPlan& pl, bool reversed, double* T)
+{
+    const RgfView v{b.ls, reversed};
+    auto sub_probes = [&](int i, cplx* D) {
+        const int p = v.layer(i), np = pl.poff[p + 1] - pl.poff[p];
+        if (np == 0) return;
+        ProfScope ps(b.c, "rgf");
+        launch_rgf_sub_probes(b.c->stream, v.n(i), np, b.nb, pl.d_porder + pl.poff[p], pl.dK, pl.d_ioff, pl.d_soff, pl.d_rows,
+                              b.ls->d_tm_sig, D, b.ls->stride);
+    };
+    int rc = rgf_factor_sweep(b, v, sub_probes, rgf_no_step);
+    return rc ? rc : rgf_solve_sweep(b, v, RgfStrips{v, pl, T, pl.strip[0], pl.strip[1]});
+}
+
+// The batches of a device-resident call, once its work areas stand: per batch its info cleared and the Sigma blocks of
+// the chain terminals evaluated into their d_blk, then body(batch)
+template <class Body>
+int rgf_batches(const RgfRun& r, int m, const double* E_dev, Body&& body)
+{
+    negf_ctx* c = r.c;
+    int rc;
+    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
+        const RgfBatch b{r, m0, std::min(r.nb_max, m - m0), reinterpret_cast<const cplx*>(E_dev)};
+        NEGF_HIP_CHECK(hipMemsetAsync(c->d_info + m0, 0, (size_t)b.nb * sizeof(int), c->stream));
+        for (auto* t : r.ls->terms)
+            if (t->kind == 1 && (rc = run_sigma_blocks(c, t->chain, b.nb, b.E + m0, r.ls->d_iters, r.ls->d_conv, m0, t->d_blk.p))) return rc;
+        if ((rc = body(b))) return rc;
+    }
+    c->last_m = m;
     NEGF_HIP_CHECK(hipGetLastError());
     return NEGF_OK;
 }
@@ -981,45 +1037,37 @@ int negf_layered_transmission_dev(negf_ctx* c, int h, int term_a, int term_b, in
     RgfTerminal *ta = ls->terms[term_a], *tb = ls->terms[term_b];
     if (ta->end == tb->end) return NEGF_EINVAL;                     // the corner blocks connect opposite end layers only
     if (!T_dev || (m > 0 && !E_dev)) return NEGF_EINVAL;
-    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
     RgfRun r;
-    if ((rc = rgf_workspace(c, ls, m, false, &r))) return rc;
+    if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, false, &r))) return rc;
     const int Ka = ta->K, Kb = tb->K;
-    const size_t kab = (size_t)Ka * Kb, sa = (size_t)Ka * Ka, sb = (size_t)Kb * Kb;
-    const size_t per = sa + sb + 3 * kab;
-    if ((rc = ensure_cap(c, ls->d_small, per * r.nb_max))) return rc;
-    cplx* gamA = ls->d_small;
-    cplx* gamB = gamA + sa * r.nb_max;
-    cplx* Gab = gamB + sb * r.nb_max;
-    cplx* Xs = Gab + kab * r.nb_max;
-    cplx* Ys = Xs + kab * r.nb_max;
-    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
+    const size_t kab = (size_t)Ka * Kb, sa = (size_t)Ka * Ka, sb = (size_t)Kb * Kb, nbm = (size_t)r.nb_max;
+    if ((rc = ensure_cap(c, ls->d_small, (sa + sb + 3 * kab) * nbm))) return rc;
+    RgfCarve small{ls->d_small.p};
+    cplx *gamA = small.take(sa * nbm), *gamB = small.take(sb * nbm);
+    cplx *Gab = small.take(kab * nbm), *Xs = small.take(kab * nbm), *Ys = small.take(kab * nbm);
     // a on the last layer: G_ab is cut from G_{L-1,0} (X); a on layer 0: from G_{0,L-1} (Y)
-    const int corner = ta->end == 1 ? 1 : 2;
-    const int ld = corner == 1 ? ls->n[0] : ls->n[ls->L - 1];
-    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
-        const int nb = std::min(r.nb_max, m - m0);
+    const bool lower = ta->end == 1;
+    const int ld = lower ? ls->n[0] : ls->n[ls->L - 1];
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) {
         cplx* Gc = nullptr;
-        if ((rc = rgf_forward(c, r, m0, nb, E, false, corner, &Gc))) return rc;
+        if (int e = rgf_corner_sweep(b, lower, &Gc)) return e;
         const cplx *sA, *sB; size_t stA, stB;
-        rgf_sigma_of(ta, m0, &sA, &stA); rgf_sigma_of(tb, m0, &sB, &stB);
+        rgf_sigma_of(ta, b.m0, &sA, &stA); rgf_sigma_of(tb, b.m0, &sB, &stB);
         {
             ProfScope ps(c, "gamma");
-            launch_rgf_gamma(c->stream, Ka, nb, sA, stA, gamA, sa);
-            launch_rgf_gamma(c->stream, Kb, nb, sB, stB, gamB, sb);
+            launch_rgf_gamma(c->stream, Ka, b.nb, sA, stA, gamA, sa);
+            launch_rgf_gamma(c->stream, Kb, b.nb, sB, stB, gamB, sb);
         }
         {
             ProfScope ps(c, "zgemm");
-            launch_gather_block(c->stream, ld, Ka, Kb, nb, Gc, ls->stride, ta->d_idx, tb->d_idx, Gab, kab);
-            launch_zgemm(c->stream, Ka, Kb, Ka, nb, gamA, Ka, sa, Gab, Kb, kab, 0, Xs, Kb, kab);
-            launch_zgemm(c->stream, Ka, Kb, Kb, nb, Xs, Kb, kab, gamB, Kb, sb, 0, Ys, Kb, kab);
+            launch_gather_block(c->stream, ld, Ka, Kb, b.nb, Gc, ls->stride, ta->d_idx, tb->d_idx, Gab, kab);
+            launch_zgemm(c->stream, Ka, Kb, Ka, b.nb, gamA, Ka, sa, Gab, Kb, kab, 0, Xs, Kb, kab);
+            launch_zgemm(c->stream, Ka, Kb, Kb, b.nb, Xs, Kb, kab, gamB, Kb, sb, 0, Ys, Kb, kab);
         }
         ProfScope ps(c, "trace");
-        launch_trace_dot(c->stream, Ka, Kb, nb, Ys, Kb, kab, Gab, Kb, kab, T_dev + m0, 1);
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        launch_trace_dot(c->stream, Ka, Kb, b.nb, Ys, Kb, kab, Gab, Kb, kab, T_dev + b.m0, 1);
+        return NEGF_OK;
+    });
 }
 
 int negf_layered_transmission(negf_ctx* c, int h, int term_a, int term_b, int m, const double* E, double* T, int* info)
@@ -1036,157 +1084,114 @@ int negf_layered_transmission(negf_ctx* c, int h, int term_a, int term_b, int m,
     return fetch_result_and_info(c, m, c->d_scal, (size_t)m * sizeof(double), T, info);
 }
 
-int negf_layered_dos_dev(negf_ctx* c, int h, int form, int m, const double* E_dev, double* dos_total_dev, double* dos_site_dev)
+// negf_layered_dos_dev (ind null) and negf_layered_contact_dos_dev
+static int rgf_dev_dos(negf_ctx* c, int h, int form, const int* ind, int m, const double* E_dev, double* dos_total_dev, double* dos_site_dev)
 {
     LayeredSystem* ls;
     int rc = rgf_open(c, h, m, &ls);
     if (rc) return rc;
     if ((form != 0 && form != 1) || (m > 0 && (!E_dev || !dos_total_dev || !dos_site_dev))) return NEGF_EINVAL;
-    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
+    RgfLess less;
+    if (ind && (rc = rgf_less_select(c, ls, *ind, &less))) return rc;
     RgfRun r;
-    if ((rc = rgf_workspace(c, ls, m, true, &r))) return rc;
-    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    RgfDosArg arg{form, dos_site_dev};
-    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
-        const int nb = std::min(r.nb_max, m - m0);
-        if ((rc = rgf_forward(c, r, m0, nb, E, true, 0, nullptr))) return rc;
-        if ((rc = rgf_backward(c, r, m0, nb, E, rgf_consume_dos, &arg))) return rc;
+    if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, true, &r, less.per_energy))) return rc;
+    if (ind) rgf_less_layout(r, &less);
+    const RgfDosBlocks dos{form, dos_site_dev};
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) {
+        if (int e = rgf_pattern_batch(b, ind ? &less : nullptr, dos)) return e;
         ProfScope ps(c, "rgf");
-        launch_rgf_dos_total(c->stream, ls->N, nb, dos_site_dev + (size_t)m0 * ls->N, (size_t)ls->N, dos_total_dev + m0);
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        launch_rgf_dos_total(c->stream, ls->N, b.nb, dos_site_dev + (size_t)b.m0 * ls->N, (size_t)ls->N, dos_total_dev + b.m0);
+        return NEGF_OK;
+    });
 }
 
-int negf_layered_dos(negf_ctx* c, int h, int form, int m, const double* E, double* dos_total, double* dos_site, int* info)
+int negf_layered_dos_dev(negf_ctx* c, int h, int form, int m, const double* E_dev, double* dos_total_dev, double* dos_site_dev)
+{
+    return rgf_dev_dos(c, h, form, nullptr, m, E_dev, dos_total_dev, dos_site_dev);
+}
+
+int negf_layered_contact_dos_dev(negf_ctx* c, int h, int ind, int m, const double* E_dev, double* dos_total_dev, double* dos_site_dev)
+{
+    return rgf_dev_dos(c, h, 1, &ind, m, E_dev, dos_total_dev, dos_site_dev);
+}
+
+// negf_layered_gr_int_dev (ind null) and negf_layered_gless_int_dev
+static int rgf_dev_pattern_int(negf_ctx* c, int h, const int* ind, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
+    RgfLess less;
+    if (ind && (rc = rgf_less_select(c, ls, *ind, &less))) return rc;
+    RgfRun r;
+    if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, true, &r, less.per_energy))) return rc;
+    if (ind) rgf_less_layout(r, &less);
+    const RgfSumBlocks sum{reinterpret_cast<const cplx*>(w_dev), reinterpret_cast<cplx*>(out_dev)};
+    NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, (ls->dtot + 2 * ls->utot) * sizeof(cplx), c->stream));
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) { return rgf_pattern_batch(b, ind ? &less : nullptr, sum); });
+}
+
+int negf_layered_gr_int_dev(negf_ctx* c, int h, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    return rgf_dev_pattern_int(c, h, nullptr, m, E_dev, w_dev, out_dev);
+}
+
+int negf_layered_gless_int_dev(negf_ctx* c, int h, int ind, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    return rgf_dev_pattern_int(c, h, &ind, m, E_dev, w_dev, out_dev);
+}
+
+static int rgf_host_pattern_int(negf_ctx* c, int h, const int* ind, int m, const double* E, const double* w, double* out, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
+    if (ind && !rgf_less_ind_ok(ls, *ind)) return NEGF_EINVAL;
+    const size_t tot = ls->dtot + 2 * ls->utot;
+    if ((rc = stage_grid(c, m, 1, E, w, tot * sizeof(cplx)))) return rc;
+    if ((rc = ensure_cap(c, ls->d_out, tot))) return rc;
+    if ((rc = rgf_dev_pattern_int(c, h, ind, m, reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
+                                  reinterpret_cast<double*>(ls->d_out.p)))) return rc;
+    return fetch_result_and_info(c, m, ls->d_out.p, tot * sizeof(cplx), out, info);
+}
+
+int negf_layered_gr_int(negf_ctx* c, int h, int m, const double* E, const double* w, double* out, int* info)
+{
+    return rgf_host_pattern_int(c, h, nullptr, m, E, w, out, info);
+}
+
+int negf_layered_gless_int(negf_ctx* c, int h, int ind, int m, const double* E, const double* w, double* out, int* info)
+{
+    return rgf_host_pattern_int(c, h, &ind, m, E, w, out, info);
+}
+
+// negf_layered_dos (form, ind null) and negf_layered_contact_dos: grid staged, totals and per-site rows fetched
+static int rgf_host_dos(negf_ctx* c, int h, int form, const int* ind, int m, const double* E, double* dos_total, double* dos_site, int* info)
 {
     LayeredSystem* ls;
     int rc = rgf_open(c, h, m, &ls);
     if (rc) return rc;
     if ((form != 0 && form != 1) || (m > 0 && (!E || !dos_total))) return NEGF_EINVAL;
+    if (ind && !rgf_less_ind_ok(ls, *ind)) return NEGF_EINVAL;
     if (m == 0) return NEGF_OK;
     if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
     if ((rc = ensure_cap(c, ls->d_site, (size_t)m * ls->N))) return rc;
-    if ((rc = negf_layered_dos_dev(c, h, form, m, reinterpret_cast<double*>(c->d_E), c->d_scal, ls->d_site))) return rc;
+    if ((rc = rgf_dev_dos(c, h, form, ind, m, reinterpret_cast<double*>(c->d_E), c->d_scal, ls->d_site))) return rc;
     if (dos_site && (rc = download(c, dos_site, ls->d_site.p, (size_t)m * ls->N))) return rc;
     if ((rc = download(c, dos_total, c->d_scal, (size_t)m))) return rc;
     return reduce_info(c, m, info);
 }
 
-int negf_layered_gr_int_dev(negf_ctx* c, int h, int m, const double* E_dev, const double* w_dev, double* out_dev)
+int negf_layered_dos(negf_ctx* c, int h, int form, int m, const double* E, double* dos_total, double* dos_site, int* info)
 {
-    LayeredSystem* ls;
-    int rc = rgf_open(c, h, m, &ls);
-    if (rc) return rc;
-    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
-    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
-    RgfRun r;
-    if ((rc = rgf_workspace(c, ls, m, true, &r))) return rc;
-    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    RgfSumArg arg{reinterpret_cast<const cplx*>(w_dev), reinterpret_cast<cplx*>(out_dev)};
-    NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, (ls->dtot + 2 * ls->utot) * sizeof(cplx), c->stream));
-    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
-        const int nb = std::min(r.nb_max, m - m0);
-        if ((rc = rgf_forward(c, r, m0, nb, E, true, 0, nullptr))) return rc;
-        if ((rc = rgf_backward(c, r, m0, nb, E, rgf_consume_sum, &arg))) return rc;
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
-}
-
-int negf_layered_gr_int(negf_ctx* c, int h, int m, const double* E, const double* w, double* out, int* info)
-{
-    LayeredSystem* ls;
-    int rc = rgf_open(c, h, m, &ls);
-    if (rc) return rc;
-    if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    const size_t tot = ls->dtot + 2 * ls->utot;
-    if ((rc = stage_grid(c, m, 1, E, w, tot * sizeof(cplx)))) return rc;
-    if ((rc = ensure_cap(c, ls->d_out, tot))) return rc;
-    if ((rc = negf_layered_gr_int_dev(c, h, m, reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
-                                      reinterpret_cast<double*>(ls->d_out.p)))) return rc;
-    return fetch_result_and_info(c, m, ls->d_out.p, tot * sizeof(cplx), out, info);
-}
-
-int negf_layered_gless_int_dev(negf_ctx* c, int h, int ind, int m, const double* E_dev, const double* w_dev, double* out_dev)
-{
-    LayeredSystem* ls;
-    int rc = rgf_open(c, h, m, &ls);
-    if (rc) return rc;
-    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
-    RgfLess less;
-    if ((rc = rgf_less_select(c, ls, ind, &less))) return rc;
-    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
-    RgfRun r;
-    if ((rc = rgf_workspace(c, ls, m, true, &r, less.per_energy))) return rc;
-    rgf_less_layout(r, &less);
-    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    RgfSumArg arg{reinterpret_cast<const cplx*>(w_dev), reinterpret_cast<cplx*>(out_dev)};
-    less.consume = rgf_consume_less_sum; less.arg = &arg;
-    NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, (ls->dtot + 2 * ls->utot) * sizeof(cplx), c->stream));
-    for (int m0 = 0; m0 < m; m0 += r.nb_max)
-        if ((rc = rgf_less_batch(c, r, &less, m0, std::min(r.nb_max, m - m0), E))) return rc;
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
-}
-
-int negf_layered_gless_int(negf_ctx* c, int h, int ind, int m, const double* E, const double* w, double* out, int* info)
-{
-    LayeredSystem* ls;
-    int rc = rgf_open(c, h, m, &ls);
-    if (rc) return rc;
-    if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    if (!rgf_less_ind_ok(ls, ind)) return NEGF_EINVAL;
-    const size_t tot = ls->dtot + 2 * ls->utot;
-    if ((rc = stage_grid(c, m, 1, E, w, tot * sizeof(cplx)))) return rc;
-    if ((rc = ensure_cap(c, ls->d_out, tot))) return rc;
-    if ((rc = negf_layered_gless_int_dev(c, h, ind, m, reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
-                                         reinterpret_cast<double*>(ls->d_out.p)))) return rc;
-    return fetch_result_and_info(c, m, ls->d_out.p, tot * sizeof(cplx), out, info);
-}
-
-int negf_layered_contact_dos_dev(negf_ctx* c, int h, int ind, int m, const double* E_dev, double* dos_total_dev, double* dos_site_dev)
-{
-    LayeredSystem* ls;
-    int rc = rgf_open(c, h, m, &ls);
-    if (rc) return rc;
-    if (m > 0 && (!E_dev || !dos_total_dev || !dos_site_dev)) return NEGF_EINVAL;
-    RgfLess less;
-    if ((rc = rgf_less_select(c, ls, ind, &less))) return rc;
-    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
-    RgfRun r;
-    if ((rc = rgf_workspace(c, ls, m, true, &r, less.per_energy))) return rc;
-    rgf_less_layout(r, &less);
-    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    less.consume = rgf_consume_less_dos; less.arg = dos_site_dev;
-    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
-        const int nb = std::min(r.nb_max, m - m0);
-        if ((rc = rgf_less_batch(c, r, &less, m0, nb, E))) return rc;
-        ProfScope ps(c, "rgf");
-        launch_rgf_dos_total(c->stream, ls->N, nb, dos_site_dev + (size_t)m0 * ls->N, (size_t)ls->N, dos_total_dev + m0);
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+    return rgf_host_dos(c, h, form, nullptr, m, E, dos_total, dos_site, info);
 }
 
 int negf_layered_contact_dos(negf_ctx* c, int h, int ind, int m, const double* E, double* dos_total, double* dos_site, int* info)
 {
-    LayeredSystem* ls;
-    int rc = rgf_open(c, h, m, &ls);
-    if (rc) return rc;
-    if (m > 0 && (!E || !dos_total)) return NEGF_EINVAL;
-    if (!rgf_less_ind_ok(ls, ind)) return NEGF_EINVAL;
-    if (m == 0) return NEGF_OK;
-    if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
-    if ((rc = ensure_cap(c, ls->d_site, (size_t)m * ls->N))) return rc;
-    if ((rc = negf_layered_contact_dos_dev(c, h, ind, m, reinterpret_cast<double*>(c->d_E), c->d_scal, ls->d_site))) return rc;
-    if (dos_site && (rc = download(c, dos_site, ls->d_site.p, (size_t)m * ls->N))) return rc;
-    if ((rc = download(c, dos_total, c->d_scal, (size_t)m))) return rc;
-    return reduce_info(c, m, info);
+    return rgf_host_dos(c, h, 1, &ind, m, E, dos_total, dos_site, info);
 }
 
 int negf_layered_transmission_matrix_dev(negf_ctx* c, int h, int n_probes, const int* probe_nk, const int* probe_inds,
@@ -1200,45 +1205,32 @@ int negf_layered_transmission_matrix_dev(negf_ctx* c, int h, int n_probes, const
     if ((rc = rgf_tmat_plan(ls, n_probes, probe_nk, probe_inds, psig, &pl))) return rc;
     if (m > 0 && (!E_dev || !T_dev)) return NEGF_EINVAL;
     if (m == 0) { c->last_m = 0; return NEGF_OK; }
-    if ((rc = ensure_mbuffers(c, m, 1))) return rc;
     RgfRun r;
-    if ((rc = rgf_workspace(c, ls, m, true, &r, pl.per_energy))) return rc;
+    if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, true, &r, pl.per_energy))) return rc;
     ls->work_bytes += 16LL * (long long)pl.stat;
     if ((rc = rgf_tmat_setup(c, ls, psig, &pl))) return rc;
-    {
-        const size_t nbm = (size_t)r.nb_max;
-        cplx* q = ls->d_cols.p;
-        pl.strip[0] = q; q += pl.cs * nbm;
-        pl.strip[1] = q; q += pl.cs * nbm;
-        pl.gdyn = q; q += pl.dyn * nbm;
-        pl.Gab = q; q += pl.big_kk * nbm;
-        pl.Xs = q; q += pl.big_kk * nbm;
-        pl.Ys = q;
-    }
-    const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    const size_t C2 = (size_t)pl.C * pl.C;
-    for (int m0 = 0; m0 < m; m0 += r.nb_max) {
-        const int nb = std::min(r.nb_max, m - m0);
-        double* T = T_dev + C2 * m0;
-        NEGF_HIP_CHECK(hipMemsetAsync(c->d_info + m0, 0, (size_t)nb * sizeof(int), c->stream));
-        if ((rc = rgf_chain_sigmas(c, ls, m0, nb, E))) return rc;
+    const size_t nbm = (size_t)r.nb_max, C2 = (size_t)pl.C * pl.C;
+    RgfCarve cols{ls->d_cols.p};
+    pl.strip[0] = cols.take(pl.cs * nbm); pl.strip[1] = cols.take(pl.cs * nbm);
+    pl.gdyn = cols.take(pl.dyn * nbm);
+    pl.Gab = cols.take(pl.big_kk * nbm); pl.Xs = cols.take(pl.big_kk * nbm); pl.Ys = cols.take(pl.big_kk * nbm);
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) {
+        double* T = T_dev + C2 * b.m0;
         {
             ProfScope ps(c, "tmat");
             for (int t = 0; t < pl.nt; ++t) {
                 if (ls->terms[t]->kind == 0) continue;
                 const cplx* sig; size_t st;
-                rgf_sigma_of(ls->terms[t], m0, &sig, &st);
-                launch_rgf_gamma(c->stream, pl.K[t], nb, sig, st, pl.gdyn + pl.goff[t], pl.dyn);
+                rgf_sigma_of(ls->terms[t], b.m0, &sig, &st);
+                launch_rgf_gamma(c->stream, pl.K[t], b.nb, sig, st, pl.gdyn + pl.goff[t], pl.dyn);
             }
         }
         for (int pass = 0; pass < (pl.two_pass ? 2 : 1); ++pass)
-            if ((rc = rgf_tmat_pass(c, r, pl, pass, m0, nb, E, T))) return rc;
+            if (int e = rgf_tmat_pass(b, pl, pass == 1, T)) return e;
         ProfScope ps(c, "tmat");
-        launch_tmat_nan(c->stream, pl.C, nb, c->d_info + m0, T);
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        launch_tmat_nan(c->stream, pl.C, b.nb, c->d_info + b.m0, T);
+        return NEGF_OK;
+    });
 }
 
 int negf_layered_transmission_matrix(negf_ctx* c, int h, int n_probes, const int* probe_nk, const int* probe_inds,
