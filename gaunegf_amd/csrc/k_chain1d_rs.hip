@@ -126,9 +126,9 @@ __global__ void rs_rr_init_kernel(RsQueue* q, unsigned cap, unsigned jobs)
 // DS instruction, a lane needs ONE address register per operand stream.  The matrix has 16*T16 rows
 // of which rows >= n (and the columns >= n of a row) stay zero: operands of the padded tiles are read
 // without clamps or selects and are finite.
-// RR: the round-robin instantiation (a persistent workgroup that takes its jobs from the queue); the plain one -- a launch
-// whose jobs all fit the resident slots -- carries none of the job loop (its per-job values are loop invariants again:
-// 4.7 % fewer scalar instructions per sweep, 1.7 % faster).
+// RR: the round-robin instantiation (a persistent workgroup that takes its jobs from the queue: every launch with more jobs
+// than resident slots); the plain one -- a launch whose jobs all fit the resident slots -- carries none of the job loop (its
+// per-job values are loop invariants again: equal jobs, four rounds of 768, 61.9 against 62.6 us per sweep and slot).
 // a value / pointer that is the same in every lane, kept in scalar registers
 __device__ __forceinline__ double rs_uniform(double v)
 {
@@ -762,74 +762,143 @@ size_t chain1d_lds_scratch_elems(int nc_max, int n_contacts, int nb, int max_swe
 
 namespace {
 
+// The launch configuration of pitch class P: workgroups per CU from the LDS share of a workgroup (+ < 1 KB of static
+// LDS) -- the work matrix alone when the old iterate goes to global scratch (gold_global), both matrices otherwise
+// (allocated in granules of 1280 bytes: 53.8 KB per workgroup is the most that still fits three times).
+struct RsConfig { int occ; bool gold_global; size_t smem; };
 template <int P>
-void chain1d_rs_launch(hipStream_t st, ChainRsArgs a, int n_max, int n_contacts, int nb, const cplx* E, cplx* blk,
-                       int* iters, int* conv, cplx* gold_scratch, int occ_env, int rr_slots, unsigned rr_cap, bool rr_forced)
+RsConfig rs_config(int n_max, bool have_scratch, int occ_env)
 {
     constexpr int T16 = (P - 1 + 15) / 16;
+    constexpr int OCC_MAX = T16 <= 2 ? 4 : 3;          // register budget: 128 VGPRs (T16 <= 2), 168 above
     const size_t wmat = (size_t)(16 * T16 * P + 16) * sizeof(cplx);
     const size_t gold_lds = (size_t)n_max * n_max * sizeof(cplx);
-    // occupancy from the LDS share of a workgroup (+ < 1 KB of static LDS): the work matrix alone when the
-    // old iterate goes to global scratch, both matrices otherwise
-    // (allocated in granules of 1280 bytes: 53.8 KB per workgroup is the most that still fits three times)
     auto fits = [](size_t smem, int per_cu) { return ((smem + 832 + 1279) / 1280) * 1280 * per_cu <= 160 * 1024; };
-    // old iterate behind the work matrix (all slots in LDS) ...
-    ChainRsArgs al = a; al.gold_lds_off = 16 * T16 * P + 16;
-    // ... or its first slots in the unused rows n_max+2 .. of the work matrix, the rest in global scratch
-    ChainRsArgs ag = a; ag.gold_lds_off = (n_max + 2) * P;
+    if (occ_env != 2 && fits(wmat + gold_lds, OCC_MAX)) return {OCC_MAX, false, wmat + gold_lds};
+    if (occ_env != 2 && have_scratch && fits(wmat, OCC_MAX)) return {OCC_MAX, true, wmat};
+    if (fits(wmat + gold_lds, 2) || !have_scratch) return {2, false, wmat + gold_lds};
+    return {2, true, wmat};
+}
+int rs_occ_env()
+{
+    static int occ_env = -1;
+    if (occ_env < 0) { const char* e = getenv("NEGF_CHAIN1D_OCC"); occ_env = e ? atoi(e) : 0; }
+    return occ_env;
+}
+int rs_n_cus()
+{
     static int n_cus = 0;
     if (!n_cus) {
         int dev = 0; hipDeviceProp_t prop;
         n_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
     }
-    auto launch = [&](auto kern, auto kern_rr, size_t smem, int occ) {
-        ChainRsArgs aa = smem > wmat ? al : ag;
+    return n_cus;
+}
+// One instantiation per pitch class of the largest contact (smaller contacts of the same launch run
+// in the same padded matrix): the smallest odd pitch of the list that holds n_max columns.  The remainder-strip
+// classes (19, 35, 51: the last tile holds <= 4 rows / columns and runs on the 4x4x4 instruction) store their
+// full tiles unguarded and count every k-step below the strip as inside the matrix, i.e. they assume that EVERY
+// contact of the launch reaches into the strip, n > 16 TR.  A launch whose smallest contact does not (contacts of
+// unequal size, e.g. n_c = (50, 40)) takes the next class without strips, whose stores and k-steps are guarded
+// by the contact's own n.
+// rs_class_n: the size that selects the class; RS_CLASSES(n, CASE): CASE(P) of that class.
+int rs_class_n(const SigmaProvider& p)
+{
+    int n = p.nc_max, n_min = n;
+    for (int k : p.nc) n_min = std::min(n_min, k);
+    const int strip_base = n <= 16 ? -1 : n <= 19 ? 16 : (n > 32 && n <= 35) ? 32 : (n > 48 && n <= 51) ? 48 : -1;
+    if (strip_base > 0 && n_min <= strip_base) n = strip_base == 16 ? 25 : strip_base == 32 ? 41 : 57;
+    return n;
+}
+#ifdef RS_FAST_BUILD
+#define RS_CLASSES(n, CASE) do { if ((n) <= 16) CASE(17); else CASE(51); } while (0)
+#else
+#define RS_CLASSES(n, CASE) do { \
+    if ((n) <= 16) CASE(17); \
+    else if ((n) <= 19) CASE(19);                /* 16 + a remainder strip */ \
+    else if ((n) <= 25) CASE(25); \
+    else if ((n) <= 32) CASE(33); \
+    else if ((n) <= 35) CASE(35);                /* 32 + a remainder strip */ \
+    else if ((n) <= 41) CASE(41); \
+    else if ((n) <= 48) CASE(49); \
+    else if ((n) <= 51) CASE(51); \
+    else if ((n) <= 57) CASE(57); \
+    else CASE(65); } while (0)
+#endif
+// resident slots of a launch: workgroups per CU of its class x compute units (rr_slots > 0: at most that many -- tests)
+int rs_launch_slots(const SigmaProvider& p, bool have_scratch, int rr_slots)
+{
+    int occ = 2;
+#define RS_CASE(PP) occ = rs_config<PP>(p.nc_max, have_scratch, rs_occ_env()).occ
+    RS_CLASSES(rs_class_n(p), RS_CASE);
+#undef RS_CASE
+    const int slots = occ * rs_n_cus();
+    return rr_slots > 0 ? std::min(rr_slots, slots) : slots;
+}
+
+template <int P>
+void chain1d_rs_launch(hipStream_t st, ChainRsArgs a, int n_max, int n_contacts, int nb, const cplx* E, cplx* blk,
+                       int* iters, int* conv, cplx* gold_scratch, int slots, unsigned rr_cap)
+{
+    constexpr int T16 = (P - 1 + 15) / 16;
+    const RsConfig cf = rs_config<P>(n_max, gold_scratch != nullptr, rs_occ_env());
+    // old iterate behind the work matrix (all slots in LDS), or its first slots in the unused rows n_max+2 .. of the
+    // work matrix and the rest in global scratch
+    a.gold_lds_off = cf.gold_global ? (n_max + 2) * P : 16 * T16 * P + 16;
+    auto launch = [&](auto kern, auto kern_rr) {
         dim3 grid(n_contacts, nb);
-        // Round robin pays when jobs have to wait for a slot AND nothing is known about their lengths (the first
-        // evaluation of a grid by this provider: 725 against 800 ms in launch order on the C3 grid): one persistent
-        // workgroup per resident slot then.  With a predicted order the plain launch, longest job first, is the faster
-        // one (718 against 726 ms: its kernel carries no job loop), so the round robin is left to the launches without
-        // an order or with one predicted from too few points (order_trusted) -- unless the caller set the quantum
-        // himself (negf_set_chain_round_robin: tests, A/B).
-        const int jobs = n_contacts * nb, slots = rr_slots > 0 ? std::min(rr_slots, occ * n_cus) : occ * n_cus;
-        const bool rr = aa.rr_quantum > 0 && jobs > slots && (aa.order == nullptr || rr_forced);
+        // A launch with more jobs than resident slots (a.rr_quantum > 0: launch_chain1d_lds) runs from the job queue, one
+        // persistent workgroup per slot, whether or not an order is known.  On the C3 grid (4000 jobs, 768 slots; 2760 jobs
+        // run to the 2000-sweep cap) the queue takes 576.4 ms per step started in the learned order and 576.1 ms in launch
+        // order, the plain kernel dealt longest first 584.9 ms (spreads 1.6 - 2.3 ms, scripts/time_chain_rule.py).  The
+        // likely reason, not measured on its own: under the queue the capped jobs advance together and end with the chip
+        // full; dealt one by one the slots finish up to one short job apart.  The job loop itself costs 1.2 % per sweep at
+        // the most (equal jobs: 62.6 against 61.9 us per sweep and slot), less than that tail.
+        // A launch that fits the chip runs the plain kernel in the predicted order (648 jobs: 42 against 48 ms).
+        const int jobs = n_contacts * nb;
+        const bool rr = a.rr_quantum > 0;
         if (rr) {
-            hipLaunchKernelGGL(rs_rr_init_kernel, dim3((rr_cap + 255) / 256), dim3(256), 0, st, aa.rr_q, rr_cap, (unsigned)jobs);
+            hipLaunchKernelGGL(rs_rr_init_kernel, dim3((rr_cap + 255) / 256), dim3(256), 0, st, a.rr_q, rr_cap, (unsigned)jobs);
             grid = dim3(slots, 1);
-        } else aa.rr_quantum = 0;
+        }
         static int log_env = -1;
         if (log_env < 0) log_env = getenv("NEGF_CHAIN_LOG") ? 1 : 0;
-        if (log_env) fprintf(stderr, "[chain launch] jobs %d slots %d quantum %d order %d gc_mode %d\n", jobs, slots, aa.rr_quantum, aa.order ? 1 : 0, aa.gc_mode);
+        if (log_env) fprintf(stderr, "[chain launch] jobs %d slots %d quantum %d order %d gc_mode %d\n", jobs, slots, a.rr_quantum, a.order ? 1 : 0, a.gc_mode);
         auto go = [&](auto k) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) != hipSuccess)
                 (void)hipGetLastError();
-            hipLaunchKernelGGL(k, grid, dim3(RS_THREADS), smem, st, aa, E, blk, iters, conv);
+            hipLaunchKernelGGL(k, grid, dim3(RS_THREADS), cf.smem, st, a, E, blk, iters, conv);
         };
         if (rr) go(kern_rr); else go(kern);
     };
-    constexpr int OCC_MAX = T16 <= 2 ? 4 : 3;          // register budget: 128 VGPRs (T16 <= 2), 168 above
+    constexpr int OCC_MAX = T16 <= 2 ? 4 : 3;          // (rs_config)
+#define RS_PICK(KERN) do { \
+        if (cf.occ == OCC_MAX && !cf.gold_global) launch(KERN<P, OCC_MAX, false, false>, KERN<P, OCC_MAX, false, true>); \
+        else if (cf.occ == OCC_MAX) launch(KERN<P, OCC_MAX, true, false>, KERN<P, OCC_MAX, true, true>); \
+        else if (!cf.gold_global) launch(KERN<P, 2, false, false>, KERN<P, 2, false, true>); \
+        else launch(KERN<P, 2, true, false>, KERN<P, 2, true, true>); } while (0)
     // a strip class launched with the roles by wave number runs the kernels with the generic inverse
     constexpr bool STRIPS = T16 >= 2 && P - 16 * (T16 - 1) <= 4;
     if constexpr (STRIPS && rs_stage_sched(T16 - 1)) {
-        if (!a.simd_roles) {
-            if (occ_env != 2 && fits(wmat + gold_lds, OCC_MAX)) launch(chain1d_rs_wn_kernel<P, OCC_MAX, false, false>, chain1d_rs_wn_kernel<P, OCC_MAX, false, true>, wmat + gold_lds, OCC_MAX);
-            else if (occ_env != 2 && gold_scratch && fits(wmat, OCC_MAX)) launch(chain1d_rs_wn_kernel<P, OCC_MAX, true, false>, chain1d_rs_wn_kernel<P, OCC_MAX, true, true>, wmat, OCC_MAX);
-            else if (fits(wmat + gold_lds, 2) || !gold_scratch) launch(chain1d_rs_wn_kernel<P, 2, false, false>, chain1d_rs_wn_kernel<P, 2, false, true>, wmat + gold_lds, 2);
-            else launch(chain1d_rs_wn_kernel<P, 2, true, false>, chain1d_rs_wn_kernel<P, 2, true, true>, wmat, 2);
-            return;
-        }
+        if (!a.simd_roles) { RS_PICK(chain1d_rs_wn_kernel); return; }
     }
-    if (occ_env != 2 && fits(wmat + gold_lds, OCC_MAX)) launch(chain1d_rs_kernel<P, OCC_MAX, false, false>, chain1d_rs_kernel<P, OCC_MAX, false, true>, wmat + gold_lds, OCC_MAX);
-    else if (occ_env != 2 && gold_scratch && fits(wmat, OCC_MAX)) launch(chain1d_rs_kernel<P, OCC_MAX, true, false>, chain1d_rs_kernel<P, OCC_MAX, true, true>, wmat, OCC_MAX);
-    else if (fits(wmat + gold_lds, 2) || !gold_scratch) launch(chain1d_rs_kernel<P, 2, false, false>, chain1d_rs_kernel<P, 2, false, true>, wmat + gold_lds, 2);
-    else launch(chain1d_rs_kernel<P, 2, true, false>, chain1d_rs_kernel<P, 2, true, true>, wmat, 2);
+    RS_PICK(chain1d_rs_kernel);
+#undef RS_PICK
 }
 
 }  // namespace
 
+// does this launch (a miss, with its scratch) run from the job queue?  More jobs than resident slots, and a ring to set
+// jobs aside in: a quantum (rr_quantum as in launch_chain1d_lds; 0: never) below the launch's sweep cap
+bool chain1d_lds_runs_queue(const SigmaProvider& p, int nb, int rr_quantum, int rr_slots)
+{
+    return rs_ring_entries(p.n_contacts, nb, std::max(p.max_iter, p.force_iters), rr_quantum) > 0 &&
+           p.n_contacts * nb > rs_launch_slots(p, true, rr_slots);
+}
+
 void launch_chain1d_lds(hipStream_t st, const SigmaProvider& p, const int* d_nc, const int* d_blk_off, int nb,
                         const cplx* E, cplx* blk, int* iters, int* conv, cplx* gold_scratch, const int* order,
-                        cplx* gcache, int gc_mode, int rr_quantum, int rr_slots, bool order_trusted)
+                        cplx* gcache, int gc_mode, int rr_quantum, int rr_slots)
 {
     ChainRsArgs a;
     a.order = order;
@@ -844,12 +913,11 @@ void launch_chain1d_lds(hipStream_t st, const SigmaProvider& p, const int* d_nc,
     // the job queue sits behind the iterate copies (chain1d_lds_scratch_elems); a cache hit runs no sweeps
     a.rr_quantum = 0; a.rr_q = nullptr;
     unsigned rr_cap = 0;
-    {
-        const size_t cap = rs_ring_entries(p.n_contacts, nb, std::max(p.max_iter, p.force_iters), rr_quantum);
-        if (gold_scratch && cap && a.gc_mode != 2) {
-            a.rr_q = reinterpret_cast<RsQueue*>(gold_scratch + rs_gold_elems(p.nc_max, p.n_contacts, nb));
-            rr_cap = (unsigned)cap; a.rr_quantum = rs_rr_quantum(rr_quantum);
-        }
+    const int slots = rs_launch_slots(p, gold_scratch != nullptr, rr_slots);
+    if (gold_scratch && a.gc_mode != 2 && chain1d_lds_runs_queue(p, nb, rr_quantum, rr_slots)) {
+        a.rr_q = reinterpret_cast<RsQueue*>(gold_scratch + rs_gold_elems(p.nc_max, p.n_contacts, nb));
+        rr_cap = (unsigned)rs_ring_entries(p.n_contacts, nb, std::max(p.max_iter, p.force_iters), rr_quantum);
+        a.rr_quantum = rs_rr_quantum(rr_quantum);
     }
     static unsigned long long* d_stamps = nullptr;
     static int want_stamps = -1;
@@ -859,41 +927,12 @@ void launch_chain1d_lds(hipStream_t st, const SigmaProvider& p, const int* d_nc,
     }
     a.stamps = d_stamps;
     { const char* e = getenv("NEGF_CHAIN_STAMP_SWEEP"); a.stamp_sweep = e ? atoi(e) : 10; }
-    static int occ_env = -1;
-    if (occ_env < 0) { const char* e = getenv("NEGF_CHAIN1D_OCC"); occ_env = e ? atoi(e) : 0; }
     static int roles_env = -1;
     if (roles_env < 0) { const char* e = getenv("NEGF_CHAIN1D_ROLES"); roles_env = e ? atoi(e) : 1; }
     a.simd_roles = roles_env;
-    // one instantiation per pitch class of the largest contact (smaller contacts of the same launch run
-    // in the same padded matrix): the smallest odd pitch of the list that holds n_max columns.  The remainder-strip
-    // classes (19, 35, 51: the last tile holds <= 4 rows / columns and runs on the 4x4x4 instruction) store their
-    // full tiles unguarded and count every k-step below the strip as inside the matrix, i.e. they assume that EVERY
-    // contact of the launch reaches into the strip, n > 16 TR.  A launch whose smallest contact does not (contacts of
-    // unequal size, e.g. n_c = (50, 40)) takes the next class without strips, whose stores and k-steps are guarded
-    // by the contact's own n.
     const int n_max = p.nc_max;
-    int n = n_max;                                  // selects the class
-    {
-        int n_min = n;
-        for (int k : p.nc) n_min = std::min(n_min, k);
-        const int strip_base = n <= 16 ? -1 : n <= 19 ? 16 : (n > 32 && n <= 35) ? 32 : (n > 48 && n <= 51) ? 48 : -1;
-        if (strip_base > 0 && n_min <= strip_base) n = strip_base == 16 ? 25 : strip_base == 32 ? 41 : 57;
-    }
-#define RS_CASE(PP) chain1d_rs_launch<PP>(st, a, n_max, p.n_contacts, nb, E, blk, iters, conv, gold_scratch, occ_env, rr_slots, rr_cap, rr_quantum > 0 || !order_trusted)
-#ifdef RS_FAST_BUILD
-    if (n <= 16) RS_CASE(17); else RS_CASE(51);
-#else
-    if (n <= 16) RS_CASE(17);
-    else if (n <= 19) RS_CASE(19);                // 16 + a remainder strip
-    else if (n <= 25) RS_CASE(25);
-    else if (n <= 32) RS_CASE(33);
-    else if (n <= 35) RS_CASE(35);                // 32 + a remainder strip
-    else if (n <= 41) RS_CASE(41);
-    else if (n <= 48) RS_CASE(49);
-    else if (n <= 51) RS_CASE(51);
-    else if (n <= 57) RS_CASE(57);
-    else RS_CASE(65);
-#endif
+#define RS_CASE(PP) chain1d_rs_launch<PP>(st, a, n_max, p.n_contacts, nb, E, blk, iters, conv, gold_scratch, slots, rr_cap)
+    RS_CLASSES(rs_class_n(p), RS_CASE);
 #undef RS_CASE
     if (d_stamps) {
         (void)hipStreamSynchronize(st);

@@ -457,25 +457,25 @@ int chain_cached_launch(negf_ctx* c, ChainGEntry* ent, bool hit, int jobs, int* 
 // device, no host sync; the first evaluation runs in launch order.  What the order is for: a launch with FEWER jobs
 // than resident slots (the SCF-sized grids) is dispatched to the compute units in this order, so the long jobs are
 // spread over the chip instead of sharing a unit with their neighbours in energy (648 jobs: 42 against 48 ms); a
-// launch with MORE jobs runs them round robin (k_chain1d_rs.hip) and only takes the order as the initial content of
-// its queue.
-// record = false, before the launch: *order = the predicted order (nullptr: launch order), *trusted = false when the
-// prediction comes from fewer than half as many energies as the launch evaluates -- a guess: such a launch runs round robin.
+// launch with MORE jobs runs them round robin (k_chain1d_rs.hip), where the initial content of the queue is worth
+// nothing (C3 grid: 576.4 ms per step in the learned order, 576.1 ms in launch order), so no order is predicted for it.
+// record = false, before the launch: *order = the predicted order (nullptr: launch order); order = nullptr: the launch
+// takes no order, only the record of the previous evaluation is promoted.
 // record = true, after it: the chunk's energies and counts are appended to the record of the evaluation in progress.
 int chain_learn_order(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, const int* iters, int m0, bool record,
-                      const int** order = nullptr, bool* trusted = nullptr)
+                      const int** order = nullptr)
 {
     const int jobs = nb * p->n_contacts;
     if (!record) {
-        int rc = ensure_cap(c, p->d_order, (size_t)jobs);
-        if (rc) return rc;
         if (m0 == 0 && p->cur_n > 0) {
             // a new evaluation begins: the one recorded so far becomes the reference
             std::swap(p->d_prevE, p->d_curE); std::swap(p->d_prev_iters, p->d_cur_iters);
             std::swap(p->prev_cap, p->cur_cap);
             p->prev_n = p->cur_n; p->cur_n = 0;
         }
-        *trusted = 2 * (p->prev_n > 0 ? p->prev_n : p->cur_n) >= nb;
+        if (!order) return NEGF_OK;
+        int rc = ensure_cap(c, p->d_order, (size_t)jobs);
+        if (rc) return rc;
         if (p->prev_n > 0) {
             launch_chain1d_predict_order(c->stream, p->d_prevE, p->d_prev_iters, p->prev_n, p->n_contacts, E, nb, p->d_order);
             *order = p->d_order;
@@ -549,13 +549,14 @@ int run_sigma_blocks(negf_ctx* c, SigmaProvider* p, int nb, const cplx* E, int* 
         return NEGF_OK;
     }
     const bool learn = !hit && p->force_iters < 0 && iters && chain1d_order_supported(jobs);
+    // (a launch with more jobs than resident slots runs round robin and takes no order)
     const int* order = nullptr;
-    bool order_trusted = true;
-    if (learn && (rc = chain_learn_order(c, p, nb, E, iters, m0, false, &order, &order_trusted))) return rc;
+    const bool queue = chain1d_lds_runs_queue(*p, nb, c->chain_rr_quantum, c->chain_rr_slots);
+    if (learn && (rc = chain_learn_order(c, p, nb, E, iters, m0, false, queue ? nullptr : &order))) return rc;
     rc = chain_cached_launch(c, ent, hit, jobs, iters, conv, [&](cplx* g, int mode) {
         if (mode == 2) launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, blk, iters, conv, c->d_scratch, nullptr, g, 2);
         else launch_chain1d_lds(c->stream, *p, p->d_nc, p->d_blk_off, nb, E, blk, iters, conv, c->d_scratch, order, g, 1,
-                                c->chain_rr_quantum, c->chain_rr_slots, order_trusted);
+                                c->chain_rr_quantum, c->chain_rr_slots);
     });
     if (rc || !learn) return rc;
     return chain_learn_order(c, p, nb, E, iters, m0, true);

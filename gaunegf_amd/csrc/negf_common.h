@@ -389,15 +389,16 @@ bool chain1d_lds_supported(int nc_max);
 // the kernel then keeps the old iterate in LDS at a lower occupancy)
 // (+ the job queue of a round-robin launch: rr_quantum < 0 = the default, NEGF_CHAIN_RR)
 size_t chain1d_lds_scratch_elems(int nc_max, int n_contacts, int nb, int max_sweeps, int rr_quantum);
+// does a launch of nb energies that runs its fixed points (no cache hit, scratch given) run round robin: more jobs than
+// resident slots, and a quantum below its sweep cap?  Such a launch needs no order (rr_quantum / rr_slots as below)
+bool chain1d_lds_runs_queue(const SigmaProvider& p, int nb, int rr_quantum, int rr_slots);
 // order: launch slot -> job (energy * n_contacts + contact) or null for launch order
 // gcache / gc_mode: see ChainGEntry -- 0 no cache, 1 store the final iterates, 2 load them and only form Sigma
 // rr_quantum / rr_slots: round-robin execution of a launch with more jobs than resident slots (ChainRsArgs; < 0 / 0:
-// the defaults -- NEGF_CHAIN_RR or 100 sweeps, every slot of the device); order_trusted = false: the order is a
-// guess (predicted from few points), a launch with more jobs than slots runs round robin all the same
+// the defaults -- NEGF_CHAIN_RR or 100 sweeps, every slot of the device; rr_quantum 0: never)
 void launch_chain1d_lds(hipStream_t st, const SigmaProvider& p, const int* d_nc, const int* d_blk_off, int nb,
                         const cplx* E, cplx* blk, int* iters, int* conv, cplx* gold_scratch, const int* order,
-                        cplx* gcache = nullptr, int gc_mode = 0, int rr_quantum = -1, int rr_slots = 0,
-                        bool order_trusted = true);
+                        cplx* gcache = nullptr, int gc_mode = 0, int rr_quantum = -1, int rr_slots = 0);
 // renormalisation-decimation solver (k_chain1d_rd.hip; p.conv = tol, p.max_iter = max_steps, p.force_iters = force_steps).
 // scratch: chain1d_rd_scratch_elems() complex values; gcache / gc_mode as in launch_chain1d_lds (n_c <= 64 only)
 size_t chain1d_rd_scratch_elems(int nc_max, int n_contacts, int nb);

@@ -1,6 +1,6 @@
-"""A provider that has only seen 8 energies evaluates the 2000-point C3 grid: the order predicted from 8 points is a
-guess, so the launch runs round robin (negf_api.hip: order_trusted) -- against the same launch forced plain
-(negf_set_chain_round_robin(0, 0)) in that guessed order."""
+"""A provider that has only seen 8 energies evaluates the 2000-point C3 grid: the order predicted from 8 points would
+be a guess; the launch has more jobs than resident slots, so it runs round robin and takes no order (k_chain1d_rs.hip,
+chain1d_lds_runs_queue) -- against the same launch forced plain (negf_set_chain_round_robin(0, 0)) in that guessed order."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
