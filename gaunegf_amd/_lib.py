@@ -130,6 +130,8 @@ SIGNATURES = {
     "negf_zgemm_batched": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_longlong,
                                      _vp, C.c_int, C.c_longlong, C.c_int, _vp, C.c_int, C.c_longlong, C.c_int]),
     "negf_zgemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _ip, C.c_int]),
+    "negf_inverse_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "negf_inverse_last": (C.c_int, [_vp, _ip, _ip, _ip]),
 }
 
 _lib = None

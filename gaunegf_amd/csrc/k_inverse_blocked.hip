@@ -1443,7 +1443,7 @@ __global__ void gj_state_init_kernel(int n, int* __restrict__ piv_all, int* __re
 double g_gj_vector_flops = 0;            // 3M-equivalent flops of the last launch that ran as VECTOR work (strip window kernels)
 
 template <int NBI, int RPT>
-void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t stride, int* piv, int* info, GjSideStreams* sdp, int win_mode, bool skip_gather)
+void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t stride, int* piv, int* info, GjSideStreams* sdp, const GjPlan& plan, GjRecord* rec)
 {
     const size_t smem = (size_t)(2 * PW * NBI + 2 * NBI * WIN) * sizeof(cplx);      // candidate rows + Q of two sub-panels
     auto kern = gj_window_kernel<NBI, RPT>;
@@ -1456,90 +1456,73 @@ void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t str
     static int want_stamps = -1;
     static unsigned long long* d_stamps = nullptr;
     if (want_stamps < 0) {
-        want_stamps = getenv("NEGF_GJ_STAMPS") ? 1 : 0;
+        want_stamps = gj_params().stamps;
         if (want_stamps) { (void)hipMalloc(&d_stamps, 64 * sizeof(unsigned long long)); (void)hipMemset(d_stamps, 0, 64 * sizeof(unsigned long long)); }
     }
-    static int winla = -1;
-    if (winla < 0) { const char* e = getenv("NEGF_GJ_WINLA"); winla = e ? atoi(e) : 1; }
-    // Which window kernel (win_mode 0 = auto, 1 = strip wherever an instantiation serves n, 2 = team kernels only;
-    // NEGF_GJ_STRIP = 0 / 1 sets the auto rule's answer for A/B runs).  Measured on MI355X, inverse ms, strip / team:
-    //   1000 matrices: n = 256 4.01 / 5.26 (single-workgroup kernel), 300 6.62 / 7.53, 400 13.0 / 14.6, 500 21.5 / 24.5 (the
-    //   strip kernel moves 3.3 MB per window and matrix instead of 4.9, and both run at the ~4.3 TB/s this access pattern
-    //   gets out of the memory system), 650 55.5 / 53.5, 800 84.8 / 84.4, 1000 147.9 / 150.4 (the 8-wave, one-per-CU form);
-    //   small batches (stream groups of m / 4): 32 x n = 500 2.29 / 2.20, 128 x 500 4.10 / 3.97, 250 x 500 6.20 / 6.12 (a lean
-    //   4-wave workgroup has a longer chain per matrix than the 12-wave look-ahead kernel), 12 x 800 5.51 / 5.77,
-    //   61 x 800 7.54 / 8.10, 64 x 1000 13.1 / 14.1, 128 x 1000 23.0 / 23.9, 486 x 800 42.5 / 42.4.
-    static int strip_env = -2;
-    if (strip_env == -2) { const char* e = getenv("NEGF_GJ_STRIP"); strip_env = e ? atoi(e) : -1; }
-    static int strip_min = -1;           // matrices per stream group from which the auto rule takes the strip kernel (257 <= n <= 512)
-    if (strip_min < 0) { const char* e = getenv("NEGF_GJ_STRIP_MIN"); strip_min = e ? atoi(e) : 64; }
-    static int strip_cfg = -1;           // 0: the measured choice per size; 1: n <= 512 fat (8 waves x 1 row, sub-windows of 32); 3: n <= 256 with sub-windows of 16; 4: n <= 512 lean with two chunks in flight
-    if (strip_cfg < 0) { const char* e = getenv("NEGF_GJ_STRIP_CFG"); strip_cfg = e ? atoi(e) : 0; }
+    // Which window kernel, pairs or not, which update form, how many groups: gj_plan (below) decides, from the
+    // measurements recorded there; this function launches what the plan says and notes each launch in rec.
     static int strip_dbg = -1;           // timing ablations of the strip kernel (wrong results)
     if (strip_dbg < 0) { const char* e = getenv("NEGF_GJ_STRIP_DBG"); strip_dbg = e ? atoi(e) : 0; }
-    static int pair = -1;                // windows in pairs (one pass over the other column blocks per pair); 0: one by one
-    if (pair < 0) { const char* e = getenv("NEGF_GJ_PAIR"); pair = e ? atoi(e) : 1; }
-    static long pair_min = -1, fat_max = -1, fat_total_max = -1;
-    // (round 5, with the strip window kernels, inverse ms without / with pairs: 122 x N = 800 (330 workgroups per group) 13.46 /
-    //  12.09, 128 x N = 500 (192) 3.93 / 3.94, 61 x N = 800 (165) 7.39 / 8.95: the threshold moved from 352 to 256)
-    if (pair_min < 0) { const char* e = getenv("NEGF_GJ_PAIR_MIN"); pair_min = e ? atol(e) : 256; }
-    if (fat_max < 0) { const char* e = getenv("NEGF_GJ_FAT_MAX"); fat_max = e ? atol(e) : 256; }
-    if (fat_total_max < 0) { const char* e = getenv("NEGF_GJ_FAT_TOTAL_MAX"); fat_total_max = e ? atol(e) : 2000; }
-    const int nblk = (n + 63) / 64;
+    const int nblk = plan.nblk;
     // the chain of one group of matrices: per window the panel kernel (one workgroup per matrix: a latency chain
     // that covers at most `count` CUs) and the column-block update (throughput-bound), then the gather
-    auto chain = [&](hipStream_t s, int first, int count) {
+    auto chain = [&](hipStream_t s, int gi) {
+        const GjGroup& gp = plan.g[gi];
+        const int first = gp.first, count = gp.count;
+        unsigned none = 0;
+        unsigned& did = rec ? rec->mask[gi] : none;
         cplx* Ag = A + (size_t)first * stride; cplx* Bg = B + (size_t)first * stride;
         int* pg = piv + (size_t)first * 2 * n; int* ig = info + first;
         hipLaunchKernelGGL(gj_state_init_kernel, dim3(count), dim3(256), 0, s, n, pg, ig);
         auto window = [&](int c0, int cw) {
             unsigned long long* stp = (c0 == WIN && first == 0) ? d_stamps : (unsigned long long*)nullptr;
             // (matrix-core flop accounting: with the strip kernel the window's own 6 n cw^2 are vector work)
-            const bool strip = NBI == 16 && (win_mode == 1 || (win_mode == 0 && (strip_env >= 0 ? strip_env != 0 : (n <= 256 || (n <= 512 ? count >= strip_min : (count <= 160 || n >= 900))))));
-            if (strip) {
+            if (gp.wk >= GJ_WK_STRIP_256 && gp.wk <= GJ_WK_STRIP_1024)
                 g_gj_vector_flops += 6.0 * (double)((n + 15) & ~15) * cw * (double)cw * count;
-                if (n <= 256 && strip_cfg != 3)
-                    hipLaunchKernelGGL((gj_window_strip_kernel<1, 32, 4, 2, 4>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
-                else if (n <= 256)
-                    hipLaunchKernelGGL((gj_window_strip_kernel<1, 16, 4, 3, 4>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
-                else if (n <= 512 && strip_cfg == 1)
-                    hipLaunchKernelGGL((gj_window_strip_kernel<1, 32, 8, 1, 4>), dim3(count), dim3(512), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
-                else if (n <= 512 && strip_cfg == 4)     // two chunks in flight: 72 spilled registers, 23.3 ms against 22.6 (1000 x n = 500)
-                    hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 4, 2, 2>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
-                else if (n <= 512)
-                    hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 4, 2, 1>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
-                else
-                    hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 8, 1, 2>), dim3(count), dim3(512), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
-                return;
-            }
-            if (NBI == 16 && RPT == 1 && winla && n <= 256)
+            switch (gp.wk) {
+            case GJ_WK_STRIP_256:
+                hipLaunchKernelGGL((gj_window_strip_kernel<1, 32, 4, 2, 4>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
+                did |= 1u << GJ_WK_STRIP_256; break;
+            case GJ_WK_STRIP_256_S16:
+                hipLaunchKernelGGL((gj_window_strip_kernel<1, 16, 4, 3, 4>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
+                did |= 1u << GJ_WK_STRIP_256_S16; break;
+            case GJ_WK_STRIP_512_FAT:
+                hipLaunchKernelGGL((gj_window_strip_kernel<1, 32, 8, 1, 4>), dim3(count), dim3(512), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
+                did |= 1u << GJ_WK_STRIP_512_FAT; break;
+            case GJ_WK_STRIP_512_2CH:    // two chunks in flight: 72 spilled registers, 23.3 ms against 22.6 (1000 x n = 500)
+                hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 4, 2, 2>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
+                did |= 1u << GJ_WK_STRIP_512_2CH; break;
+            case GJ_WK_STRIP_512:
+                hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 4, 2, 1>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
+                did |= 1u << GJ_WK_STRIP_512; break;
+            case GJ_WK_STRIP_1024:
+                hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 8, 1, 2>), dim3(count), dim3(512), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
+                did |= 1u << GJ_WK_STRIP_1024; break;
+            case GJ_WK_LA_6:
                 hipLaunchKernelGGL((gj_window_la_kernel<16, 4, 6>), dim3(count), dim3(6 * 64), smem, s, n, Ag, stride, pg, ig, c0, cw, stp);
-            else if (NBI == 16 && RPT == 1 && winla)
+                did |= 1u << GJ_WK_LA_6; break;
+            case GJ_WK_LA_12:
                 hipLaunchKernelGGL((gj_window_la_kernel<16, 8, 12>), dim3(count), dim3(12 * 64), smem, s, n, Ag, stride, pg, ig, c0, cw, stp);
-            else
+                did |= 1u << GJ_WK_LA_12; break;
+            default:
                 hipLaunchKernelGGL(kern, dim3(count), dim3(PT), smem, s, n, Ag, stride, pg, ig, c0, cw, stp);
+                did |= 1u << GJ_WK_TEAM; break;
+            }
         };
         auto colupdate = [&](int c0, int cw, int only_blk) {
             const int blocks = only_blk >= 0 ? 1 : nblk - 1;
             const dim3 grid(8 * ((count + 7) / 8) * blocks);
-            // eight waves per column block where the launch has fewer workgroups than the chip has CUs AND the whole
-            // batch (all stream groups together) leaves the chip room: there a column block's latency counts, not the
-            // CU's throughput (MI355X, inverse ms, lean / fat: 61 x N = 800 8.87 / 7.57, 64 x N = 1000 14.40 / 13.83,
-            // 250 x N = 500 6.81 / 6.49 (single-block launches of the pairs); but 1000 x N = 500 25.4 / 29.8: a fat
-            // workgroup takes a CU's whole LDS and shuts the other groups' kernels out)
-            if ((long)count * blocks > fat_max || (long)nb * nblk > fat_total_max)
+            if ((only_blk >= 0 ? gp.upd_single : gp.upd_full) == 4) {
                 hipLaunchKernelGGL(gj_colupdate_kernel<4>, grid, dim3(256), 0, s, n, count, Ag, stride, (const int*)pg, c0, cw, only_blk);
-            else
+                did |= GJ_BIT_UPD4;
+            } else {
                 hipLaunchKernelGGL(gj_colupdate_kernel<8>, grid, dim3(512), 0, s, n, count, Ag, stride, (const int*)pg, c0, cw, only_blk);
+                did |= GJ_BIT_UPD8;
+            }
         };
-        // Pairs pay where the update is throughput-bound (they halve its traffic); a small group of matrices is a
-        // latency chain of kernels, to which a pair adds two single-block launches: measured cross-over (MI355X,
-        // workgroups of the fused kernel per group) 61 x N = 800 in four groups (165: 8.87 ms one by one, 9.25 in
-        // pairs), 250 x N = 500 (372: 6.91 / 6.81), 128 x N = 1000 (448: 24.0 / 22.95)
-        const bool use_pairs = pair && nblk >= 3 && (long)count * (nblk - 2) >= pair_min;
         for (int c0 = 0; c0 < n; c0 += WIN) {
             const int cw = min(WIN, n - c0);
-            if (use_pairs && c0 + WIN < n) {
+            if (gp.pairs && c0 + WIN < n) {
                 // windows A = [c0, c0 + 64) and B = the next one as a pair: every block outside the two is read and
                 // written once for both (gj_colupdate2_kernel)
                 const int cB = c0 + WIN, cwB = min(WIN, n - cB), jA = c0 / WIN;
@@ -1549,68 +1532,48 @@ void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t str
                 colupdate(cB, cwB, jA);                           // B -> block A: the pair's transform is now [P''A | P'B]
                 hipLaunchKernelGGL(gj_colupdate2_kernel, dim3(8 * ((count + 7) / 8) * (nblk - 2)), dim3(CU_THREADS), 0, s,
                                    n, count, Ag, stride, (const int*)pg, c0, cwB);
+                did |= GJ_BIT_UPD2;
                 c0 += WIN;
                 continue;
             }
             window(c0, cw);
             if (nblk > 1) colupdate(c0, cw, -1);
         }
-        // (skip_gather: the caller resolves G[i][j] = W[pivrow[i]][colof[j]] itself -- the weighted sum of GrInt reads the
+        // (no gather: the caller resolves G[i][j] = W[pivrow[i]][colof[j]] itself -- the weighted sum of GrInt reads the
         //  reduced matrices through the permutation, launch_accumulate_perm, and G is never written)
-        if (!skip_gather)
+        if (plan.gather) {
             hipLaunchKernelGGL(gj_gather_kernel, dim3(n, count), dim3(256), 0, s, n, (const cplx*)Ag, Bg, stride,
                                (const int*)pg, (const int*)ig);
-    };
-    // Small batches -- what the energy grid of BASELINE's multi-GPU configurations leaves one GPU: C4 sharded 8
-    // ways is 61 matrices of N = 800, C5 128 of N = 1000 -- cannot cover the chip with one panel workgroup per
-    // matrix, and window k+1 waits for the column update of window k.  The batch is then cut into up to four
-    // groups on streams of their own: while one group factors a panel (a few CUs), the column updates of the
-    // others use the rest of the chip: 61 x N = 800 24.5 -> 30.5 TF, 128 x N = 1000 34.9 -> 40.0 TF.  At full batch both
-    // kernels fill the chip by themselves and the groups mostly run in lockstep: + 2 % (1000 x N = 500 33.1 -> 33.8 TF).
-    static int split_max = -1;
-    if (split_max < 0) { const char* e = getenv("NEGF_GJ_SPLIT_MAX"); split_max = e ? atoi(e) : 1 << 30; }
-    static int grp_max = -1, grp_min = -1;          // NEGF_GJ_GROUP_MAX (<= GjSideStreams::MAXG), NEGF_GJ_GROUP_MIN: matrices per group
-    if (grp_max < 0) { const char* e = getenv("NEGF_GJ_GROUP_MAX"); grp_max = e ? std::min(std::max(atoi(e), 1), (int)GjSideStreams::MAXG) : 4; }
-    if (grp_min < 0) { const char* e = getenv("NEGF_GJ_GROUP_MIN"); grp_min = e ? std::max(atoi(e), 1) : 12; }
-    const int groups = (nb <= split_max && !d_stamps) ? std::max(1, std::min(grp_max, nb / grp_min)) : 1;
-    if (groups == 1) {
-        chain(st, 0, nb);
-    } else {
-        // side streams and fork / join events belong to the CONTEXT (created on its device at first use, destroyed with
-        // it): two contexts never record the same events
-        if (!sdp) { chain(st, 0, nb); return; }
-        GjSideStreams& sd = *sdp;
-        if (!sd.ok) {
-            bool good = hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) == hipSuccess;
-            for (int g = 0; g < GjSideStreams::MAXG - 1; ++g) {
-                good = good && hipStreamCreateWithFlags(&sd.s[g], hipStreamNonBlocking) == hipSuccess;
-                good = good && hipEventCreateWithFlags(&sd.join[g], hipEventDisableTiming) == hipSuccess;
-            }
-            if (!good) { (void)hipGetLastError(); chain(st, 0, nb); return; }
-            sd.ok = true;
+            did |= GJ_BIT_GATHER;
         }
+    };
+    // (why small batches are cut into groups on streams of their own: gj_plan)
+    if (rec) rec->groups = plan.groups;
+    if (plan.groups == 1) {
+        chain(st, 0);
+    } else {
+        // side streams and fork / join events belong to the CONTEXT (gj_side_ready, called before the plan was made):
+        // two contexts never record the same events
+        GjSideStreams& sd = *sdp;
         hipStream_t* side = sd.s;
         hipEvent_t ev_fork = sd.fork;
         hipEvent_t* ev_join = sd.join;
         (void)hipEventRecord(ev_fork, st);
-        const int per = (nb + groups - 1) / groups;
-        for (int g = 1; g < groups; ++g) {
-            const int first = g * per, count = std::min(per, nb - first);
-            if (count <= 0) continue;
+        for (int g = 1; g < plan.groups; ++g) {
             (void)hipStreamWaitEvent(side[g - 1], ev_fork, 0);
-            chain(side[g - 1], first, count);
+            chain(side[g - 1], g);
             (void)hipEventRecord(ev_join[g - 1], side[g - 1]);
         }
-        chain(st, 0, std::min(per, nb));
-        for (int g = 1; g < groups; ++g)
-            if (g * per < nb) (void)hipStreamWaitEvent(st, ev_join[g - 1], 0);
+        chain(st, 0);
+        for (int g = 1; g < plan.groups; ++g) (void)hipStreamWaitEvent(st, ev_join[g - 1], 0);
     }
     if (d_stamps) {
         (void)hipStreamSynchronize(st);
         unsigned long long h[64];
         (void)hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);
         auto us = [&](int i) { return (double)(h[i] - h[0]) / 100.0; };
-        if (NBI == 16 && (win_mode == 1 || (win_mode == 0 && strip_env != 0))) {
+        const int wk0 = plan.g[0].wk;
+        if (wk0 >= GJ_WK_STRIP_256 && wk0 <= GJ_WK_STRIP_1024) {
             fprintf(stderr, "[gj strip stamps] n=%d window 1, workgroup 0 (us since the window's start):", n);
             for (int sp = 0; sp < 4; ++sp)
                 fprintf(stderr, " | sub %d: top %.1f loaded %.1f forward %.1f factored %.1f stored %.1f staged %.1f backward %.1f", sp,
@@ -1619,7 +1582,7 @@ void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t str
                     (long long)(h[41] - h[40]), (long long)(h[42] - h[40]), (long long)(h[43] - h[40]), (long long)(h[44] - h[40]), (long long)(h[45] - h[40]), (long long)(h[45] - h[40]));
             return;
         }
-        if (NBI == 16 && RPT == 1 && winla) {
+        if (wk0 == GJ_WK_LA_6 || wk0 == GJ_WK_LA_12) {
             fprintf(stderr, "[gj window-la stamps] n=%d window 1, workgroup 0 (us):", n);
             for (int sp = 0; sp < 4; ++sp)
                 fprintf(stderr, " | sub %d: A %.1f panel %.1f upd-team %.1f B %.1f C %.1f look-ahead %.1f", sp, us(1 + 6 * sp), us(2 + 6 * sp),
@@ -1652,44 +1615,185 @@ int gj_large_pick(int n)
 
 bool inverse_blocked_supported(int n) { return gj_pick(n) != 0 || gj_large_pick(n) != 0; }
 
-// In-place reduction of A with B as scratch; the inverses are gathered into B.
-// piv: [nb][2][n] ints of pivot bookkeeping (used by the large-matrix path).
-// Returns true: the result is in B.
 double inverse_blocked_vector_flops() { return g_gj_vector_flops; }
 
-bool launch_inverse_blocked(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t stride, int* piv, int* info, GjSideStreams* side, int win_mode,
-                            bool* skip_gather)
+// This process's thresholds: the defaults of GjParams with the NEGF_GJ_* switches applied, read once.
+const GjParams& gj_params()
 {
-    g_gj_vector_flops = 0;
-    // single-workgroup kernel up to 256 rows (its 32-column panel configuration); above, the windowed
-    // path with 16-column sub-panels is faster (measured on MI355X, ms per 1000 matrices: n = 260 9.3 vs
+    static const GjParams params = [] {
+        GjParams p;
+        auto geti = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+        auto getl = [](const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; };
+        p.large_min = geti("NEGF_GJ_LARGE_MIN", p.large_min);
+        p.small_win_min = geti("NEGF_GJ_SMALL_WIN_MIN", p.small_win_min);
+        p.winla = geti("NEGF_GJ_WINLA", p.winla);
+        p.strip_env = geti("NEGF_GJ_STRIP", p.strip_env);
+        p.strip_min = geti("NEGF_GJ_STRIP_MIN", p.strip_min);
+        p.strip_cfg = geti("NEGF_GJ_STRIP_CFG", p.strip_cfg);
+        p.pair = geti("NEGF_GJ_PAIR", p.pair);
+        p.pair_min = getl("NEGF_GJ_PAIR_MIN", p.pair_min);
+        p.fat_max = getl("NEGF_GJ_FAT_MAX", p.fat_max);
+        p.fat_total_max = getl("NEGF_GJ_FAT_TOTAL_MAX", p.fat_total_max);
+        p.split_max = geti("NEGF_GJ_SPLIT_MAX", p.split_max);
+        if (const char* e = getenv("NEGF_GJ_GROUP_MAX")) p.grp_max = std::min(std::max(atoi(e), 1), (int)GjSideStreams::MAXG);
+        if (const char* e = getenv("NEGF_GJ_GROUP_MIN")) p.grp_min = std::max(atoi(e), 1);
+        p.stamps = getenv("NEGF_GJ_STAMPS") ? 1 : 0;
+        return p;
+    }();
+    return params;
+}
+
+// The launch rule of the blocked inverse, all of it, with the measurements (MI355X) behind each threshold.
+int gj_plan(int n, int nb, int win_mode, bool defer, const GjParams& p, GjPlan* out)
+{
+    if (n < 1 || nb < 1 || win_mode < 0 || win_mode > 2 || !out) return NEGF_EINVAL;
+    GjPlan pl;
+    // Single-workgroup kernel or windows.  The single-workgroup kernel serves up to 256 rows (its 32-column panel
+    // configuration); above, the windowed path with 16-column sub-panels is faster (ms per 1000 matrices: n = 260 9.3 vs
     // 9.1, 300 13.3 vs 11.1, 340 20.5 vs 17.3, 370 28.5 vs 20.1); NEGF_GJ_LARGE_MIN moves the switch-over
     // (round 5: with the strip window kernel the windowed path wins from n = 209 on -- ms per 1000 matrices, windowed /
     // single workgroup: n = 192 2.45 / 2.58 but 200 3.01 / 3.01 and 208 3.08 / 3.08 (a ragged fourth window), 224 3.33 / 3.56,
-    // 240 3.70 / 4.49, 256 4.01 / 5.26)
-    static int large_min = -1;
-    if (large_min < 0) { const char* e = getenv("NEGF_GJ_LARGE_MIN"); large_min = e ? atoi(e) : 209; }
+    // 240 3.70 / 4.49, 256 4.01 / 5.26).
     // win_mode 1 (tests, A/B) takes the windowed path with the strip kernel wherever it exists (64 <= n), win_mode 2 the
     // pre-strip configuration (single workgroup up to 256, team window kernels above)
     // (below large_min the single-workgroup kernel keeps the batches that do not fill the chip -- one matrix per CU costs what a
     // single matrix does: 108 x n = 200 0.65 ms against 0.94 windowed -- and the windowed path takes the rest, ms per 1000
     // matrices windowed / single workgroup: n = 100 0.87 / 0.93, 128 1.09 / 1.29, 160 1.60 / 1.83, 192 2.21 / 2.60,
     // 200 2.67 / 2.97 (C2), 208 2.66 / 3.09; 324 x n = 200 1.26 / 1.36)
-    static int small_win_min = -1;       // matrices from which 100 <= n < large_min goes windowed
-    if (small_win_min < 0) { const char* e = getenv("NEGF_GJ_SMALL_WIN_MIN"); small_win_min = e ? atoi(e) : 257; }
-    const bool single_wg = win_mode == 1 ? n < 64 : win_mode == 2 ? n <= 256 : (n < large_min && !(n >= 100 && nb >= small_win_min));
-    const bool defer = skip_gather && *skip_gather;               // only the windowed path can leave the gather to the caller
-    if (skip_gather) *skip_gather = false;
-    if (single_wg && gj_pick(n) == 1) { gj_launch<CfgSplit>(st, n, nb, A, B, stride, info); return true; }
-    if (defer && gj_large_pick(n) != 0) *skip_gather = true;
-    // sub-panels of 16 columns up to n = 1024 (measured on MI355X, 1000 matrices: n = 500 46.2 -> 41.1 ms,
-    // n = 1000 296 -> 257 ms against sub-panels of 8: half as many passes over the 64-column window)
-    switch (gj_large_pick(n)) {
-    case 1: gj_large_launch<16, 2>(st, n, nb, A, B, stride, piv, info, side, win_mode, defer); return true;
-    case 2: gj_large_launch<8, 4>(st, n, nb, A, B, stride, piv, info, side, win_mode, defer); return true;
-    case 3: gj_large_launch<4, 8>(st, n, nb, A, B, stride, piv, info, side, win_mode, defer); return true;
-    case 4: gj_large_launch<16, 1>(st, n, nb, A, B, stride, piv, info, side, win_mode, defer); return true;
-    case 5: gj_large_launch<2, 16>(st, n, nb, A, B, stride, piv, info, side, win_mode, defer); return true;
-    default: return false;
+    const bool single_wg = win_mode == 1 ? n < 64 : win_mode == 2 ? n <= 256 : (n < p.large_min && !(n >= 100 && nb >= p.small_win_min));
+    if (single_wg && gj_pick(n) == 1) {
+        pl.path = 1;
+        pl.groups = 1;
+        pl.g[0].first = 0; pl.g[0].count = nb; pl.g[0].wk = GJ_WK_SINGLE; pl.g[0].mask = 1u << GJ_WK_SINGLE;
+        *out = pl;                       // (only the windowed path can leave the gather to the caller)
+        return NEGF_OK;
     }
+    // the class: sub-panels of 16 columns up to n = 1024 (1000 matrices: n = 500 46.2 -> 41.1 ms, n = 1000 296 -> 257 ms
+    // against sub-panels of 8: half as many passes over the 64-column window)
+    switch (gj_large_pick(n)) {
+    case 1: pl.nbi = 16; pl.rpt = 2; break;
+    case 2: pl.nbi = 8; pl.rpt = 4; break;
+    case 3: pl.nbi = 4; pl.rpt = 8; break;
+    case 4: pl.nbi = 16; pl.rpt = 1; break;
+    case 5: pl.nbi = 2; pl.rpt = 16; break;
+    default: *out = pl; return NEGF_OK;  // path 0: the unblocked kernel
+    }
+    pl.path = 2;
+    pl.nblk = (n + 63) / 64;
+    pl.deferred = defer ? 1 : 0;
+    pl.gather = defer ? 0 : 1;
+    // Small batches -- what the energy grid of BASELINE's multi-GPU configurations leaves one GPU: C4 sharded 8
+    // ways is 61 matrices of N = 800, C5 128 of N = 1000 -- cannot cover the chip with one panel workgroup per
+    // matrix, and window k+1 waits for the column update of window k.  The batch is then cut into up to four
+    // groups on streams of their own: while one group factors a panel (a few CUs), the column updates of the
+    // others use the rest of the chip: 61 x N = 800 24.5 -> 30.5 TF, 128 x N = 1000 34.9 -> 40.0 TF.  At full batch both
+    // kernels fill the chip by themselves and the groups mostly run in lockstep: + 2 % (1000 x N = 500 33.1 -> 33.8 TF).
+    const int want = (nb <= p.split_max && !p.stamps) ? std::max(1, std::min(std::min(p.grp_max, (int)GjSideStreams::MAXG), nb / std::max(p.grp_min, 1))) : 1;
+    const int per = (nb + want - 1) / want;
+    for (int g = 0; g < want && g * per < nb; ++g) {
+        GjGroup& gp = pl.g[pl.groups++];
+        gp.first = g * per;
+        gp.count = std::min(per, nb - gp.first);
+    }
+    for (int g = 0; g < pl.groups; ++g) {
+        GjGroup& gp = pl.g[g];
+        const int count = gp.count;
+        // Which window kernel (win_mode 0 = auto, 1 = strip wherever an instantiation serves n, 2 = team kernels only;
+        // NEGF_GJ_STRIP = 0 / 1 sets the auto rule's answer for A/B runs).  Inverse ms, strip / team:
+        //   1000 matrices: n = 256 4.01 / 5.26 (single-workgroup kernel), 300 6.62 / 7.53, 400 13.0 / 14.6, 500 21.5 / 24.5 (the
+        //   strip kernel moves 3.3 MB per window and matrix instead of 4.9, and both run at the ~4.3 TB/s this access pattern
+        //   gets out of the memory system), 650 55.5 / 53.5, 800 84.8 / 84.4, 1000 147.9 / 150.4 (the 8-wave, one-per-CU form);
+        //   small batches (stream groups of m / 4): 32 x n = 500 2.29 / 2.20, 128 x 500 4.10 / 3.97, 250 x 500 6.20 / 6.12 (a lean
+        //   4-wave workgroup has a longer chain per matrix than the 12-wave look-ahead kernel), 12 x 800 5.51 / 5.77,
+        //   61 x 800 7.54 / 8.10, 64 x 1000 13.1 / 14.1, 128 x 1000 23.0 / 23.9, 486 x 800 42.5 / 42.4.
+        const bool strip = pl.nbi == 16 &&
+            (win_mode == 1 || (win_mode == 0 && (p.strip_env >= 0 ? p.strip_env != 0
+                                                 : (n <= 256 || (n <= 512 ? count >= p.strip_min : (count <= p.strip_max || n >= p.strip_always))))));
+        // strip_cfg 0: the measured choice per size; 1: n <= 512 fat (8 waves x 1 row, sub-windows of 32); 3: n <= 256 with
+        // sub-windows of 16; 4: n <= 512 lean with two chunks in flight
+        if (strip)
+            gp.wk = n <= 256 ? (p.strip_cfg != 3 ? GJ_WK_STRIP_256 : GJ_WK_STRIP_256_S16)
+                  : n <= 512 ? (p.strip_cfg == 1 ? GJ_WK_STRIP_512_FAT : p.strip_cfg == 4 ? GJ_WK_STRIP_512_2CH : GJ_WK_STRIP_512)
+                  : GJ_WK_STRIP_1024;
+        else if (pl.nbi == 16 && pl.rpt == 1 && p.winla)
+            gp.wk = n <= 256 ? GJ_WK_LA_6 : GJ_WK_LA_12;
+        else
+            gp.wk = GJ_WK_TEAM;
+        // Pairs pay where the update is throughput-bound (they halve its traffic); a small group of matrices is a
+        // latency chain of kernels, to which a pair adds two single-block launches: measured cross-over (workgroups of
+        // the fused kernel per group) 61 x N = 800 in four groups (165: 8.87 ms one by one, 9.25 in pairs), 250 x N = 500
+        // (372: 6.91 / 6.81), 128 x N = 1000 (448: 24.0 / 22.95)
+        // (round 5, with the strip window kernels, inverse ms without / with pairs: 122 x N = 800 (330 workgroups per group) 13.46 /
+        //  12.09, 128 x N = 500 (192) 3.93 / 3.94, 61 x N = 800 (165) 7.39 / 8.95: the threshold moved from 352 to 256)
+        gp.pairs = (p.pair && pl.nblk >= 3 && (long)count * (pl.nblk - 2) >= p.pair_min) ? 1 : 0;
+        // The update: eight waves per column block where the launch has fewer workgroups than the chip has CUs AND the whole
+        // batch (all stream groups together) leaves the chip room: there a column block's latency counts, not the
+        // CU's throughput (inverse ms, lean / fat: 61 x N = 800 8.87 / 7.57, 64 x N = 1000 14.40 / 13.83,
+        // 250 x N = 500 6.81 / 6.49 (single-block launches of the pairs); but 1000 x N = 500 25.4 / 29.8: a fat
+        // workgroup takes a CU's whole LDS and shuts the other groups' kernels out)
+        auto waves = [&](int blocks) { return ((long)count * blocks > p.fat_max || (long)nb * pl.nblk > p.fat_total_max) ? 4 : 8; };
+        // launches over all other blocks: every window without pairs, the odd last window with them
+        if (pl.nblk > 1 && (!gp.pairs || (pl.nblk & 1))) gp.upd_full = waves(pl.nblk - 1);
+        if (gp.pairs) gp.upd_single = waves(1);
+        gp.mask = 1u << gp.wk;
+        if (gp.upd_full == 4 || gp.upd_single == 4) gp.mask |= GJ_BIT_UPD4;
+        if (gp.upd_full == 8 || gp.upd_single == 8) gp.mask |= GJ_BIT_UPD8;
+        if (gp.pairs) gp.mask |= GJ_BIT_UPD2;
+        if (pl.gather) gp.mask |= GJ_BIT_GATHER;
+    }
+    *out = pl;
+    return NEGF_OK;
+}
+
+namespace {
+
+// the context's side streams and fork / join events, created on its device at first use and destroyed with it
+bool gj_side_ready(GjSideStreams* sdp)
+{
+    if (!sdp) return false;
+    GjSideStreams& sd = *sdp;
+    if (sd.ok) return true;
+    bool good = hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) == hipSuccess;
+    for (int g = 0; g < GjSideStreams::MAXG - 1; ++g) {
+        good = good && hipStreamCreateWithFlags(&sd.s[g], hipStreamNonBlocking) == hipSuccess;
+        good = good && hipEventCreateWithFlags(&sd.join[g], hipEventDisableTiming) == hipSuccess;
+    }
+    if (!good) { (void)hipGetLastError(); return false; }
+    sd.ok = true;
+    return true;
+}
+
+}  // namespace
+
+// In-place reduction of A with B as scratch; the inverses are gathered into B.
+// piv: [nb][2][n] ints of pivot bookkeeping (used by the large-matrix path).
+// Returns true: the result is in B.
+bool launch_inverse_blocked(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t stride, int* piv, int* info, GjSideStreams* side, int win_mode,
+                            bool* skip_gather, GjRecord* rec)
+{
+    g_gj_vector_flops = 0;
+    const bool defer = skip_gather && *skip_gather;
+    if (skip_gather) *skip_gather = false;
+    if (rec) *rec = GjRecord{};
+    GjPlan plan;
+    if (gj_plan(n, nb, win_mode, defer, gj_params(), &plan) != NEGF_OK) plan = GjPlan{};
+    if (plan.groups > 1 && !gj_side_ready(side)) {         // no side streams: the whole batch as one group
+        GjParams one = gj_params();
+        one.grp_max = 1;
+        (void)gj_plan(n, nb, win_mode, defer, one, &plan);
+    }
+    if (rec) rec->path = plan.path;
+    if (plan.path == 0) return false;
+    if (plan.path == 1) {
+        gj_launch<CfgSplit>(st, n, nb, A, B, stride, info);
+        if (rec) { rec->groups = 1; rec->mask[0] |= 1u << GJ_WK_SINGLE; }
+        return true;
+    }
+    if (skip_gather) *skip_gather = plan.deferred != 0;
+    if (plan.nbi == 16 && plan.rpt == 1) gj_large_launch<16, 1>(st, n, nb, A, B, stride, piv, info, side, plan, rec);
+    else if (plan.nbi == 16) gj_large_launch<16, 2>(st, n, nb, A, B, stride, piv, info, side, plan, rec);
+    else if (plan.nbi == 8) gj_large_launch<8, 4>(st, n, nb, A, B, stride, piv, info, side, plan, rec);
+    else if (plan.nbi == 4) gj_large_launch<4, 8>(st, n, nb, A, B, stride, piv, info, side, plan, rec);
+    else gj_large_launch<2, 16>(st, n, nb, A, B, stride, piv, info, side, plan, rec);
+    return true;
 }

@@ -401,6 +401,8 @@ int run_inverse(negf_ctx* c, int nb, int* info)
     ProfScope ps(c, "inverse");
     int algo = c->inverse_algo;
     c->G_deferred = false;
+    c->gj_last = GjRecord{};
+    c->gj_last.path = 0;                                         // (the unblocked kernel, unless the blocked launch says otherwise)
     if (algo == 0) algo = inverse_blocked_supported(c->n) ? 2 : 1;
     const int win_mode = algo == 3 ? 1 : algo == 4 ? 2 : 0;      // 3 / 4: the blocked path with the window kernel chosen
     if (algo > 2) algo = 2;
@@ -408,7 +410,7 @@ int run_inverse(negf_ctx* c, int nb, int* info)
     if (algo == 2) {
         // false: no blocked kernel serves this n (nothing was launched) -> the unblocked kernel
         bool skip = c->defer_gather;
-        in_b = launch_inverse_blocked(c->stream, c->n, nb, c->d_A, c->d_T1, (size_t)c->n * c->n, c->d_ipiv, info, &c->gj_side, win_mode, &skip);
+        in_b = launch_inverse_blocked(c->stream, c->n, nb, c->d_A, c->d_T1, (size_t)c->n * c->n, c->d_ipiv, info, &c->gj_side, win_mode, &skip, &c->gj_last);
         c->G_deferred = skip;
         if (!in_b) algo = 1;
     }
@@ -2370,6 +2372,41 @@ int negf_eigh_batched(negf_ctx* c, int K, int m, const double* A, double* w, dou
         if (hi[i] != 0) rc = NEGF_ESINGULAR;
     }
     return rc;
+}
+
+// ------------------------------------------------------- the blocked inverse's launch rule (diagnostic)
+int negf_inverse_plan(int n, int nb, int algo, int defer, int* path, int* nbi, int* rpt, int* nblk, int* groups,
+                      int* group_tab, int* gather, int* deferred)
+{
+    if (n < 1 || nb < 1 || algo < 0 || algo > 4) return NEGF_EINVAL;
+    GjPlan pl;
+    if (algo != 1) {                     // (1: the unblocked kernel, path 0)
+        const int rc = gj_plan(n, nb, algo == 3 ? 1 : algo == 4 ? 2 : 0, defer != 0, gj_params(), &pl);
+        if (rc) return rc;
+    }
+    if (path) *path = pl.path;
+    if (nbi) *nbi = pl.nbi;
+    if (rpt) *rpt = pl.rpt;
+    if (nblk) *nblk = pl.nblk;
+    if (groups) *groups = pl.groups;
+    if (gather) *gather = pl.gather;
+    if (deferred) *deferred = pl.deferred;
+    if (group_tab)
+        for (int g = 0; g < 4; ++g) {
+            const GjGroup& gp = pl.g[g];
+            const int row[7] = {gp.first, gp.count, gp.wk, gp.pairs, gp.upd_full, gp.upd_single, (int)gp.mask};
+            for (int k = 0; k < 7; ++k) group_tab[g * 7 + k] = g < pl.groups ? row[k] : 0;
+        }
+    return NEGF_OK;
+}
+
+int negf_inverse_last(negf_ctx* c, int* path, int* groups, int* masks)
+{
+    if (!c) return NEGF_EINVAL;
+    if (path) *path = c->gj_last.path;
+    if (groups) *groups = c->gj_last.groups;
+    if (masks) for (int g = 0; g < 4; ++g) masks[g] = (int)c->gj_last.mask[g];
+    return NEGF_OK;
 }
 
 // ------------------------------------------------------- the product kernels, called directly (diagnostic)

@@ -176,6 +176,75 @@ struct GjSideStreams {
     bool ok = false;
 };
 
+// What the blocked inverse launches for a shape (gj_plan, k_inverse_blocked.hip; negf_inverse_plan): the launch code
+// reads this and decides nothing itself.
+// window kernel ids (also the bit positions of a group's launch mask):
+enum {
+    GJ_WK_NONE = 0,
+    GJ_WK_STRIP_256 = 1,       // gj_window_strip_kernel<1, 32, 4, 2, 4>: n <= 256, sub-windows of 32
+    GJ_WK_STRIP_256_S16 = 2,   // gj_window_strip_kernel<1, 16, 4, 3, 4> (NEGF_GJ_STRIP_CFG = 3)
+    GJ_WK_STRIP_512_FAT = 3,   // gj_window_strip_kernel<1, 32, 8, 1, 4> (NEGF_GJ_STRIP_CFG = 1)
+    GJ_WK_STRIP_512_2CH = 4,   // gj_window_strip_kernel<2, 16, 4, 2, 2> (NEGF_GJ_STRIP_CFG = 4)
+    GJ_WK_STRIP_512 = 5,       // gj_window_strip_kernel<2, 16, 4, 2, 1>: 257 ... 512, the lean 4-wave form
+    GJ_WK_STRIP_1024 = 6,      // gj_window_strip_kernel<2, 16, 8, 1, 2>: 513 ... 1024, 8 waves
+    GJ_WK_LA_6 = 7,            // gj_window_la_kernel<16, 4, 6>
+    GJ_WK_LA_12 = 8,           // gj_window_la_kernel<16, 8, 12>
+    GJ_WK_TEAM = 9,            // gj_window_kernel<NBI, RPT>
+    GJ_WK_SINGLE = 10,         // gj_blocked_kernel (one workgroup per matrix, no windows)
+};
+// further bits of a group's launch mask
+enum {
+    GJ_BIT_UPD4 = 1 << 12,     // gj_colupdate_kernel<4> (lean)
+    GJ_BIT_UPD8 = 1 << 13,     // gj_colupdate_kernel<8> (fat)
+    GJ_BIT_UPD2 = 1 << 14,     // gj_colupdate2_kernel (a pair of windows)
+    GJ_BIT_GATHER = 1 << 15,   // gj_gather_kernel
+};
+// the thresholds of the rule with their defaults; gj_params() is this process's set (NEGF_GJ_* read once)
+struct GjParams {
+    int large_min = 209;             // NEGF_GJ_LARGE_MIN: n from which the windowed path serves every batch
+    int small_win_min = 257;         // NEGF_GJ_SMALL_WIN_MIN: matrices from which 100 <= n < large_min goes windowed
+    int winla = 1;                   // NEGF_GJ_WINLA: the look-ahead team kernels for the <16,1> class
+    int strip_env = -1;              // NEGF_GJ_STRIP: -1 = the rule, 0 / 1 = its answer
+    int strip_min = 64;              // NEGF_GJ_STRIP_MIN: matrices per group from which 257 <= n <= 512 takes the strip kernel
+    int strip_max = 160;             // matrices per group up to which 513 <= n < strip_always takes it
+    int strip_always = 900;          // n from which the <16,2> class always takes it
+    int strip_cfg = 0;               // NEGF_GJ_STRIP_CFG
+    int pair = 1;                    // NEGF_GJ_PAIR
+    long pair_min = 256;             // NEGF_GJ_PAIR_MIN: count * (nblk - 2) from which windows go in pairs
+    long fat_max = 256;              // NEGF_GJ_FAT_MAX: workgroups of an update launch up to which it is fat ...
+    long fat_total_max = 2000;       // NEGF_GJ_FAT_TOTAL_MAX: ... if nb * nblk does not exceed this
+    int split_max = 1 << 30;         // NEGF_GJ_SPLIT_MAX
+    int grp_max = 4;                 // NEGF_GJ_GROUP_MAX (<= GjSideStreams::MAXG)
+    int grp_min = 12;                // NEGF_GJ_GROUP_MIN: matrices per group
+    int stamps = 0;                  // NEGF_GJ_STAMPS: time stamps of one workgroup (one group)
+};
+struct GjGroup {
+    int first = 0, count = 0;        // matrices [first, first + count)
+    int wk = GJ_WK_NONE;             // window kernel id
+    int pairs = 0;                   // windows in pairs (gj_colupdate2_kernel; an odd last window on its own)
+    int upd_full = 0;                // waves per column block (4 lean, 8 fat) of the update launches over all other blocks, 0: none
+    int upd_single = 0;              // ... of the single-block launches of a pair, 0: none
+    unsigned mask = 0;               // the launches of this group: 1 << wk | GJ_BIT_*
+};
+struct GjPlan {
+    int path = 0;                    // 0 = no blocked kernel serves n (unblocked), 1 = single workgroup, 2 = windowed
+    int nbi = 0, rpt = 0;            // windowed: the class (sub-panel width, rows per lane)
+    int nblk = 0;                    // windowed: 64-column windows
+    int groups = 0;
+    GjGroup g[4];
+    int gather = 0;                  // gj_gather_kernel runs
+    int deferred = 0;                // the result stays un-gathered for launch_accumulate_perm
+};
+// per context: what the last inverse really launched (each launch site adds its bit)
+struct GjRecord {
+    int path = -1;                   // -1: no inverse yet
+    int groups = 0;
+    unsigned mask[4] = {};
+};
+const GjParams& gj_params();
+// NEGF_OK / NEGF_EINVAL (n < 1, nb < 1, win_mode outside 0 ... 2); no HIP call
+int gj_plan(int n, int nb, int win_mode, bool defer, const GjParams& p, GjPlan* out);
+
 // A layered (block-tridiagonal) system of the recursive Green's function path: an object of its own inside the context
 // (negf_layered_*; defined in negf_layered_impl.h)
 struct LayeredSystem;
@@ -267,6 +336,7 @@ struct negf_ctx {
     DevBuf<cplx> d_deph_D;         // [batch][K_U^2] dephased coupling matrices on the union of the orbitals involved
     DevBuf<int> d_deph_tab;        // the union U [K_U] | the terminals' orbital lists as positions in U | the terminals added, in order
     GjSideStreams gj_side;
+    GjRecord gj_last;              // what the last run_inverse / rgf_inverse launched (negf_inverse_last)
     int chain_rr_quantum = -1, chain_rr_slots = 0;   // negf_set_chain_round_robin
     int small_algo = 0;            // 0: n <= 96 takes the fused single-kernel path, 1: never (negf_set_small_algo)
     // pinned host staging of the host-pointer entry points: [E | w] up, [result | info] down, ONE synchronisation
@@ -316,8 +386,9 @@ bool launch_inverse_unblocked(hipStream_t st, int n, int nb, cplx* A, int* info,
 // skip_gather (in / out): in = the caller can read the reduced matrices through the pivot bookkeeping itself
 // (G[i][j] = A[pivrow[i]][colof[j]], piv = [nb][2][n]); out = the gather was left out (windowed path only) -- the return
 // value then still says "B", but B was not written
+// rec: receives what was launched (reset first; path 0 when the return value is false)
 bool launch_inverse_blocked(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t stride, int* piv, int* info,
-                            GjSideStreams* side = nullptr, int win_mode = 0, bool* skip_gather = nullptr);
+                            GjSideStreams* side = nullptr, int win_mode = 0, bool* skip_gather = nullptr, GjRecord* rec = nullptr);
 bool inverse_blocked_supported(int n);
 // of the last launch_inverse_blocked: the part of its 6 n np^2 three-real-product flops that ran on the VECTOR pipe
 // (the register-strip window kernels), i.e. was not issued to the matrix cores

@@ -303,12 +303,14 @@ int rgf_inverse(const RgfBatch& b, int i, cplx* A, cplx* B, cplx** res)
     {
         ProfScope ps(c, "inverse");
         int algo = c->inverse_algo;
+        c->gj_last = GjRecord{};
+        c->gj_last.path = 0;
         if (algo == 0) algo = inverse_blocked_supported(n) ? 2 : 1;
         const int win_mode = algo == 3 ? 1 : algo == 4 ? 2 : 0;
         if (algo > 2) algo = 2;
         bool in_b = false;
         if (algo == 2) {
-            in_b = launch_inverse_blocked(c->stream, n, nb, A, B, ls->stride, ls->d_piv, ls->d_linfo, &c->gj_side, win_mode, nullptr);
+            in_b = launch_inverse_blocked(c->stream, n, nb, A, B, ls->stride, ls->d_piv, ls->d_linfo, &c->gj_side, win_mode, nullptr, &c->gj_last);
             if (!in_b) algo = 1;
         }
         if (algo == 1 && !launch_inverse_unblocked(c->stream, n, nb, A, ls->d_linfo, ls->stride)) return NEGF_EINVAL;

@@ -1248,6 +1248,35 @@ class Engine:
         return {"kernel": ku.value, "opB": oe.value, "blocks": (blocks[0], blocks[1]),
                 "grid": (grid[0], grid[1], grid[2]), "decode": decode}
 
+    INVERSE_WINDOW_KERNELS = {0: "none", 1: "strip<1,32,4,2,4>", 2: "strip<1,16,4,3,4>", 3: "strip<1,32,8,1,4>",
+                              4: "strip<2,16,4,2,2>", 5: "strip<2,16,4,2,1>", 6: "strip<2,16,8,1,2>", 7: "la<16,4,6>",
+                              8: "la<16,8,12>", 9: "team", 10: "single"}
+
+    @staticmethod
+    def inverse_plan(n, nb, algo=0, defer=False):
+        """What the inverse of ``nb`` matrices of dimension ``n`` launches (negf_inverse_plan; needs no GPU): a dict
+        with ``path`` (0 unblocked, 1 single workgroup, 2 windowed), ``cls`` = (NBI, RPT), ``nblk``, ``gather``,
+        ``deferred`` and ``groups``: a list of dicts ``first``, ``count``, ``wk`` (window kernel id, named by
+        INVERSE_WINDOW_KERNELS), ``pairs``, ``upd_full`` / ``upd_single`` (4 lean, 8 fat, 0 none) and ``mask``."""
+        lib = _lib.load()
+        v = [C.c_int(0) for _ in range(7)]
+        tab = (C.c_int * 28)()
+        check(lib.negf_inverse_plan(int(n), int(nb), int(algo), int(bool(defer)), C.byref(v[0]), C.byref(v[1]),
+                                    C.byref(v[2]), C.byref(v[3]), C.byref(v[4]), tab, C.byref(v[5]), C.byref(v[6])),
+              "negf_inverse_plan")
+        keys = ("first", "count", "wk", "pairs", "upd_full", "upd_single", "mask")
+        groups = [dict(zip(keys, tab[7 * g:7 * g + 7])) for g in range(v[4].value)]
+        return {"path": v[0].value, "cls": (v[1].value, v[2].value), "nblk": v[3].value, "groups": groups,
+                "gather": bool(v[5].value), "deferred": bool(v[6].value)}
+
+    def inverse_last(self):
+        """What this engine's last inverse launched (negf_inverse_last): ``path`` and ``masks``, the launch mask of
+        every group -- equal to ``[g["mask"] for g in inverse_plan(...)["groups"]]`` when the launch followed the plan."""
+        path, groups = C.c_int(0), C.c_int(0)
+        masks = (C.c_int * 4)()
+        check(self._lib.negf_inverse_last(self._ctx, C.byref(path), C.byref(groups), masks), "negf_inverse_last")
+        return {"path": path.value, "masks": [masks[g] for g in range(groups.value)]}
+
 
 def get_engine(device=None):
     """Process-wide engine for ``device`` (default: LOCAL_RANK, else 0)."""

@@ -699,6 +699,32 @@ int negf_zgemm_batched(negf_ctx* ctx, int M, int N, int K, int nb, const double*
  * (in triples) below grid[0] is NEGF_EINVAL, as are the invalid arguments of negf_zgemm_batched. */
 int negf_zgemm_plan(int M, int N, int K, int opB, int nb, int kernel, int* kernel_used, int* opB_eff, int* blocks,
                     int* grid, int* decode, int decode_cap);
+/* What the inverse of nb matrices of dimension n launches under negf_set_inverse_algo(algo); a host function that
+ * needs no device.  It is the rule the launch code itself follows (one function, k_inverse_blocked.hip), with this
+ * process's NEGF_GJ_* switches applied (read once).  defer != 0: the caller reads the reduced matrices through the
+ * pivot bookkeeping (negf_gr_int does), so the windowed path leaves its gather out.  The fused kernel of n <= 96
+ * (negf_set_small_algo 0) never reaches the inverse and is not part of the plan.  Outputs, each may be NULL:
+ *   path      0 = no blocked kernel serves n, or algo = 1 (the unblocked kernel); 1 = the single-workgroup kernel;
+ *             2 = 64-column windows
+ *   nbi, rpt  path 2: the class -- sub-panel width and rows per lane of the team window kernel: (16, 1) up to n = 512,
+ *             (16, 2) up to 1024, (8, 4) up to 2048, (4, 8) up to 4096, (2, 16) up to 8192
+ *   nblk      path 2: windows
+ *   groups    stream groups (1 .. 4; 1 for path 1, 0 for path 0); the groups tile [0, nb) in order
+ *   group_tab [4][7] = per group: first, count, window kernel id, pairs (0 / 1), waves of the update launches over all
+ *             other column blocks (4 = lean, 8 = fat, 0 = none), waves of the single-block update launches of a pair
+ *             (0 = none), launch mask; rows from `groups` on are zero.  Window kernel ids: 1 .. 6 register-strip kernels
+ *             (1 = n <= 256, 5 = 257 .. 512 lean, 6 = 513 .. 1024 eight waves; 2, 3, 4 the NEGF_GJ_STRIP_CFG alternates),
+ *             7 / 8 = look-ahead team kernels of 6 / 12 waves, 9 = the team kernel of the class, 10 = single workgroup.
+ *             Launch mask: bit (window kernel id), bit 12 = lean update, 13 = fat update, 14 = the fused update of a
+ *             pair of windows, 15 = gather
+ *   gather    the gather kernel runs;  deferred: the result stays un-gathered (path 2 with defer)
+ * NEGF_EINVAL: n < 1, nb < 1, algo outside 0 .. 4. */
+int negf_inverse_plan(int n, int nb, int algo, int defer, int* path, int* nbi, int* rpt, int* nblk, int* groups,
+                      int* group_tab, int* gather, int* deferred);
+/* What the context's last inverse (dense or layered: the last layer inverted) really launched: every launch site adds
+ * its bit next to its launch.  path as above (-1: no inverse yet), groups, masks[4] = the launch mask per group as in
+ * negf_inverse_plan.  Each may be NULL. */
+int negf_inverse_last(negf_ctx* ctx, int* path, int* groups, int* masks);
 
 #ifdef __cplusplus
 }

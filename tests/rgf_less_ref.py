@@ -130,7 +130,7 @@ def dense(c, E, sel):
 
 @functools.lru_cache(maxsize=None)
 def _truth_columns(name, E):
-    c = {k.name: k for k in rr.cases()}[name]
+    c = rr.window_case() if name == "w" else {k.name: k for k in rr.cases()}[name]
     xprec.require_extended()
     cols = np.concatenate([c.left_global, c.right_global])
     (X, _), = xprec.refine([(rr.assembled(c, E, LD), cols)], [2.0 ** -55])
@@ -196,21 +196,38 @@ def truth_table():
     table = {}
     for tag, c, E, w in inputs():
         for sel in SELECTIONS:
-            ent = dict(case=c, E=E, w=w, sel=sel)
-            for form in ("truth", "lr", "rl", "dense"):
-                ent[form] = evaluate(form, c, E, w, sel)
-            for form in ("lr", "rl", "dense"):
-                ent["err_" + form] = {k: rr.rel_err(ent[form][k], ent["truth"][k]) for k in KEYS}
-                # energy by energy, for the calibration: (blocks, rows) of each energy alone
-                ent["err1_" + form] = [(rr.rel_err(ent[form]["single"][j], ent["truth"]["single"][j]),
-                                        rr.rel_err(ent[form]["rows"][j], ent["truth"]["rows"][j])) for j in range(len(E))]
-            table[(tag, sel)] = ent
+            table[(tag, sel)] = _entry(c, E, w, sel)
     return table
+
+
+def _entry(c, E, w, sel):
+    ent = dict(case=c, E=E, w=w, sel=sel)
+    for form in ("truth", "lr", "rl", "dense"):
+        ent[form] = evaluate(form, c, E, w, sel)
+    for form in ("lr", "rl", "dense"):
+        ent["err_" + form] = {k: rr.rel_err(ent[form][k], ent["truth"][k]) for k in KEYS}
+        # energy by energy, for the calibration: (blocks, rows) of each energy alone
+        ent["err1_" + form] = [(rr.rel_err(ent[form]["single"][j], ent["truth"]["single"][j]),
+                                rr.rel_err(ent[form]["rows"][j], ent["truth"]["rows"][j])) for j in range(len(E))]
+    return ent
+
+
+@functools.lru_cache(maxsize=None)
+def window_entry(sel="LR"):
+    """the truth_table()-style entry of rgf_ref.window_case() (not an input of the calibration) for one selection; the
+    blocks of energy j alone -- layered_gless_int with one-hot weights -- are ent[form]["single"][j], bar_single"""
+    c = rr.window_case()
+    return _entry(c, c.energies, np.array([0.4, 0.7, 1.1, 1.6]), sel)
 
 
 def bar(ent, key):
     """what a result of quantity `key` on this input may err by"""
     return C_LESS * max(ent["err_lr"][key], ent["err_rl"][key])
+
+
+def bar_single(ent, j):
+    """... and the blocks of energy j alone"""
+    return C_LESS * max(ent["err1_lr"][j][0], ent["err1_rl"][j][0])
 
 
 def ind_of(sel):

@@ -116,8 +116,12 @@ def test_auto_large_batch_ladder_spread(engine, truth):
 
 @pytest.mark.parametrize("name", ["G1", "G2"])
 def test_auto_1030_pairs(engine, truth, name):
-    """n = 1030 (the two-rows-per-lane windowed kernel) in batches of two."""
+    """n = 1030 in batches of two: the <8,4> class (four rows per lane, sub-panels of 8 columns, the team window kernel --
+    there is no strip kernel beyond sub-panels of 16), one stream group, the windows one by one with fat updates."""
     from gaunegf_amd.integrate import GrBatch
+    plan = engine.inverse_plan(1030, 2)
+    assert plan["path"] == 2 and plan["cls"] == (8, 4) and [g["wk"] for g in plan["groups"]] == [9]
+    assert [(g["pairs"], g["upd_full"]) for g in plan["groups"]] == [(0, 8)]
     case = _table(1030)[name]
     t = truth(case)
     g = _provider(case)

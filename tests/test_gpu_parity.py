@@ -115,11 +115,20 @@ def test_window_kernels_by_force(engine, N, M, algo):
     four), rows that end inside a wave, inside a slab, on the slab boundary (256, 512, 1024).  Oracle on a sample,
     the residual on every matrix."""
     from gaunegf_amd.integrate import GrBatch
+    plan = engine.inverse_plan(N, M, algo)
+    if algo == 3:                        # strip: 1 = n <= 256 (sub-windows of 32), 5 = 257 ... 512 lean, 6 = above, eight waves
+        want = (2, (16, 1 if N <= 512 else 2), [1 if N <= 256 else 5 if N <= 512 else 6])
+    elif N <= 256:                       # 10 = the single-workgroup kernel
+        want = (1, (0, 0), [10])
+    else:                                # 8 = the look-ahead team kernel of the <16,1> class, 9 = the team kernel of the class
+        want = (2, (16, 1 if N <= 512 else 2), [8 if N <= 512 else 9])
+    assert (plan["path"], plan["cls"], [g["wk"] for g in plan["groups"]]) == want, (N, M, algo, plan)
     F, S, g_dev, g_ref = _const_provider(N, 900 + N, nc=min(20, N // 4))
     E = np.linspace(-2.5, 2.5, M) + 0.02j
     engine.set_inverse_algo(algo)
     try:
         G = GrBatch(F, S, g_dev, E)
+        assert engine.inverse_last() == {"path": plan["path"], "masks": [g["mask"] for g in plan["groups"]]}
     finally:
         engine.set_inverse_algo(0)
     for k in (0, M - 1):
@@ -384,6 +393,9 @@ def test_largest_window_configurations(engine, N):
     16 rows per lane and sub-panels of 2; one energy, checked through the residual G A = I (an oracle
     inverse of this size costs seconds of CPU)."""
     from gaunegf_amd.integrate import GrBatch
+    plan = engine.inverse_plan(N, 1)
+    assert plan["path"] == 2 and plan["cls"] == ((4, 8) if N <= 4096 else (2, 16)) and N > 2048
+    assert [g["wk"] for g in plan["groups"]] == [9]              # the team window kernel of the class
     F, S, g_dev, g_ref = _const_provider(N, 77, nc=30)
     E = np.array([0.4 + 0.05j])
     G = GrBatch(F, S, g_dev, E)[0]
