@@ -108,6 +108,10 @@ SIGNATURES = {
     "negf_layered_contact_dos_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "negf_layered_transmission_matrix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "negf_layered_transmission_matrix_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+    "negf_layered_local_transmission": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "negf_layered_local_transmission_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "negf_layered_bond_int": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "negf_layered_bond_int_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "negf_layered_workspace_bytes": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_longlong)]),
     "negf_sync": (C.c_int, [_vp]),
     "negf_last_info": (C.c_int, [_vp, C.c_int, _vp]),

@@ -12,6 +12,9 @@
 //   rgf_sub_probes / rgf_strip_pair: the transmission matrix with probes on any layer (negf_layered_transmission_matrix):
 //                   the probes' Sigma blocks subtracted from an assembled diagonal matrix, and T[a][b] of the terminal pairs
 //                   of one layer level from the column strip [G_ii[:, J_i] | G_{i,i+1}[:, J_{i+1}] | ...] of that level
+//   rgf_bond_*    : bond currents and local transmission on the pattern of S (negf_layered_local_transmission,
+//                   negf_layered_bond_int): flow = 2 Im[(E S - F) conj(A)] of a block of A = G Gamma G^H per energy, its
+//                   group table, and its weighted sum over the energies; a transposed form of each for the lower blocks
 // Every matrix of a batch is compact row-major (leading dimension = its own column count) at a batch stride the
 // caller gives; consecutive lanes touch consecutive 16-byte elements.  No atomics.
 #include "negf_common.h"
@@ -477,4 +480,223 @@ void launch_rgf_strip_pairs(hipStream_t st, int cls, int C, int npairs, int max_
         hipLaunchKernelGGL(rgf_strip_pair_kernel<256>, dim3(npairs, nb), dim3(256), lds, st, C, pairs, tK, ioff, goff,
                            gstride, tcol, col0, rows, cpos, strip, ld, strideS, gstat, gdyn, T);
     }
+}
+
+// ------------------------------------------------------------ bond currents and local transmission on the pattern of S
+// flow[r][c](E) = 2 Im[K_rc conj(A_rc)], K = E S - F formed in registers in rgf_diag's operation order (k_bond.hip's
+// bond_flow on a layered system; negf_layered_local_transmission, negf_layered_bond_int).  The row-major kernels serve a
+// diagonal block and an upper block (i, i+1): element (r, c) of the result needs element (r, c) of S, F and A.  The lower
+// block (i+1, i) is 2 Im[K_l[r][c] A_u[c][r]] (A_{i+1,i} = A_{i,i+1}^H is never formed): its kernels read the stored lower
+// blocks of S and F at the element they write and A_u through rgf_accumulate_ct's padded 16 x 16 LDS tile, so that the read
+// of A_u and the write of the result both run along rows.  A singular energy (info != 0) gives a NaN table.  No atomics:
+// every sum below has ONE order.  The flow itself is formed without FP contraction, so that every kernel here gives the
+// same bits for the same element (one-hot weights of the integral reproduce the per-energy table).
+static __device__ __forceinline__ double rgf_bond_flow(const cplx e, const cplx s, const cplx h, const cplx a)
+{
+#pragma clang fp contract(off)
+    const double kx = e.x * s.x - e.y * s.y - h.x;
+    const double ky = e.x * s.y + e.y * s.x - h.y;
+    return 2.0 * (ky * a.x - kx * a.y);
+}
+
+// out[b][i] = flow(E_b, S[i], F[i], A_b[i]) over `count` elements
+__global__ __launch_bounds__(RGF_THREADS) void rgf_bond_flow_kernel(
+    int count, const cplx* __restrict__ E, const cplx* __restrict__ S, const cplx* __restrict__ F,
+    const cplx* __restrict__ A, size_t strideA, const int* __restrict__ info, double* __restrict__ out, size_t stride_out)
+{
+    const int b = blockIdx.y;
+    const cplx e = E[b];
+    const cplx* Ab = A + (size_t)b * strideA;
+    double* o = out + (size_t)b * stride_out;
+    const bool bad = info[b] != 0;                                     // (uniform)
+    const double qnan = __builtin_nan("");
+    for (int i = blockIdx.x * RGF_THREADS + threadIdx.x; i < count; i += gridDim.x * RGF_THREADS)
+        o[i] = bad ? qnan : rgf_bond_flow(e, S[i], F[i], Ab[i]);
+}
+
+void launch_rgf_bond_flow(hipStream_t st, int count, int nb, const cplx* E, const cplx* S, const cplx* F, const cplx* A,
+                          size_t strideA, const int* info, double* out, size_t stride_out)
+{
+    if (count <= 0 || nb <= 0) return;
+    hipLaunchKernelGGL(rgf_bond_flow_kernel, dim3(rgf_grid((size_t)count), nb), dim3(RGF_THREADS), 0, st, count, E, S, F, A,
+                       strideA, info, out, stride_out);
+}
+
+// out[b][c][r] = 2 Im[K_l[c][r] A_b[r][c]]   (A nr x nc: the upper block; Sl, Fl, out nc x nr: the lower one)
+__global__ __launch_bounds__(RGF_CT_TILE * RGF_CT_TILE) void rgf_bond_flow_t_kernel(
+    int nr, int nc, const cplx* __restrict__ E, const cplx* __restrict__ Sl, const cplx* __restrict__ Fl,
+    const cplx* __restrict__ A, size_t strideA, const int* __restrict__ info, double* __restrict__ out, size_t stride_out)
+{
+    __shared__ double tre[RGF_CT_TILE][RGF_CT_TILE + 1], tim[RGF_CT_TILE][RGF_CT_TILE + 1];
+    const int b = blockIdx.z;
+    const int tx = threadIdx.x & (RGF_CT_TILE - 1), ty = threadIdx.x / RGF_CT_TILE;
+    const int r0 = blockIdx.y * RGF_CT_TILE, c0 = blockIdx.x * RGF_CT_TILE;
+    const bool in_ok = r0 + ty < nr && c0 + tx < nc;        // A[r0 + ty][c0 + tx]
+    const bool out_ok = c0 + ty < nc && r0 + tx < nr;       // out[c0 + ty][r0 + tx]
+    const size_t in_at = (size_t)(r0 + ty) * nc + c0 + tx, out_at = (size_t)(c0 + ty) * nr + r0 + tx;
+    if (in_ok) { const cplx x = A[(size_t)b * strideA + in_at]; tre[ty][tx] = x.x; tim[ty][tx] = x.y; }
+    __syncthreads();
+    if (!out_ok) return;
+    double* o = out + (size_t)b * stride_out;
+    if (info[b] != 0) { o[out_at] = __builtin_nan(""); return; }
+    // 2 Im[K a] = 2 Im[K conj(conj(a))]
+    o[out_at] = rgf_bond_flow(E[b], Sl[out_at], Fl[out_at], cmake(tre[tx][ty], -tim[tx][ty]));
+}
+
+void launch_rgf_bond_flow_t(hipStream_t st, int nr, int nc, int nb, const cplx* E, const cplx* Sl, const cplx* Fl,
+                            const cplx* A, size_t strideA, const int* info, double* out, size_t stride_out)
+{
+    if (nr <= 0 || nc <= 0 || nb <= 0) return;
+    hipLaunchKernelGGL(rgf_bond_flow_t_kernel,
+                       dim3((nc + RGF_CT_TILE - 1) / RGF_CT_TILE, (nr + RGF_CT_TILE - 1) / RGF_CT_TILE, nb),
+                       dim3(RGF_CT_TILE * RGF_CT_TILE), 0, st, nr, nc, E, Sl, Fl, A, strideA, info, out, stride_out);
+}
+
+// Group table of one block, bond_group_kernel's scheme with a map per layer: one workgroup per (energy b, row group a).
+// rperm / cperm: the orbitals of the block's row / column layer sorted by group (ascending inside a group), rgoff / cgoff
+// [groups + 1]: where each group starts.  Pass 1: thread q owns the column cperm[q] and adds the rows of group a in rperm
+// order -> colsum[q] in LDS.  Pass 2: a wave per column group g: lane l adds colsum[cgoff[g] + l], [.. + l + 64], ... in
+// order, then the 6-step shuffle tree.  The order of every addition depends on the positions inside the groups only:
+// relabelling the groups permutes the table bit for bit.
+// lower = 0: out[a][g] of the block itself (diagonal, upper).  lower = 1: A is the upper block (i, i+1) and the table is
+// the lower block's, out[g][a] = sum_{c in g, r in a} 2 Im[K_l[c][r] A[r][c]]; K_l[c][r] is read as conj of the upper S
+// and F at [r][c] -- the stored lower blocks are those conjugates bit for bit (negf_layered_create) -- so that this read
+// runs along the rows of A as well.
+template <int LOWER>
+__global__ __launch_bounds__(RGF_THREADS) void rgf_bond_group_kernel(
+    int nc, int ngr, int ngc, const cplx* __restrict__ E, const cplx* __restrict__ S, const cplx* __restrict__ F,
+    const cplx* __restrict__ A, size_t strideA, const int* __restrict__ info, const int* __restrict__ rperm,
+    const int* __restrict__ rgoff, const int* __restrict__ cperm, const int* __restrict__ cgoff,
+    double* __restrict__ out, size_t stride_out)
+{
+    extern __shared__ double rgf_bond_colsum[];             // [nc]
+    const int b = blockIdx.x, a = blockIdx.y, tid = threadIdx.x;
+    double* o = out + (size_t)b * stride_out;
+    const size_t o_at = LOWER ? (size_t)a : (size_t)a * ngc, o_step = LOWER ? (size_t)ngr : 1;
+    if (info[b] != 0) {                                     // (uniform)
+        const double qnan = __builtin_nan("");
+        for (int g = tid; g < ngc; g += RGF_THREADS) o[o_at + g * o_step] = qnan;
+        return;
+    }
+    const cplx e = E[b];
+    const cplx* Ab = A + (size_t)b * strideA;
+    const int r0 = rgoff[a], r1 = rgoff[a + 1];
+    for (int q = tid; q < nc; q += RGF_THREADS) {
+        const int j = cperm[q];
+        double acc = 0.0;
+#pragma unroll 4
+        for (int r = r0; r < r1; ++r) {
+            const size_t t = (size_t)rperm[r] * nc + j;
+            const cplx s = S[t], h = F[t], x = Ab[t];
+            acc += LOWER ? rgf_bond_flow(e, cmake(s.x, -s.y), cmake(h.x, -h.y), cmake(x.x, -x.y)) : rgf_bond_flow(e, s, h, x);
+        }
+        rgf_bond_colsum[q] = acc;
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int g = wave; g < ngc; g += RGF_THREADS / 64) {
+        double s = 0.0;
+        for (int q = cgoff[g] + lane; q < cgoff[g + 1]; q += 64) s += rgf_bond_colsum[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+        if (lane == 0) o[o_at + g * o_step] = s;
+    }
+}
+
+void launch_rgf_bond_group(hipStream_t st, int nc, int ngr, int ngc, int nb, bool lower, const cplx* E, const cplx* S,
+                           const cplx* F, const cplx* A, size_t strideA, const int* info, const int* rperm, const int* rgoff,
+                           const int* cperm, const int* cgoff, double* out, size_t stride_out)
+{
+    if (nc <= 0 || ngr <= 0 || ngc <= 0 || nb <= 0) return;
+    const size_t lds = (size_t)nc * sizeof(double);         // a layer holds at most 8192 orbitals: 64 KB
+    if (lower)
+        hipLaunchKernelGGL(rgf_bond_group_kernel<1>, dim3(nb, ngr), dim3(RGF_THREADS), lds, st, nc, ngr, ngc, E, S, F, A,
+                           strideA, info, rperm, rgoff, cperm, cgoff, out, stride_out);
+    else
+        hipLaunchKernelGGL(rgf_bond_group_kernel<0>, dim3(nb, ngr), dim3(RGF_THREADS), lds, st, nc, ngr, ngc, E, S, F, A,
+                           strideA, info, rperm, rgoff, cperm, cgoff, out, stride_out);
+}
+
+// acc[i] += sum_b w_b flow(E_b, S[i], F[i], A_b[i]) with real w: rgf_accumulate's rule, one chain per element with b
+// ascending, carried through acc from batch to batch -- bitwise independent of the batch cut
+__global__ __launch_bounds__(RGF_THREADS) void rgf_bond_accumulate_kernel(
+    int count, int nb, const cplx* __restrict__ E, const double* __restrict__ w, const cplx* __restrict__ S,
+    const cplx* __restrict__ F, const cplx* __restrict__ A, size_t strideA, double* __restrict__ acc)
+{
+    const int i = blockIdx.x * RGF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const cplx s = S[i], h = F[i];
+    double v = acc[i];
+    for (int b = 0; b < nb; ++b) v += w[b] * rgf_bond_flow(E[b], s, h, A[(size_t)b * strideA + i]);
+    acc[i] = v;
+}
+
+void launch_rgf_bond_accumulate(hipStream_t st, int count, int nb, const cplx* E, const double* w, const cplx* S,
+                                const cplx* F, const cplx* A, size_t strideA, double* acc)
+{
+    if (count <= 0 || nb <= 0) return;
+    hipLaunchKernelGGL(rgf_bond_accumulate_kernel, dim3((count + RGF_THREADS - 1) / RGF_THREADS), dim3(RGF_THREADS), 0, st,
+                       count, nb, E, w, S, F, A, strideA, acc);
+}
+
+// acc[c][r] += sum_b w_b 2 Im[K_l[c][r](E_b) A_b[r][c]]   (A nr x nc, Sl, Fl, acc nc x nr): the lower block's chain
+__global__ __launch_bounds__(RGF_CT_TILE * RGF_CT_TILE) void rgf_bond_accumulate_t_kernel(
+    int nr, int nc, int nb, const cplx* __restrict__ E, const double* __restrict__ w, const cplx* __restrict__ Sl,
+    const cplx* __restrict__ Fl, const cplx* __restrict__ A, size_t strideA, double* __restrict__ acc)
+{
+    __shared__ double tre[RGF_CT_TILE][RGF_CT_TILE + 1], tim[RGF_CT_TILE][RGF_CT_TILE + 1];
+    const int tx = threadIdx.x & (RGF_CT_TILE - 1), ty = threadIdx.x / RGF_CT_TILE;
+    const int r0 = blockIdx.y * RGF_CT_TILE, c0 = blockIdx.x * RGF_CT_TILE;
+    const bool in_ok = r0 + ty < nr && c0 + tx < nc;        // A[r0 + ty][c0 + tx]
+    const bool out_ok = c0 + ty < nc && r0 + tx < nr;       // acc[c0 + ty][r0 + tx]
+    const size_t in_at = (size_t)(r0 + ty) * nc + c0 + tx, out_at = (size_t)(c0 + ty) * nr + r0 + tx;
+    cplx s = cmake(0.0, 0.0), h = s;
+    double v = 0.0;
+    if (out_ok) { s = Sl[out_at]; h = Fl[out_at]; v = acc[out_at]; }
+    for (int b = 0; b < nb; ++b) {
+        if (in_ok) { const cplx x = A[(size_t)b * strideA + in_at]; tre[ty][tx] = x.x; tim[ty][tx] = x.y; }
+        __syncthreads();
+        if (out_ok) v += w[b] * rgf_bond_flow(E[b], s, h, cmake(tre[tx][ty], -tim[tx][ty]));
+        __syncthreads();
+    }
+    if (out_ok) acc[out_at] = v;
+}
+
+void launch_rgf_bond_accumulate_t(hipStream_t st, int nr, int nc, int nb, const cplx* E, const double* w, const cplx* Sl,
+                                  const cplx* Fl, const cplx* A, size_t strideA, double* acc)
+{
+    if (nr <= 0 || nc <= 0 || nb <= 0) return;
+    hipLaunchKernelGGL(rgf_bond_accumulate_t_kernel,
+                       dim3((nc + RGF_CT_TILE - 1) / RGF_CT_TILE, (nr + RGF_CT_TILE - 1) / RGF_CT_TILE),
+                       dim3(RGF_CT_TILE * RGF_CT_TILE), 0, st, nr, nc, nb, E, w, Sl, Fl, A, strideA, acc);
+}
+
+// A[b] = (A[b] + A[b]^H) / 2 in place (n x n): the Hermitian part of a diagonal block A_ii = (W Gamma) W^H, which is
+// Hermitian only to the rounding of its products.  One workgroup per pair of mirrored 16 x 16 tiles (bx >= by; the others
+// leave at once), both tiles through the padded LDS tile so that every read and write runs along rows.  Element (r, c)
+// and element (c, r) are formed from the same two numbers by commutative sums: exact conjugates of each other.
+__global__ __launch_bounds__(RGF_CT_TILE * RGF_CT_TILE) void rgf_bond_hermitize_kernel(int n, cplx* __restrict__ A, size_t strideA)
+{
+    __shared__ double ure[RGF_CT_TILE][RGF_CT_TILE + 1], uim[RGF_CT_TILE][RGF_CT_TILE + 1];   // the tile (by, bx)
+    __shared__ double lre[RGF_CT_TILE][RGF_CT_TILE + 1], lim[RGF_CT_TILE][RGF_CT_TILE + 1];   // the tile (bx, by)
+    if (blockIdx.x < blockIdx.y) return;                   // (uniform)
+    const int tx = threadIdx.x & (RGF_CT_TILE - 1), ty = threadIdx.x / RGF_CT_TILE;
+    const int r0 = blockIdx.y * RGF_CT_TILE, c0 = blockIdx.x * RGF_CT_TILE;
+    cplx* Ab = A + (size_t)blockIdx.z * strideA;
+    const bool u_ok = r0 + ty < n && c0 + tx < n;          // A[r0 + ty][c0 + tx]
+    const bool l_ok = c0 + ty < n && r0 + tx < n;          // A[c0 + ty][r0 + tx]
+    const size_t u_at = (size_t)(r0 + ty) * n + c0 + tx, l_at = (size_t)(c0 + ty) * n + r0 + tx;
+    if (u_ok) { const cplx x = Ab[u_at]; ure[ty][tx] = x.x; uim[ty][tx] = x.y; }
+    if (l_ok) { const cplx x = Ab[l_at]; lre[ty][tx] = x.x; lim[ty][tx] = x.y; }
+    __syncthreads();
+    // (on a diagonal tile pair both stores write the same tile with the same values)
+    if (u_ok) Ab[u_at] = cmake(0.5 * (ure[ty][tx] + lre[tx][ty]), 0.5 * (uim[ty][tx] - lim[tx][ty]));
+    if (l_ok) Ab[l_at] = cmake(0.5 * (lre[ty][tx] + ure[tx][ty]), 0.5 * (lim[ty][tx] - uim[tx][ty]));
+}
+
+void launch_rgf_bond_hermitize(hipStream_t st, int n, int nb, cplx* A, size_t strideA)
+{
+    if (n <= 0 || nb <= 0) return;
+    const int t = (n + RGF_CT_TILE - 1) / RGF_CT_TILE;
+    hipLaunchKernelGGL(rgf_bond_hermitize_kernel, dim3(t, t, nb), dim3(RGF_CT_TILE * RGF_CT_TILE), 0, st, n, A, strideA);
 }

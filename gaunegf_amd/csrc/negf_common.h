@@ -644,6 +644,27 @@ void launch_rgf_accumulate_ct(hipStream_t st, int nr, int nc, int nb, const cplx
 void launch_rgf_pop_block(hipStream_t st, int nr, int nk, int nb, const cplx* A, size_t strideA, const cplx* X,
                           double* row_site, bool accumulate_rows, double* col_site, size_t site_stride);
 void launch_rgf_merge_info(hipStream_t st, int nb, int offset, const int* linfo, int* info);
+// Bond currents and local transmission on the pattern of S (negf_layered_local_transmission, negf_layered_bond_int):
+// flow = 2 Im[(E_b S - F) conj(A[b])] element by element; info[b] != 0 -> NaN.
+// out[b * stride_out + i] = flow over `count` elements (a diagonal or an upper block)
+void launch_rgf_bond_flow(hipStream_t st, int count, int nb, const cplx* E, const cplx* S, const cplx* F, const cplx* A,
+                          size_t strideA, const int* info, double* out, size_t stride_out);
+// the lower block from the upper A (nr x nc): out[b][c][r] = 2 Im[(E_b Sl - Fl)[c][r] A[b][r][c]]   (Sl, Fl, out nc x nr)
+void launch_rgf_bond_flow_t(hipStream_t st, int nr, int nc, int nb, const cplx* E, const cplx* Sl, const cplx* Fl,
+                            const cplx* A, size_t strideA, const int* info, double* out, size_t stride_out);
+// group table of a block with nc columns: rperm / rgoff, cperm / cgoff = the orbitals of its row / column layer sorted by
+// group and the groups' offsets (device).  lower false: out[b][a][g] (ngr x ngc) of the block (S, F, A) itself; true: S, F,
+// A are the UPPER block and out[b][g][a] (ngc x ngr) is the lower block's table
+void launch_rgf_bond_group(hipStream_t st, int nc, int ngr, int ngc, int nb, bool lower, const cplx* E, const cplx* S,
+                           const cplx* F, const cplx* A, size_t strideA, const int* info, const int* rperm, const int* rgoff,
+                           const int* cperm, const int* cgoff, double* out, size_t stride_out);
+// A[b] = (A[b] + A[b]^H) / 2 in place (n x n): elements (r, c) and (c, r) leave as exact conjugates
+void launch_rgf_bond_hermitize(hipStream_t st, int n, int nb, cplx* A, size_t strideA);
+// acc[i] += sum_b w[b] flow_b[i] with real w, one chain per element with b ascending; _t: the lower block from the upper A
+void launch_rgf_bond_accumulate(hipStream_t st, int count, int nb, const cplx* E, const double* w, const cplx* S,
+                                const cplx* F, const cplx* A, size_t strideA, double* acc);
+void launch_rgf_bond_accumulate_t(hipStream_t st, int nr, int nc, int nb, const cplx* E, const double* w, const cplx* Sl,
+                                  const cplx* Fl, const cplx* A, size_t strideA, double* acc);
 // Transmission matrix with probes on any layer (negf_layered_transmission_matrix):
 // the columns idx of G into the first K columns of a strip of width ld (out[b][r * ld + a] = G[b][r][idx[a]])
 void launch_rgf_strip_head(hipStream_t st, int n, int K, int ld, int nb, const cplx* G, size_t strideG, const int* idx,

@@ -27,8 +27,8 @@
 //
 // The recursion stands once.  rgf_factor_sweep keeps every g_i in d_gstore and takes two callables, run before and after
 // the inverse of a level (the strips' probes; the columns' x / z chain); rgf_solve_sweep hands each level as it stands
-// (RgfLevel) to a visitor: the block visitors RgfSumBlocks / RgfDosBlocks, the column visitor RgfColumns, the strip
-// visitor RgfStrips.  Only a block visitor has G_{i+1,i} formed.  rgf_corner_sweep shares the level (rgf_factor_level) but
+// (RgfLevel) to a visitor: the block visitors RgfSumBlocks / RgfDosBlocks / RgfBondBlocks (the last one behind the
+// column visitor only), the column visitor RgfColumns, the strip visitor RgfStrips.  Only a block visitor has G_{i+1,i} formed.  rgf_corner_sweep shares the level (rgf_factor_level) but
 // not the loop: it alone lets g_{i-2} go.  All of them walk the levels of an RgfView, which the strips' second pass reverses.
 // The ten work areas have names (RgfAreas says who writes each, and when); the two places that lend one out say so:
 // rgf_corner_sweep and RgfColumns::level.  Every device-resident call is its checks, its work areas, then rgf_batches.
@@ -66,6 +66,8 @@ struct LayeredSystem {
     DevBuf<double> d_site;                      // dos: [m][N] staging of the host-pointer entry point
     DevBuf<int> d_tm_tab;                       // transmission matrix: the terminal tables, union lists and pair lists
     DevBuf<cplx> d_tm_sig, d_tm_gam;            // ... the probes' Sigma blocks; the Gamma blocks that do not depend on E
+    DevBuf<int> d_bond_map;                     // bond tables: perm [N] (layer by layer) | goff [sum (g_i + 1)] of the call's groups
+    DevBuf<double> d_bond_out;                  // ... the staging of the host-pointer entry points
     DevBuf<int> d_piv, d_linfo, d_iters, d_conv;
     int batch = 0;                              // energies the work areas are laid out for
     long long work_bytes = 0;                   // of the last call: pool + stored g + column sets
@@ -89,7 +91,8 @@ void free_layered(LayeredSystem* ls)
     dev_free(ls->dFd); dev_free(ls->dSd); dev_free(ls->dFu); dev_free(ls->dSu); dev_free(ls->dFl); dev_free(ls->dSl);
     release_bufs(ls->d_pool, ls->d_gstore, ls->d_small, ls->d_out, ls->d_cols);
     release_bufs(ls->d_site);
-    release_bufs(ls->d_J, ls->d_tm_tab);
+    release_bufs(ls->d_J, ls->d_tm_tab, ls->d_bond_map);
+    release_bufs(ls->d_bond_out);
     release_bufs(ls->d_tm_sig, ls->d_tm_gam);
     release_bufs(ls->d_piv, ls->d_linfo, ls->d_iters, ls->d_conv);
     delete ls;
@@ -495,6 +498,100 @@ struct RgfDosBlocks {
     }
 };
 
+// The groups of a bond-table call: g[i] groups on layer i, the tables' block offsets in negf_layered_gr_int's order with g
+// in place of n, and on the device per layer the orbitals sorted by group (perm, at off[i]) and the groups' offsets in
+// that list (goff, at gat[i]).  Without a map (orbital level) g = n and nothing is uploaded.
+struct RgfBondGroups {
+    bool mapped = false;
+    std::vector<int> g, gat;
+    std::vector<size_t> doff, uoff;
+    size_t dtot = 0, utot = 0;
+    std::vector<int> map;                                               // host: perm [N] | goff [sum (g_i + 1)]
+    const int* d_map = nullptr;
+    size_t table() const { return dtot + 2 * utot; }                    // doubles per energy
+};
+
+// validation and the host tables of the groups; NEGF_EINVAL before anything is launched
+int rgf_bond_groups(const LayeredSystem* ls, const int* groups_per_layer, const int* group_of, RgfBondGroups* bg)
+{
+    if ((groups_per_layer == nullptr) != (group_of == nullptr)) return NEGF_EINVAL;
+    const int L = ls->L;
+    bg->mapped = group_of != nullptr;
+    bg->g.assign(ls->n.begin(), ls->n.end());
+    if (bg->mapped)
+        for (int i = 0; i < L; ++i) {
+            if (groups_per_layer[i] < 1) return NEGF_EINVAL;
+            bg->g[i] = groups_per_layer[i];
+            for (int o = ls->off[i]; o < ls->off[i] + ls->n[i]; ++o)
+                if (group_of[o] < 0 || group_of[o] >= bg->g[i]) return NEGF_EINVAL;
+        }
+    bg->doff.resize(L); bg->uoff.resize(L - 1);
+    for (int i = 0; i < L; ++i) {
+        bg->doff[i] = bg->dtot; bg->dtot += (size_t)bg->g[i] * bg->g[i];
+        if (i + 1 < L) { bg->uoff[i] = bg->utot; bg->utot += (size_t)bg->g[i] * bg->g[i + 1]; }
+    }
+    if (!bg->mapped) return NEGF_OK;
+    bg->gat.resize(L);
+    size_t at = (size_t)ls->N;
+    for (int i = 0; i < L; ++i) { bg->gat[i] = (int)at; at += (size_t)bg->g[i] + 1; }
+    bg->map.assign(at, 0);
+    for (int i = 0; i < L; ++i) {                                       // a counting sort per layer: ascending inside a group
+        int* perm = bg->map.data() + ls->off[i];
+        int* goff = bg->map.data() + bg->gat[i];
+        const int* go = group_of + ls->off[i];
+        for (int o = 0; o < ls->n[i]; ++o) ++goff[go[o] + 1];
+        for (int k = 0; k < bg->g[i]; ++k) goff[k + 1] += goff[k];
+        std::vector<int> next(goff, goff + bg->g[i]);
+        for (int o = 0; o < ls->n[i]; ++o) perm[next[go[o]]++] = o;
+    }
+    return NEGF_OK;
+}
+
+// ... and this one, which stands behind the column visitor only (less(); no Green's function sweep feeds it), turns the
+// blocks of A = G Gamma G^H into the flow 2 Im[K conj(A)], K = E S - F, where RgfSumBlocks::less would sum them: per energy
+// at orbital level or as group tables (negf_layered_local_transmission; w null), or summed with real weights
+// (negf_layered_bond_int).  The lower block (i+1, i) comes from the upper A read transposed: A_{i+1,i} is never formed.
+struct RgfBondBlocks {
+    const double* w;                                                    // null: per-energy tables
+    double* out;                                                        // diagonal | upper | lower, [m] of those without w
+    const RgfBondGroups* bg;
+    void less(const RgfBatch& b, int i, const cplx* A, bool up) const
+    {
+        ProfScope ps(b.c, "bond");
+        const LayeredSystem* ls = b.ls;
+        hipStream_t st = b.c->stream;
+        const size_t s = ls->stride;
+        const cplx* E = b.E + b.m0;
+        const int ni = ls->n[i], nb = b.nb;
+        const cplx *S = up ? ls->dSu + ls->uoff[i] : ls->dSd + ls->doff[i], *F = up ? ls->dFu + ls->uoff[i] : ls->dFd + ls->doff[i];
+        const int nc = up ? ls->n[i + 1] : ni;
+        const size_t at = up ? bg->dtot + bg->uoff[i] : bg->doff[i];   // the block's place in a table; the lower one's: + utot
+        // A_ii = (W Gamma) W^H is Hermitian to the rounding of its products only; the flow of a diagonal block reads its
+        // Hermitian part, formed in place (the block lies in one of the column visitor's own areas, which nobody reads
+        // again), so that at real E flow_ii is antisymmetric bit for bit as the coupling blocks' flows are
+        if (!up) launch_rgf_bond_hermitize(st, ni, nb, const_cast<cplx*>(A), s);
+        if (w) {
+            launch_rgf_bond_accumulate(st, ni * nc, nb, E, w + b.m0, S, F, A, s, out + at);
+            if (up) launch_rgf_bond_accumulate_t(st, ni, nc, nb, E, w + b.m0, ls->dSl + ls->uoff[i], ls->dFl + ls->uoff[i], A, s,
+                                                 out + at + bg->utot);
+            return;
+        }
+        const size_t tab = bg->table();
+        double* o = out + tab * b.m0 + at;
+        const int* info = b.c->d_info + b.m0;
+        if (!bg->mapped) {
+            launch_rgf_bond_flow(st, ni * nc, nb, E, S, F, A, s, info, o, tab);
+            if (up) launch_rgf_bond_flow_t(st, ni, nc, nb, E, ls->dSl + ls->uoff[i], ls->dFl + ls->uoff[i], A, s, info, o + bg->utot, tab);
+            return;
+        }
+        const int j = up ? i + 1 : i;
+        const int *rperm = bg->d_map + ls->off[i], *rgoff = bg->d_map + bg->gat[i];
+        const int *cperm = bg->d_map + ls->off[j], *cgoff = bg->d_map + bg->gat[j];
+        launch_rgf_bond_group(st, nc, bg->g[i], bg->g[j], nb, false, E, S, F, A, s, info, rperm, rgoff, cperm, cgoff, o, tab);
+        if (up) launch_rgf_bond_group(st, nc, bg->g[i], bg->g[j], nb, true, E, S, F, A, s, info, rperm, rgoff, cperm, cgoff, o + bg->utot, tab);
+    }
+};
+
 bool rgf_less_ind_ok(const LayeredSystem* ls, int ind)
 {
     const int nt = (int)ls->terms.size();
@@ -619,14 +716,14 @@ struct RgfColumns {
 };
 
 // One batch of a call on the pattern of S.  Without `less` the two sweeps of the Green's function, its blocks to the block
-// visitor; with it G Gamma G^H: factor sweep with the layer-0 chain, the Gamma of the selected terminals on their union
-// lists, solve sweep with the column visitor in front of the block visitor
+// visitor; with it G Gamma G^H (rgf_less_batch, which asks of the block visitor its less() only): factor sweep with the
+// layer-0 chain, the Gamma of the selected terminals on their union lists, solve sweep with the column visitor in front of
+// the block visitor
 template <class Blocks>
-int rgf_pattern_batch(const RgfBatch& b, RgfLess* less, const Blocks& sink)
+int rgf_less_batch(const RgfBatch& b, RgfLess* less, const Blocks& sink)
 {
     const RgfView v{b.ls, false};
     int rc;
-    if (!less) return (rc = rgf_factor_sweep(b, v, rgf_no_step, rgf_no_step)) ? rc : rgf_solve_sweep(b, v, sink);
     if ((rc = rgf_factor_sweep(b, v, rgf_no_step, [&](int i, const cplx* g) { rgf_less_chain(b, less, i, g); }))) return rc;
     {
         ProfScope ps(b.c, "gamma");
@@ -636,6 +733,15 @@ int rgf_pattern_batch(const RgfBatch& b, RgfLess* less, const Blocks& sink)
                                        (size_t)less->K[e] * less->K[e]);
     }
     return rgf_solve_sweep(b, v, RgfColumns<Blocks>{less, sink});
+}
+
+template <class Blocks>
+int rgf_pattern_batch(const RgfBatch& b, RgfLess* less, const Blocks& sink)
+{
+    if (less) return rgf_less_batch(b, less, sink);
+    const RgfView v{b.ls, false};
+    const int rc = rgf_factor_sweep(b, v, rgf_no_step, rgf_no_step);
+    return rc ? rc : rgf_solve_sweep(b, v, sink);
 }
 
 // ------------------------------------------------- transmission matrix between all terminals, probes on any layer
@@ -1250,6 +1356,85 @@ int negf_layered_transmission_matrix(negf_ctx* c, int h, int n_probes, const int
                                                    reinterpret_cast<double*>(c->d_E), c->d_bond_T))) return rc;
     if ((rc = download(c, T, c->d_bond_T.p, cnt))) return rc;
     return reduce_info(c, m, info);
+}
+
+// negf_layered_local_transmission_dev (w null, per-energy tables) and negf_layered_bond_int_dev: negf_local_transmission_dev
+// and negf_bond_int_dev on a layered system -- the G Gamma G^H call of rgf_dev_pattern_int with RgfBondBlocks as its sink
+static int rgf_dev_bond(negf_ctx* c, int h, int ind, int m, const double* E_dev, const double* w_dev, bool integral,
+                        const int* groups_per_layer, const int* group_of, double* out_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!rgf_less_ind_ok(ls, ind)) return NEGF_EINVAL;
+    if (integral ? (!out_dev || (m > 0 && (!E_dev || !w_dev))) : (m > 0 && (!E_dev || !out_dev))) return NEGF_EINVAL;
+    RgfBondGroups bg;
+    if ((rc = rgf_bond_groups(ls, groups_per_layer, group_of, &bg))) return rc;
+    RgfLess less;
+    if ((rc = rgf_less_select(c, ls, ind, &less))) return rc;
+    RgfRun r;
+    if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, true, &r, less.per_energy))) return rc;
+    rgf_less_layout(r, &less);
+    if (bg.mapped) {
+        if ((rc = ensure_cap(c, ls->d_bond_map, bg.map.size())) || (rc = upload(c, ls->d_bond_map.p, bg.map.data(), bg.map.size()))) return rc;
+        bg.d_map = ls->d_bond_map;
+        ls->work_bytes += (long long)(bg.map.size() * sizeof(int));
+    }
+    if (integral) NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, bg.table() * sizeof(double), c->stream));
+    const RgfBondBlocks bond{integral ? w_dev : nullptr, out_dev, &bg};
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) { return rgf_less_batch(b, &less, bond); });
+}
+
+int negf_layered_local_transmission_dev(negf_ctx* c, int h, int ind, int m, const double* E_dev, const int* groups_per_layer,
+                                        const int* group_of, double* out_dev)
+{
+    return rgf_dev_bond(c, h, ind, m, E_dev, nullptr, false, groups_per_layer, group_of, out_dev);
+}
+
+int negf_layered_bond_int_dev(negf_ctx* c, int h, int ind, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    return rgf_dev_bond(c, h, ind, m, E_dev, w_dev, true, nullptr, nullptr, out_dev);
+}
+
+int negf_layered_local_transmission(negf_ctx* c, int h, int ind, int m, const double* E, const int* groups_per_layer,
+                                    const int* group_of, double* out, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!rgf_less_ind_ok(ls, ind) || (m > 0 && (!E || !out))) return NEGF_EINVAL;
+    RgfBondGroups bg;
+    if ((rc = rgf_bond_groups(ls, groups_per_layer, group_of, &bg))) return rc;
+    if (m == 0) return NEGF_OK;
+    if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
+    const size_t cnt = (size_t)m * bg.table();
+    if ((rc = ensure_cap(c, ls->d_bond_out, cnt))) return rc;
+    if ((rc = rgf_dev_bond(c, h, ind, m, reinterpret_cast<double*>(c->d_E), nullptr, false, groups_per_layer, group_of,
+                           ls->d_bond_out))) return rc;
+    ls->work_bytes += (long long)(cnt * sizeof(double));
+    if ((rc = download(c, out, ls->d_bond_out.p, cnt))) return rc;
+    return reduce_info(c, m, info);
+}
+
+int negf_layered_bond_int(negf_ctx* c, int h, int ind, int m, const double* E, const double* w, double* out, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!rgf_less_ind_ok(ls, ind) || !out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
+    const size_t tot = ls->dtot + 2 * ls->utot, ob = tot * sizeof(double);
+    if ((rc = stage_grid(c, m, 1, E, nullptr, ob))) return rc;
+    // the real weights ride in the [w] part of the pinned buffer and of d_w, as negf_bond_int's do
+    unsigned char* pw = c->h_pin + PinLayout(m, ob).w;
+    double* dw = reinterpret_cast<double*>(c->d_w);
+    if (m > 0) {
+        std::memcpy(pw, w, (size_t)m * sizeof(double));
+        NEGF_HIP_CHECK(hipMemcpyAsync(dw, pw, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = ensure_cap(c, ls->d_bond_out, tot))) return rc;
+    if ((rc = rgf_dev_bond(c, h, ind, m, reinterpret_cast<double*>(c->d_E), dw, true, nullptr, nullptr, ls->d_bond_out))) return rc;
+    ls->work_bytes += (long long)ob;
+    return fetch_result_and_info(c, m, ls->d_bond_out.p, ob, out, info);
 }
 
 int negf_layered_workspace_bytes(negf_ctx* c, int h, long long* work)

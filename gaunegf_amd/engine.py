@@ -1135,6 +1135,88 @@ class Engine:
                                                                     _ptr(sig), int(m), C.c_void_p(E_ptr), C.c_void_p(T_ptr)),
                      "negf_layered_transmission_matrix_dev")
 
+    def _lgroups(self, handle, groups_per_layer, group_of):
+        """(g [L] sizes of the tables, the two host arrays or None) of a bond-table call; only the lengths are checked
+        here -- the library must not read past an array -- everything else is the library's NEGF_EINVAL."""
+        sizes = self._lsizes(handle)
+        gpl = go = None
+        if groups_per_layer is not None:
+            gpl = np.ascontiguousarray(np.asarray(groups_per_layer).ravel(), dtype=np.int32)
+            if gpl.size != len(sizes):
+                raise ValueError(f"groups_per_layer must have one entry per layer ({len(sizes)}), got {gpl.size}")
+        if group_of is not None:
+            go = np.ascontiguousarray(np.asarray(group_of).ravel(), dtype=np.int32)
+            if go.size != sum(sizes):
+                raise ValueError(f"group_of must map each of the {sum(sizes)} orbitals to a group of its layer, got {go.size} entries")
+        g = tuple(int(x) for x in gpl) if gpl is not None and go is not None else sizes
+        return g, gpl, go
+
+    @staticmethod
+    def _lsplit_tables(g, flat):
+        """[m, table] -> (diag, upper, lower) block lists [m, g_i, g_j], negf_layered_gr_int's order with g in place of n"""
+        m = flat.shape[0]
+        diag, up, low, o = [], [], [], 0
+        for n in g:
+            diag.append(flat[:, o:o + n * n].reshape(m, n, n)); o += n * n
+        for a, b in zip(g[:-1], g[1:]):
+            up.append(flat[:, o:o + a * b].reshape(m, a, b)); o += a * b
+        for a, b in zip(g[:-1], g[1:]):
+            low.append(flat[:, o:o + a * b].reshape(m, b, a)); o += a * b
+        return diag, up, low
+
+    @staticmethod
+    def layered_table_size(g):
+        return sum(n * n for n in g) + 2 * sum(a * b for a, b in zip(g[:-1], g[1:]))
+
+    def layered_local_transmission(self, handle, ind, E, groups_per_layer=None, group_of=None):
+        """Local (bond) transmission of the current injected by terminal ``ind`` (None: all) on the pattern of S
+        (negf_layered_local_transmission): (diag, upper, lower) block lists, entry [k, a, b] of a block =
+        sum_{r in a, c in b} 2 Im[(E_k S - F)_rc (G Gamma G^H)_cr].  ``groups_per_layer`` [L] and ``group_of`` [N] (for each
+        orbital its group inside its own layer) reduce the blocks to [m, g_i, g_j]; both None: per orbital pair.  Tables of
+        singular energies are NaN (with a warning, as layered_transmission)."""
+        g, gpl, go = self._lgroups(handle, groups_per_layer, group_of)
+        E, _ = self._grid(E)
+        flat = np.zeros((E.size, self.layered_table_size(g)), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_local_transmission(self._ctx, int(handle), _ind(ind), E.size, _ptr(E),
+                                                                    _ptr(gpl), _ptr(go), _ptr(flat), _ptr(info)),
+                          "negf_layered_local_transmission")
+        self._numerical(rc, info[:E.size], "layered_local_transmission")
+        return self._lsplit_tables(g, flat)
+
+    def layered_local_transmission_dev(self, handle, ind, m, E_ptr, out_ptr, groups_per_layer=None, group_of=None):
+        """negf_layered_local_transmission_dev: grid and the [m, layered_table_size(g)] result in HBM; the groups stay
+        host arrays (or None)."""
+        _, gpl, go = self._lgroups(handle, groups_per_layer, group_of)
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_local_transmission_dev(self._ctx, int(handle), _ind(ind), int(m),
+                                                                   C.c_void_p(E_ptr), _ptr(gpl), _ptr(go), C.c_void_p(out_ptr)),
+                     "negf_layered_local_transmission_dev")
+
+    def layered_bond_int(self, handle, ind, E, w):
+        """sum_k w_k flow(E_k) at orbital level with REAL weights, one pass (negf_layered_bond_int): (diagonal blocks,
+        upper blocks, lower blocks) of float64."""
+        w = np.asarray(w).ravel()
+        if np.iscomplexobj(w):
+            if np.any(w.imag != 0):
+                raise ValueError("layered_bond_int takes real weights")
+            w = w.real
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        E, _ = self._grid(E)
+        assert E.size == w.size, "Elist and weights must have the same length"
+        flat = np.zeros(self.layered_pattern_size(handle), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_bond_int(self._ctx, int(handle), _ind(ind), E.size, _ptr(E), _ptr(w),
+                                                          _ptr(flat), _ptr(info)), "negf_layered_bond_int")
+        self._numerical(rc, info[:E.size], "layered_bond_int")
+        return self._lsplit(handle, flat)
+
+    def layered_bond_int_dev(self, handle, ind, m, E_ptr, w_ptr, out_ptr):
+        """negf_layered_bond_int_dev: E complex128 [m], w float64 [m] and out float64 [layered_pattern_size] in HBM."""
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_bond_int_dev(self._ctx, int(handle), _ind(ind), int(m), C.c_void_p(E_ptr),
+                                                         C.c_void_p(w_ptr), C.c_void_p(out_ptr)), "negf_layered_bond_int_dev")
+
     def layered_workspace_bytes(self, handle):
         v = C.c_longlong(0)
         self._lcheck(self._lib.negf_layered_workspace_bytes(self._ctx, int(handle), C.byref(v)), "negf_layered_workspace_bytes")

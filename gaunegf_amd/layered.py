@@ -16,6 +16,10 @@ namesakes in transport.py / integrate.py:
     dephasing_probes_layered(system, groups, gamma)                 -> the probes' (indices, block) list
     calculate_effective_transmission_layered(system, leads, energy_list, probes)     -> (T_eff [m], T_coherent [m])
     calculate_effective_current_layered(system, leads, fermi, qV, probes)            -> the current with floating probes
+    calculate_bond_transmission_layered(system, leads, energy_list, contact=0, groups=None)
+                                                                    -> (diag, up, low, labels): where the transmission flows
+    calculate_bond_currents_layered(system, leads, fermi, qV, contact=0, groups=None) -> the same in amperes, integrated
+    calculate_interlayer_transmission(system, leads, energy_list, contact=0)         -> [m, L - 1] flow across each boundary
 
 Per energy the work is L inverses and a handful of products of layer size instead of one N x N inverse.
 G Gamma_c G^H is formed on the pattern of S only -- what Tr[P S], a tight-binding Fock builder and the Mulliken populations
@@ -23,8 +27,10 @@ read -- from the columns of G on the lead's orbitals, which the two sweeps yield
 The transmission matrix between all terminals, with Buettiker / D'Amato-Pastawski probes on ANY layer, comes from column
 strips of G on the terminals' orbitals that the backward sweep carries from layer to layer, one pass over the layers
 as they are and one in reverse order; no block of G between distant layers is formed.
-Everything that needs more of G than that raises instead of guessing: eigenchannels, bond currents, the floating
-probes' response and G^<, spin layouts other than 'r', sharding over ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``)
+The local (bond) transmission flow[i, j] = 2 Im[K_ij A_ji], K = E S - F, vanishes wherever S and F do: the complete
+orbital-resolved flow map lives on the pattern of S and costs one more pass over the blocks of G Gamma G^H.
+Everything that needs more of G than that raises instead of guessing: eigenchannels, flows with floating probes, the
+floating probes' response and G^<, spin layouts other than 'r', sharding over ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``)
 is host-side numpy.
 """
 import numpy as np
@@ -404,13 +410,144 @@ def calculate_effective_current_layered(system, leads, fermi, qV, probes, T=None
     return 2 * total
 
 
-def _not_served(name):
+def _layer_groups(system, groups):
+    """``groups``: an integer label >= 0 per orbital of the whole system.  Returns (groups_per_layer [L], group_of [N]: the
+    position of each orbital's label among the ascending labels of its own layer, labels_per_layer); (None, None, None)
+    without groups.  Raises ValueError for a wrong length, a negative label, and a label whose orbitals span two layers."""
+    if not isinstance(system, LayeredSystem):
+        raise TypeError("expected a LayeredSystem (LayeredSystem.from_dense / partition make one)")
+    if groups is None:
+        return None, None, None
+    g = np.asarray(groups).ravel()
+    if g.size != system.n or not np.issubdtype(g.dtype, np.integer):
+        raise ValueError(f"groups must be an integer label per orbital (length {system.n}), got {g.size} entries of {g.dtype}")
+    if g.min() < 0:
+        raise ValueError(f"group labels must be non-negative, got {int(g.min())}")
+    offs = system.offsets
+    layer = np.repeat(np.arange(system.n_layers), system.sizes)
+    first = {}
+    for lab, lay in zip(g.tolist(), layer.tolist()):
+        if first.setdefault(lab, lay) != lay:
+            raise ValueError(f"group label {lab} spans layers {first[lab]} and {lay}: a group of a layered system lies "
+                             "inside one layer")
+    labels, group_of = [], np.zeros(system.n, dtype=np.int32)
+    for i in range(system.n_layers):
+        lab, inv = np.unique(g[offs[i]:offs[i + 1]], return_inverse=True)          # ascending
+        labels.append(lab)
+        group_of[offs[i]:offs[i + 1]] = inv
+    return np.array([len(lab) for lab in labels], dtype=np.int32), group_of, labels
+
+
+def calculate_bond_transmission_layered(system, leads, energy_list, contact=0, groups=None, spin=None, engine=None):
+    """Local (bond) transmission on a layered system, as calculate_local_transmission: WHERE the transmission injected by
+    lead ``contact`` (an index into ``leads``, None: all of them) flows.  flow[i, j] = 2 Im[K_ij A_ji] with K = E S - F and
+    A = G Gamma_c G^H is zero wherever S and F are, so the complete map lives on the pattern of S: returns (diag, upper,
+    lower, labels_per_layer), block lists with entries [m, g_i, g_j] -- the flow inside layer i, from layer i into layer
+    i + 1, and from layer i + 1 into layer i.  ``groups``: an integer label >= 0 per orbital of the whole system (atoms,
+    fragments), each label inside ONE layer; the labels of a layer are taken in ascending order (labels_per_layer[i][a] is
+    the label of row a of layer i's blocks).  None: per orbital pair (g_i = n_i, labels_per_layer None).
+    pattern_to_dense(...) assembles an [m, G, G] table for small systems."""
+    _only_restricted(spin)
+    gpl, group_of, labels = _layer_groups(system, groups)
+    with _Bound(system, leads, engine) as b:
+        d, u, l = b.eng.layered_local_transmission(b.h, b.term_of(contact), np.asarray(energy_list), gpl, group_of)
+    return d, u, l, labels
+
+
+def calculate_interlayer_transmission(system, leads, energy_list, contact=0, spin=None, engine=None):
+    """[m, L - 1]: the flow from layer i into layer i + 1 of the transmission injected by lead ``contact`` -- the sum of the
+    upper block i of calculate_bond_transmission_layered, obtained with one group per layer (nothing orbital-sized comes
+    back).  For one injecting lead at real energies every column equals the transmission into the leads of the other
+    end (with the sign of the direction): the current is conserved from boundary to boundary."""
+    _only_restricted(spin)
+    if not isinstance(system, LayeredSystem):
+        raise TypeError("expected a LayeredSystem (LayeredSystem.from_dense / partition make one)")
+    gpl = np.ones(system.n_layers, dtype=np.int32)
+    with _Bound(system, leads, engine) as b:
+        _, u, _ = b.eng.layered_local_transmission(b.h, b.term_of(contact), np.asarray(energy_list), gpl,
+                                                   np.zeros(system.n, dtype=np.int32))
+    return np.stack([blk[:, 0, 0] for blk in u], axis=1)
+
+
+def calculate_bond_currents_layered(system, leads, fermi, qV, T=None, contact=0, groups=None, dE=None, spin=None,
+                                    engine=None):
+    """Bond currents in amperes on the pattern of S, as calculate_bond_currents: the local transmission of lead
+    ``contact`` integrated over transport.current_grid's energies with its occupation factor, trapezoid weights (signed
+    step for qV < 0), e/h and the factor 2 of spin 'r', in ONE pass over the grid (Engine.layered_bond_int).  Returns
+    (diag, upper, lower, labels_per_layer) with [g_i, g_j] blocks; ``groups`` as calculate_bond_transmission_layered's, summed
+    on the host with the orbitals of a group in ascending order.  qV ~ 0 returns zeros."""
+    from . import transport as tp
+    _only_restricted(spin)
+    T = tp.TEMPERATURE if T is None else T
+    dE = tp.ENERGY_STEP if dE is None else dE
+    if fermi is None or qV is None:
+        raise ValueError("fermi and qV must be provided for current calculations")
+    gpl, group_of, labels = _layer_groups(system, groups)
+    sizes = system.sizes
+    if np.allclose(0, qV):
+        g = sizes if gpl is None else tuple(int(x) for x in gpl)
+        return ([np.zeros((a, a)) for a in g], [np.zeros((a, c)) for a, c in zip(g[:-1], g[1:])],
+                [np.zeros((c, a)) for a, c in zip(g[:-1], g[1:])], labels)
+    energies, muL, muR = tp.current_grid(fermi, qV, T, dE)
+    if len(energies) == 0:
+        raise ValueError("No energies in integration window. Check fermi, qV, and dE.")
+    # trapezoid(y * occupation, energies) = sum_k w_k y_k
+    w = np.zeros(len(energies))
+    if len(energies) > 1:
+        d = np.diff(energies)
+        w[:-1] += d / 2
+        w[1:] += d / 2
+    if T != 0:
+        w = w * np.abs(1 / (np.exp((energies - muR) / (tp.kB * T)) + 1) - 1 / (np.exp((energies - muL) / (tp.kB * T)) + 1))
+    with _Bound(system, leads, engine) as b:
+        blocks = b.eng.layered_bond_int(b.h, b.term_of(contact), energies, w)
+    blocks = [[2 * tp.eoverh * blk for blk in kind] for kind in blocks]
+    if gpl is not None:
+        offs = system.offsets
+        loc = [group_of[offs[i]:offs[i + 1]] for i in range(system.n_layers)]
+
+        def summed(blk, i, j):
+            out = np.zeros((gpl[i], gpl[j]))
+            for a in range(gpl[i]):
+                rows = blk[loc[i] == a]                                       # ascending orbitals
+                for c in range(gpl[j]):
+                    out[a, c] = rows[:, loc[j] == c].sum()
+            return out
+        L = system.n_layers
+        blocks = [[summed(blocks[0][i], i, i) for i in range(L)], [summed(blocks[1][i], i, i + 1) for i in range(L - 1)],
+                  [summed(blocks[2][i], i + 1, i) for i in range(L - 1)]]
+    return blocks[0], blocks[1], blocks[2], labels
+
+
+def pattern_to_dense(sizes, diag, upper, lower):
+    """The block lists of a result on the pattern of S (blocks [..., n_i, n_j], any leading axes) as one [..., N, N] array,
+    zero outside the pattern -- for small systems and tests."""
+    sizes = [int(n) for n in sizes]
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    if len(diag) != len(sizes) or len(upper) != len(sizes) - 1 or len(lower) != len(sizes) - 1:
+        raise ValueError("expected L diagonal blocks and L - 1 upper and lower blocks")
+    lead = np.shape(diag[0])[:-2]
+    out = np.zeros(lead + (offs[-1], offs[-1]), dtype=np.result_type(*diag, *upper, *lower))
+    for i, blk in enumerate(diag):
+        out[..., offs[i]:offs[i + 1], offs[i]:offs[i + 1]] = blk
+    for i in range(len(sizes) - 1):
+        out[..., offs[i]:offs[i + 1], offs[i + 1]:offs[i + 2]] = upper[i]
+        out[..., offs[i + 1]:offs[i + 2], offs[i]:offs[i + 1]] = lower[i]
+    return out
+
+
+def _not_served(name, why):
     def fn(*args, **kwargs):
-        raise NotImplementedError(f"{name} is not served on layered systems: it needs blocks of G outside the pattern of S, "
-                                  "the two corner blocks and the leads' columns (use the dense engine on system.to_dense())")
+        raise NotImplementedError(f"{name} is not served on layered systems: {why}")
     fn.__name__ = name
     return fn
 
 
-calculate_transmission_channels_layered = _not_served("calculate_transmission_channels_layered")
-calculate_local_transmission_layered = _not_served("calculate_local_transmission_layered")
+calculate_transmission_channels_layered = _not_served(
+    "calculate_transmission_channels_layered",
+    "it needs blocks of G outside the pattern of S, the two corner blocks and the leads' columns (use the dense engine on "
+    "system.to_dense())")
+calculate_local_transmission_layered = _not_served(
+    "calculate_local_transmission_layered",
+    "the local transmission of a layered system lives on the pattern of S and is calculate_bond_transmission_layered's "
+    "(block lists instead of an N x N table; pattern_to_dense assembles one)")

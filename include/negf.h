@@ -518,7 +518,7 @@ int negf_gr_int_probes_dev(negf_ctx* ctx, int handle, int n_probes, const int* p
  * A singular layer sets info[k] = the 1-based column of the zero pivot counted over the whole system and returns
  * NEGF_ESINGULAR, as the dense calls do.  negf_set_batch and negf_set_inverse_algo apply.  Every sum has a fixed order:
  * results are bitwise equal from run to run, do not depend on negf_set_batch, and permuting the energies permutes them.
- * Not served: eigenchannels, bond currents, the floating probes' response and G^< on a layered system,
+ * Not served: eigenchannels, flows with floating probes, the floating probes' response and G^< on a layered system,
  * TERMINALS (leads) on interior layers -- probes, which are arguments of negf_layered_transmission_matrix, may sit on any
  * layer --, spin layouts other than 'r', sharding, checkpoints. */
 int negf_layered_create(negf_ctx* ctx, int n_layers, const int* sizes, const double* F_diag_c128, const double* F_up_c128,
@@ -618,12 +618,48 @@ int negf_layered_transmission_matrix(negf_ctx* ctx, int handle, int n_probes, co
 int negf_layered_transmission_matrix_dev(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk,
                                          const int* probe_inds, const double* probe_sigma_c128, int m, const double* E_dev,
                                          double* T_dev);
+/* Where the current injected by the terminals `ind` flows -- negf_local_transmission / negf_bond_int on a layered system:
+ *   flow[i][j](E) = 2 Im[K_ij A_ji],  K = E S - F,  A = G Gamma G^H of negf_layered_gless_int for the same `ind`.
+ * K is zero wherever S and F are, so the complete orbital-resolved flow lives on the pattern of S, nothing truncated:
+ *   diagonal block i:     flow[r][c] = 2 Im[K_ii[r][c] conj(A_ii[r][c])]
+ *   upper block (i, i+1): flow[r][c] = 2 Im[K_u[r][c] conj(A_u[r][c])]
+ *   lower block (i+1, i): flow[r][c] = 2 Im[K_l[r][c] A_u[c][r]]        (a transposed read of the upper block of A)
+ * (A_ii = (W Gamma) W^H is Hermitian to the rounding of its products only: the diagonal block's flow reads its Hermitian part
+ * (A_ii + A_ii^H) / 2, so that at real E every block of the flow is antisymmetric bit for bit, flow_l = -flow_u^T included)
+ * applied literally for complex E as well (then the flow is not conserved and the lower block is not minus the
+ * transpose of the upper one).  K is formed per element from E and the stored blocks of S and F and never stored.  For
+ * one injecting terminal at real E the sum of upper block i -- the flow from layer i into layer i + 1 -- is the
+ * transmission, at every one of the L - 1 boundaries.
+ * negf_layered_local_transmission: per energy.  groups_per_layer (host int[L], g_i >= 1) and group_of (host int[N]: for
+ * each orbital in layer order its group inside its own layer, in [0, g_i); empty groups are allowed) reduce each block
+ * to out[a][b] = sum_{r in a, c in b} flow[r][c]; both NULL: every orbital its own group (g_i = n_i).  out: doubles in
+ * negf_layered_gr_int's block order with g in place of n -- diagonal g_i x g_i, upper g_i x g_{i+1}, lower g_{i+1} x g_i --
+ * and [m] of those.  The order of the additions depends on the orbitals' positions inside their groups only: relabelling
+ * the groups permutes the tables bit for bit.  A singular layer gives a NaN table for that energy, its info (the
+ * whole-system column) and NEGF_ESINGULAR; other energies are unaffected.
+ * negf_layered_bond_int: sum_k w_k flow(E_k) with REAL weights w [m] (doubles) at orbital level, sum n_i^2 +
+ * 2 sum n_i n_{i+1} doubles in the same order; energy k enters every element's sum after k - 1, and a singular energy
+ * enters it as it enters negf_layered_gless_int's.
+ * NEGF_EINVAL before anything is launched: an unknown handle, `ind` as negf_layered_gless_int refuses it, a group_of entry
+ * outside its layer's range, exactly one of the two group pointers NULL, g_i < 1, more energies than a `blocks` terminal
+ * holds, null pointers.  No floating-point atomics; results are bitwise equal from run to run, independent of
+ * negf_set_batch, and permuting the energies permutes the per-energy tables.  Profile family "bond". */
+int negf_layered_local_transmission(negf_ctx* ctx, int handle, int ind, int m, const double* E_c128,
+                                    const int* groups_per_layer, const int* group_of, double* out, int* info);
+int negf_layered_local_transmission_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev,
+                                        const int* groups_per_layer, const int* group_of, double* out_dev);
+int negf_layered_bond_int(negf_ctx* ctx, int handle, int ind, int m, const double* E_c128, const double* w, double* out,
+                          int* info);
+int negf_layered_bond_int_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, const double* w_dev,
+                              double* out_dev);
 /* device bytes of the work areas of the system's last call: (10 + L for a backward sweep) matrices of the largest layer
  * per energy in flight, and for a G Gamma G^H call its column sets -- with cs = n_max K_max: (L + 4) cs + K^2 for the set of
  * layer 0 (the z_i, x twice, W twice, Y, Gamma), 3 cs + K^2 for the last layer's.  For a transmission-matrix call, per
  * energy in flight: the 10 + L matrices, two strips of n_max K_tot, the Gamma blocks of the chain and blocks terminals and
  * three K_a K_b areas of the largest pair that takes the matrix-core path; once per call: the Gamma blocks of the probes
- * and const terminals (sum K^2).  The result [m][C][C] is the caller's. */
+ * and const terminals (sum K^2).  The result [m][C][C] is the caller's.  A bond call (negf_layered_local_transmission,
+ * negf_layered_bond_int) is a G Gamma G^H call plus, with groups, the maps (N + sum (g_i + 1) ints) and, in the host form,
+ * the staging of its result (m tables / one table of doubles). */
 int negf_layered_workspace_bytes(negf_ctx* ctx, int handle, long long* work);
 
 /* ------------------------------------------------------------- diagnostics */
