@@ -864,7 +864,21 @@ void negf_destroy(negf_ctx* c)
 int negf_set_stream(negf_ctx* c, void* s)
 {
     if (!c) return NEGF_EINVAL;
-    c->stream = reinterpret_cast<hipStream_t>(s);
+    hipStream_t next = reinterpret_cast<hipStream_t>(s);
+    if (next == c->stream) return NEGF_OK;                 // (bench.py's workers call this once each: no runtime call)
+    // Work queued on the old stream still owns the context's work areas (d_A, d_T1, d_T2, d_ipiv, d_info, d_acc, the
+    // pinned staging buffer, the g(E) cache entries), and every host-side decision of this file (ensure_cap, ensure_pinned,
+    // the cache eviction, negf_destroy) waits for c->stream alone: the new stream is ordered BEHIND the old one with an
+    // event, on the device, so that c->stream stays the one stream whose completion covers everything in flight.  The
+    // host does not wait.  (The wait takes the event's state at this call: the event goes back to the pool at once.)
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    hipEvent_t e = prof_get_event(c);
+    if (!e) return NEGF_EHIP;
+    hipError_t err = hipEventRecord(e, c->stream);
+    if (err == hipSuccess) err = hipStreamWaitEvent(next, e, 0);
+    c->ev_pool.push_back(e);
+    NEGF_HIP_CHECK(err);
+    c->stream = next;
     return NEGF_OK;
 }
 

@@ -86,6 +86,14 @@ class Engine:
             pass
 
     def set_stream(self, stream_ptr):
+        """Launch everything on this hipStream_t (``torch.cuda.Stream().cuda_stream``; 0 / None: the default stream).
+        The new stream is ordered behind the old one on the device -- work queued before the switch finishes before
+        anything queued after it starts; the host does not wait -- and setting the stream already set is free.
+        The ``*_dev`` methods then follow the stream contract of include/negf.h: inputs are read in stream order,
+        the output buffers are overwritten (never accumulated into, no need to zero them), results are valid in stream
+        order on that stream or after ``sync()``.  A warm call returns without waiting, except with a 1-D chain
+        provider while the g(E) cache is on (one download of the grid per launch), with host tables to upload (probes,
+        groups, ``layered_gless_int_dev`` / ``layered_contact_dos_dev``), and whenever a buffer has to grow."""
         check(self._lib.negf_set_stream(self._ctx, C.c_void_p(stream_ptr or 0)), "negf_set_stream")
 
     def set_batch(self, batch):

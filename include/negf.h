@@ -64,7 +64,13 @@ int         negf_create(negf_ctx** out, int device);
 void        negf_destroy(negf_ctx* ctx);
 const char* negf_strerror(int code);
 const char* negf_version(void);
-/* launch everything on this hipStream_t (NULL = the default stream) */
+/* Launch everything on this hipStream_t (NULL = the default stream).  A context has ONE stream at a time: its work
+ * areas are reused from call to call in that stream's order.  When the stream changes, the new one is ordered behind
+ * the old one ON THE DEVICE (an event recorded on the old stream, waited for by the new one): work queued before the
+ * switch finishes before anything queued after it starts, and the host does not wait.  The old stream must still
+ * exist at the call.  Setting the stream that is already set does nothing and costs nothing.  Work the CALLER has on
+ * other streams is the caller's to order (events), as with any stream-ordered library; two contexts are independent
+ * of each other, whatever their streams. */
 int         negf_set_stream(negf_ctx* ctx, void* hip_stream);
 /* energies processed per sweep of the workspace (0 = choose from n and free HBM);
  * replaces MAX_VMAP_MEMORY_GB batching, integrate.py:55,100-142 */
@@ -238,7 +244,32 @@ int negf_dos(negf_ctx* ctx, int handle, int m, const double* E_c128,
  * the context's GPU (used by bench.py and by the multi-GPU driver, which
  * all-reduces out_dev with RCCL through torch.distributed).  Asynchronous on
  * the context's stream; negf_sync waits.  negf_last_info copies the per-energy
- * info of the last *_dev call. */
+ * info of the last *_dev call.
+ *
+ * The stream contract of every *_dev entry point in this header (these, the layered ones and the later sections'):
+ *   - E_dev, w_dev and every other device input are READ IN STREAM ORDER: work the caller queued on the context's
+ *     stream before the call (copies into E_dev, kernels that produce the weights) is seen, whether or not it has
+ *     finished when the call returns.  Host arrays (seg_end, probe and group tables) are read before the call returns.
+ *   - out_dev / T_dev / ... are OVERWRITTEN: never accumulated into, never read; the caller need not zero them.
+ *   - Results are valid IN STREAM ORDER on that stream -- work queued behind the call sees them -- or on the host
+ *     after negf_sync (or any other wait for that stream).  negf_last_info and negf_last_iters wait themselves.
+ *   - Calls on one context may follow each other without a wait in between: they share the context's work areas in
+ *     stream order (also across negf_set_stream, see there).
+ *   - The call itself does not wait for the stream, EXCEPT
+ *       * a call that has to grow a buffer of the context (the first call of a shape, a larger grid, a larger batch):
+ *         it drains the stream before it frees the old buffer;
+ *       * a CHAIN1D provider (and a chain terminal of a layered system) while the g(E) cache is on
+ *         (negf_set_chain_cache, on by default): the energies are the cache key, so E_dev is downloaded -- one copy
+ *         and one wait per launch of the chain kernels, in stream order like every other read;
+ *       * a CHAIN1D provider with a free-running fixed point (force_iters < 0) whose record of sweep counts has to grow;
+ *       * an entry point that stages host tables on the device uploads them with a wait on every call: the probe and
+ *         group tables of the transmission-matrix, dephasing, bond and population calls, and the selected terminals'
+ *         orbital lists of negf_layered_gless_int_dev and negf_layered_contact_dos_dev.
+ *     With the cache off, CONST / PRECOMPUTED / BETHE providers and CHAIN1D at a fixed sweep count, a warm call of
+ *     negf_gr_int_dev, negf_gless_int_dev, negf_gr_int_seg_dev, negf_gless_int_seg_dev, negf_transmission_dev,
+ *     negf_layered_gr_int_dev, negf_layered_dos_dev and negf_layered_transmission_dev returns while the stream is
+ *     still busy with earlier work.
+ *   - A singular energy is no error of a *_dev call: it is reported through negf_last_info (non-zero at that energy). */
 int negf_gr_int_dev(negf_ctx* ctx, int handle, int m, const double* E_dev,
                     const double* w_dev, double* out_dev);
 int negf_gless_int_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev,
@@ -250,6 +281,8 @@ int negf_gr_int_seg_dev(negf_ctx* ctx, int handle, int m, const double* E_dev, c
                         int nseg, const int* seg_end, double* out_dev);
 int negf_gless_int_seg_dev(negf_ctx* ctx, int handle, int ind, int m, const double* E_dev, const double* w_dev,
                            int nseg, const int* seg_end, double* out_dev);
+/* NEGF_SPIN_RESTRICTED writes T_dev [m]; NEGF_SPIN_BLOCK writes Tspin_dev [m][4] only (T_dev is not touched: the
+ * total is the sum of the four components, which negf_transmission forms on the host). */
 int negf_transmission_dev(negf_ctx* ctx, int handle, int contact_L, int contact_R,
                           int spin_mode, int m, const double* E_dev,
                           double* T_dev, double* Tspin_dev);
