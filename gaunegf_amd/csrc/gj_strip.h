@@ -34,6 +34,11 @@
 // lesson of the chain kernel).
 #pragma once
 
+#ifndef GJ_STRIP_ABLATE
+#define GJ_STRIP_ABLATE 0             // diagnostic builds only (wrong results; timing): 1 no forward FMAs, 2 no backward FMAs,
+#endif                                //    4 no pivot steps, 8 no backward (NEGF_EXTRA_HIPCC_FLAGS=-DGJ_STRIP_ABLATE=.., loaded
+                                      //    with NEGF_LIB_PATH); the launches pass it as the kernels' dbg argument
+
 // maximum of a 32-bit key over the wave (all lanes active), wave-uniform: four DPP steps inside the rows of 16 lanes, then
 // row_bcast:15 / row_bcast:31 carry the row maxima into lane 63 (the chain kernel's rs_wave_max_u32)
 template <int CTRL, int ROW_MASK = 0xF>
@@ -57,9 +62,9 @@ template <int RPL, int SW, int NW, int OCC, int PF /* chunks of 4 columns in fli
 __global__ __launch_bounds__(NW * 64, OCC) void gj_window_strip_kernel(
     int n, cplx* __restrict__ bufA, cplx* __restrict__ bufB /* unused */, size_t mat_stride, int* __restrict__ piv_all /* [nb][2][n]: pivrow, colof */, int* __restrict__ info, int c0, int cw,
     unsigned long long* __restrict__ stamps /* diagnostic (NEGF_GJ_STAMPS): workgroup 0, [sub-window][8]; nullptr in production */,
-    int dbg /* timing ablations (NEGF_GJ_STRIP_DBG; wrong results): 1 no forward FMAs, 2 no backward FMAs, 4 no pivot steps, 8 no
-               backward.  A RUN-TIME value on purpose: compiled out (constexpr 0) the uniform branches around the FMA blocks go away and
-               the register allocator hoists across them -- 1314 spilled registers instead of 3 (measured) */)
+    int dbg /* GJ_STRIP_ABLATE, passed by the host.  A kernel ARGUMENT on purpose: as a constant 0 inside the kernel the uniform
+               branches around the FMA blocks go away and the register allocator hoists across them (scratch bytes per lane
+               <1,32,4,2,4> 84 -> 6388, <2,16,4,2,1> 12 -> 1004, <2,16,8,1,2> 160 -> 1612) */)
 {
     constexpr int T = NW * 64;
     constexpr int KMAX = WIN - SW;                   // columns of the window in front of its last sub-window

@@ -731,13 +731,10 @@ __global__ __launch_bounds__(RS_THREADS, OCC) void chain1d_rs_wn_kernel(
 bool chain1d_lds_supported(int nc_max) { return nc_max <= 64; }
 
 namespace {
-// sweeps a job runs before it makes room for a waiting one (NEGF_CHAIN_RR, 0 = every job runs to its end in one go)
+// sweeps a job runs before it makes room for a waiting one (0 = every job runs to its end in one go)
 int rs_rr_quantum(int user)
 {
-    if (user >= 0) return user;                      // negf_set_chain_round_robin
-    static int q = -1;
-    if (q < 0) { const char* e = getenv("NEGF_CHAIN_RR"); q = e ? std::max(atoi(e), 0) : 100; }
-    return q;
+    return user >= 0 ? user : 100;                   // negf_set_chain_round_robin, or the default
 }
 size_t rs_gold_elems(int nc_max, int n_contacts, int nb)
 {

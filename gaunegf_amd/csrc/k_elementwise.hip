@@ -347,9 +347,7 @@ void launch_accumulate_perm(hipStream_t st, int n, int nb, const cplx* w, const 
     const int n2 = n * n;
     const int g = (n2 + EW_THREADS - 1) / EW_THREADS;
     const int nchunks = (nb + ACC_CHUNK - 1) / ACC_CHUNK;
-    static int rows = -1;
-    if (rows < 0) { const char* e = getenv("NEGF_ACC_PERM_ROWS"); rows = e ? atoi(e) : 1; }
-    if (rows && n <= APR_MAXN)
+    if (n <= APR_MAXN)
         hipLaunchKernelGGL(accumulate_perm_rows_kernel, dim3(n, nchunks), dim3(EW_THREADS), (size_t)2 * n * sizeof(cplx), st, n, nb, w, W, piv, info, part, AccChunks{});
     else
         hipLaunchKernelGGL(accumulate_perm_partial_kernel, dim3(g, nchunks), dim3(EW_THREADS), 0, st, n, nb, w, W, piv, info, part);
@@ -363,9 +361,7 @@ void launch_accumulate_perm(hipStream_t st, int n, int nb, const cplx* w, const 
 bool launch_accumulate_ranges(hipStream_t st, int n, bool perm, const cplx* w, const cplx* XW, const int* piv, const int* info,
                               int nranges, const int* lo, const int* hi, const int* slot, cplx* out, cplx* part)
 {
-    static int rows = -1;
-    if (rows < 0) { const char* e = getenv("NEGF_ACC_PERM_ROWS"); rows = e ? atoi(e) : 1; }
-    if (nranges > ACC_TAB_SEGS || (perm && !(rows && n <= APR_MAXN))) return false;
+    if (nranges > ACC_TAB_SEGS || (perm && n > APR_MAXN)) return false;
     AccChunks tab{};
     for (int r = 0; r < nranges; ++r) {
         tab.first[r] = tab.nchunks; tab.slot[r] = slot[r];

@@ -48,6 +48,11 @@
 #include "negf_common.h"
 #include "wave_utils.h"
 
+#ifndef GJ_ABLATE
+#define GJ_ABLATE 0                   // diagnostic builds only (wrong results; timing): gj_blocked_kernel with 16 = U-team idle,
+#endif                                //    32 = no pivot steps (NEGF_EXTRA_HIPCC_FLAGS=-DGJ_ABLATE=32, loaded with NEGF_LIB_PATH);
+                                      //    the launch passes it as the kernel's dbg argument
+
 namespace {
 
 // NB panel width, CPR strips per panel row, RPT rows per panel thread, PW panel-team waves,
@@ -337,8 +342,8 @@ __device__ __forceinline__ void gj_update_item(const cplx* __restrict__ Pt, int 
 template <class C>
 __global__ __launch_bounds__(C::THREADS) void gj_blocked_kernel(
     int n, cplx* __restrict__ bufA, cplx* __restrict__ bufB, size_t mat_stride, int* __restrict__ info,
-    int dbg /* ablation switches, 0 in production: 16 = U-team idle, 32 = no pivot steps */,
-    unsigned long long* __restrict__ stamps /* diagnostic build only (NEGF_GJ_STAMPS): wall-clock
+    int dbg /* GJ_ABLATE, passed by the host (an argument: as a constant inside the kernel its code moves) */,
+    unsigned long long* __restrict__ stamps /* diagnostic only (NEGF_GJ_STAMPS): wall-clock
                stamps of workgroup 0, [step+1][8]; nullptr in production */)
 {
     constexpr int NB = C::NB, RPT = C::RPT, PW = C::PW;
@@ -595,16 +600,16 @@ void gj_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t stride, i
                                   (int)LDS_LIMIT);
         attr_set = true;
     }
-    static int dbg = -1;
+    static int want_stamps = -1;
     static unsigned long long* d_stamps = nullptr;
-    if (dbg < 0) {
-        const char* e = getenv("NEGF_GJ_DEBUG"); dbg = e ? atoi(e) : 0;
-        if (getenv("NEGF_GJ_STAMPS")) {
+    if (want_stamps < 0) {
+        want_stamps = gj_params().stamps;
+        if (want_stamps) {
             (void)hipMalloc(&d_stamps, 64 * 8 * sizeof(unsigned long long));
             (void)hipMemset(d_stamps, 0, 64 * 8 * sizeof(unsigned long long));
         }
     }
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(C::THREADS), smem, st, n, A, B, stride, info, dbg, d_stamps);
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(C::THREADS), smem, st, n, A, B, stride, info, GJ_ABLATE, d_stamps);
     if (d_stamps) {
         (void)hipStreamSynchronize(st);
         unsigned long long h[64 * 8];
@@ -1446,12 +1451,13 @@ template <int NBI, int RPT>
 void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t stride, int* piv, int* info, GjSideStreams* sdp, const GjPlan& plan, GjRecord* rec)
 {
     const size_t smem = (size_t)(2 * PW * NBI + 2 * NBI * WIN) * sizeof(cplx);      // candidate rows + Q of two sub-panels
-    auto kern = gj_window_kernel<NBI, RPT>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(100 * 1024));
-        attr_set = true;
+    if constexpr (!(NBI == 16 && RPT == 1)) {
+        static bool attr_set = false;
+        if (!attr_set) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gj_window_kernel<NBI, RPT>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(100 * 1024));
+            attr_set = true;
+        }
     }
     static int want_stamps = -1;
     static unsigned long long* d_stamps = nullptr;
@@ -1461,8 +1467,6 @@ void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t str
     }
     // Which window kernel, pairs or not, which update form, how many groups: gj_plan (below) decides, from the
     // measurements recorded there; this function launches what the plan says and notes each launch in rec.
-    static int strip_dbg = -1;           // timing ablations of the strip kernel (wrong results)
-    if (strip_dbg < 0) { const char* e = getenv("NEGF_GJ_STRIP_DBG"); strip_dbg = e ? atoi(e) : 0; }
     const int nblk = plan.nblk;
     // the chain of one group of matrices: per window the panel kernel (one workgroup per matrix: a latency chain
     // that covers at most `count` CUs) and the column-block update (throughput-bound), then the gather
@@ -1481,22 +1485,13 @@ void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t str
                 g_gj_vector_flops += 6.0 * (double)((n + 15) & ~15) * cw * (double)cw * count;
             switch (gp.wk) {
             case GJ_WK_STRIP_256:
-                hipLaunchKernelGGL((gj_window_strip_kernel<1, 32, 4, 2, 4>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
+                hipLaunchKernelGGL((gj_window_strip_kernel<1, 32, 4, 2, 4>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, GJ_STRIP_ABLATE);
                 did |= 1u << GJ_WK_STRIP_256; break;
-            case GJ_WK_STRIP_256_S16:
-                hipLaunchKernelGGL((gj_window_strip_kernel<1, 16, 4, 3, 4>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
-                did |= 1u << GJ_WK_STRIP_256_S16; break;
-            case GJ_WK_STRIP_512_FAT:
-                hipLaunchKernelGGL((gj_window_strip_kernel<1, 32, 8, 1, 4>), dim3(count), dim3(512), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
-                did |= 1u << GJ_WK_STRIP_512_FAT; break;
-            case GJ_WK_STRIP_512_2CH:    // two chunks in flight: 72 spilled registers, 23.3 ms against 22.6 (1000 x n = 500)
-                hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 4, 2, 2>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
-                did |= 1u << GJ_WK_STRIP_512_2CH; break;
             case GJ_WK_STRIP_512:
-                hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 4, 2, 1>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
+                hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 4, 2, 1>), dim3(count), dim3(256), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, GJ_STRIP_ABLATE);
                 did |= 1u << GJ_WK_STRIP_512; break;
             case GJ_WK_STRIP_1024:
-                hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 8, 1, 2>), dim3(count), dim3(512), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, strip_dbg);
+                hipLaunchKernelGGL((gj_window_strip_kernel<2, 16, 8, 1, 2>), dim3(count), dim3(512), 0, s, n, Ag, Bg, stride, pg, ig, c0, cw, stp, GJ_STRIP_ABLATE);
                 did |= 1u << GJ_WK_STRIP_1024; break;
             case GJ_WK_LA_6:
                 hipLaunchKernelGGL((gj_window_la_kernel<16, 4, 6>), dim3(count), dim3(6 * 64), smem, s, n, Ag, stride, pg, ig, c0, cw, stp);
@@ -1505,8 +1500,12 @@ void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t str
                 hipLaunchKernelGGL((gj_window_la_kernel<16, 8, 12>), dim3(count), dim3(12 * 64), smem, s, n, Ag, stride, pg, ig, c0, cw, stp);
                 did |= 1u << GJ_WK_LA_12; break;
             default:
-                hipLaunchKernelGGL(kern, dim3(count), dim3(PT), smem, s, n, Ag, stride, pg, ig, c0, cw, stp);
-                did |= 1u << GJ_WK_TEAM; break;
+                // (the <16, 1> class never runs the team kernel: gj_plan answers strip or look-ahead there)
+                if constexpr (!(NBI == 16 && RPT == 1)) {
+                    hipLaunchKernelGGL((gj_window_kernel<NBI, RPT>), dim3(count), dim3(PT), smem, s, n, Ag, stride, pg, ig, c0, cw, stp);
+                    did |= 1u << GJ_WK_TEAM;
+                }
+                break;
             }
         };
         auto colupdate = [&](int c0, int cw, int only_blk) {
@@ -1603,7 +1602,7 @@ void gj_large_launch(hipStream_t st, int n, int nb, cplx* A, cplx* B, size_t str
 int gj_large_pick(int n)
 {
     if (n < 64) return 0;
-    if (n <= PT) return 4;               // <= 512: sub-panel 16, 1 row per thread (only above NEGF_GJ_LARGE_MIN)
+    if (n <= PT) return 4;               // <= 512: sub-panel 16, 1 row per thread
     if (n <= PT * 2) return 1;           // <= 1024: sub-panel 16, 2 rows per thread
     if (n <= PT * 4) return 2;           // <= 2048: sub-panel 8, 4 rows per thread
     if (n <= PT * 8) return 3;           // <= 4096: sub-panel 4, 8 rows per thread
@@ -1617,26 +1616,11 @@ bool inverse_blocked_supported(int n) { return gj_pick(n) != 0 || gj_large_pick(
 
 double inverse_blocked_vector_flops() { return g_gj_vector_flops; }
 
-// This process's thresholds: the defaults of GjParams with the NEGF_GJ_* switches applied, read once.
+// This process's thresholds: the defaults of GjParams; NEGF_GJ_STAMPS (a diagnostic, read once) is the only variable.
 const GjParams& gj_params()
 {
     static const GjParams params = [] {
         GjParams p;
-        auto geti = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
-        auto getl = [](const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; };
-        p.large_min = geti("NEGF_GJ_LARGE_MIN", p.large_min);
-        p.small_win_min = geti("NEGF_GJ_SMALL_WIN_MIN", p.small_win_min);
-        p.winla = geti("NEGF_GJ_WINLA", p.winla);
-        p.strip_env = geti("NEGF_GJ_STRIP", p.strip_env);
-        p.strip_min = geti("NEGF_GJ_STRIP_MIN", p.strip_min);
-        p.strip_cfg = geti("NEGF_GJ_STRIP_CFG", p.strip_cfg);
-        p.pair = geti("NEGF_GJ_PAIR", p.pair);
-        p.pair_min = getl("NEGF_GJ_PAIR_MIN", p.pair_min);
-        p.fat_max = getl("NEGF_GJ_FAT_MAX", p.fat_max);
-        p.fat_total_max = getl("NEGF_GJ_FAT_TOTAL_MAX", p.fat_total_max);
-        p.split_max = geti("NEGF_GJ_SPLIT_MAX", p.split_max);
-        if (const char* e = getenv("NEGF_GJ_GROUP_MAX")) p.grp_max = std::min(std::max(atoi(e), 1), (int)GjSideStreams::MAXG);
-        if (const char* e = getenv("NEGF_GJ_GROUP_MIN")) p.grp_min = std::max(atoi(e), 1);
         p.stamps = getenv("NEGF_GJ_STAMPS") ? 1 : 0;
         return p;
     }();
@@ -1650,7 +1634,7 @@ int gj_plan(int n, int nb, int win_mode, bool defer, const GjParams& p, GjPlan* 
     GjPlan pl;
     // Single-workgroup kernel or windows.  The single-workgroup kernel serves up to 256 rows (its 32-column panel
     // configuration); above, the windowed path with 16-column sub-panels is faster (ms per 1000 matrices: n = 260 9.3 vs
-    // 9.1, 300 13.3 vs 11.1, 340 20.5 vs 17.3, 370 28.5 vs 20.1); NEGF_GJ_LARGE_MIN moves the switch-over
+    // 9.1, 300 13.3 vs 11.1, 340 20.5 vs 17.3, 370 28.5 vs 20.1)
     // (round 5: with the strip window kernel the windowed path wins from n = 209 on -- ms per 1000 matrices, windowed /
     // single workgroup: n = 192 2.45 / 2.58 but 200 3.01 / 3.01 and 208 3.08 / 3.08 (a ragged fourth window), 224 3.33 / 3.56,
     // 240 3.70 / 4.49, 256 4.01 / 5.26).
@@ -1688,7 +1672,7 @@ int gj_plan(int n, int nb, int win_mode, bool defer, const GjParams& p, GjPlan* 
     // groups on streams of their own: while one group factors a panel (a few CUs), the column updates of the
     // others use the rest of the chip: 61 x N = 800 24.5 -> 30.5 TF, 128 x N = 1000 34.9 -> 40.0 TF.  At full batch both
     // kernels fill the chip by themselves and the groups mostly run in lockstep: + 2 % (1000 x N = 500 33.1 -> 33.8 TF).
-    const int want = (nb <= p.split_max && !p.stamps) ? std::max(1, std::min(std::min(p.grp_max, (int)GjSideStreams::MAXG), nb / std::max(p.grp_min, 1))) : 1;
+    const int want = !p.stamps ? std::max(1, std::min(std::min(p.grp_max, (int)GjSideStreams::MAXG), nb / std::max(p.grp_min, 1))) : 1;
     const int per = (nb + want - 1) / want;
     for (int g = 0; g < want && g * per < nb; ++g) {
         GjGroup& gp = pl.g[pl.groups++];
@@ -1698,8 +1682,8 @@ int gj_plan(int n, int nb, int win_mode, bool defer, const GjParams& p, GjPlan* 
     for (int g = 0; g < pl.groups; ++g) {
         GjGroup& gp = pl.g[g];
         const int count = gp.count;
-        // Which window kernel (win_mode 0 = auto, 1 = strip wherever an instantiation serves n, 2 = team kernels only;
-        // NEGF_GJ_STRIP = 0 / 1 sets the auto rule's answer for A/B runs).  Inverse ms, strip / team:
+        // Which window kernel (win_mode 0 = auto, 1 = strip wherever an instantiation serves n, 2 = team kernels only).
+        // Inverse ms, strip / team:
         //   1000 matrices: n = 256 4.01 / 5.26 (single-workgroup kernel), 300 6.62 / 7.53, 400 13.0 / 14.6, 500 21.5 / 24.5 (the
         //   strip kernel moves 3.3 MB per window and matrix instead of 4.9, and both run at the ~4.3 TB/s this access pattern
         //   gets out of the memory system), 650 55.5 / 53.5, 800 84.8 / 84.4, 1000 147.9 / 150.4 (the 8-wave, one-per-CU form);
@@ -1707,15 +1691,12 @@ int gj_plan(int n, int nb, int win_mode, bool defer, const GjParams& p, GjPlan* 
         //   4-wave workgroup has a longer chain per matrix than the 12-wave look-ahead kernel), 12 x 800 5.51 / 5.77,
         //   61 x 800 7.54 / 8.10, 64 x 1000 13.1 / 14.1, 128 x 1000 23.0 / 23.9, 486 x 800 42.5 / 42.4.
         const bool strip = pl.nbi == 16 &&
-            (win_mode == 1 || (win_mode == 0 && (p.strip_env >= 0 ? p.strip_env != 0
-                                                 : (n <= 256 || (n <= 512 ? count >= p.strip_min : (count <= p.strip_max || n >= p.strip_always))))));
-        // strip_cfg 0: the measured choice per size; 1: n <= 512 fat (8 waves x 1 row, sub-windows of 32); 3: n <= 256 with
-        // sub-windows of 16; 4: n <= 512 lean with two chunks in flight
+            (win_mode == 1 || (win_mode == 0 && (n <= 256 || (n <= 512 ? count >= p.strip_min : (count <= p.strip_max || n >= p.strip_always)))));
+        // (the strip instantiation per size is the measured choice; the look-ahead kernels serve the <16, 1> class, the team
+        //  kernel every other)
         if (strip)
-            gp.wk = n <= 256 ? (p.strip_cfg != 3 ? GJ_WK_STRIP_256 : GJ_WK_STRIP_256_S16)
-                  : n <= 512 ? (p.strip_cfg == 1 ? GJ_WK_STRIP_512_FAT : p.strip_cfg == 4 ? GJ_WK_STRIP_512_2CH : GJ_WK_STRIP_512)
-                  : GJ_WK_STRIP_1024;
-        else if (pl.nbi == 16 && pl.rpt == 1 && p.winla)
+            gp.wk = n <= 256 ? GJ_WK_STRIP_256 : n <= 512 ? GJ_WK_STRIP_512 : GJ_WK_STRIP_1024;
+        else if (pl.nbi == 16 && pl.rpt == 1)
             gp.wk = n <= 256 ? GJ_WK_LA_6 : GJ_WK_LA_12;
         else
             gp.wk = GJ_WK_TEAM;
@@ -1725,7 +1706,7 @@ int gj_plan(int n, int nb, int win_mode, bool defer, const GjParams& p, GjPlan* 
         // (372: 6.91 / 6.81), 128 x N = 1000 (448: 24.0 / 22.95)
         // (round 5, with the strip window kernels, inverse ms without / with pairs: 122 x N = 800 (330 workgroups per group) 13.46 /
         //  12.09, 128 x N = 500 (192) 3.93 / 3.94, 61 x N = 800 (165) 7.39 / 8.95: the threshold moved from 352 to 256)
-        gp.pairs = (p.pair && pl.nblk >= 3 && (long)count * (pl.nblk - 2) >= p.pair_min) ? 1 : 0;
+        gp.pairs = (pl.nblk >= 3 && (long)count * (pl.nblk - 2) >= p.pair_min) ? 1 : 0;
         // The update: eight waves per column block where the launch has fewer workgroups than the chip has CUs AND the whole
         // batch (all stream groups together) leaves the chip room: there a column block's latency counts, not the
         // CU's throughput (inverse ms, lean / fat: 61 x N = 800 8.87 / 7.57, 64 x N = 1000 14.40 / 13.83,

@@ -364,7 +364,7 @@ __global__ __launch_bounds__(ZF_THREADS) void zgemm_flex_kernel(
 
 // Plain VALU version (no matrix cores, the four-product form): kept as the independent cross-check of
 // the MFMA fragment maps (tests/test_zgemm_accuracy_gpu.py compares the three kernels through
-// negf_zgemm_batched) and selectable with NEGF_ZGEMM_ALGO=valu for debugging.
+// negf_zgemm_batched).
 __global__ __launch_bounds__(256) void zgemm_valu_kernel(
     int M, int N, int K,
     const cplx* __restrict__ Aall, int lda, size_t strideA,
@@ -421,16 +421,6 @@ __global__ __launch_bounds__(256) void zgemm_valu_kernel(
                 else C[(size_t)gi * ldc + gj] = acc[a][c];
             }
         }
-}
-
-static int zgemm_algo()
-{
-    static int algo = -1;
-    if (algo < 0) {
-        const char* e = getenv("NEGF_ZGEMM_ALGO");
-        algo = (e && strcmp(e, "valu") == 0) ? 1 : 0;
-    }
-    return algo;
 }
 
 // The production rule: how much of the 64 x 64 blocks' area is padding beyond the 16-granular tiles?  Above 20 % the
@@ -504,19 +494,14 @@ void launch_zgemm_as(hipStream_t st, int kernel, bool herm_on, int M, int N, int
     }
 }
 
-// The production entry: the kernel by the padding rule and the Hermitian form on, unless the environment says otherwise
-// (read once per process: NEGF_ZGEMM_ALGO=valu, NEGF_ZGEMM_FLEX=0 / 2: never / always the flexible kernel,
-// NEGF_ZGEMM_HERM=0: compute Hermitian products in full -- A/B runs; tests choose through negf_zgemm_batched).
+// The production entry: the kernel by the padding rule and the Hermitian form on (tests and A/B runs choose another
+// kernel through negf_zgemm_batched).
 void launch_zgemm(hipStream_t st, int M, int N, int K, int nb,
                   const cplx* A, int lda, size_t strideA,
                   const cplx* B, int ldb, size_t strideB, int opB,
                   cplx* C, int ldc, size_t strideC)
 {
-    static int herm_env = -1, flex_env = -1;
-    if (herm_env < 0) { const char* e = getenv("NEGF_ZGEMM_HERM"); herm_env = e ? atoi(e) : 1; }
-    if (flex_env < 0) { const char* e = getenv("NEGF_ZGEMM_FLEX"); flex_env = e ? atoi(e) : 1; }
-    const int kernel = zgemm_algo() == 1 ? ZGEMM_VALU : flex_env == 2 ? ZGEMM_FLEX : flex_env == 1 ? ZGEMM_AUTO : ZGEMM_MFMA;
-    launch_zgemm_as(st, kernel, herm_env != 0, M, N, K, nb, A, lda, strideA, B, ldb, strideB, opB, C, ldc, strideC);
+    launch_zgemm_as(st, ZGEMM_AUTO, true, M, N, K, nb, A, lda, strideA, B, ldb, strideB, opB, C, ldc, strideC);
 }
 
 // What launch_zgemm_as(kernel, herm on) does with a shape, without a device: see negf_zgemm_plan (negf.h).

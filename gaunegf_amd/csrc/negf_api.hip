@@ -290,19 +290,14 @@ int ensure_workspace(negf_ctx* c, int m, int blk_stride, int min_batch = 1)
 // Wait for the context's stream at the end of a host-pointer call.  hipStreamSynchronize parks the thread and is woken
 // by an interrupt -- tens of microseconds after the GPU is done, as much as a small integral itself takes -- so the
 // stream is POLLED for the first 2 ms (an SCF-sized call is over long before) and only then handed to the blocking wait.
-// NEGF_SYNC_SPIN=0: always block.
 int wait_stream(negf_ctx* c)
 {
-    static int spin = -1;
-    if (spin < 0) { const char* e = getenv("NEGF_SYNC_SPIN"); spin = e ? atoi(e) : 1; }
-    if (spin) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            const hipError_t q = hipStreamQuery(c->stream);
-            if (q == hipSuccess) return NEGF_OK;
-            if (q != hipErrorNotReady) { (void)hipGetLastError(); break; }
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-        }
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q == hipSuccess) return NEGF_OK;
+        if (q != hipErrorNotReady) { (void)hipGetLastError(); break; }
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
     }
     NEGF_HIP_CHECK(hipStreamSynchronize(c->stream));
     return NEGF_OK;
@@ -749,20 +744,12 @@ void fill_trivial_iters(size_t cnt, int* iters, int* converged)
     for (size_t i = 0; i < cnt; ++i) { if (iters) iters[i] = 0; if (converged) converged[i] = 1; }
 }
 
-// NEGF_GATHER_FUSED=0: the weighted sums of G run the gather + accumulate sequence
-bool gather_fused()
-{
-    static int fused = -1;
-    if (fused < 0) { const char* e = getenv("NEGF_GATHER_FUSED"); fused = e ? atoi(e) : 1; }
-    return fused != 0;
-}
-
 // assemble + inverse for a weighted sum of G, which needs no G itself: the windowed inverse leaves its gather out and
 // the sum reads the reduced matrices through the pivot bookkeeping.  *perm: that is how the result was left (in c->W1,
 // with c->d_ipiv); otherwise it is in c->G as usual.
 int run_inverse_for_sum(negf_ctx* c, SigmaProvider* p, int m0, int nb, const cplx* E, bool* perm)
 {
-    c->defer_gather = gather_fused();
+    c->defer_gather = true;
     const int rc = run_assemble_inverse(c, p, m0, nb, E);
     c->defer_gather = false;
     *perm = c->G_deferred;

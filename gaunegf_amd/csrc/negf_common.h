@@ -182,9 +182,7 @@ struct GjSideStreams {
 enum {
     GJ_WK_NONE = 0,
     GJ_WK_STRIP_256 = 1,       // gj_window_strip_kernel<1, 32, 4, 2, 4>: n <= 256, sub-windows of 32
-    GJ_WK_STRIP_256_S16 = 2,   // gj_window_strip_kernel<1, 16, 4, 3, 4> (NEGF_GJ_STRIP_CFG = 3)
-    GJ_WK_STRIP_512_FAT = 3,   // gj_window_strip_kernel<1, 32, 8, 1, 4> (NEGF_GJ_STRIP_CFG = 1)
-    GJ_WK_STRIP_512_2CH = 4,   // gj_window_strip_kernel<2, 16, 4, 2, 2> (NEGF_GJ_STRIP_CFG = 4)
+                               // (2, 3, 4: retired strip variants, LAB_NOTES.md "retired environment switches"; unused numbers)
     GJ_WK_STRIP_512 = 5,       // gj_window_strip_kernel<2, 16, 4, 2, 1>: 257 ... 512, the lean 4-wave form
     GJ_WK_STRIP_1024 = 6,      // gj_window_strip_kernel<2, 16, 8, 1, 2>: 513 ... 1024, 8 waves
     GJ_WK_LA_6 = 7,            // gj_window_la_kernel<16, 4, 6>
@@ -199,23 +197,18 @@ enum {
     GJ_BIT_UPD2 = 1 << 14,     // gj_colupdate2_kernel (a pair of windows)
     GJ_BIT_GATHER = 1 << 15,   // gj_gather_kernel
 };
-// the thresholds of the rule with their defaults; gj_params() is this process's set (NEGF_GJ_* read once)
+// the thresholds of the rule; gj_params() is this process's set: these numbers, and stamps from NEGF_GJ_STAMPS
 struct GjParams {
-    int large_min = 209;             // NEGF_GJ_LARGE_MIN: n from which the windowed path serves every batch
-    int small_win_min = 257;         // NEGF_GJ_SMALL_WIN_MIN: matrices from which 100 <= n < large_min goes windowed
-    int winla = 1;                   // NEGF_GJ_WINLA: the look-ahead team kernels for the <16,1> class
-    int strip_env = -1;              // NEGF_GJ_STRIP: -1 = the rule, 0 / 1 = its answer
-    int strip_min = 64;              // NEGF_GJ_STRIP_MIN: matrices per group from which 257 <= n <= 512 takes the strip kernel
+    int large_min = 209;             // n from which the windowed path serves every batch
+    int small_win_min = 257;         // matrices from which 100 <= n < large_min goes windowed
+    int strip_min = 64;              // matrices per group from which 257 <= n <= 512 takes the strip kernel
     int strip_max = 160;             // matrices per group up to which 513 <= n < strip_always takes it
     int strip_always = 900;          // n from which the <16,2> class always takes it
-    int strip_cfg = 0;               // NEGF_GJ_STRIP_CFG
-    int pair = 1;                    // NEGF_GJ_PAIR
-    long pair_min = 256;             // NEGF_GJ_PAIR_MIN: count * (nblk - 2) from which windows go in pairs
-    long fat_max = 256;              // NEGF_GJ_FAT_MAX: workgroups of an update launch up to which it is fat ...
-    long fat_total_max = 2000;       // NEGF_GJ_FAT_TOTAL_MAX: ... if nb * nblk does not exceed this
-    int split_max = 1 << 30;         // NEGF_GJ_SPLIT_MAX
-    int grp_max = 4;                 // NEGF_GJ_GROUP_MAX (<= GjSideStreams::MAXG)
-    int grp_min = 12;                // NEGF_GJ_GROUP_MIN: matrices per group
+    long pair_min = 256;             // count * (nblk - 2) from which windows go in pairs
+    long fat_max = 256;              // workgroups of an update launch up to which it is fat ...
+    long fat_total_max = 2000;       // ... if nb * nblk does not exceed this
+    int grp_max = 4;                 // stream groups (<= GjSideStreams::MAXG; 1 where the context has no side streams)
+    int grp_min = 12;                // matrices per group
     int stamps = 0;                  // NEGF_GJ_STAMPS: time stamps of one workgroup (one group)
 };
 struct GjGroup {
@@ -458,7 +451,7 @@ size_t chain1d_scratch_per_wg(int nc_max);
 bool chain1d_lds_supported(int nc_max);
 // gold_scratch: chain1d_lds_scratch_elems() complex values of lane-private scratch (may be null:
 // the kernel then keeps the old iterate in LDS at a lower occupancy)
-// (+ the job queue of a round-robin launch: rr_quantum < 0 = the default, NEGF_CHAIN_RR)
+// (+ the job queue of a round-robin launch: rr_quantum < 0 = the default, 100 sweeps)
 size_t chain1d_lds_scratch_elems(int nc_max, int n_contacts, int nb, int max_sweeps, int rr_quantum);
 // does a launch of nb energies that runs its fixed points (no cache hit, scratch given) run round robin: more jobs than
 // resident slots, and a quantum below its sweep cap?  Such a launch needs no order (rr_quantum / rr_slots as below)
@@ -466,7 +459,7 @@ bool chain1d_lds_runs_queue(const SigmaProvider& p, int nb, int rr_quantum, int 
 // order: launch slot -> job (energy * n_contacts + contact) or null for launch order
 // gcache / gc_mode: see ChainGEntry -- 0 no cache, 1 store the final iterates, 2 load them and only form Sigma
 // rr_quantum / rr_slots: round-robin execution of a launch with more jobs than resident slots (ChainRsArgs; < 0 / 0:
-// the defaults -- NEGF_CHAIN_RR or 100 sweeps, every slot of the device; rr_quantum 0: never)
+// the defaults -- 100 sweeps, every slot of the device; rr_quantum 0: never)
 void launch_chain1d_lds(hipStream_t st, const SigmaProvider& p, const int* d_nc, const int* d_blk_off, int nb,
                         const cplx* E, cplx* blk, int* iters, int* conv, cplx* gold_scratch, const int* order,
                         cplx* gcache = nullptr, int gc_mode = 0, int rr_quantum = -1, int rr_slots = 0);

@@ -1338,9 +1338,8 @@ class Engine:
         return {"kernel": ku.value, "opB": oe.value, "blocks": (blocks[0], blocks[1]),
                 "grid": (grid[0], grid[1], grid[2]), "decode": decode}
 
-    INVERSE_WINDOW_KERNELS = {0: "none", 1: "strip<1,32,4,2,4>", 2: "strip<1,16,4,3,4>", 3: "strip<1,32,8,1,4>",
-                              4: "strip<2,16,4,2,2>", 5: "strip<2,16,4,2,1>", 6: "strip<2,16,8,1,2>", 7: "la<16,4,6>",
-                              8: "la<16,8,12>", 9: "team", 10: "single"}
+    INVERSE_WINDOW_KERNELS = {0: "none", 1: "strip<1,32,4,2,4>", 5: "strip<2,16,4,2,1>", 6: "strip<2,16,8,1,2>",
+                              7: "la<16,4,6>", 8: "la<16,8,12>", 9: "team", 10: "single"}    # (2, 3, 4: retired, unused)
 
     @staticmethod
     def inverse_plan(n, nb, algo=0, defer=False):

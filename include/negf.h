@@ -727,7 +727,7 @@ int negf_set_small_algo(negf_ctx* ctx, int algo);
  * point runs `quantum` sweeps and, when others wait, goes to the back of a device-side queue with its iterate.  The
  * chip then stays full until fewer fixed points than slots are left, whatever order they were started in; results
  * do not depend on it (a fixed point is a sequence of sweeps on its own data).  quantum: < 0 = default -- quanta of
- * NEGF_CHAIN_RR (else 100) sweeps for every such launch, whether or not its sweep counts can be predicted from the
+ * 100 sweeps for every such launch, whether or not its sweep counts can be predicted from the
  * provider's previous evaluation (on the C3 grid the queue is 1.5 % faster than one workgroup per fixed point started
  * longest first, and its initial order is worth nothing); 0 = never round robin: one workgroup per fixed point, longest
  * first by the predicted counts; > 0 = this quantum.  Launches that fit the device, or whose sweep cap is not above
@@ -761,7 +761,7 @@ int negf_zgemm_batched(negf_ctx* ctx, int M, int N, int K, int nb, const double*
                        long long strideC, int kernel);
 /* What negf_zgemm_batched does with a shape; a host function that needs no device.  kernel as above (0: the rule the
  * library's own products follow -- the flexible kernel where the 64 x 64 blocks would be more than a sixth padding;
- * the NEGF_ZGEMM_* environment switches are not consulted).  Outputs, each may be NULL: kernel_used (1 .. 3), opB_eff
+ * no environment variable changes it).  Outputs, each may be NULL: kernel_used (1 .. 3), opB_eff
  * (opB after the demotion of bit 1), blocks[2] = block rows and columns, grid[3] = the launch grid (x, y, z).  For a
  * Hermitian launch of kernel 1 or 2 (opB_eff bit 1) and decode != NULL: decode[3 L .. 3 L + 2] = (block row, block
  * column, batch member) of workgroup L < grid[0], or (-1, -1, -1) for a workgroup that returns at once; decode_cap
@@ -769,8 +769,8 @@ int negf_zgemm_batched(negf_ctx* ctx, int M, int N, int K, int nb, const double*
 int negf_zgemm_plan(int M, int N, int K, int opB, int nb, int kernel, int* kernel_used, int* opB_eff, int* blocks,
                     int* grid, int* decode, int decode_cap);
 /* What the inverse of nb matrices of dimension n launches under negf_set_inverse_algo(algo); a host function that
- * needs no device.  It is the rule the launch code itself follows (one function, k_inverse_blocked.hip), with this
- * process's NEGF_GJ_* switches applied (read once).  defer != 0: the caller reads the reduced matrices through the
+ * needs no device.  It is the rule the launch code itself follows (one function, k_inverse_blocked.hip); of the
+ * environment only the diagnostic NEGF_GJ_STAMPS acts on it (one stream group).  defer != 0: the caller reads the reduced matrices through the
  * pivot bookkeeping (negf_gr_int does), so the windowed path leaves its gather out.  The fused kernel of n <= 96
  * (negf_set_small_algo 0) never reaches the inverse and is not part of the plan.  Outputs, each may be NULL:
  *   path      0 = no blocked kernel serves n, or algo = 1 (the unblocked kernel); 1 = the single-workgroup kernel;
@@ -782,7 +782,7 @@ int negf_zgemm_plan(int M, int N, int K, int opB, int nb, int kernel, int* kerne
  *   group_tab [4][7] = per group: first, count, window kernel id, pairs (0 / 1), waves of the update launches over all
  *             other column blocks (4 = lean, 8 = fat, 0 = none), waves of the single-block update launches of a pair
  *             (0 = none), launch mask; rows from `groups` on are zero.  Window kernel ids: 1 .. 6 register-strip kernels
- *             (1 = n <= 256, 5 = 257 .. 512 lean, 6 = 513 .. 1024 eight waves; 2, 3, 4 the NEGF_GJ_STRIP_CFG alternates),
+ *             (1 = n <= 256, 5 = 257 .. 512 lean, 6 = 513 .. 1024 eight waves; 2, 3, 4 retired variants, never answered),
  *             7 / 8 = look-ahead team kernels of 6 / 12 waves, 9 = the team kernel of the class, 10 = single workgroup.
  *             Launch mask: bit (window kernel id), bit 12 = lean update, 13 = fat update, 14 = the fused update of a
  *             pair of windows, 15 = gather

@@ -1,6 +1,6 @@
 """First against repeated evaluation of the C3 grid (2000 energies x 2 leads of n_c = 50): a FRESH provider has no sweep
 counts to predict an order from, so its first launch runs in launch order -- unless the launch runs round robin
-(NEGF_CHAIN_RR, negf_set_chain_round_robin), which needs no order.  GrInt through the device-pointer entry point,
+(negf_set_chain_round_robin), which needs no order.  GrInt through the device-pointer entry point,
 workspace allocated beforehand, g(E) cache off."""
 import os, sys, time
 import numpy as np

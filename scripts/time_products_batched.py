@@ -1,6 +1,6 @@
 """The two product forms of zgemm_mfma_kernel with BOTH operands batched: G Gamma_b (A B) and X G^H (A B^H) at n = 1000,
-256 energies, through GrLessInt over a PRECOMPUTED provider (a coupling matrix per energy).  Run with NEGF_ZGEMM_HERM=0
-under a kernel trace: with a constant-Sigma provider (scripts/time_products.py) the first product's B operand is ONE
+256 energies, through GrLessInt over a PRECOMPUTED provider (a coupling matrix per energy).  Written for runs with the Hermitian form off
+(NEGF_ZGEMM_HERM=0, a switch the library no longer has; LAB_NOTES.md, "Retired environment switches") under a kernel trace: with a constant-Sigma provider (scripts/time_products.py) the first product's B operand is ONE
 matrix shared by the whole batch, which is what made the A B form look faster than A B^H (profiles/r04_zgemm_forms.txt)."""
 import os, sys, time
 import numpy as np

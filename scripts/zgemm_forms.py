@@ -1,5 +1,5 @@
 """Per-dispatch comparison of the two product forms of zgemm_mfma_kernel in a `time_products.py 1000` run with
-NEGF_ZGEMM_HERM=0: dispatches alternate  X = G Gamma (A B)  and  X G^H (A B^H, the conjugate-transposed operand read in
+the Hermitian form off (NEGF_ZGEMM_HERM=0, a switch of round 4 the library no longer has): dispatches alternate  X = G Gamma (A B)  and  X G^H (A B^H, the conjugate-transposed operand read in
 place).  Reads the rocprofv3 outputs of scripts/gpu_profiles_r4.sh (PMC pass and kernel trace) under the given directory
 and prints durations and LDS / matrix-pipe counters per form."""
 import csv, glob, os, sys
