@@ -6,6 +6,7 @@
 #include <atomic>
 #include <thread>
 #include <cstdlib>
+#include <initializer_list>
 #include <new>
 
 static hipEvent_t prof_get_event(negf_ctx* c)
@@ -391,6 +392,12 @@ int norm_contact(const SigmaProvider* p, int ind)
     return ind;
 }
 
+// the terminals of a call with n_probes probes: the provider's contacts and the probes, TMAT_MAX_TERMINALS at most
+bool probes_count_ok(const SigmaProvider* p, int n_probes)
+{
+    return n_probes >= 0 && (long)p->n_contacts + n_probes <= TMAT_MAX_TERMINALS;
+}
+
 int run_inverse(negf_ctx* c, int nb, int* info)
 {
     ProfScope ps(c, "inverse");
@@ -738,10 +745,19 @@ int open_call(negf_ctx* c, int handle, int m, SigmaProvider** p, int indA = 0, i
     return NEGF_OK;
 }
 
-// sweep counts and flags of a provider without a fixed point: none run, all converged
-void fill_trivial_iters(size_t cnt, int* iters, int* converged)
+// sweep counts and flags [m][n_contacts] of the last evaluation of p (either may be null); a provider without a fixed
+// point: none run, all converged
+int fetch_iters(negf_ctx* c, const SigmaProvider* p, int m, int* iters, int* converged)
 {
+    const size_t cnt = (size_t)m * p->n_contacts;
+    int rc;
+    if (p->kind == SK_CHAIN1D || p->kind == SK_BETHE) {
+        if (iters && (rc = download(c, iters, c->d_iters, cnt))) return rc;
+        if (converged && (rc = download(c, converged, c->d_conv, cnt))) return rc;
+        return NEGF_OK;
+    }
     for (size_t i = 0; i < cnt; ++i) { if (iters) iters[i] = 0; if (converged) converged[i] = 1; }
+    return NEGF_OK;
 }
 
 // assemble + inverse for a weighted sum of G, which needs no G itself: the windowed inverse leaves its gather out and
@@ -780,6 +796,45 @@ int reduce_info(negf_ctx* c, int m, int* info_host)
     if (rc) return rc;
     for (int i = 0; i < m; ++i) if (dst[i] != 0) return NEGF_ESINGULAR;
     return NEGF_OK;
+}
+
+// how a device-resident call ends once everything is queued: the grid length noted, a launch error reported
+int close_call(negf_ctx* c, int m)
+{
+    c->last_m = m;
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
+}
+
+// The batches of a call that sweeps the n x n workspace over a grid of m energies, the dense twin of rgf_batches
+// (negf_layered_impl.h): the per-energy buffers and the workspace stand (ensure_workspace may set c->batch: it is read
+// after it), setup(batch) runs once -- what the call sizes by the batch or queues in front of its first batch --, then
+// body(m0, nb) per batch [m0, m0 + nb); the first nonzero rc ends the call.  An entry point that treats m == 0 on its
+// own (an early return, a result to clear) does so before it gets here.  Not its clients:
+//   - the small_path branches of negf_gr_int_dev and gr_seg_core: one fused kernel per chunk of SMALL_CHUNK energies
+//     (per call for the segments) and no n x n workspace;
+//   - negf_transmission_dev: a workspace of two energies at least, swept by HALF the batch (the other half is scratch).
+template <class Setup, class Body>
+int dense_batches(negf_ctx* c, SigmaProvider* p, int m, Setup&& setup, Body&& body)
+{
+    int rc;
+    if ((rc = ensure_mbuffers(c, m, p->n_contacts)) || (rc = ensure_workspace(c, m, p->blk_stride))) return rc;
+    const int batch = c->batch;
+    if ((rc = setup(batch))) return rc;
+    for (int m0 = 0; m0 < m; m0 += batch)
+        if ((rc = body(m0, std::min(batch, m - m0)))) return rc;
+    return close_call(c, m);
+}
+template <class Body>
+int dense_batches(negf_ctx* c, SigmaProvider* p, int m, Body&& body)
+{
+    return dense_batches(c, p, m, [](int) { return NEGF_OK; }, body);
+}
+
+// the setup of a call that sums into `out`: cleared in front of the first batch
+auto clear_first(negf_ctx* c, void* out, size_t bytes)
+{
+    return [=](int) -> int { NEGF_HIP_CHECK(hipMemsetAsync(out, 0, bytes, c->stream)); return NEGF_OK; };
 }
 
 }  // namespace
@@ -1389,26 +1444,40 @@ int negf_gr_int_dev(negf_ctx* c, int handle, int m, const double* E_dev, const d
             if (m0 > 0) launch_cadd(c->stream, n2, out, chunk_sum, out);
             negf_count_flops(8.0 * c->n * (double)c->n * c->n * nb, 0.0);
         }
-        c->last_m = m;
-        NEGF_HIP_CHECK(hipGetLastError());
-        return NEGF_OK;
+        return close_call(c, m);
     }
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
     const cplx* w = reinterpret_cast<const cplx*>(w_dev);
     cplx* out = reinterpret_cast<cplx*>(out_dev);
-    NEGF_HIP_CHECK(hipMemsetAsync(out, 0, n2 * sizeof(cplx), c->stream));
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
+    return dense_batches(c, p, m, clear_first(c, out, n2 * sizeof(cplx)), [&](int m0, int nb) {
         bool perm;
-        if ((rc = run_inverse_for_sum(c, p, m0, nb, E, &perm))) return rc;
+        if (int e = run_inverse_for_sum(c, p, m0, nb, E, &perm)) return e;
         ProfScope ps(c, "accumulate");
         if (perm) launch_accumulate_perm(c->stream, c->n, nb, w + m0, c->W1, c->d_ipiv, c->d_info + m0, out, c->W2);
         else launch_accumulate(c->stream, (int)n2, nb, w + m0, c->G, out, c->W2);
+        return NEGF_OK;
+    });
+}
+
+// c->W1 = G D G^H of the batch in c->G for a Hermitian D [nb] (stride sD; Gamma_c, or the dephased coupling): on the K
+// columns idx of G (D is K x K; G[:, idx] and X live in the free buffer W2, 2 n K <= n^2) or, idx null, dense (D n x n).
+// X = (. D)^H -- the first product stores its result conjugate-transposed -- and W1 = . X ( = G D^H G^H), upper block
+// tiles computed, lower ones mirrored: both products read their second operand in the plain form (k_zgemm.hip: the
+// operand conjugate-transposed on the fly costs the L2 twice the requests).
+static void launch_g_d_gh(negf_ctx* c, int nb, int K, const int* idx, const cplx* D, size_t sD)
+{
+    const int n = c->n;
+    const size_t n2 = (size_t)n * n;
+    if (!idx) {
+        launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, D, n, sD, 4, c->W2, n, n2);
+        launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, c->W2, n, n2, 2, c->W1, n, n2);
+        return;
     }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+    cplx* Gc = c->W2;                              // [nb][n x K]
+    cplx* X = c->W2 + (size_t)n * K;               // [nb][n x K]
+    launch_gather_block(c->stream, n, n, K, nb, c->G, n2, nullptr, idx, Gc, n2);
+    launch_zgemm(c->stream, n, K, K, nb, Gc, K, n2, D, K, sD, 4, X, n, n2);
+    launch_zgemm(c->stream, n, n, K, nb, Gc, K, n2, X, n, n2, 2, c->W1, n, n2);
 }
 
 // A_c = G Gamma_c G^H for the batch [m0, m0 + nb) -> c->W1 (Hermitian unless the caller handed in its own coupling
@@ -1420,38 +1489,22 @@ static int run_gless_products(negf_ctx* c, SigmaProvider* p, int contact, int m0
     const int n = c->n;
     if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
     if (compact_available(c, p)) {
-        // G Gamma G^H = (G[:, I] Gamma_II) G[:, I]^H : Gc and X live in the free buffer W2
+        // G Gamma G^H = (G[:, I] Gamma_II) G[:, I]^H
         GammaSmall g;
         { ProfScope ps(c, "gamma"); if ((rc = run_gamma_small(c, p, contact, nb, 0, &g))) return rc; }
-        cplx* Gc = c->W2;                              // [nb][n x K]
-        cplx* X = c->W2 + (size_t)n * g.K;             // [nb][n x K]   (2 n K <= n^2)
         ProfScope ps(c, "zgemm");
-        launch_gather_block(c->stream, n, n, g.K, nb, c->G, n2, nullptr, g.idx, Gc, n2);
-        // X = (Gc Gamma)^H, K x n, stored conjugate-transposed by the first product; W1 = Gc X: the second operand
-        // in the plain form (see the dense products below)
-        launch_zgemm(c->stream, n, g.K, g.K, nb, Gc, g.K, n2, g.mat, g.K, g.stride, 4, X, n, n2);
-        launch_zgemm(c->stream, n, n, g.K, nb, Gc, g.K, n2, X, n, n2, 2, c->W1, n, n2);     // Hermitian result
+        launch_g_d_gh(c, nb, g.K, g.idx, g.mat, g.stride);
         return NEGF_OK;
     }
     size_t gs = 0;
     const cplx* gam = nullptr;
     { ProfScope ps(c, "gamma"); if ((rc = run_gamma(c, p, contact, m0, nb, c->W1, c->W2, &gam, &gs))) return rc; }
     ProfScope ps(c, "zgemm");
-    // G Gamma G^H (integrate.py:81).  Gamma = i (Sigma - Sigma^H) is Hermitian, element by element, and so is the
-    // result: W2 = (G Gamma)^H -- the first product stores its result conjugate-transposed -- and W1 = G W2
-    // ( = G Gamma^H G^H), upper block tiles computed, lower ones mirrored.  Both products read their second
-    // operand in the plain form (k_zgemm.hip: the operand conjugate-transposed on the fly costs the L2 twice
-    // the requests).
-    // (coupling matrices handed in by the caller -- pre_is_gamma -- need not be Hermitian: X = G Gamma, then
-    //  the full product X G^H)
-    const bool full = p->kind == SK_PRECOMPUTED && p->pre_is_gamma;
-    if (!full) {
-        launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, gam, n, gs, 4, c->W2, n, n2);
-        launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, c->W2, n, n2, 2, c->W1, n, n2);
-    } else {
-        launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, gam, n, gs, 0, c->W2, n, n2);
-        launch_zgemm(c->stream, n, n, n, nb, c->W2, n, n2, c->G, n, n2, 1, c->W1, n, n2);
-    }
+    // G Gamma G^H (integrate.py:81).  Gamma = i (Sigma - Sigma^H) is Hermitian, element by element, and so is the result.
+    if (!(p->kind == SK_PRECOMPUTED && p->pre_is_gamma)) { launch_g_d_gh(c, nb, n, nullptr, gam, gs); return NEGF_OK; }
+    // (coupling matrices handed in by the caller need not be Hermitian: X = G Gamma, then the full product X G^H)
+    launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, gam, n, gs, 0, c->W2, n, n2);
+    launch_zgemm(c->stream, n, n, n, nb, c->W2, n, n2, c->G, n, n2, 1, c->W1, n, n2);
     return NEGF_OK;
 }
 
@@ -1460,26 +1513,17 @@ static int run_gless_products(negf_ctx* c, SigmaProvider* p, int contact, int m0
 static int gless_core(negf_ctx* c, SigmaProvider* p, int contact, int m, const cplx* E, const cplx* w, cplx* out,
                       int nseg, const int* seg_end)
 {
-    int rc;
     const size_t n2 = (size_t)c->n * c->n;
-    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
-    NEGF_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)std::max(nseg, 1) * n2 * sizeof(cplx), c->stream));
-    auto accumulate = [&](const cplx* X, int m0, int nb) {
+    return dense_batches(c, p, m, clear_first(c, out, (size_t)std::max(nseg, 1) * n2 * sizeof(cplx)), [&](int m0, int nb) {
+        if (int e = run_gless_products(c, p, contact, m0, nb, E)) return e;
+        const cplx* X = c->W1;
         ProfScope ps(c, "accumulate");
-        if (nseg == 0) { launch_accumulate(c->stream, (int)n2, nb, w + m0, X, out, c->W2); return; }
+        if (nseg == 0) { launch_accumulate(c->stream, (int)n2, nb, w + m0, X, out, c->W2); return NEGF_OK; }
         const SegShares sh = batch_shares(nseg, seg_end, m0, nb);
         for (size_t k = 0; k < sh.slot.size(); ++k)
             launch_accumulate(c->stream, (int)n2, sh.hi[k] - sh.lo[k], w + m0 + sh.lo[k], X + (size_t)sh.lo[k] * n2, out + (size_t)sh.slot[k] * n2, c->W2);
-    };
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
-        if ((rc = run_gless_products(c, p, contact, m0, nb, E))) return rc;
-        accumulate(c->W1, m0, nb);
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        return NEGF_OK;
+    });
 }
 
 int negf_gless_int_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev,
@@ -1594,9 +1638,7 @@ int negf_transmission_dev(negf_ctx* c, int handle, int contact_L, int contact_R,
             }
         }
     }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+    return close_call(c, m);
 }
 
 int negf_sync(negf_ctx* c)
@@ -1616,16 +1658,8 @@ int negf_last_iters(negf_ctx* c, int handle, int m, int* iters, int* converged)
 {
     SigmaProvider* p = get_provider(c, handle);
     if (!c || !p || m < 0 || m > c->m_cap) return NEGF_EINVAL;
-    const size_t cnt = (size_t)m * p->n_contacts;
-    if (p->kind == SK_CHAIN1D || p->kind == SK_BETHE) {
-        if (p->n_contacts > c->contacts_cap) return NEGF_EINVAL;
-        int rc;
-        if (iters && (rc = download(c, iters, c->d_iters, cnt))) return rc;
-        if (converged && (rc = download(c, converged, c->d_conv, cnt))) return rc;
-    } else {
-        fill_trivial_iters(cnt, iters, converged);
-    }
-    return NEGF_OK;
+    if ((p->kind == SK_CHAIN1D || p->kind == SK_BETHE) && p->n_contacts > c->contacts_cap) return NEGF_EINVAL;
+    return fetch_iters(c, p, m, iters, converged);
 }
 
 // --------------------------------------------------------------- host variants
@@ -1644,6 +1678,11 @@ struct PinLayout {
         bytes = info + (size_t)m * sizeof(int) + 64;
     }
 };
+
+// the device side of a staged call as the *_dev forms take it: the grid, the weights, the n x n accumulator
+static double* dev_E(negf_ctx* c) { return reinterpret_cast<double*>(c->d_E); }
+static double* dev_w(negf_ctx* c) { return reinterpret_cast<double*>(c->d_w); }
+static double* dev_acc(negf_ctx* c) { return reinterpret_cast<double*>(c->d_acc); }
 
 // the grid goes up; the pinned buffer has room for a result of result_bytes (at least one n x n matrix) + extra_bytes
 static int stage_grid(negf_ctx* c, int m, int contacts, const double* E, const double* w, size_t result_bytes = 0,
@@ -1686,17 +1725,48 @@ static int fetch_result_and_info(negf_ctx* c, int m, const void* d_src, size_t b
     return rc;
 }
 
-int negf_gr_int(negf_ctx* c, int handle, int m, const double* E, const double* w, double* out,
-                int* info)
+// The same way back for results too large to pin (G(E), psi, per-energy tables): every output [count] comes down with a
+// pageable copy and a wait of its own, in the order given, then the info (reduce_info, one more copy and wait).
+extern "C++" struct HostOut {
+    void* dst; const void* src; size_t bytes;
+    template <typename T>
+    HostOut(T* host_dst, const T* dev_src, size_t count) : dst(host_dst), src(dev_src), bytes(count * sizeof(T)) {}
+};
+static int fetch_pageable(negf_ctx* c, int m, std::initializer_list<HostOut> outs, int* info_host)
+{
+    for (const HostOut& o : outs)
+        if (int rc = download(c, static_cast<unsigned char*>(o.dst), static_cast<const unsigned char*>(o.src), o.bytes)) return rc;
+    return reduce_info(c, m, info_host);
+}
+
+// real weights w [m] of a bond integral: they ride in the [w] part of the pinned buffer and of d_w (m doubles of their m
+// complex values); stage_grid has run with a result of result_bytes
+static int stage_real_weights(negf_ctx* c, int m, const double* w, size_t result_bytes)
+{
+    if (m <= 0) return NEGF_OK;
+    unsigned char* pw = c->h_pin + PinLayout(m, result_bytes).w;
+    std::memcpy(pw, w, (size_t)m * sizeof(double));
+    NEGF_HIP_CHECK(hipMemcpyAsync(c->d_w, pw, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return NEGF_OK;
+}
+
+// The host form of an integral into ONE n x n matrix -- GrInt, GrLessInt, either with n_probes probes --: grid and weights
+// staged, dev(E, w, acc) run on the staged device pointers, matrix and info back through the pinned buffer
+extern "C++" template <class Dev>
+static int host_integral(negf_ctx* c, int handle, int n_probes, int m, const double* E, const double* w, double* out, int* info, Dev&& dev)
 {
     SigmaProvider* p;
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
-    if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
-    if ((rc = negf_gr_int_dev(c, handle, m, reinterpret_cast<double*>(c->d_E),
-                              reinterpret_cast<double*>(c->d_w), reinterpret_cast<double*>(c->d_acc)))) return rc;
+    if (!probes_count_ok(p, n_probes) || !out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, w)) || (rc = dev(dev_E(c), dev_w(c), dev_acc(c)))) return rc;
     return fetch_result_and_info(c, m, c->d_acc, (size_t)c->n * c->n * sizeof(cplx), out, info);
+}
+
+int negf_gr_int(negf_ctx* c, int handle, int m, const double* E, const double* w, double* out, int* info)
+{
+    return host_integral(c, handle, 0, m, E, w, out, info,
+                         [&](double* Ed, double* wd, double* acc) { return negf_gr_int_dev(c, handle, m, Ed, wd, acc); });
 }
 
 // Several integrals of the same system in ONE pass: the energies are nseg consecutive segments (seg_end[s] = index one
@@ -1727,33 +1797,28 @@ static int gr_seg_core(negf_ctx* c, SigmaProvider* p, int m, const cplx* Ed, con
         a.w = wd; a.partial = c->d_small_part; a.out = out; a.nseg = nseg; a.seg_end = seg_end;
         launch_small_fused(c->stream, a);
         negf_count_flops(8.0 * c->n * (double)c->n * c->n * m, 0.0);
-    } else {
-        if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
-        NEGF_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)nseg * n2 * sizeof(cplx), c->stream));
-        for (int m0 = 0; m0 < m; m0 += c->batch) {
-            const int nb = std::min(c->batch, m - m0);
-            bool perm;
-            if ((rc = run_inverse_for_sum(c, p, m0, nb, Ed, &perm))) return rc;
-            ProfScope ps(c, "accumulate");
-            // every segment's share of this batch in ONE launch pair (a joint arc + tail probe: 12 segments = 24 launches
-            // of a few microseconds each behind a millisecond of inverse)
-            const SegShares sh = batch_shares(nseg, seg_end, m0, nb);
-            if (launch_accumulate_ranges(c->stream, c->n, perm, wd + m0, perm ? c->W1 : c->G, c->d_ipiv, c->d_info + m0,
-                                         (int)sh.slot.size(), sh.lo.data(), sh.hi.data(), sh.slot.data(), out, c->W2)) continue;
-            for (size_t k = 0; k < sh.slot.size(); ++k) {
-                const int lo = sh.lo[k], cnt = sh.hi[k] - lo;
-                cplx* dst = out + (size_t)sh.slot[k] * n2;
-                if (perm)
-                    launch_accumulate_perm(c->stream, c->n, cnt, wd + m0 + lo, c->W1 + (size_t)lo * n2,
-                                           c->d_ipiv + (size_t)lo * 2 * c->n, c->d_info + m0 + lo, dst, c->W2);
-                else
-                    launch_accumulate(c->stream, (int)n2, cnt, wd + m0 + lo, c->G + (size_t)lo * n2, dst, c->W2);
-            }
-        }
+        return close_call(c, m);
     }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+    return dense_batches(c, p, m, clear_first(c, out, (size_t)nseg * n2 * sizeof(cplx)), [&](int m0, int nb) {
+        bool perm;
+        if (int e = run_inverse_for_sum(c, p, m0, nb, Ed, &perm)) return e;
+        ProfScope ps(c, "accumulate");
+        // every segment's share of this batch in ONE launch pair (a joint arc + tail probe: 12 segments = 24 launches
+        // of a few microseconds each behind a millisecond of inverse)
+        const SegShares sh = batch_shares(nseg, seg_end, m0, nb);
+        if (launch_accumulate_ranges(c->stream, c->n, perm, wd + m0, perm ? c->W1 : c->G, c->d_ipiv, c->d_info + m0,
+                                     (int)sh.slot.size(), sh.lo.data(), sh.hi.data(), sh.slot.data(), out, c->W2)) return NEGF_OK;
+        for (size_t k = 0; k < sh.slot.size(); ++k) {
+            const int lo = sh.lo[k], cnt = sh.hi[k] - lo;
+            cplx* dst = out + (size_t)sh.slot[k] * n2;
+            if (perm)
+                launch_accumulate_perm(c->stream, c->n, cnt, wd + m0 + lo, c->W1 + (size_t)lo * n2,
+                                       c->d_ipiv + (size_t)lo * 2 * c->n, c->d_info + m0 + lo, dst, c->W2);
+            else
+                launch_accumulate(c->stream, (int)n2, cnt, wd + m0 + lo, c->G + (size_t)lo * n2, dst, c->W2);
+        }
+        return NEGF_OK;
+    });
 }
 
 int negf_gr_int_seg_dev(negf_ctx* c, int handle, int m, const double* E_dev, const double* w_dev, int nseg,
@@ -1768,19 +1833,27 @@ int negf_gr_int_seg_dev(negf_ctx* c, int handle, int m, const double* E_dev, con
                        reinterpret_cast<cplx*>(out_dev));
 }
 
+// negf_gr_int_seg (ind null) and negf_gless_int_seg: [nseg][n*n] sums on the device, then one download of all of them and
+// the info, one synchronisation
+static int host_seg_int(negf_ctx* c, int handle, const int* ind, int m, const double* E, const double* w, int nseg,
+                        const int* seg_end, double* out, int* info)
+{
+    SigmaProvider* p;
+    int contact = -1;
+    int rc = open_call(c, handle, m, &p, ind ? *ind : 0, ind ? &contact : nullptr);
+    if (rc) return rc;
+    if (!out || (m > 0 && (!E || !w)) || check_segments(m, nseg, seg_end)) return NEGF_EINVAL;
+    const size_t cnt = (size_t)nseg * c->n * c->n;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, w, cnt * sizeof(cplx))) || (rc = ensure_cap(c, c->d_seg_out, cnt))) return rc;
+    if ((rc = ind ? gless_core(c, p, contact, m, c->d_E, c->d_w, c->d_seg_out, nseg, seg_end)
+                  : gr_seg_core(c, p, m, c->d_E, c->d_w, nseg, seg_end, c->d_seg_out))) return rc;
+    return fetch_result_and_info(c, m, c->d_seg_out, cnt * sizeof(cplx), out, info);
+}
+
 int negf_gr_int_seg(negf_ctx* c, int handle, int m, const double* E, const double* w, int nseg,
                     const int* seg_end, double* out, int* info)
 {
-    SigmaProvider* p;
-    int rc = open_call(c, handle, m, &p);
-    if (rc) return rc;
-    if (!out || (m > 0 && (!E || !w)) || check_segments(m, nseg, seg_end)) return NEGF_EINVAL;
-    // results: [nseg][n*n] on the device, then one download of all segment sums and the info, one synchronisation
-    const size_t cnt = (size_t)nseg * c->n * c->n;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, w, cnt * sizeof(cplx)))) return rc;
-    if ((rc = ensure_cap(c, c->d_seg_out, cnt))) return rc;
-    if ((rc = gr_seg_core(c, p, m, c->d_E, c->d_w, nseg, seg_end, c->d_seg_out))) return rc;
-    return fetch_result_and_info(c, m, c->d_seg_out, cnt * sizeof(cplx), out, info);
+    return host_seg_int(c, handle, nullptr, m, E, w, nseg, seg_end, out, info);
 }
 
 // Adaptive nested quadrature with the refinement ON THE DEVICE (integratePointsAdaptiveANT, density.py:211-273): the m energies
@@ -1873,16 +1946,7 @@ int negf_gr_int_refine(negf_ctx* c, int handle, int m, const double* E, const do
 int negf_gless_int_seg(negf_ctx* c, int handle, int ind, int m, const double* E, const double* w, int nseg,
                        const int* seg_end, double* out, int* info)
 {
-    SigmaProvider* p;
-    int contact;
-    int rc = open_call(c, handle, m, &p, ind, &contact);
-    if (rc) return rc;
-    if (!out || (m > 0 && (!E || !w)) || check_segments(m, nseg, seg_end)) return NEGF_EINVAL;
-    const size_t cnt = (size_t)nseg * c->n * c->n;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, w, cnt * sizeof(cplx)))) return rc;
-    if ((rc = ensure_cap(c, c->d_seg_out, cnt))) return rc;
-    if ((rc = gless_core(c, p, contact, m, c->d_E, c->d_w, c->d_seg_out, nseg, seg_end))) return rc;
-    return fetch_result_and_info(c, m, c->d_seg_out, cnt * sizeof(cplx), out, info);
+    return host_seg_int(c, handle, &ind, m, E, w, nseg, seg_end, out, info);
 }
 
 int negf_gless_int_seg_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev, const double* w_dev, int nseg,
@@ -1897,17 +1961,10 @@ int negf_gless_int_seg_dev(negf_ctx* c, int handle, int ind, int m, const double
                       reinterpret_cast<cplx*>(out_dev), nseg, seg_end);
 }
 
-int negf_gless_int(negf_ctx* c, int handle, int ind, int m, const double* E, const double* w,
-                   double* out, int* info)
+int negf_gless_int(negf_ctx* c, int handle, int ind, int m, const double* E, const double* w, double* out, int* info)
 {
-    SigmaProvider* p;
-    int rc = open_call(c, handle, m, &p);
-    if (rc) return rc;
-    if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
-    if ((rc = negf_gless_int_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E),
-                                 reinterpret_cast<double*>(c->d_w), reinterpret_cast<double*>(c->d_acc)))) return rc;
-    return fetch_result_and_info(c, m, c->d_acc, (size_t)c->n * c->n * sizeof(cplx), out, info);
+    return host_integral(c, handle, 0, m, E, w, out, info,
+                         [&](double* Ed, double* wd, double* acc) { return negf_gless_int_dev(c, handle, ind, m, Ed, wd, acc); });
 }
 
 int negf_gr_batch(negf_ctx* c, int handle, int m, const double* E, double* G_out, int* info)
@@ -1918,14 +1975,11 @@ int negf_gr_batch(negf_ctx* c, int handle, int m, const double* E, double* G_out
     if (m > 0 && (!E || !G_out)) return NEGF_EINVAL;
     const size_t n2 = (size_t)c->n * c->n;
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
-        if ((rc = run_assemble_inverse(c, p, m0, nb, c->d_E))) return rc;
-        if ((rc = download(c, reinterpret_cast<cplx*>(G_out) + n2 * m0, c->G, n2 * nb))) return rc;
-    }
-    c->last_m = m;
-    return reduce_info(c, m, info);
+    rc = dense_batches(c, p, m, [&](int m0, int nb) {
+        if (int e = run_assemble_inverse(c, p, m0, nb, c->d_E)) return e;
+        return download(c, reinterpret_cast<cplx*>(G_out) + n2 * m0, c->G, n2 * nb);
+    });
+    return rc ? rc : reduce_info(c, m, info);      // (every batch came down as it was ready: nothing is left but the info)
 }
 
 int negf_transmission(negf_ctx* c, int handle, int contact_L, int contact_R, int spin_mode, int m,
@@ -1939,18 +1993,12 @@ int negf_transmission(negf_ctx* c, int handle, int contact_L, int contact_R, int
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     double* dT = c->d_scal;                 // [m]
     double* dTs = c->d_scal + c->m_cap;     // [m][4]
-    if ((rc = negf_transmission_dev(c, handle, contact_L, contact_R, spin_mode, m,
-                                    reinterpret_cast<double*>(c->d_E), dT, dTs))) return rc;
-    if (spin_mode == NEGF_SPIN_BLOCK) {
-        if ((rc = download(c, Tspin, dTs, (size_t)m * 4))) return rc;
-        for (int i = 0; i < m; ++i) {
-            // total = sum of the four components in order, as jnp.sum(T_spin) (transport.py:181)
-            T[i] = ((Tspin[4 * i] + Tspin[4 * i + 1]) + Tspin[4 * i + 2]) + Tspin[4 * i + 3];
-        }
-    } else {
-        if ((rc = download(c, T, dT, (size_t)m))) return rc;
-    }
-    return reduce_info(c, m, info);
+    if ((rc = negf_transmission_dev(c, handle, contact_L, contact_R, spin_mode, m, dev_E(c), dT, dTs))) return rc;
+    if (spin_mode != NEGF_SPIN_BLOCK) return fetch_pageable(c, m, {{T, dT, (size_t)m}}, info);
+    rc = fetch_pageable(c, m, {{Tspin, dTs, (size_t)m * 4}}, info);
+    // total = sum of the four components in order, as jnp.sum(T_spin) (transport.py:181)
+    for (int i = 0; rc >= 0 && i < m; ++i) T[i] = ((Tspin[4 * i] + Tspin[4 * i + 1]) + Tspin[4 * i + 2]) + Tspin[4 * i + 3];
+    return rc;
 }
 
 int negf_dos(negf_ctx* c, int handle, int m, const double* E, double* dos_total, double* dos_site,
@@ -1961,16 +2009,12 @@ int negf_dos(negf_ctx* c, int handle, int m, const double* E, double* dos_total,
     if (rc) return rc;
     if (m > 0 && (!E || !dos_total)) return NEGF_EINVAL;
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
-        if ((rc = run_assemble_inverse(c, p, m0, nb, c->d_E))) return rc;
+    rc = dense_batches(c, p, m, [&](int m0, int nb) {
+        if (int e = run_assemble_inverse(c, p, m0, nb, c->d_E)) return e;
         { ProfScope ps(c, "trace"); launch_dos(c->stream, c->n, nb, c->G, c->d_scal + m0, dos_site ? c->d_site : nullptr); }
-        if (dos_site && (rc = download(c, dos_site + (size_t)m0 * c->n, c->d_site, (size_t)nb * c->n))) return rc;
-    }
-    if ((rc = download(c, dos_total, c->d_scal, (size_t)m))) return rc;
-    c->last_m = m;
-    return reduce_info(c, m, info);
+        return dos_site ? download(c, dos_site + (size_t)m0 * c->n, c->d_site, (size_t)nb * c->n) : NEGF_OK;
+    });
+    return rc ? rc : fetch_pageable(c, m, {{dos_total, c->d_scal, (size_t)m}}, info);
 }
 
 int negf_sigma_eval(negf_ctx* c, int handle, int contact, int m, const double* E, double* sigma_out,
@@ -1983,52 +2027,39 @@ int negf_sigma_eval(negf_ctx* c, int handle, int contact, int m, const double* E
     if (m > 0 && (!E || !sigma_out)) return NEGF_EINVAL;
     const size_t n2 = (size_t)c->n * c->n;
     if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
     cplx* out = reinterpret_cast<cplx*>(sigma_out);
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
+    rc = dense_batches(c, p, m, [&](int m0, int nb) {
+        int e;
         switch (p->kind) {
         case SK_CONST: {
             const cplx* src = ct < 0 ? p->d_const_tot : p->d_const_c + n2 * ct;
             for (int b = 0; b < nb; ++b)
-                if ((rc = download(c, out + n2 * (m0 + b), src, n2))) return rc;
-            break;
+                if ((e = download(c, out + n2 * (m0 + b), src, n2))) return e;
+            return NEGF_OK;
         }
         case SK_PRECOMPUTED: {
-            const cplx* src = (ct < 0 || !p->d_pre_c) ? p->d_pre_tot + n2 * m0 : nullptr;
-            if (src) { if ((rc = download(c, out + n2 * m0, src, n2 * nb))) return rc; }
-            else {
-                const int pn = std::max(p->pre_nc, 1);
-                for (int b = 0; b < nb; ++b)
-                    if ((rc = download(c, out + n2 * (m0 + b), p->d_pre_c + n2 * ((size_t)(m0 + b) * pn + ct), n2))) return rc;
-            }
-            break;
+            if (ct < 0 || !p->d_pre_c) return download(c, out + n2 * m0, p->d_pre_tot + n2 * m0, n2 * nb);
+            const int pn = std::max(p->pre_nc, 1);
+            for (int b = 0; b < nb; ++b)
+                if ((e = download(c, out + n2 * (m0 + b), p->d_pre_c + n2 * ((size_t)(m0 + b) * pn + ct), n2))) return e;
+            return NEGF_OK;
         }
         case SK_CHAIN1D:
         case SK_BETHE: {
-            if ((rc = run_sigma_blocks(c, p, nb, c->d_E + m0, c->d_iters + (size_t)m0 * p->n_contacts,
-                                       c->d_conv + (size_t)m0 * p->n_contacts, m0))) return rc;
+            if ((e = run_sigma_blocks(c, p, nb, c->d_E + m0, c->d_iters + (size_t)m0 * p->n_contacts,
+                                      c->d_conv + (size_t)m0 * p->n_contacts, m0))) return e;
             launch_scatter_blocks(c->stream, c->n, nb, c->d_blk, p->blk_stride, p->n_contacts, p->d_nc,
                                   p->d_blk_off, p->d_inds_off, p->d_inds, ct, c->d_A);
-            cplx* res = c->d_A;
             if (p->d_xi) {
                 launch_zgemm(c->stream, c->n, c->n, c->n, nb, p->d_xi, c->n, 0, c->d_A, c->n, n2, 0, c->d_T2, c->n, n2);
                 launch_zgemm(c->stream, c->n, c->n, c->n, nb, c->d_T2, c->n, n2, p->d_xi, c->n, 0, 0, c->d_A, c->n, n2);
             }
-            if ((rc = download(c, out + n2 * m0, res, n2 * nb))) return rc;
-            break;
+            return download(c, out + n2 * m0, c->d_A, n2 * nb);
         }
         default: return NEGF_EINVAL;
         }
-    }
-    if (p->kind == SK_CHAIN1D || p->kind == SK_BETHE) {
-        if (iters && (rc = download(c, iters, c->d_iters, (size_t)m * p->n_contacts))) return rc;
-        if (converged && (rc = download(c, converged, c->d_conv, (size_t)m * p->n_contacts))) return rc;
-    } else {
-        fill_trivial_iters((size_t)m * p->n_contacts, iters, converged);
-    }
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+    });
+    return rc ? rc : fetch_iters(c, p, m, iters, converged);
 }
 
 int negf_bethe_raw(negf_ctx* c, const double* H, const double* Slist, const double* Vlist, double eta,
@@ -2062,31 +2093,153 @@ done:
     return rc;
 }
 
-// ---------------------------------------------------------------- eigenchannels
-// T(E) = sum_n T_n(E), T_n the eigenvalues of t^H t, t = Gamma_R^{1/2} G_RL Gamma_L^{1/2}.  On the contact with the
-// smaller orbital list s (L unless K_R < K_L; o the other one): Gamma_s = L L^H by pivoted Cholesky, and the T_n are
-// the eigenvalues of H = L^H B L, B = G_LR Gamma_R G_LR^H (s = L) or G_LR^H Gamma_L G_LR (s = R), G_LR = G[I_L, I_R].
-// Per energy: Z = L^H op(G_LR) (K_s x K_o), W = Z Gamma_o, H = W Z^H -- three small batched products -- and the
-// Jacobi eigenvalues of H's leading rank x rank block.
+// ---------------------------------------------------------------- eigenchannels and their scattering states
+// T(E) = sum_n T_n(E), T_n the eigenvalues of t^H t, t = Gamma_R^{1/2} G_RL Gamma_L^{1/2}.  On a contact s with orbital
+// list I_s (o the other one): Gamma_s = L L^H by pivoted Cholesky, and the T_n are the eigenvalues of H = L^H B L,
+// B = G_so Gamma_o G_so^H, G_so = G[I_s, I_o].  Per energy: Z = L^H G_so (K_s x K_o), W = Z Gamma_o, H = W Z^H -- three
+// small batched products -- and the Jacobi eigenproblem of H's leading rank x rank block.
+//   negf_transmission_channels: s = the contact with the smaller list (L unless K_R < K_L), eigenvalues only.  The block
+//     is gathered as G[I_L, I_R] either way: with s = R it enters the first product conjugate-transposed (the MIRROR form).
+//   negf_channel_states: s = the SOURCE contact always (no division by sqrt(T_n): closed channels keep well-defined
+//     states), in the mirror form (G[I_d, I_s] gathered); psi_n = G[:, I_s] L u_n with H u_n = T_n u_n.  The eigenvector
+//     kernel starts its accumulator from L, so it leaves C = L U, stored as C^H; conj(Psi) = C^H G[:, I_s]^H is one
+//     product, and the gauge pass conjugates it back while it fixes the phases.
 namespace {
 
-struct ChanPlan { int cL, cR, KL, KR, Ks, Ko; bool mirror; };
+// providers whose Gamma_c is confined to a known orbital list
+bool gamma_on_lists(const SigmaProvider* p)
+{
+    return (p->kind == SK_CONST && p->has_blocks) || ((p->kind == SK_CHAIN1D || p->kind == SK_BETHE) && !p->d_xi);
+}
 
-int chan_plan(negf_ctx* c, SigmaProvider* p, int contact_L, int contact_R, ChanPlan* pl)
+// The plan (who is s, who is o, which form) and, once chan_carve has run, the work area of the batch in c->d_chan:
+// G_so | Z | W (K_s K_o each) | H (K_s^2) | mid | L^H | tail per energy -- L^H once for a CONST provider (Gamma does not
+// depend on E: factored once per call) --, sized here, not carved out of the n x n workspace (contact lists may cover
+// more than half of the orbitals).  mid and tail are the caller's (the states' C^H and eigenvector scratch).
+struct ChanWork {
+    int cs, co, Ks, Ko;
+    bool mirror;                // G[I_o, I_s] is gathered and enters Z conjugate-transposed
+    int s_slot;                 // the slot of run_gamma_small that takes Gamma_s; Gamma_o takes the other one
+    bool constant;
+    size_t kk, ks2, lstride;
+    cplx *Gso, *Z, *W, *H, *mid, *Lh, *tail;
+};
+
+int chan_plan(negf_ctx* c, SigmaProvider* p, int contact_L, int contact_R, ChanWork* w)
 {
     if (!c || c->n <= 0) return NEGF_ESTATE;
     if (!p) return NEGF_EINVAL;
-    // providers whose Gamma_c is confined to a known orbital list
-    const bool ok = (p->kind == SK_CONST && p->has_blocks) ||
-                    ((p->kind == SK_CHAIN1D || p->kind == SK_BETHE) && !p->d_xi);
-    if (!ok) return NEGF_EINVAL;
+    if (!gamma_on_lists(p)) return NEGF_EINVAL;
     const int cL = norm_contact(p, contact_L), cR = norm_contact(p, contact_R);
     if (cL < 0 || cR < 0) return NEGF_EINVAL;                   // (the total self-energy is not a contact)
-    pl->cL = cL; pl->cR = cR; pl->KL = p->nc[cL]; pl->KR = p->nc[cR];
-    pl->mirror = pl->KR < pl->KL;
-    pl->Ks = std::min(pl->KL, pl->KR); pl->Ko = std::max(pl->KL, pl->KR);
-    if (pl->Ks > channels_kmax()) return NEGF_EINVAL;
+    w->mirror = p->nc[cR] < p->nc[cL];
+    w->s_slot = w->mirror ? 1 : 0;                              // (Gamma_L goes to slot 0, Gamma_R to slot 1)
+    w->cs = w->mirror ? cR : cL; w->co = w->mirror ? cL : cR;
+    w->Ks = p->nc[w->cs]; w->Ko = p->nc[w->co];
+    if (w->Ks > channels_kmax()) return NEGF_EINVAL;
     return NEGF_OK;
+}
+
+int state_plan(negf_ctx* c, SigmaProvider* p, int contact_src, int contact_dst, bool need_dst, ChanWork* w)
+{
+    if (!c || c->n <= 0) return NEGF_ESTATE;
+    if (!p) return NEGF_EINVAL;
+    if (!gamma_on_lists(p)) return NEGF_EINVAL;
+    const int cs = norm_contact(p, contact_src), cd = need_dst ? norm_contact(p, contact_dst) : cs;
+    if (cs < 0 || cd < 0) return NEGF_EINVAL;                   // (the total self-energy is not a contact)
+    w->cs = cs; w->co = cd; w->Ks = p->nc[cs]; w->Ko = p->nc[cd];
+    w->mirror = true; w->s_slot = 0;
+    if (w->Ks < 1 || w->Ko < 1 || w->Ks > channels_kmax()) return NEGF_EINVAL;   // (K_d is not limited)
+    return NEGF_OK;
+}
+
+int chan_carve(negf_ctx* c, SigmaProvider* p, ChanWork* w, int batch, size_t mid_per, size_t tail_per)
+{
+    w->constant = p->kind == SK_CONST;
+    w->kk = (size_t)w->Ks * w->Ko; w->ks2 = (size_t)w->Ks * w->Ks; w->lstride = w->constant ? 0 : w->ks2;
+    const size_t nl = w->constant ? 1 : (size_t)batch;          // factors L^H and their pivoted Cholesky ranks
+    int rc;
+    if ((rc = ensure_cap(c, c->d_chan, (3 * w->kk + w->ks2 + mid_per + tail_per) * batch + w->ks2 * nl)) ||
+        (rc = ensure_cap(c, c->d_chan_rank, nl))) return rc;
+    w->Gso = c->d_chan;
+    w->Z = w->Gso + w->kk * batch;
+    w->W = w->Z + w->kk * batch;
+    w->H = w->W + w->kk * batch;
+    w->mid = w->H + w->ks2 * batch;
+    w->Lh = w->mid + mid_per * batch;
+    w->tail = w->Lh + w->ks2 * nl;
+    return NEGF_OK;
+}
+
+// G of the batch [m0, m0 + nb), the two Gammas, L^H (once per call for a CONST provider), and H; *gs: Gamma_s and I_s
+int chan_build_H(negf_ctx* c, SigmaProvider* p, const ChanWork& w, int m0, int nb, const cplx* E, GammaSmall* gs)
+{
+    int rc;
+    const int n = c->n, Ks = w.Ks, Ko = w.Ko;
+    const size_t n2 = (size_t)n * n, kk = w.kk;
+    if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
+    GammaSmall g[2];
+    {
+        ProfScope ps(c, "gamma");
+        if ((rc = run_gamma_small(c, p, w.s_slot ? w.co : w.cs, nb, 0, &g[0]))) return rc;
+        if ((rc = run_gamma_small(c, p, w.s_slot ? w.cs : w.co, nb, 1, &g[1]))) return rc;
+    }
+    const GammaSmall& go = g[1 - w.s_slot];
+    *gs = g[w.s_slot];
+    if (!w.constant || m0 == 0) {
+        ProfScope ps(c, "eig");
+        if (!launch_pivoted_cholesky(c->stream, Ks, w.constant ? 1 : nb, gs->mat, gs->stride, w.Lh, w.ks2, c->d_chan_rank))
+            return NEGF_EINVAL;
+    }
+    ProfScope ps(c, "zgemm");
+    const GammaSmall& rows = w.mirror ? go : *gs;
+    const GammaSmall& cols = w.mirror ? *gs : go;
+    launch_gather_block(c->stream, n, rows.K, cols.K, nb, c->G, n2, rows.idx, cols.idx, w.Gso, kk);
+    // Z = L^H G_so: the block as it is (K_s x K_o), or gathered K_o x K_s and conjugate-transposed on the way (stored
+    // N x K, opB = 1) in the mirror form; W = Z Gamma_o; H = W Z^H
+    launch_zgemm(c->stream, Ks, Ko, Ks, nb, w.Lh, Ks, w.lstride, w.Gso, w.mirror ? Ks : Ko, kk, w.mirror ? 1 : 0, w.Z, Ko, kk);
+    launch_zgemm(c->stream, Ks, Ko, Ko, nb, w.Z, Ko, kk, go.mat, Ko, go.stride, 0, w.W, Ko, kk);
+    launch_zgemm(c->stream, Ks, Ks, Ko, nb, w.W, Ko, kk, w.Z, Ko, kk, 1, w.H, Ks, w.ks2);
+    return NEGF_OK;
+}
+
+// negf_eigvalsh_batched (V null) and negf_eigh_batched: m Hermitian K x K matrices up, w and V down
+int eigh_host(negf_ctx* c, int K, int m, const double* A, double* w, double* V, int* info)
+{
+    if (!c) return NEGF_EINVAL;
+    if (K < 1 || K > channels_kmax() || m < 0 || (m > 0 && (!A || !w))) return NEGF_EINVAL;
+    if (m == 0) return NEGF_OK;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    const size_t k2 = (size_t)K * K, xg_per = V ? eigh_scratch_elems(K) : 0;
+    cplx *dA = nullptr, *dV = nullptr, *dx = nullptr; double* dw = nullptr; int* di = nullptr;
+    std::vector<int> hi((size_t)m);
+    // (one way out: whatever fails, everything allocated so far is freed below)
+    int rc = dev_alloc(&dA, k2 * m);
+    if (!rc && V) rc = dev_alloc(&dV, k2 * m);
+    if (!rc) rc = dev_alloc(&dw, (size_t)K * m);
+    if (!rc) rc = dev_alloc(&di, (size_t)m);
+    if (!rc && xg_per) rc = dev_alloc(&dx, xg_per * m);
+    if (!rc) rc = upload(c, dA, reinterpret_cast<const cplx*>(A), k2 * m);
+    if (!rc) {
+        ProfScope ps(c, "eig");
+        JacVec v{};
+        v.xg = dx;
+        v.out = dV; v.out_stride = k2; v.out_ri = K; v.out_cj = 1; v.ncol = K;      // eigenvector j in column j
+        const bool ok = V ? launch_eigh_batched(c->stream, K, m, dA, K, k2, nullptr, 0, dw, K, K, false, di, false, 1, v)
+                          : launch_eigvalsh_batched(c->stream, K, m, dA, K, k2, nullptr, 0, dw, K, K, false, di, false, 1);
+        if (!ok) rc = NEGF_EINVAL;
+    }
+    if (!rc && hipGetLastError() != hipSuccess) rc = NEGF_EHIP;
+    if (!rc) rc = download(c, w, dw, (size_t)K * m);
+    if (!rc && V) rc = download(c, reinterpret_cast<cplx*>(V), dV, k2 * m);
+    if (!rc) rc = download(c, hi.data(), di, (size_t)m);
+    dev_free(dA); dev_free(dV); dev_free(dw); dev_free(di); dev_free(dx);
+    if (rc) return rc;
+    for (int i = 0; i < m; ++i) {
+        if (info) info[i] = hi[i];
+        if (hi[i] != 0) rc = NEGF_ESINGULAR;
+    }
+    return rc;
 }
 
 }  // namespace
@@ -2094,10 +2247,10 @@ int chan_plan(negf_ctx* c, SigmaProvider* p, int contact_L, int contact_R, ChanP
 int negf_channel_count(negf_ctx* c, int handle, int contact_L, int contact_R, int* nchan)
 {
     if (!nchan) return NEGF_EINVAL;
-    ChanPlan pl;
-    const int rc = chan_plan(c, get_provider(c, handle), contact_L, contact_R, &pl);
+    ChanWork w;
+    const int rc = chan_plan(c, get_provider(c, handle), contact_L, contact_R, &w);
     if (rc) return rc;
-    *nchan = pl.Ks;
+    *nchan = w.Ks;
     return NEGF_OK;
 }
 
@@ -2107,62 +2260,19 @@ int negf_transmission_channels_dev(negf_ctx* c, int handle, int contact_L, int c
     SigmaProvider* p;
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
-    ChanPlan pl;
-    if ((rc = chan_plan(c, p, contact_L, contact_R, &pl))) return rc;
+    ChanWork w;
+    if ((rc = chan_plan(c, p, contact_L, contact_R, &w))) return rc;
     if (nchan < 1 || !T_dev || (m > 0 && !E_dev)) return NEGF_EINVAL;
-    const int n = c->n;
-    const size_t n2 = (size_t)n * n;
-    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
-    const bool constant = p->kind == SK_CONST;
-    const int Ks = pl.Ks, Ko = pl.Ko, batch = c->batch;
-    // work area per energy: G_LR | Z | W (K_s K_o each) | H (K_s^2), then L^H: one matrix (CONST: Gamma does not
-    // depend on E, factored once per call) or one per energy -- sized here, not carved out of the n x n workspace
-    // (contact lists may cover more than half of the orbitals)
-    const size_t kk = (size_t)Ks * Ko, ks2 = (size_t)Ks * Ks, per = 3 * kk + ks2;
-    const size_t need = per * batch + ks2 * (constant ? 1 : batch);
-    const size_t need_r = constant ? 1 : (size_t)batch;      // pivoted Cholesky ranks
-    if ((rc = ensure_cap(c, c->d_chan, need)) || (rc = ensure_cap(c, c->d_chan_rank, need_r))) return rc;
-    cplx* Glr = c->d_chan;
-    cplx* Z = Glr + kk * batch;
-    cplx* W = Z + kk * batch;
-    cplx* H = W + kk * batch;
-    cplx* Lh = H + ks2 * batch;
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    for (int m0 = 0; m0 < m; m0 += batch) {
-        const int nb = std::min(batch, m - m0);
-        if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
-        GammaSmall gL, gR;
-        {
-            ProfScope ps(c, "gamma");
-            if ((rc = run_gamma_small(c, p, pl.cL, nb, 0, &gL))) return rc;
-            if ((rc = run_gamma_small(c, p, pl.cR, nb, 1, &gR))) return rc;
-        }
-        const GammaSmall& gs = pl.mirror ? gR : gL;
-        const GammaSmall& go = pl.mirror ? gL : gR;
-        const size_t lstride = constant ? 0 : ks2;
-        if (!constant || m0 == 0) {
-            ProfScope ps(c, "eig");
-            if (!launch_pivoted_cholesky(c->stream, Ks, constant ? 1 : nb, gs.mat, gs.stride, Lh, ks2, c->d_chan_rank))
-                return NEGF_EINVAL;
-        }
-        {
-            ProfScope ps(c, "zgemm");
-            launch_gather_block(c->stream, n, pl.KL, pl.KR, nb, c->G, n2, gL.idx, gR.idx, Glr, kk);
-            // Z = L^H op(G_LR): G_LR (K_L x K_R) as it is, or its conjugate transpose (stored N x K, opB = 1) in the mirror form
-            launch_zgemm(c->stream, Ks, Ko, Ks, nb, Lh, Ks, lstride, Glr, pl.mirror ? Ks : Ko, kk, pl.mirror ? 1 : 0, Z, Ko, kk);
-            launch_zgemm(c->stream, Ks, Ko, Ko, nb, Z, Ko, kk, go.mat, Ko, go.stride, 0, W, Ko, kk);
-            launch_zgemm(c->stream, Ks, Ks, Ko, nb, W, Ko, kk, Z, Ko, kk, 1, H, Ks, ks2);
-        }
+    return dense_batches(c, p, m, [&](int batch) { return chan_carve(c, p, &w, batch, 0, 0); }, [&](int m0, int nb) {
+        GammaSmall gs;
+        if (int e = chan_build_H(c, p, w, m0, nb, E, &gs)) return e;
         ProfScope ps(c, "eig");
         // (the rank of a CONST factor serves every energy: rank stride 0.  All nchan columns are written: values,
         //  zeros beyond the rank or K_s, or a whole NaN row for a singular energy)
-        if (!launch_eigvalsh_batched(c->stream, Ks, nb, H, Ks, ks2, c->d_chan_rank, constant ? 0 : 1, T_dev + (size_t)m0 * nchan, nchan,
-                                     nchan, true, c->d_info + m0, true, -1)) return NEGF_EINVAL;
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        return launch_eigvalsh_batched(c->stream, w.Ks, nb, w.H, w.Ks, w.ks2, c->d_chan_rank, w.constant ? 0 : 1,
+                                       T_dev + (size_t)m0 * nchan, nchan, nchan, true, c->d_info + m0, true, -1) ? NEGF_OK : NEGF_EINVAL;
+    });
 }
 
 int negf_transmission_channels(negf_ctx* c, int handle, int contact_L, int contact_R, int m, const double* E,
@@ -2172,78 +2282,24 @@ int negf_transmission_channels(negf_ctx* c, int handle, int contact_L, int conta
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (nchan < 1 || (m > 0 && (!E || !T_chan))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     const size_t cnt = (size_t)m * nchan;
-    if ((rc = ensure_cap(c, c->d_chan_T, cnt))) return rc;
-    if ((rc = negf_transmission_channels_dev(c, handle, contact_L, contact_R, m, reinterpret_cast<double*>(c->d_E), nchan,
-                                             c->d_chan_T))) return rc;
-    if ((rc = download(c, T_chan, c->d_chan_T.p, cnt))) return rc;
-    return reduce_info(c, m, info);
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr)) || (rc = ensure_cap(c, c->d_chan_T, cnt))) return rc;
+    if ((rc = negf_transmission_channels_dev(c, handle, contact_L, contact_R, m, dev_E(c), nchan, c->d_chan_T))) return rc;
+    return fetch_pageable(c, m, {{T_chan, c->d_chan_T.p, cnt}}, info);
 }
 
 int negf_eigvalsh_batched(negf_ctx* c, int K, int m, const double* A, double* w, int* info)
 {
-    if (!c) return NEGF_EINVAL;
-    if (K < 1 || K > channels_kmax() || m < 0 || (m > 0 && (!A || !w))) return NEGF_EINVAL;
-    if (m == 0) return NEGF_OK;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
-    const size_t k2 = (size_t)K * K;
-    cplx* dA = nullptr; double* dw = nullptr; int* di = nullptr;
-    int rc;
-    if ((rc = dev_alloc(&dA, k2 * m)) || (rc = dev_alloc(&dw, (size_t)K * m)) || (rc = dev_alloc(&di, (size_t)m))) {
-        dev_free(dA); dev_free(dw); return rc;
-    }
-    std::vector<int> hi((size_t)m);
-    rc = upload(c, dA, reinterpret_cast<const cplx*>(A), k2 * m);
-    if (!rc) {
-        ProfScope ps(c, "eig");
-        if (!launch_eigvalsh_batched(c->stream, K, m, dA, K, k2, nullptr, 0, dw, K, K, false, di, false, 1)) rc = NEGF_EINVAL;
-    }
-    if (!rc && hipGetLastError() != hipSuccess) rc = NEGF_EHIP;
-    if (!rc) rc = download(c, w, dw, (size_t)K * m);
-    if (!rc) rc = download(c, hi.data(), di, (size_t)m);
-    dev_free(dA); dev_free(dw); dev_free(di);
-    if (rc) return rc;
-    for (int i = 0; i < m; ++i) {
-        if (info) info[i] = hi[i];
-        if (hi[i] != 0) rc = NEGF_ESINGULAR;
-    }
-    return rc;
+    return eigh_host(c, K, m, A, w, nullptr, info);
 }
-
-// ------------------------------------------------------- eigenchannel scattering states
-// psi_n = G[:, I_s] L u_n with Gamma_s = L L^H (pivoted Cholesky) and H u_n = T_n u_n, H = L^H G_ds^H Gamma_d G_ds L,
-// G_ds = G[I_d, I_s]: the eigenproblem always on the SOURCE contact (no division by sqrt(T_n): closed channels keep
-// well-defined states).  H is built as the mirror form of the channels above builds it; the eigenvector kernel starts
-// its accumulator from L, so it leaves C = L U, stored as C^H; conj(Psi) = C^H G[:, I_s]^H is one product, and the
-// gauge pass conjugates it back while it fixes the phases.
-namespace {
-
-struct StatePlan { int cs, cd, Ks, Kd; };
-
-int state_plan(negf_ctx* c, SigmaProvider* p, int contact_src, int contact_dst, bool need_dst, StatePlan* pl)
-{
-    if (!c || c->n <= 0) return NEGF_ESTATE;
-    if (!p) return NEGF_EINVAL;
-    const bool ok = (p->kind == SK_CONST && p->has_blocks) ||
-                    ((p->kind == SK_CHAIN1D || p->kind == SK_BETHE) && !p->d_xi);
-    if (!ok) return NEGF_EINVAL;
-    const int cs = norm_contact(p, contact_src), cd = need_dst ? norm_contact(p, contact_dst) : cs;
-    if (cs < 0 || cd < 0) return NEGF_EINVAL;                   // (the total self-energy is not a contact)
-    pl->cs = cs; pl->cd = cd; pl->Ks = p->nc[cs]; pl->Kd = p->nc[cd];
-    if (pl->Ks < 1 || pl->Kd < 1 || pl->Ks > channels_kmax()) return NEGF_EINVAL;   // (K_d is not limited)
-    return NEGF_OK;
-}
-
-}  // namespace
 
 int negf_channel_states_count(negf_ctx* c, int handle, int contact_src, int* count)
 {
     if (!count) return NEGF_EINVAL;
-    StatePlan pl;
-    const int rc = state_plan(c, get_provider(c, handle), contact_src, 0, false, &pl);
+    ChanWork w;
+    const int rc = state_plan(c, get_provider(c, handle), contact_src, 0, false, &w);
     if (rc) return rc;
-    *count = pl.Ks;
+    *count = w.Ks;
     return NEGF_OK;
 }
 
@@ -2253,74 +2309,39 @@ int negf_channel_states_dev(negf_ctx* c, int handle, int contact_src, int contac
     SigmaProvider* p;
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
-    StatePlan pl;
-    if ((rc = state_plan(c, p, contact_src, contact_dst, true, &pl))) return rc;
+    ChanWork w;
+    if ((rc = state_plan(c, p, contact_src, contact_dst, true, &w))) return rc;
     if (nchan < 1 || !T_dev || !psi_dev || (m > 0 && !E_dev)) return NEGF_EINVAL;
-    const int n = c->n;
+    const int n = c->n, Ks = w.Ks;
     const size_t n2 = (size_t)n * n;
-    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
-    const bool constant = p->kind == SK_CONST;
-    const int Ks = pl.Ks, Kd = pl.Kd, batch = c->batch;
     const int nce = std::min(nchan, Ks);                     // channels computed; the columns beyond are zeros
-    // work area per energy: G_ds | Z | W (K_s K_d each) | H | C^H (K_s^2 each), then L^H (one for CONST, else one per
-    // energy) and the eigenvector kernel's scratch; G[:, I_s] and conj(Psi) (n K_s, nce n <= n^2) go to the free n x n
-    // work areas W2 and W1
-    const size_t kk = (size_t)Ks * Kd, ks2 = (size_t)Ks * Ks, per = 3 * kk + 2 * ks2, xg_per = eigh_scratch_elems(Ks);
-    const size_t need = per * batch + ks2 * (constant ? 1 : batch) + xg_per * batch;
-    if ((rc = ensure_cap(c, c->d_chan, need)) || (rc = ensure_cap(c, c->d_chan_rank, constant ? 1 : (size_t)batch))) return rc;
-    cplx* Gds = c->d_chan;
-    cplx* Z = Gds + kk * batch;
-    cplx* W = Z + kk * batch;
-    cplx* H = W + kk * batch;
-    cplx* Ch = H + ks2 * batch;
-    cplx* Lh = Ch + ks2 * batch;
-    cplx* xg = xg_per ? Lh + ks2 * (constant ? 1 : batch) : nullptr;
+    // behind H: C^H (K_s^2 per energy); behind L^H: the eigenvector kernel's scratch.  G[:, I_s] and conj(Psi) (n K_s,
+    // nce n <= n^2) go to the free n x n work areas W2 and W1
+    const size_t xg_per = eigh_scratch_elems(Ks);
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
     cplx* psi = reinterpret_cast<cplx*>(psi_dev);
-    for (int m0 = 0; m0 < m; m0 += batch) {
-        const int nb = std::min(batch, m - m0);
-        if ((rc = run_assemble_inverse(c, p, m0, nb, E))) return rc;
-        GammaSmall gs, gd;
-        {
-            ProfScope ps(c, "gamma");
-            if ((rc = run_gamma_small(c, p, pl.cs, nb, 0, &gs))) return rc;
-            if ((rc = run_gamma_small(c, p, pl.cd, nb, 1, &gd))) return rc;
-        }
-        const size_t lstride = constant ? 0 : ks2;
-        if (!constant || m0 == 0) {
-            ProfScope ps(c, "eig");
-            if (!launch_pivoted_cholesky(c->stream, Ks, constant ? 1 : nb, gs.mat, gs.stride, Lh, ks2, c->d_chan_rank))
-                return NEGF_EINVAL;
-        }
-        {
-            ProfScope ps(c, "zgemm");
-            launch_gather_block(c->stream, n, Kd, Ks, nb, c->G, n2, gd.idx, gs.idx, Gds, kk);
-            // Z = L^H G_ds^H (G_ds stored K_d x K_s: opB = 1), W = Z Gamma_d, H = W Z^H
-            launch_zgemm(c->stream, Ks, Kd, Ks, nb, Lh, Ks, lstride, Gds, Ks, kk, 1, Z, Kd, kk);
-            launch_zgemm(c->stream, Ks, Kd, Kd, nb, Z, Kd, kk, gd.mat, Kd, gd.stride, 0, W, Kd, kk);
-            launch_zgemm(c->stream, Ks, Ks, Kd, nb, W, Kd, kk, Z, Kd, kk, 1, H, Ks, ks2);
-        }
+    return dense_batches(c, p, m, [&](int batch) { return chan_carve(c, p, &w, batch, (size_t)Ks * Ks, xg_per); }, [&](int m0, int nb) {
+        GammaSmall gs;
+        if (int e = chan_build_H(c, p, w, m0, nb, E, &gs)) return e;
+        cplx* Ch = w.mid;
         {
             ProfScope ps(c, "eig");
             // X0 = L, read out of L^H; the sorted columns of C = L U leave as the rows of C^H (nce x K_s)
             JacVec v{};
-            v.x0 = Lh; v.x0_stride = lstride; v.x0_ri = 1; v.x0_cj = Ks; v.x0_conj = 1;
-            v.xg = xg;
-            v.out = Ch; v.out_stride = ks2; v.out_ri = 1; v.out_cj = Ks; v.out_conj = 1; v.ncol = nce;
-            if (!launch_eigh_batched(c->stream, Ks, nb, H, Ks, ks2, c->d_chan_rank, constant ? 0 : 1, T_dev + (size_t)m0 * nchan,
+            v.x0 = w.Lh; v.x0_stride = w.lstride; v.x0_ri = 1; v.x0_cj = Ks; v.x0_conj = 1;
+            v.xg = xg_per ? w.tail : nullptr;
+            v.out = Ch; v.out_stride = w.ks2; v.out_ri = 1; v.out_cj = Ks; v.out_conj = 1; v.ncol = nce;
+            if (!launch_eigh_batched(c->stream, Ks, nb, w.H, Ks, w.ks2, c->d_chan_rank, w.constant ? 0 : 1, T_dev + (size_t)m0 * nchan,
                                      nchan, nchan, true, c->d_info + m0, true, -1, v)) return NEGF_EINVAL;
         }
         ProfScope ps(c, "zgemm");
         launch_gather_block(c->stream, n, n, Ks, nb, c->G, n2, nullptr, gs.idx, c->W2, n2);
         // conj(Psi) = C^H G[:, I_s]^H (nce x n; G[:, I_s] stored n x K_s: opB = 1)
-        launch_zgemm(c->stream, nce, n, Ks, nb, Ch, Ks, ks2, c->W2, Ks, n2, 1, c->W1, n, n2);
-        launch_channel_gauge(c->stream, n, nce, nchan, nb, c->W1, n2, c->d_chan_rank, constant ? 0 : 1, c->d_info + m0,
+        launch_zgemm(c->stream, nce, n, Ks, nb, Ch, Ks, w.ks2, c->W2, Ks, n2, 1, c->W1, n, n2);
+        launch_channel_gauge(c->stream, n, nce, nchan, nb, c->W1, n2, c->d_chan_rank, w.constant ? 0 : 1, c->d_info + m0,
                              psi + (size_t)m0 * nchan * n);
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        return NEGF_OK;
+    });
 }
 
 int negf_channel_states(negf_ctx* c, int handle, int contact_src, int contact_dst, int m, const double* E, int nchan,
@@ -2330,49 +2351,18 @@ int negf_channel_states(negf_ctx* c, int handle, int contact_src, int contact_ds
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     if (nchan < 1 || (m > 0 && (!E || !T_chan || !psi))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     const size_t cnt = (size_t)m * nchan, pcnt = cnt * c->n;
-    if ((rc = ensure_cap(c, c->d_chan_T, std::max<size_t>(cnt, 1))) || (rc = ensure_cap(c, c->d_chan_psi, std::max<size_t>(pcnt, 1)))) return rc;
-    if ((rc = negf_channel_states_dev(c, handle, contact_src, contact_dst, m, reinterpret_cast<double*>(c->d_E), nchan,
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr)) || (rc = ensure_cap(c, c->d_chan_T, std::max<size_t>(cnt, 1))) ||
+        (rc = ensure_cap(c, c->d_chan_psi, std::max<size_t>(pcnt, 1)))) return rc;
+    if ((rc = negf_channel_states_dev(c, handle, contact_src, contact_dst, m, dev_E(c), nchan,
                                       c->d_chan_T, reinterpret_cast<double*>(c->d_chan_psi.p)))) return rc;
-    if ((rc = download(c, T_chan, c->d_chan_T.p, cnt))) return rc;
-    if ((rc = download(c, reinterpret_cast<cplx*>(psi), c->d_chan_psi.p, pcnt))) return rc;
-    return reduce_info(c, m, info);
+    return fetch_pageable(c, m, {{T_chan, c->d_chan_T.p, cnt}, {reinterpret_cast<cplx*>(psi), c->d_chan_psi.p, pcnt}}, info);
 }
 
 int negf_eigh_batched(negf_ctx* c, int K, int m, const double* A, double* w, double* V, int* info)
 {
-    if (!c) return NEGF_EINVAL;
-    if (K < 1 || K > channels_kmax() || m < 0 || (m > 0 && (!A || !w || !V))) return NEGF_EINVAL;
-    if (m == 0) return NEGF_OK;
-    NEGF_HIP_CHECK(hipSetDevice(c->device));
-    const size_t k2 = (size_t)K * K, xg_per = eigh_scratch_elems(K);
-    cplx *dA = nullptr, *dV = nullptr, *dx = nullptr; double* dw = nullptr; int* di = nullptr;
-    int rc;
-    if ((rc = dev_alloc(&dA, k2 * m)) || (rc = dev_alloc(&dV, k2 * m)) || (rc = dev_alloc(&dw, (size_t)K * m)) ||
-        (rc = dev_alloc(&di, (size_t)m)) || (xg_per && (rc = dev_alloc(&dx, xg_per * m)))) {
-        dev_free(dA); dev_free(dV); dev_free(dw); dev_free(di); return rc;
-    }
-    std::vector<int> hi((size_t)m);
-    rc = upload(c, dA, reinterpret_cast<const cplx*>(A), k2 * m);
-    if (!rc) {
-        ProfScope ps(c, "eig");
-        JacVec v{};
-        v.xg = dx;
-        v.out = dV; v.out_stride = k2; v.out_ri = K; v.out_cj = 1; v.ncol = K;      // eigenvector j in column j
-        if (!launch_eigh_batched(c->stream, K, m, dA, K, k2, nullptr, 0, dw, K, K, false, di, false, 1, v)) rc = NEGF_EINVAL;
-    }
-    if (!rc && hipGetLastError() != hipSuccess) rc = NEGF_EHIP;
-    if (!rc) rc = download(c, w, dw, (size_t)K * m);
-    if (!rc) rc = download(c, reinterpret_cast<cplx*>(V), dV, k2 * m);
-    if (!rc) rc = download(c, hi.data(), di, (size_t)m);
-    dev_free(dA); dev_free(dV); dev_free(dw); dev_free(di); dev_free(dx);
-    if (rc) return rc;
-    for (int i = 0; i < m; ++i) {
-        if (info) info[i] = hi[i];
-        if (hi[i] != 0) rc = NEGF_ESINGULAR;
-    }
-    return rc;
+    if (m > 0 && !V) return NEGF_EINVAL;
+    return eigh_host(c, K, m, A, w, V, info);
 }
 
 // ------------------------------------------------------- the blocked inverse's launch rule (diagnostic)
@@ -2465,19 +2455,20 @@ int bond_open(negf_ctx* c, int handle, int m, int ind, SigmaProvider** p, int* c
 }
 
 // The orbital -> group map sorted once per call: perm = the orbitals by group, ascending inside a group; goff = the
-// groups' offsets in perm.  *identity: every orbital is its own group, in order (the elementwise kernel serves it).
-int bond_stage_groups(negf_ctx* c, int n_groups, const int* group_of, bool* identity)
+// groups' offsets in perm (both on the device).  Both null: every orbital is its own group, in order (the elementwise
+// kernel serves it).
+struct BondMap { const int *perm = nullptr, *goff = nullptr; };
+int bond_stage_groups(negf_ctx* c, int n_groups, const int* group_of, BondMap* bm)
 {
     const int n = c->n;
-    *identity = true;
+    bool identity = true;
     if (!group_of) return n_groups == n ? NEGF_OK : NEGF_EINVAL;
     if (n_groups < 1 || n_groups > n) return NEGF_EINVAL;
     for (int i = 0; i < n; ++i) {
         if (group_of[i] < 0 || group_of[i] >= n_groups) return NEGF_EINVAL;
-        if (group_of[i] != i) *identity = false;
+        if (group_of[i] != i) identity = false;
     }
-    if (*identity && n_groups == n) return NEGF_OK;
-    *identity = false;
+    if (identity && n_groups == n) return NEGF_OK;
     std::vector<int> map((size_t)n + n_groups + 1, 0);
     int* perm = map.data();
     int* goff = map.data() + n;
@@ -2487,6 +2478,7 @@ int bond_stage_groups(negf_ctx* c, int n_groups, const int* group_of, bool* iden
     for (int i = 0; i < n; ++i) perm[next[group_of[i]]++] = i;
     int rc = ensure_cap(c, c->d_bond_map, map.size());
     if (rc) return rc;
+    bm->perm = c->d_bond_map; bm->goff = c->d_bond_map + n;
     return upload(c, c->d_bond_map.p, map.data(), map.size());
 }
 
@@ -2500,25 +2492,17 @@ int negf_local_transmission_dev(negf_ctx* c, int handle, int ind, int m, const d
     int rc = bond_open(c, handle, m, ind, &p, &contact);
     if (rc) return rc;
     if (m > 0 && (!E_dev || !out_dev)) return NEGF_EINVAL;
-    bool identity = true;
-    if ((rc = bond_stage_groups(c, n_groups, group_of, &identity))) return rc;
+    BondMap bm;
+    if ((rc = bond_stage_groups(c, n_groups, group_of, &bm))) return rc;
     const int n = c->n;
-    const int* perm = identity ? nullptr : c->d_bond_map;
-    const int* goff = identity ? nullptr : c->d_bond_map + n;
-    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
     const size_t tab = (size_t)n_groups * n_groups;
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
-        if ((rc = run_gless_products(c, p, contact, m0, nb, E))) return rc;
+    return dense_batches(c, p, m, [&](int m0, int nb) {
+        if (int e = run_gless_products(c, p, contact, m0, nb, E)) return e;
         ProfScope ps(c, "bond");
-        if (!launch_bond_tables(c->stream, n, nb, E + m0, c->d_S, c->d_F, c->W1, c->d_info + m0, n_groups, perm, goff,
-                                out_dev + tab * m0)) return NEGF_EINVAL;
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        return launch_bond_tables(c->stream, n, nb, E + m0, c->d_S, c->d_F, c->W1, c->d_info + m0, n_groups, bm.perm, bm.goff,
+                                  out_dev + tab * m0) ? NEGF_OK : NEGF_EINVAL;
+    });
 }
 
 int negf_local_transmission(negf_ctx* c, int handle, int ind, int m, const double* E, int n_groups, const int* group_of,
@@ -2529,13 +2513,10 @@ int negf_local_transmission(negf_ctx* c, int handle, int ind, int m, const doubl
     int rc = bond_open(c, handle, m, ind, &p, &contact);
     if (rc) return rc;
     if (n_groups < 1 || (m > 0 && (!E || !out))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     const size_t cnt = (size_t)m * n_groups * n_groups;
-    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
-    if ((rc = negf_local_transmission_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), n_groups, group_of,
-                                          c->d_bond_T))) return rc;
-    if ((rc = download(c, out, c->d_bond_T.p, cnt))) return rc;
-    return reduce_info(c, m, info);
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr)) || (rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
+    if ((rc = negf_local_transmission_dev(c, handle, ind, m, dev_E(c), n_groups, group_of, c->d_bond_T))) return rc;
+    return fetch_pageable(c, m, {{out, c->d_bond_T.p, cnt}}, info);
 }
 
 int negf_bond_int_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev, const double* w_dev, double* out_dev)
@@ -2546,22 +2527,19 @@ int negf_bond_int_dev(negf_ctx* c, int handle, int ind, int m, const double* E_d
     if (rc) return rc;
     if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
     const size_t n2 = (size_t)c->n * c->n;
-    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
-    if ((rc = ensure_cap(c, c->d_bond_carry, n2))) return rc;
-    NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, n2 * sizeof(double), c->stream));
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
-        if ((rc = run_gless_products(c, p, contact, m0, nb, E))) return rc;
+    auto setup = [&](int) {
+        if (int e = ensure_cap(c, c->d_bond_carry, n2)) return e;
+        return clear_first(c, out_dev, n2 * sizeof(double))(0);
+    };
+    return dense_batches(c, p, m, setup, [&](int m0, int nb) {
+        if (int e = run_gless_products(c, p, contact, m0, nb, E)) return e;
         ProfScope ps(c, "bond");
         // (the chunk records go where the products' temporaries were: (nb / 32 + 2) n^2 doubles of W2's 2 nb n^2)
         launch_bond_int(c->stream, (int)n2, m, m0, nb, E + m0, w_dev + m0, c->d_S, c->d_F, c->W1, c->d_bond_carry,
                         reinterpret_cast<double*>(c->W2), out_dev);
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        return NEGF_OK;
+    });
 }
 
 int negf_bond_int(negf_ctx* c, int handle, int ind, int m, const double* E, const double* w, double* out, int* info)
@@ -2571,17 +2549,10 @@ int negf_bond_int(negf_ctx* c, int handle, int ind, int m, const double* E, cons
     int rc = bond_open(c, handle, m, ind, &p, &contact);
     if (rc) return rc;
     if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
-    // the real weights ride in the [w] part of the pinned buffer and of d_w (m doubles of their m complex values)
     const size_t ob = (size_t)c->n * c->n * sizeof(double);
-    unsigned char* pw = c->h_pin + PinLayout(m, ob).w;
-    double* dw = reinterpret_cast<double*>(c->d_w);
-    if (m > 0) {
-        std::memcpy(pw, w, (size_t)m * sizeof(double));
-        NEGF_HIP_CHECK(hipMemcpyAsync(dw, pw, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    double* dout = reinterpret_cast<double*>(c->d_acc);          // n^2 doubles of its n^2 complex values
-    if ((rc = negf_bond_int_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), dw, dout))) return rc;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr)) || (rc = stage_real_weights(c, m, w, ob))) return rc;
+    double* dout = dev_acc(c);          // n^2 doubles of its n^2 complex values
+    if ((rc = negf_bond_int_dev(c, handle, ind, m, dev_E(c), dev_w(c), dout))) return rc;
     return fetch_result_and_info(c, m, dout, ob, out, info);
 }
 
@@ -2627,28 +2598,20 @@ int negf_population_dev(negf_ctx* c, int handle, int ind, int op, int rows_only,
     if (rc) return rc;
     if ((op != 0 && op != 1) || (rows_only != 0 && rows_only != 1)) return NEGF_EINVAL;
     if (m > 0 && (!E_dev || !out_dev)) return NEGF_EINVAL;
-    bool identity = true;
-    if ((rc = bond_stage_groups(c, n_groups, group_of, &identity))) return rc;
+    BondMap bm;
+    if ((rc = bond_stage_groups(c, n_groups, group_of, &bm))) return rc;
     const int n = c->n;
-    const int* perm = identity ? nullptr : c->d_bond_map;
-    const int* goff = identity ? nullptr : c->d_bond_map + n;
-    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
     const cplx* X = op == 0 ? c->d_S : c->d_F;
     const size_t per = rows_only ? (size_t)n_groups : (size_t)n_groups * n_groups;
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
+    return dense_batches(c, p, m, [&](int m0, int nb) {
         const cplx* M;
         cplx* unused;
-        if ((rc = pop_matrix(c, p, ind, contact, m0, nb, E, &M, &unused))) return rc;
+        if (int e = pop_matrix(c, p, ind, contact, m0, nb, E, &M, &unused)) return e;
         ProfScope ps(c, "pop");
-        if (!launch_population(c->stream, n, nb, ind == NEGF_IND_RETARDED, X, M, c->d_info + m0, rows_only, n_groups, perm,
-                               goff, out_dev + per * m0)) return NEGF_EINVAL;
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        return launch_population(c->stream, n, nb, ind == NEGF_IND_RETARDED, X, M, c->d_info + m0, rows_only, n_groups, bm.perm,
+                                 bm.goff, out_dev + per * m0) ? NEGF_OK : NEGF_EINVAL;
+    });
 }
 
 int negf_population(negf_ctx* c, int handle, int ind, int op, int rows_only, int m, const double* E, int n_groups,
@@ -2659,13 +2622,10 @@ int negf_population(negf_ctx* c, int handle, int ind, int op, int rows_only, int
     int rc = pop_open(c, handle, m, ind, &p, &contact);
     if (rc) return rc;
     if (n_groups < 1 || n_groups > c->n || (rows_only != 0 && rows_only != 1) || (m > 0 && (!E || !out))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     const size_t cnt = (size_t)m * n_groups * (rows_only ? 1 : n_groups);
-    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
-    if ((rc = negf_population_dev(c, handle, ind, op, rows_only, m, reinterpret_cast<double*>(c->d_E), n_groups, group_of,
-                                  c->d_bond_T))) return rc;
-    if ((rc = download(c, out, c->d_bond_T.p, cnt))) return rc;
-    return reduce_info(c, m, info);
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr)) || (rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
+    if ((rc = negf_population_dev(c, handle, ind, op, rows_only, m, dev_E(c), n_groups, group_of, c->d_bond_T))) return rc;
+    return fetch_pageable(c, m, {{out, c->d_bond_T.p, cnt}}, info);
 }
 
 int negf_projected_dos_dev(negf_ctx* c, int handle, int ind, int m, const double* E_dev, int k, const double* W_dev,
@@ -2681,23 +2641,22 @@ int negf_projected_dos_dev(negf_ctx* c, int handle, int ind, int m, const double
     const size_t nk = (size_t)n * k, n2 = (size_t)n * n;
     if ((rc = ensure_cap(c, c->d_pop_Wt, nk))) return rc;
     cplx* Wt = c->d_pop_Wt;
-    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
-    { ProfScope ps(c, "pop"); launch_pop_transpose_w(c->stream, n, k, reinterpret_cast<const cplx*>(W_dev), Wt); }
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
+    auto setup = [&](int) {
+        ProfScope ps(c, "pop");
+        launch_pop_transpose_w(c->stream, n, k, reinterpret_cast<const cplx*>(W_dev), Wt);
+        return NEGF_OK;
+    };
+    return dense_batches(c, p, m, setup, [&](int m0, int nb) {
         const cplx* M;
         cplx* Y;
-        if ((rc = pop_matrix(c, p, ind, contact, m0, nb, E, &M, &Y))) return rc;
+        if (int e = pop_matrix(c, p, ind, contact, m0, nb, E, &M, &Y)) return e;
         // Y_b = M_b Wt (n x k): Wt shared by the batch
         { ProfScope ps(c, "zgemm"); launch_zgemm(c->stream, n, k, n, nb, M, n, n2, Wt, k, 0, 0, Y, k, nk); }
         ProfScope ps(c, "pop");
         launch_pop_coldot(c->stream, n, k, nb, ind == NEGF_IND_RETARDED, Wt, Y, nk, c->d_info + m0, out_dev + (size_t)k * m0);
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        return NEGF_OK;
+    });
 }
 
 int negf_projected_dos(negf_ctx* c, int handle, int ind, int m, const double* E, int k, const double* W, double* out,
@@ -2709,15 +2668,12 @@ int negf_projected_dos(negf_ctx* c, int handle, int ind, int m, const double* E,
     if (rc) return rc;
     const int n = c->n;
     if (k < 1 || k > n || !W || (m > 0 && (!E || !out))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
     const size_t nk = (size_t)n * k, cnt = (size_t)m * k;
-    if ((rc = ensure_cap(c, c->d_pop_W, nk))) return rc;
-    if ((rc = upload(c, c->d_pop_W.p, reinterpret_cast<const cplx*>(W), nk))) return rc;
-    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
-    if ((rc = negf_projected_dos_dev(c, handle, ind, m, reinterpret_cast<double*>(c->d_E), k,
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr)) || (rc = ensure_cap(c, c->d_pop_W, nk)) ||
+        (rc = upload(c, c->d_pop_W.p, reinterpret_cast<const cplx*>(W), nk)) || (rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
+    if ((rc = negf_projected_dos_dev(c, handle, ind, m, dev_E(c), k,
                                      reinterpret_cast<const double*>(c->d_pop_W.p), c->d_bond_T))) return rc;
-    if ((rc = download(c, out, c->d_bond_T.p, cnt))) return rc;
-    return reduce_info(c, m, info);
+    return fetch_pageable(c, m, {{out, c->d_bond_T.p, cnt}}, info);
 }
 
 // ------------------------------------------------- multi-terminal transmission matrix
@@ -2735,7 +2691,8 @@ struct TmatSwap {
 };
 
 struct TmatPlan {
-    int C = 0, nc = 0;
+    int C = 0, nc = 0, n_probes = 0;
+    const cplx* psig = nullptr;                            // the caller's probe blocks (host)
     std::vector<int> K, ioff, goff, gstride, soff, order, idx;
     std::vector<int> pairs[3];                             // by tmat_pair_class
     int max_elems[3] = {0, 0, 0};
@@ -2765,11 +2722,10 @@ bool tmat_probe_before(const std::vector<int>& K, const std::vector<int>& idx, c
 int tmat_plan(negf_ctx* c, SigmaProvider* p, int n_probes, const int* probe_nk, const int* probe_inds,
               const cplx* probe_sigma, TmatPlan* pl)
 {
-    const bool ok = (p->kind == SK_CONST && p->has_blocks) || ((p->kind == SK_CHAIN1D || p->kind == SK_BETHE) && !p->d_xi);
-    if (!ok) return NEGF_EINVAL;
-    if (n_probes < 0 || (n_probes > 0 && (!probe_nk || !probe_inds || !probe_sigma))) return NEGF_EINVAL;
+    pl->n_probes = n_probes; pl->psig = probe_sigma;
+    if (!gamma_on_lists(p) || !probes_count_ok(p, n_probes)) return NEGF_EINVAL;
+    if (n_probes > 0 && (!probe_nk || !probe_inds || !probe_sigma)) return NEGF_EINVAL;
     const int n = c->n, nc = p->n_contacts;
-    if ((long)nc + n_probes > TMAT_MAX_TERMINALS) return NEGF_EINVAL;
     const int C = nc + n_probes;
     pl->C = C; pl->nc = nc; pl->per_energy = p->kind != SK_CONST;
     pl->K.resize(C); pl->ioff.resize(C); pl->goff.resize(C); pl->gstride.resize(C); pl->soff.resize(C);
@@ -2823,6 +2779,7 @@ int tmat_plan(negf_ctx* c, SigmaProvider* p, int n_probes, const int* probe_nk, 
 
 // What negf_transmission_matrix and the floating-probe calls share behind tmat_plan: the device tables, the probes added
 // to the copy of F that stands in for the original while the call runs (swap), the Gamma blocks that do not depend on E.
+// The set-up of their dense_batches: the workspace stands, so c->batch is the batch the areas are sized for.
 struct TmatRun {
     TmatPlan pl;
     size_t pair_at[3] = {0, 0, 0};
@@ -2832,14 +2789,12 @@ struct TmatRun {
     TmatSwap swap;
 };
 
-int tmat_setup(negf_ctx* c, SigmaProvider* p, int n_probes, const cplx* psig, int m, TmatRun* r)
+int tmat_setup(negf_ctx* c, SigmaProvider* p, TmatRun* r)
 {
     int rc;
     const TmatPlan& pl = r->pl;
-    const int n = c->n, C = pl.C, nc = pl.nc;
+    const int n = c->n, C = pl.C, nc = pl.nc, n_probes = pl.n_probes;
     const size_t n2 = (size_t)n * n, C2 = (size_t)C * C;
-    if ((rc = ensure_mbuffers(c, m, p->n_contacts))) return rc;
-    if ((rc = ensure_workspace(c, m, p->blk_stride))) return rc;
     const int batch = c->batch;
     // the tables: K | ioff | goff | gstride | soff | probe order | orbital lists | the pair lists of the three classes
     std::vector<int> tab;
@@ -2857,7 +2812,7 @@ int tmat_setup(negf_ctx* c, SigmaProvider* p, int n_probes, const cplx* psig, in
     r->gam = c->d_tmat_gam;
     ProfScope ps(c, "tmat");
     if (n_probes > 0) {
-        if ((rc = ensure_cap(c, c->d_tmat_sig, pl.psum)) || (rc = upload(c, c->d_tmat_sig.p, psig, pl.psum))) return rc;
+        if ((rc = ensure_cap(c, c->d_tmat_sig, pl.psum)) || (rc = upload(c, c->d_tmat_sig.p, pl.psig, pl.psum))) return rc;
         if ((rc = ensure_cap(c, c->d_tmat_H, n2))) return rc;
         cplx** base = p->kind == SK_CONST ? &p->d_hbase : &c->d_F;
         NEGF_HIP_CHECK(hipMemcpyAsync(c->d_tmat_H.p, *base, n2 * sizeof(cplx), hipMemcpyDeviceToDevice, c->stream));
@@ -2935,20 +2890,13 @@ int negf_transmission_matrix_dev(negf_ctx* c, int handle, int n_probes, const in
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     TmatRun run;
-    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
-    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &run.pl))) return rc;
+    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, reinterpret_cast<const cplx*>(probe_sigma), &run.pl))) return rc;
     if (m > 0 && (!E_dev || !T_dev)) return NEGF_EINVAL;
     if (m == 0) { c->last_m = 0; return NEGF_OK; }
-    if ((rc = tmat_setup(c, p, n_probes, psig, m, &run))) return rc;
     const size_t C2 = (size_t)run.pl.C * run.pl.C;
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
-        if ((rc = tmat_batch(c, p, run, m0, nb, E, T_dev + C2 * m0))) return rc;
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+    return dense_batches(c, p, m, [&](int) { return tmat_setup(c, p, &run); },
+                         [&](int m0, int nb) { return tmat_batch(c, p, run, m0, nb, E, T_dev + C2 * m0); });
 }
 
 int negf_transmission_matrix(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
@@ -2957,14 +2905,12 @@ int negf_transmission_matrix(negf_ctx* c, int handle, int n_probes, const int* p
     SigmaProvider* p;
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
-    if (n_probes < 0 || (long)p->n_contacts + n_probes > TMAT_MAX_TERMINALS || (m > 0 && (!E || !T))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    if (!probes_count_ok(p, n_probes) || (m > 0 && (!E || !T))) return NEGF_EINVAL;
     const size_t C = (size_t)p->n_contacts + n_probes, cnt = (size_t)m * C * C;
-    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr)) || (rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
     if ((rc = negf_transmission_matrix_dev(c, handle, n_probes, probe_nk, probe_inds, probe_sigma, m,
-                                           reinterpret_cast<double*>(c->d_E), c->d_bond_T))) return rc;
-    if ((rc = download(c, T, c->d_bond_T.p, cnt))) return rc;
-    return reduce_info(c, m, info);
+                                           dev_E(c), c->d_bond_T))) return rc;
+    return fetch_pageable(c, m, {{T, c->d_bond_T.p, cnt}}, info);
 }
 
 // ------------------------------------------------- floating dephasing probes: response, G^<, G^r
@@ -2979,22 +2925,19 @@ int negf_probe_response_dev(negf_ctx* c, int handle, int n_probes, const int* pr
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     TmatRun run;
-    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
-    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &run.pl))) return rc;
+    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, reinterpret_cast<const cplx*>(probe_sigma), &run.pl))) return rc;
     if (m > 0 && (!E_dev || (n_probes > 0 && !R_dev))) return NEGF_EINVAL;
     if (m == 0) { c->last_m = 0; return NEGF_OK; }
-    if ((rc = tmat_setup(c, p, n_probes, psig, m, &run))) return rc;
     const size_t C2 = (size_t)run.pl.C * run.pl.C, pc = (size_t)n_probes * run.pl.nc;
-    if ((rc = ensure_cap(c, c->d_deph_T, C2 * c->batch))) return rc;
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
-    for (int m0 = 0; m0 < m; m0 += c->batch) {
-        const int nb = std::min(c->batch, m - m0);
-        if ((rc = tmat_batch(c, p, run, m0, nb, E, c->d_deph_T))) return rc;
-        if ((rc = deph_run_response(c, run, nb, c->d_deph_T, R_dev + pc * m0))) return rc;
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+    auto setup = [&](int batch) {
+        if (int e = tmat_setup(c, p, &run)) return e;
+        return ensure_cap(c, c->d_deph_T, C2 * batch);
+    };
+    return dense_batches(c, p, m, setup, [&](int m0, int nb) {
+        if (int e = tmat_batch(c, p, run, m0, nb, E, c->d_deph_T)) return e;
+        return deph_run_response(c, run, nb, c->d_deph_T, R_dev + pc * m0);
+    });
 }
 
 int negf_probe_response(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
@@ -3003,14 +2946,12 @@ int negf_probe_response(negf_ctx* c, int handle, int n_probes, const int* probe_
     SigmaProvider* p;
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
-    if (n_probes < 0 || (long)p->n_contacts + n_probes > TMAT_MAX_TERMINALS || (m > 0 && (!E || (n_probes > 0 && !R)))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr))) return rc;
+    if (!probes_count_ok(p, n_probes) || (m > 0 && (!E || (n_probes > 0 && !R)))) return NEGF_EINVAL;
     const size_t cnt = (size_t)m * n_probes * p->n_contacts;
-    if ((rc = ensure_cap(c, c->d_deph_R, cnt))) return rc;
+    if ((rc = stage_grid(c, m, p->n_contacts, E, nullptr)) || (rc = ensure_cap(c, c->d_deph_R, cnt))) return rc;
     if ((rc = negf_probe_response_dev(c, handle, n_probes, probe_nk, probe_inds, probe_sigma, m,
-                                      reinterpret_cast<double*>(c->d_E), c->d_deph_R))) return rc;
-    if ((rc = download(c, R, c->d_deph_R.p, cnt))) return rc;
-    return reduce_info(c, m, info);
+                                      dev_E(c), c->d_deph_R))) return rc;
+    return fetch_pageable(c, m, {{R, c->d_deph_R.p, cnt}}, info);
 }
 
 int negf_gless_int_probes_dev(negf_ctx* c, int handle, int ind, int n_probes, const int* probe_nk, const int* probe_inds,
@@ -3021,8 +2962,7 @@ int negf_gless_int_probes_dev(negf_ctx* c, int handle, int ind, int n_probes, co
     int rc = open_call(c, handle, m, &p, ind, &contact);
     if (rc) return rc;
     TmatRun run;
-    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
-    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &run.pl))) return rc;
+    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, reinterpret_cast<const cplx*>(probe_sigma), &run.pl))) return rc;
     if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
     const int n = c->n;
     const size_t n2 = (size_t)n * n;
@@ -3032,9 +2972,8 @@ int negf_gless_int_probes_dev(negf_ctx* c, int handle, int ind, int n_probes, co
         c->last_m = 0;
         return NEGF_OK;
     }
-    if ((rc = tmat_setup(c, p, n_probes, psig, m, &run))) return rc;
     const TmatPlan& pl = run.pl;
-    const int C = pl.C, nc = pl.nc, batch = c->batch;
+    const int C = pl.C, nc = pl.nc;
     const bool floating = contact >= 0 && n_probes > 0;        // the total needs no response: every weight is 1
     // the terminals that enter D, in the order they are added: the contact(s), then the probes in content order
     std::vector<int> list;
@@ -3053,22 +2992,28 @@ int negf_gless_int_probes_dev(negf_ctx* c, int handle, int ind, int n_probes, co
     std::vector<int> tab(U);
     for (int v : pl.idx) tab.push_back(where[v]);
     tab.insert(tab.end(), list.begin(), list.end());
-    if ((rc = ensure_cap(c, c->d_deph_tab, tab.size())) || (rc = upload(c, c->d_deph_tab.p, tab.data(), tab.size()))) return rc;
-    const int* d_U = c->d_deph_tab;
-    const int* d_pos = d_U + KU;
-    const int* d_list = d_pos + pl.idx.size();
-    if (floating) {
-        if ((rc = ensure_cap(c, c->d_deph_T, (size_t)C * C * batch))) return rc;
-        if ((rc = ensure_cap(c, c->d_deph_R, (size_t)n_probes * nc * batch))) return rc;
-    }
-    if (compact && (rc = ensure_cap(c, c->d_deph_D, (size_t)KU * KU * batch))) return rc;
+    const int *d_U = nullptr, *d_pos = nullptr, *d_list = nullptr;
     const cplx* E = reinterpret_cast<const cplx*>(E_dev);
     const cplx* w = reinterpret_cast<const cplx*>(w_dev);
-    NEGF_HIP_CHECK(hipMemsetAsync(out, 0, n2 * sizeof(cplx), c->stream));
-    for (int m0 = 0; m0 < m; m0 += batch) {
-        const int nb = std::min(batch, m - m0);
-        if ((rc = tmat_batch(c, p, run, m0, nb, E, floating ? c->d_deph_T.p : nullptr))) return rc;
-        if (floating && (rc = deph_run_response(c, run, nb, c->d_deph_T, c->d_deph_R))) return rc;
+    // behind the transmission matrix's set-up: the tables, the per-batch areas of the response and of D, out cleared
+    auto setup = [&](int batch) {
+        int e;
+        if ((e = tmat_setup(c, p, &run))) return e;
+        if ((e = ensure_cap(c, c->d_deph_tab, tab.size())) || (e = upload(c, c->d_deph_tab.p, tab.data(), tab.size()))) return e;
+        d_U = c->d_deph_tab;
+        d_pos = d_U + KU;
+        d_list = d_pos + pl.idx.size();
+        if (floating) {
+            if ((e = ensure_cap(c, c->d_deph_T, (size_t)C * C * batch))) return e;
+            if ((e = ensure_cap(c, c->d_deph_R, (size_t)n_probes * nc * batch))) return e;
+        }
+        if (compact && (e = ensure_cap(c, c->d_deph_D, (size_t)KU * KU * batch))) return e;
+        return clear_first(c, out, n2 * sizeof(cplx))(batch);
+    };
+    return dense_batches(c, p, m, setup, [&](int m0, int nb) {
+        int e;
+        if ((e = tmat_batch(c, p, run, m0, nb, E, floating ? c->d_deph_T.p : nullptr))) return e;
+        if (floating && (e = deph_run_response(c, run, nb, c->d_deph_T, c->d_deph_R))) return e;
         cplx* D = compact ? c->d_deph_D.p : c->W1;
         const size_t sD = compact ? (size_t)KU * KU : n2;
         {
@@ -3076,40 +3021,19 @@ int negf_gless_int_probes_dev(negf_ctx* c, int handle, int ind, int n_probes, co
             launch_deph_coupling(c->stream, KU, nc, n_probes, floating ? contact : -1, (int)list.size(), nb, d_list, run.dK,
                                  run.d_ioff, run.d_goff, run.d_gstride, d_pos, run.gam, c->d_deph_R, D, sD);
         }
-        {
-            // G D G^H as run_gless_products takes G Gamma G^H: X = (. D)^H stored conjugate-transposed, W1 = . X (Hermitian)
-            ProfScope ps(c, "zgemm");
-            if (compact) {
-                cplx* Gc = c->W2;                              // [nb][n x K_U]
-                cplx* X = c->W2 + (size_t)n * KU;              // [nb][n x K_U]   (2 n K_U <= n^2)
-                launch_gather_block(c->stream, n, n, KU, nb, c->G, n2, nullptr, d_U, Gc, n2);
-                launch_zgemm(c->stream, n, KU, KU, nb, Gc, KU, n2, D, KU, sD, 4, X, n, n2);
-                launch_zgemm(c->stream, n, n, KU, nb, Gc, KU, n2, X, n, n2, 2, c->W1, n, n2);
-            } else {
-                launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, D, n, sD, 4, c->W2, n, n2);
-                launch_zgemm(c->stream, n, n, n, nb, c->G, n, n2, c->W2, n, n2, 2, c->W1, n, n2);
-            }
-        }
+        { ProfScope ps(c, "zgemm"); launch_g_d_gh(c, nb, KU, compact ? d_U : nullptr, D, sD); }      // as run_gless_products
         ProfScope ps(c, "accumulate");
         launch_accumulate(c->stream, (int)n2, nb, w + m0, c->W1, out, c->W2);
-    }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+        return NEGF_OK;
+    });
 }
 
 int negf_gless_int_probes(negf_ctx* c, int handle, int ind, int n_probes, const int* probe_nk, const int* probe_inds,
                           const double* probe_sigma, int m, const double* E, const double* w, double* out, int* info)
 {
-    SigmaProvider* p;
-    int rc = open_call(c, handle, m, &p);
-    if (rc) return rc;
-    if (n_probes < 0 || (long)p->n_contacts + n_probes > TMAT_MAX_TERMINALS || !out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
-    if ((rc = negf_gless_int_probes_dev(c, handle, ind, n_probes, probe_nk, probe_inds, probe_sigma, m,
-                                        reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
-                                        reinterpret_cast<double*>(c->d_acc)))) return rc;
-    return fetch_result_and_info(c, m, c->d_acc, (size_t)c->n * c->n * sizeof(cplx), out, info);
+    return host_integral(c, handle, n_probes, m, E, w, out, info, [&](double* Ed, double* wd, double* acc) {
+        return negf_gless_int_probes_dev(c, handle, ind, n_probes, probe_nk, probe_inds, probe_sigma, m, Ed, wd, acc);
+    });
 }
 
 // sum_k w_k G(E_k) with the probes in A: negf_gr_int_dev's pass while the copy of F that carries the probes stands in
@@ -3120,25 +3044,20 @@ int negf_gr_int_probes_dev(negf_ctx* c, int handle, int n_probes, const int* pro
     int rc = open_call(c, handle, m, &p);
     if (rc) return rc;
     TmatRun run;
-    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
-    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, psig, &run.pl))) return rc;
+    if ((rc = tmat_plan(c, p, n_probes, probe_nk, probe_inds, reinterpret_cast<const cplx*>(probe_sigma), &run.pl))) return rc;
     if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
-    if (m > 0 && (rc = tmat_setup(c, p, n_probes, psig, m, &run))) return rc;
+    // (negf_gr_int_dev's pass, small path included, behind the set-up of a transmission-matrix call)
+    if (m > 0 && ((rc = ensure_mbuffers(c, m, p->n_contacts)) || (rc = ensure_workspace(c, m, p->blk_stride)) ||
+                  (rc = tmat_setup(c, p, &run)))) return rc;
     return negf_gr_int_dev(c, handle, m, E_dev, w_dev, out_dev);
 }
 
 int negf_gr_int_probes(negf_ctx* c, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
                        const double* probe_sigma, int m, const double* E, const double* w, double* out, int* info)
 {
-    SigmaProvider* p;
-    int rc = open_call(c, handle, m, &p);
-    if (rc) return rc;
-    if (n_probes < 0 || (long)p->n_contacts + n_probes > TMAT_MAX_TERMINALS || !out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, p->n_contacts, E, w))) return rc;
-    if ((rc = negf_gr_int_probes_dev(c, handle, n_probes, probe_nk, probe_inds, probe_sigma, m,
-                                     reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
-                                     reinterpret_cast<double*>(c->d_acc)))) return rc;
-    return fetch_result_and_info(c, m, c->d_acc, (size_t)c->n * c->n * sizeof(cplx), out, info);
+    return host_integral(c, handle, n_probes, m, E, w, out, info, [&](double* Ed, double* wd, double* acc) {
+        return negf_gr_int_probes_dev(c, handle, n_probes, probe_nk, probe_inds, probe_sigma, m, Ed, wd, acc);
+    });
 }
 
 // ------------------------------------------------------------ g(E) cache knob

@@ -998,9 +998,7 @@ int rgf_batches(const RgfRun& r, int m, const double* E_dev, Body&& body)
             if (t->kind == 1 && (rc = run_sigma_blocks(c, t->chain, b.nb, b.E + m0, r.ls->d_iters, r.ls->d_conv, m0, t->d_blk.p))) return rc;
         if ((rc = body(b))) return rc;
     }
-    c->last_m = m;
-    NEGF_HIP_CHECK(hipGetLastError());
-    return NEGF_OK;
+    return close_call(c, m);
 }
 
 }  // namespace
@@ -1188,7 +1186,7 @@ int negf_layered_transmission(negf_ctx* c, int h, int term_a, int term_b, int m,
     if (term_a < 0 || term_a >= nt || term_b < 0 || term_b >= nt || ls->terms[term_a]->end == ls->terms[term_b]->end) return NEGF_EINVAL;
     if (m == 0) return NEGF_OK;
     if ((rc = stage_grid(c, m, 1, E, nullptr, (size_t)m * sizeof(double)))) return rc;
-    if ((rc = negf_layered_transmission_dev(c, h, term_a, term_b, m, reinterpret_cast<double*>(c->d_E), c->d_scal))) return rc;
+    if ((rc = negf_layered_transmission_dev(c, h, term_a, term_b, m, dev_E(c), c->d_scal))) return rc;
     return fetch_result_and_info(c, m, c->d_scal, (size_t)m * sizeof(double), T, info);
 }
 
@@ -1258,10 +1256,8 @@ static int rgf_host_pattern_int(negf_ctx* c, int h, const int* ind, int m, const
     if (!out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
     if (ind && !rgf_less_ind_ok(ls, *ind)) return NEGF_EINVAL;
     const size_t tot = ls->dtot + 2 * ls->utot;
-    if ((rc = stage_grid(c, m, 1, E, w, tot * sizeof(cplx)))) return rc;
-    if ((rc = ensure_cap(c, ls->d_out, tot))) return rc;
-    if ((rc = rgf_dev_pattern_int(c, h, ind, m, reinterpret_cast<double*>(c->d_E), reinterpret_cast<double*>(c->d_w),
-                                  reinterpret_cast<double*>(ls->d_out.p)))) return rc;
+    if ((rc = stage_grid(c, m, 1, E, w, tot * sizeof(cplx))) || (rc = ensure_cap(c, ls->d_out, tot))) return rc;
+    if ((rc = rgf_dev_pattern_int(c, h, ind, m, dev_E(c), dev_w(c), reinterpret_cast<double*>(ls->d_out.p)))) return rc;
     return fetch_result_and_info(c, m, ls->d_out.p, tot * sizeof(cplx), out, info);
 }
 
@@ -1284,12 +1280,9 @@ static int rgf_host_dos(negf_ctx* c, int h, int form, const int* ind, int m, con
     if ((form != 0 && form != 1) || (m > 0 && (!E || !dos_total))) return NEGF_EINVAL;
     if (ind && !rgf_less_ind_ok(ls, *ind)) return NEGF_EINVAL;
     if (m == 0) return NEGF_OK;
-    if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
-    if ((rc = ensure_cap(c, ls->d_site, (size_t)m * ls->N))) return rc;
-    if ((rc = rgf_dev_dos(c, h, form, ind, m, reinterpret_cast<double*>(c->d_E), c->d_scal, ls->d_site))) return rc;
-    if (dos_site && (rc = download(c, dos_site, ls->d_site.p, (size_t)m * ls->N))) return rc;
-    if ((rc = download(c, dos_total, c->d_scal, (size_t)m))) return rc;
-    return reduce_info(c, m, info);
+    if ((rc = stage_grid(c, m, 1, E, nullptr)) || (rc = ensure_cap(c, ls->d_site, (size_t)m * ls->N))) return rc;
+    if ((rc = rgf_dev_dos(c, h, form, ind, m, dev_E(c), c->d_scal, ls->d_site))) return rc;
+    return fetch_pageable(c, m, {{dos_site, ls->d_site.p, dos_site ? (size_t)m * ls->N : 0}, {dos_total, c->d_scal, (size_t)m}}, info);
 }
 
 int negf_layered_dos(negf_ctx* c, int h, int form, int m, const double* E, double* dos_total, double* dos_site, int* info)
@@ -1349,13 +1342,11 @@ int negf_layered_transmission_matrix(negf_ctx* c, int h, int n_probes, const int
     if (rc) return rc;
     const long Cl = (long)ls->terms.size() + n_probes;
     if (n_probes < 0 || Cl < 1 || Cl > TMAT_MAX_TERMINALS || (m > 0 && (!E || !T))) return NEGF_EINVAL;
-    if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
     const size_t C = ls->terms.size() + (size_t)n_probes, cnt = (size_t)m * C * C;
-    if ((rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
+    if ((rc = stage_grid(c, m, 1, E, nullptr)) || (rc = ensure_cap(c, c->d_bond_T, cnt))) return rc;
     if ((rc = negf_layered_transmission_matrix_dev(c, h, n_probes, probe_nk, probe_inds, probe_sigma, m,
-                                                   reinterpret_cast<double*>(c->d_E), c->d_bond_T))) return rc;
-    if ((rc = download(c, T, c->d_bond_T.p, cnt))) return rc;
-    return reduce_info(c, m, info);
+                                                   dev_E(c), c->d_bond_T))) return rc;
+    return fetch_pageable(c, m, {{T, c->d_bond_T.p, cnt}}, info);
 }
 
 // negf_layered_local_transmission_dev (w null, per-energy tables) and negf_layered_bond_int_dev: negf_local_transmission_dev
@@ -1406,14 +1397,11 @@ int negf_layered_local_transmission(negf_ctx* c, int h, int ind, int m, const do
     RgfBondGroups bg;
     if ((rc = rgf_bond_groups(ls, groups_per_layer, group_of, &bg))) return rc;
     if (m == 0) return NEGF_OK;
-    if ((rc = stage_grid(c, m, 1, E, nullptr))) return rc;
     const size_t cnt = (size_t)m * bg.table();
-    if ((rc = ensure_cap(c, ls->d_bond_out, cnt))) return rc;
-    if ((rc = rgf_dev_bond(c, h, ind, m, reinterpret_cast<double*>(c->d_E), nullptr, false, groups_per_layer, group_of,
-                           ls->d_bond_out))) return rc;
+    if ((rc = stage_grid(c, m, 1, E, nullptr)) || (rc = ensure_cap(c, ls->d_bond_out, cnt))) return rc;
+    if ((rc = rgf_dev_bond(c, h, ind, m, dev_E(c), nullptr, false, groups_per_layer, group_of, ls->d_bond_out))) return rc;
     ls->work_bytes += (long long)(cnt * sizeof(double));
-    if ((rc = download(c, out, ls->d_bond_out.p, cnt))) return rc;
-    return reduce_info(c, m, info);
+    return fetch_pageable(c, m, {{out, ls->d_bond_out.p, cnt}}, info);
 }
 
 int negf_layered_bond_int(negf_ctx* c, int h, int ind, int m, const double* E, const double* w, double* out, int* info)
@@ -1423,16 +1411,8 @@ int negf_layered_bond_int(negf_ctx* c, int h, int ind, int m, const double* E, c
     if (rc) return rc;
     if (!rgf_less_ind_ok(ls, ind) || !out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
     const size_t tot = ls->dtot + 2 * ls->utot, ob = tot * sizeof(double);
-    if ((rc = stage_grid(c, m, 1, E, nullptr, ob))) return rc;
-    // the real weights ride in the [w] part of the pinned buffer and of d_w, as negf_bond_int's do
-    unsigned char* pw = c->h_pin + PinLayout(m, ob).w;
-    double* dw = reinterpret_cast<double*>(c->d_w);
-    if (m > 0) {
-        std::memcpy(pw, w, (size_t)m * sizeof(double));
-        NEGF_HIP_CHECK(hipMemcpyAsync(dw, pw, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    if ((rc = ensure_cap(c, ls->d_bond_out, tot))) return rc;
-    if ((rc = rgf_dev_bond(c, h, ind, m, reinterpret_cast<double*>(c->d_E), dw, true, nullptr, nullptr, ls->d_bond_out))) return rc;
+    if ((rc = stage_grid(c, m, 1, E, nullptr, ob)) || (rc = stage_real_weights(c, m, w, ob)) || (rc = ensure_cap(c, ls->d_bond_out, tot))) return rc;
+    if ((rc = rgf_dev_bond(c, h, ind, m, dev_E(c), dev_w(c), true, nullptr, nullptr, ls->d_bond_out))) return rc;
     ls->work_bytes += (long long)ob;
     return fetch_result_and_info(c, m, ls->d_bond_out.p, ob, out, info);
 }
