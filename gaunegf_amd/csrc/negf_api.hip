@@ -2862,11 +2862,12 @@ int tmat_batch(negf_ctx* c, SigmaProvider* p, const TmatRun& r, int m0, int nb, 
     return NEGF_OK;
 }
 
-// R [nb][P][n_c] of the batch whose matrices are in T; the global class of the response kernel goes through in chunks
+// R [nb][P][n_c] of the batch whose matrices are in T [nb][C][C] (d_order: the probes' terminal numbers in the order of
+// the rows of W); the global class of the response kernel goes through in chunks
 // of as many energies as its work area holds
-int deph_run_response(negf_ctx* c, const TmatRun& r, int nb, const double* T, double* R)
+int deph_run_response(negf_ctx* c, int C, int nc, const int* d_order, int nb, const double* T, double* R)
 {
-    const int C = r.pl.C, nc = r.pl.nc, P = C - nc;
+    const int P = C - nc;
     if (P <= 0 || nc <= 0) return NEGF_OK;
     const size_t per = deph_response_work_doubles(P, nc);
     int chunk = nb;
@@ -2876,7 +2877,7 @@ int deph_run_response(negf_ctx* c, const TmatRun& r, int nb, const double* T, do
     }
     ProfScope ps(c, "deph");
     for (int b0 = 0; b0 < nb; b0 += chunk)
-        launch_deph_response(c->stream, C, nc, std::min(chunk, nb - b0), r.d_order, T + (size_t)b0 * C * C, c->d_deph_work,
+        launch_deph_response(c->stream, C, nc, std::min(chunk, nb - b0), d_order, T + (size_t)b0 * C * C, c->d_deph_work,
                              R + (size_t)b0 * P * nc);
     return NEGF_OK;
 }
@@ -2936,7 +2937,7 @@ int negf_probe_response_dev(negf_ctx* c, int handle, int n_probes, const int* pr
     };
     return dense_batches(c, p, m, setup, [&](int m0, int nb) {
         if (int e = tmat_batch(c, p, run, m0, nb, E, c->d_deph_T)) return e;
-        return deph_run_response(c, run, nb, c->d_deph_T, R_dev + pc * m0);
+        return deph_run_response(c, run.pl.C, run.pl.nc, run.d_order, nb, c->d_deph_T, R_dev + pc * m0);
     });
 }
 
@@ -3013,7 +3014,7 @@ int negf_gless_int_probes_dev(negf_ctx* c, int handle, int ind, int n_probes, co
     return dense_batches(c, p, m, setup, [&](int m0, int nb) {
         int e;
         if ((e = tmat_batch(c, p, run, m0, nb, E, floating ? c->d_deph_T.p : nullptr))) return e;
-        if (floating && (e = deph_run_response(c, run, nb, c->d_deph_T, c->d_deph_R))) return e;
+        if (floating && (e = deph_run_response(c, C, nc, run.d_order, nb, c->d_deph_T, c->d_deph_R))) return e;
         cplx* D = compact ? c->d_deph_D.p : c->W1;
         const size_t sD = compact ? (size_t)KU * KU : n2;
         {

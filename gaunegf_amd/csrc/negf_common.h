@@ -672,6 +672,21 @@ void launch_rgf_strip_pairs(hipStream_t st, int cls, int C, int npairs, int max_
                             const int* tK, const int* ioff, const int* goff, const int* gstride, const int* tcol, int col0,
                             const int* rows, const int* cpos, const cplx* strip, int ld, size_t strideS, const cplx* gstat,
                             const cplx* gdyn, double* T);
+// Floating probes on a layered device (k_rgf_deph.hip; negf_layered_gless_int_probes).  D[b] = the blocks D_q (nJ[q] x nJ[q]
+// at Doff[q]) of the dephased coupling, one workgroup per (layer, energy): the end terminals sel[0 .. nsel) that sit on the
+// layer, then its probes porder[poff[q] .. poff[q + 1]) weighted with R[b][p][col] (col < 0: every weight 1), through cpos
+void launch_rgf_deph_coupling(hipStream_t st, int L, int nb, int nt, int P, int col, int nsel, const int* sel,
+                              const int* tlayer, const int* porder, const int* poff, const int* nJ, const int* Doff,
+                              const int* tK, const int* ioff, const int* goff, const int* gstride, const int* cpos,
+                              const cplx* gstat, const cplx* gdyn, const double* R, cplx* D, size_t strideD);
+// Y_i[b] = Cfull_i[b] blockdiag(D_q[b]) for all layers, column blocks and energies in one launch; Cfull and Y [L][nb_max][cs],
+// n_i x Ktot each; ctile [nct][2]: (q, first column inside J_q) of every column tile (rgf_blockdiag_tile_cols() wide)
+int rgf_blockdiag_row_tiles(int nmax);
+int rgf_blockdiag_col_tiles(int KJ);
+int rgf_blockdiag_tile_cols();
+void launch_rgf_blockdiag_mm(hipStream_t st, int L, int nmax, int nct, int Ktot, int nb, int nb_max, size_t cs,
+                             const int* nl, const int* nJ, const int* Joff, const int* Doff, const int* ctile,
+                             const cplx* Cfull, const cplx* D, size_t strideD, cplx* Y);
 
 bool small_fused_supported(int n);
 int small_fused_grid(int n, int m);

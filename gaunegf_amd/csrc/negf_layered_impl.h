@@ -28,7 +28,8 @@
 // The recursion stands once.  rgf_factor_sweep keeps every g_i in d_gstore and takes two callables, run before and after
 // the inverse of a level (the strips' probes; the columns' x / z chain); rgf_solve_sweep hands each level as it stands
 // (RgfLevel) to a visitor: the block visitors RgfSumBlocks / RgfDosBlocks / RgfBondBlocks (the last one behind the
-// column visitor only), the column visitor RgfColumns, the strip visitor RgfStrips.  Only a block visitor has G_{i+1,i} formed.  rgf_corner_sweep shares the level (rgf_factor_level) but
+// column visitor only), the column visitor RgfColumns, the strip visitors RgfStrips (two alternating strips) and RgfKeptStrips
+// (the strips of all layers kept, for the floating-probe calls), which share rgf_strip_level.  Only a block visitor has G_{i+1,i} formed.  rgf_corner_sweep shares the level (rgf_factor_level) but
 // not the loop: it alone lets g_{i-2} go.  All of them walk the levels of an RgfView, which the strips' second pass reverses.
 // The ten work areas have names (RgfAreas says who writes each, and when); the two places that lend one out say so:
 // rgf_corner_sweep and RgfColumns::level.  Every device-resident call is its checks, its work areas, then rgf_batches.
@@ -66,6 +67,9 @@ struct LayeredSystem {
     DevBuf<double> d_site;                      // dos: [m][N] staging of the host-pointer entry point
     DevBuf<int> d_tm_tab;                       // transmission matrix: the terminal tables, union lists and pair lists
     DevBuf<cplx> d_tm_sig, d_tm_gam;            // ... the probes' Sigma blocks; the Gamma blocks that do not depend on E
+    DevBuf<int> d_deph_tab;                     // floating probes: the tables of the coupling and block-diagonal kernels
+    DevBuf<double> d_deph_T, d_deph_R;          // ... [batch][C*C] matrices and [batch][P][n_t] responses of the batch in flight
+    DevBuf<double> d_deph_out;                  // ... [m][P][n_t] staging of the host-pointer response
     DevBuf<int> d_bond_map;                     // bond tables: perm [N] (layer by layer) | goff [sum (g_i + 1)] of the call's groups
     DevBuf<double> d_bond_out;                  // ... the staging of the host-pointer entry points
     DevBuf<int> d_piv, d_linfo, d_iters, d_conv;
@@ -94,6 +98,8 @@ void free_layered(LayeredSystem* ls)
     release_bufs(ls->d_J, ls->d_tm_tab, ls->d_bond_map);
     release_bufs(ls->d_bond_out);
     release_bufs(ls->d_tm_sig, ls->d_tm_gam);
+    release_bufs(ls->d_deph_tab);
+    release_bufs(ls->d_deph_T, ls->d_deph_R, ls->d_deph_out);
     release_bufs(ls->d_piv, ls->d_linfo, ls->d_iters, ls->d_conv);
     delete ls;
 }
@@ -769,6 +775,10 @@ struct RgfTmatPlan {
     // work areas of the batch in flight
     size_t cs = 0, per_energy = 0;
     cplx *strip[2] = {nullptr, nullptr}, *gdyn = nullptr, *Gab = nullptr, *Xs = nullptr, *Ys = nullptr;
+    // where a visitor finds the columns of terminal b in the strip of a pass, and the strip's first column
+    struct Cols { const int* d_tcol; const std::vector<int>* tcol; int col0; };
+    Cols alternating(int pass, int layer) const { return Cols{d_tcol[pass], &tcol[pass], colbase[pass][layer]}; }
+    Cols kept() const { return Cols{d_tcol[0], &tcol[0], 0}; }           // a kept strip has all K_tot columns, ascending in q
 };
 
 // validation and the host tables; NEGF_EINVAL before anything is launched
@@ -906,18 +916,19 @@ int rgf_tmat_setup(negf_ctx* c, LayeredSystem* ls, const cplx* psig, RgfTmatPlan
     return NEGF_OK;
 }
 
-// the pairs of view level i of a pass, read from the level's strip (n x ld)
-void rgf_tmat_pairs(negf_ctx* c, LayeredSystem* ls, const RgfTmatPlan& pl, int pass, int i, int nb, const cplx* strip, int ld, double* T)
+// the pairs of view level i of a pass, read from the level's strip (n x ld) whose columns `at` describes
+void rgf_tmat_pairs(negf_ctx* c, LayeredSystem* ls, const RgfTmatPlan& pl, int pass, int i, int nb, const cplx* strip, int ld,
+                    const RgfTmatPlan::Cols& at, double* T)
 {
-    const int L = ls->L, C = pl.C, p = pass ? L - 1 - i : i;
-    const int col0 = pl.colbase[pass][p];
+    const int L = ls->L, C = pl.C;
+    const int col0 = at.col0;
     const size_t k0 = ((size_t)pass * L + i) * 3;
     if (pl.pair_n[k0] + pl.pair_n[k0 + 1] + pl.pair_n[k0 + 2] == 0) return;
     ProfScope ps(c, "tmat");
     double cmadds = 0;
     for (int cls = 1; cls <= 2; ++cls) {
         launch_rgf_strip_pairs(c->stream, cls, C, pl.pair_n[k0 + cls], pl.max_elems[cls], nb, pl.d_pairs + pl.pair_at[k0 + cls],
-                               pl.dK, pl.d_ioff, pl.d_goff, pl.d_gstride, pl.d_tcol[pass], col0, pl.d_rows, pl.d_cpos, strip, ld,
+                               pl.dK, pl.d_ioff, pl.d_goff, pl.d_gstride, at.d_tcol, col0, pl.d_rows, pl.d_cpos, strip, ld,
                                pl.cs, ls->d_tm_gam, pl.gdyn, T);
         for (int q = 0; q < pl.pair_n[k0 + cls]; ++q) {
             const int pr = pl.pairs[pl.pair_at[k0 + cls] + q];
@@ -933,7 +944,7 @@ void rgf_tmat_pairs(negf_ctx* c, LayeredSystem* ls, const RgfTmatPlan& pl, int p
         const size_t kk = (size_t)Ka * Kb;
         const cplx* ga = pl.gstride[a] ? pl.gdyn + pl.goff[a] : ls->d_tm_gam + pl.goff[a];
         const cplx* gb = pl.gstride[b] ? pl.gdyn + pl.goff[b] : ls->d_tm_gam + pl.goff[b];
-        launch_gather_block(c->stream, ld, Ka, Kb, nb, strip + (pl.tcol[pass][b] - col0), pl.cs, pl.d_rows + pl.ioff[a],
+        launch_gather_block(c->stream, ld, Ka, Kb, nb, strip + ((*at.tcol)[b] - col0), pl.cs, pl.d_rows + pl.ioff[a],
                             pl.d_cpos + pl.ioff[b], pl.Gab, kk);
         launch_zgemm(c->stream, Ka, Kb, Ka, nb, ga, Ka, (size_t)pl.gstride[a], pl.Gab, Kb, kk, 0, pl.Xs, Kb, kk);
         launch_zgemm(c->stream, Ka, Kb, Kb, nb, pl.Xs, Kb, kk, gb, Kb, (size_t)pl.gstride[b], 0, pl.Ys, Kb, kk);
@@ -941,8 +952,26 @@ void rgf_tmat_pairs(negf_ctx* c, LayeredSystem* ls, const RgfTmatPlan& pl, int p
     }
 }
 
-// The strip visitor: strip_i = [G_ii[:, J_i] | U_i strip_{i+1}] in one of the two alternating strip areas, then the pairs
-// of the level read from it
+// The level code of the strip visitors.  The strip of view level i (n_i rows at the leading dimension ld, batch stride
+// pl.cs) is the columns J of its own layer cut from G_ii -- the head, nhead columns from column `head` on -- and
+// U_i times wtail columns of the strip of level i + 1 (src, leading dimension src_ld) from column `tail` on.
+void rgf_strip_level(const RgfBatch& b, const RgfView& v, const RgfTmatPlan& pl, const RgfLevel& lv, cplx* dst, int ld, int head,
+                     int nhead, int tail, const cplx* src, int src_ld, int wtail)
+{
+    const int i = lv.i, ni = v.n(i);
+    if (wtail > 0) {
+        const int nn = v.n(i + 1);
+        ProfScope ps(b.c, "zgemm");
+        launch_zgemm(b.c->stream, ni, wtail, nn, b.nb, lv.U, nn, b.ls->stride, src, src_ld, pl.cs, 0, dst + tail, ld, pl.cs);
+    }
+    if (nhead > 0) {
+        ProfScope ps(b.c, "rgf");
+        launch_rgf_strip_head(b.c->stream, ni, nhead, ld, b.nb, lv.Gii, b.ls->stride, pl.d_J + pl.Joff[v.layer(i)], dst + head, pl.cs);
+    }
+}
+
+// The strip visitor of the transmission matrix: strip_i = [G_ii[:, J_i] | U_i strip_{i+1}] in one of the two alternating
+// strip areas, then the pairs of the level read from it; the strip of level i + 1 is dropped
 struct RgfStrips {
     static constexpr bool wants_lower = false;
     const RgfView& v;
@@ -952,36 +981,94 @@ struct RgfStrips {
     int wnext = 0;                                                     // width of the strip of level i + 1
     void level(const RgfBatch& b, const RgfLevel& lv)
     {
-        const int i = lv.i, p = v.layer(i), ni = v.n(i), nj = pl.nJ[p], w = nj + wnext;
-        if (wnext > 0) {
-            const int nn = v.n(i + 1);
-            ProfScope ps(b.c, "zgemm");                                // U_i strip_{i+1} behind the head of strip_i
-            launch_zgemm(b.c->stream, ni, wnext, nn, b.nb, lv.U, nn, b.ls->stride, Snext, wnext, pl.cs, 0, Scur + nj, w, pl.cs);
-        }
-        if (nj > 0) {
-            ProfScope ps(b.c, "rgf");
-            launch_rgf_strip_head(b.c->stream, ni, nj, w, b.nb, lv.Gii, b.ls->stride, pl.d_J + pl.Joff[p], Scur, pl.cs);
-        }
-        rgf_tmat_pairs(b.c, b.ls, pl, v.reversed, i, b.nb, Scur, w, T);
+        const int i = lv.i, p = v.layer(i), nj = pl.nJ[p], w = nj + wnext;
+        rgf_strip_level(b, v, pl, lv, Scur, w, 0, nj, nj, Snext, wnext, wnext);
+        rgf_tmat_pairs(b.c, b.ls, pl, v.reversed, i, b.nb, Scur, w, pl.alternating(v.reversed, p), T);
         std::swap(Scur, Snext);
         wnext = w;
     }
 };
 
-// One pass of a batch, the pairs (a, b) with b on a's level or a later one of the view: factor sweep with the probes of
-// each level's layer taken out of its diagonal before the inverse, solve sweep with the strips
-int rgf_tmat_pass(const RgfBatch& b, const RgfTmatPlan& pl, bool reversed, double* T)
+// The strip visitor of the floating-probe calls, which need the strips of ALL layers once D is known: layer p's strip lives
+// in keep [L][nb_max][cs] as the n_p x K_tot matrix Cfull_p = [G_{p,q}[:, J_q]]_q with the column blocks in ascending q (J_q
+// at column Joff[q]).  The pass over the layers as they are writes the blocks q >= p -- the head and U_p times the same
+// columns of Cfull_{p+1} --, the reversed pass, which runs second, the blocks q < p as U_p times those columns of
+// Cfull_{p-1}: the same-layer block stays the first pass's, as the pairs of one layer are.  T null: no pairs (the total).
+struct RgfKeptStrips {
+    static constexpr bool wants_lower = false;
+    const RgfView& v;
+    const RgfTmatPlan& pl;
+    double* T;
+    cplx* keep;
+    cplx* at(const RgfBatch& b, int layer) const { return keep + (size_t)layer * b.nb_max * pl.cs; }
+    void level(const RgfBatch& b, const RgfLevel& lv)
+    {
+        const int i = lv.i, p = v.layer(i), L = b.ls->L, Kt = pl.Ktot;
+        cplx* dst = at(b, p);
+        if (!v.reversed) {
+            const int tail = pl.Joff[p] + pl.nJ[p];
+            rgf_strip_level(b, v, pl, lv, dst, Kt, pl.Joff[p], pl.nJ[p], tail, p + 1 < L ? at(b, p + 1) + tail : nullptr, Kt,
+                            p + 1 < L ? Kt - tail : 0);
+        } else {
+            rgf_strip_level(b, v, pl, lv, dst, Kt, 0, 0, 0, p > 0 ? at(b, p - 1) : nullptr, Kt, p > 0 ? pl.Joff[p] : 0);
+        }
+        if (T) rgf_tmat_pairs(b.c, b.ls, pl, v.reversed, i, b.nb, dst, Kt, pl.kept(), T);
+    }
+};
+
+// the probes of a level's layer taken out of its diagonal before the inverse: the `before` step of a factor sweep
+auto rgf_sub_probes_step(const RgfBatch& b, const RgfView& v, const RgfTmatPlan& pl)
 {
-    const RgfView v{b.ls, reversed};
-    auto sub_probes = [&](int i, cplx* D) {
+    return [&b, v, &pl](int i, cplx* D) {
         const int p = v.layer(i), np = pl.poff[p + 1] - pl.poff[p];
         if (np == 0) return;
         ProfScope ps(b.c, "rgf");
         launch_rgf_sub_probes(b.c->stream, v.n(i), np, b.nb, pl.d_porder + pl.poff[p], pl.dK, pl.d_ioff, pl.d_soff, pl.d_rows,
                               b.ls->d_tm_sig, D, b.ls->stride);
     };
-    int rc = rgf_factor_sweep(b, v, sub_probes, rgf_no_step);
-    return rc ? rc : rgf_solve_sweep(b, v, RgfStrips{v, pl, T, pl.strip[0], pl.strip[1]});
+}
+
+// One pass of a batch: factor sweep with the probes in the diagonal, solve sweep with a strip visitor -- the pairs (a, b)
+// with b on a's level or a later one of the view
+template <class Strips>
+int rgf_tmat_pass(const RgfBatch& b, const RgfTmatPlan& pl, const RgfView& v, Strips&& strips)
+{
+    int rc = rgf_factor_sweep(b, v, rgf_sub_probes_step(b, v, pl), rgf_no_step);
+    return rc ? rc : rgf_solve_sweep(b, v, strips);
+}
+
+// The Gamma blocks that depend on E, of the batch
+void rgf_tmat_gamma_dyn(const RgfBatch& b, const RgfTmatPlan& pl)
+{
+    ProfScope ps(b.c, "tmat");
+    for (int t = 0; t < pl.nt; ++t) {
+        if (b.ls->terms[t]->kind == 0) continue;
+        const cplx* sig; size_t st;
+        rgf_sigma_of(b.ls->terms[t], b.m0, &sig, &st);
+        launch_rgf_gamma(b.c->stream, pl.K[t], b.nb, sig, st, pl.gdyn + pl.goff[t], pl.dyn);
+    }
+}
+
+// T [nb][C][C] of one batch of a transmission-matrix call: the two passes with alternating strips, NaN for singular energies
+int rgf_tmat_batch(const RgfBatch& b, const RgfTmatPlan& pl, double* T)
+{
+    rgf_tmat_gamma_dyn(b, pl);
+    for (int pass = 0; pass < (pl.two_pass ? 2 : 1); ++pass) {
+        const RgfView v{b.ls, pass == 1};
+        if (int e = rgf_tmat_pass(b, pl, v, RgfStrips{v, pl, T, pl.strip[0], pl.strip[1]})) return e;
+    }
+    ProfScope ps(b.c, "tmat");
+    launch_tmat_nan(b.c->stream, pl.C, b.nb, b.c->d_info + b.m0, T);
+    return NEGF_OK;
+}
+
+// work areas of a transmission-matrix batch, out of d_cols
+void rgf_tmat_layout(const RgfRun& r, RgfTmatPlan* pl, RgfCarve* cols)
+{
+    const size_t nbm = (size_t)r.nb_max;
+    pl->strip[0] = cols->take(pl->cs * nbm); pl->strip[1] = cols->take(pl->cs * nbm);
+    pl->gdyn = cols->take(pl->dyn * nbm);
+    pl->Gab = cols->take(pl->big_kk * nbm); pl->Xs = cols->take(pl->big_kk * nbm); pl->Ys = cols->take(pl->big_kk * nbm);
 }
 
 // The batches of a device-resident call, once its work areas stand: per batch its info cleared and the Sigma blocks of
@@ -999,6 +1086,116 @@ int rgf_batches(const RgfRun& r, int m, const double* E_dev, Body&& body)
         if ((rc = body(b))) return rc;
     }
     return close_call(c, m);
+}
+
+// ------------------------------------------------- floating probes on layers: G D G^H on the pattern of S
+// What negf_layered_gless_int_probes adds to the plan of a transmission-matrix call.  D_s = scatter(Gamma_s) + sum_p R_ps
+// scatter(Gamma_p) is block diagonal over the layers (every terminal lives in one): D_q on J_q, the blocks one after the
+// other per energy.  R needs the whole T, hence both passes, before D exists: the strips of ALL layers are kept
+// (RgfKeptStrips), then Y_i = Cfull_i blockdiag(D_q) in one launch, A_ii = Y_i Cfull_i^H, A_{i,i+1} = Y_i Cfull_{i+1}^H.
+struct RgfDephPlan {
+    int contact = -1;                                                   // the column of R; -1: the total, every weight 1
+    bool floating = false;                                              // a contact and probes: T and R are needed
+    std::vector<int> sel;                                               // the end terminals that enter D, in the order they were made
+    size_t Dtot = 0, per_energy = 0;
+    int nct = 0;                                                        // column tiles of the block-diagonal product
+    const int *d_sel = nullptr, *d_tlayer = nullptr, *d_poff = nullptr, *d_nl = nullptr, *d_nJ = nullptr, *d_Joff = nullptr,
+              *d_Doff = nullptr, *d_ctile = nullptr;
+    std::vector<int> tab;
+    size_t at[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    cplx *keep = nullptr, *Y = nullptr, *D = nullptr;                   // [L][batch][cs] twice, [batch][Dtot]
+    double *T = nullptr, *R = nullptr;
+};
+
+// the host tables; NEGF_EINVAL (sizes beyond what one launch of the block-diagonal product indexes) before anything is launched
+int rgf_deph_plan(const LayeredSystem* ls, const RgfTmatPlan& pl, int ind, RgfDephPlan* dp)
+{
+    const int L = ls->L, nt = pl.nt;
+    dp->contact = ind == NEGF_IND_TOTAL ? -1 : (ind < 0 ? ind + nt : ind);
+    dp->floating = dp->contact >= 0 && pl.n_probes > 0;
+    for (int t = 0; t < nt; ++t) if (dp->contact < 0 || t == dp->contact) dp->sel.push_back(t);
+    std::vector<int> Doff(L, 0), ctile;
+    const int tj = rgf_blockdiag_tile_cols();
+    size_t dtot = 0;
+    for (int q = 0; q < L; ++q) {
+        Doff[q] = (int)dtot;
+        dtot += (size_t)pl.nJ[q] * pl.nJ[q];
+        if (dtot > ((size_t)1 << 30)) return NEGF_EINVAL;
+        for (int t = 0; t < rgf_blockdiag_col_tiles(pl.nJ[q]); ++t) { ctile.push_back(q); ctile.push_back(t * tj); }
+    }
+    dp->Dtot = dtot;
+    dp->nct = (int)(ctile.size() / 2);
+    if ((double)L * rgf_blockdiag_row_tiles(ls->nmax) * dp->nct > 2.0e9) return NEGF_EINVAL;
+    int k = 0;
+    const std::vector<int>* const parts[8] = {&dp->sel, &pl.layer, &pl.poff, &ls->n, &pl.nJ, &pl.Joff, &Doff, &ctile};
+    for (const std::vector<int>* v : parts) {
+        dp->at[k++] = dp->tab.size();
+        dp->tab.insert(dp->tab.end(), v->begin(), v->end());
+    }
+    // per energy in flight: the kept strips and Y of all layers, the Gamma blocks that depend on E, G_ab | X | Y of the
+    // class-0 pairs, D
+    dp->per_energy = 2 * (size_t)L * pl.cs + pl.dyn + 3 * pl.big_kk + dtot;
+    return NEGF_OK;
+}
+
+int rgf_deph_setup(negf_ctx* c, LayeredSystem* ls, const RgfTmatPlan& pl, const RgfRun& r, RgfDephPlan* dp)
+{
+    int rc;
+    if ((rc = ensure_cap(c, ls->d_deph_tab, dp->tab.size() + 1)) || (rc = upload(c, ls->d_deph_tab.p, dp->tab.data(), dp->tab.size()))) return rc;
+    const int* d = ls->d_deph_tab;
+    dp->d_sel = d + dp->at[0]; dp->d_tlayer = d + dp->at[1]; dp->d_poff = d + dp->at[2]; dp->d_nl = d + dp->at[3];
+    dp->d_nJ = d + dp->at[4]; dp->d_Joff = d + dp->at[5]; dp->d_Doff = d + dp->at[6]; dp->d_ctile = d + dp->at[7];
+    const size_t nbm = (size_t)r.nb_max;
+    if (dp->floating) {
+        if ((rc = ensure_cap(c, ls->d_deph_T, (size_t)pl.C * pl.C * nbm)) ||
+            (rc = ensure_cap(c, ls->d_deph_R, (size_t)pl.n_probes * pl.nt * nbm))) return rc;
+        dp->T = ls->d_deph_T; dp->R = ls->d_deph_R;
+    }
+    return NEGF_OK;
+}
+
+// One batch: both passes with the strips kept (the pairs into T only when R is needed), R, D, Y, then layer by layer the
+// blocks A_ii (a Hermitian product: D is exactly Hermitian) and A_{i,i+1} to the block visitor's less(), as RgfColumns hands them on
+template <class Blocks>
+int rgf_deph_batch(const RgfBatch& b, const RgfTmatPlan& pl, const RgfDephPlan& dp, const Blocks& sink)
+{
+    negf_ctx* c = b.c;
+    const LayeredSystem* ls = b.ls;
+    const int L = ls->L, Kt = pl.Ktot, nb = b.nb;
+    rgf_tmat_gamma_dyn(b, pl);
+    double* T = dp.floating ? dp.T : nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        const RgfView v{ls, pass == 1};
+        if (int e = rgf_tmat_pass(b, pl, v, RgfKeptStrips{v, pl, T, dp.keep})) return e;
+    }
+    if (dp.floating) {
+        { ProfScope ps(c, "tmat"); launch_tmat_nan(c->stream, pl.C, nb, c->d_info + b.m0, T); }
+        if (int e = deph_run_response(c, pl.C, pl.nt, pl.d_porder, nb, T, dp.R)) return e;
+    }
+    {
+        ProfScope ps(c, "deph");
+        launch_rgf_deph_coupling(c->stream, L, nb, pl.nt, pl.n_probes, dp.floating ? dp.contact : -1, (int)dp.sel.size(), dp.d_sel,
+                                 dp.d_tlayer, pl.d_porder, dp.d_poff, dp.d_nJ, dp.d_Doff, pl.dK, pl.d_ioff, pl.d_goff,
+                                 pl.d_gstride, pl.d_cpos, ls->d_tm_gam, pl.gdyn, dp.R, dp.D, dp.Dtot);
+        launch_rgf_blockdiag_mm(c->stream, L, ls->nmax, dp.nct, Kt, nb, b.nb_max, pl.cs, dp.d_nl, dp.d_nJ, dp.d_Joff, dp.d_Doff,
+                                dp.d_ctile, dp.keep, dp.D, dp.Dtot, dp.Y);
+        double kk = 0;
+        for (int q = 0; q < L; ++q) kk += (double)pl.nJ[q] * pl.nJ[q];
+        negf_count_flops(8.0 * (double)ls->N * kk * nb, 0.0);
+    }
+    const size_t s = ls->stride, lay = (size_t)b.nb_max * pl.cs;
+    for (int i = L - 1; i >= 0; --i) {
+        const int ni = ls->n[i];
+        const cplx *Yi = dp.Y + lay * i, *Ci = dp.keep + lay * i;
+        { ProfScope ps(c, "zgemm"); launch_zgemm(c->stream, ni, ni, Kt, nb, Yi, Kt, pl.cs, Ci, Kt, pl.cs, 3, b.a.Gup, ni, s); }
+        sink.less(b, i, b.a.Gup, false);
+        if (i + 1 == L) continue;
+        const int nn = ls->n[i + 1];
+        { ProfScope ps(c, "zgemm"); launch_zgemm(c->stream, ni, nn, Kt, nb, Yi, Kt, pl.cs, Ci + lay, Kt, pl.cs, 1, b.a.Glo, nn, s); }
+        sink.less(b, i, b.a.Glo, true);
+    }
+    NEGF_HIP_CHECK(hipGetLastError());
+    return NEGF_OK;
 }
 
 }  // namespace
@@ -1310,28 +1507,10 @@ int negf_layered_transmission_matrix_dev(negf_ctx* c, int h, int n_probes, const
     if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, true, &r, pl.per_energy))) return rc;
     ls->work_bytes += 16LL * (long long)pl.stat;
     if ((rc = rgf_tmat_setup(c, ls, psig, &pl))) return rc;
-    const size_t nbm = (size_t)r.nb_max, C2 = (size_t)pl.C * pl.C;
+    const size_t C2 = (size_t)pl.C * pl.C;
     RgfCarve cols{ls->d_cols.p};
-    pl.strip[0] = cols.take(pl.cs * nbm); pl.strip[1] = cols.take(pl.cs * nbm);
-    pl.gdyn = cols.take(pl.dyn * nbm);
-    pl.Gab = cols.take(pl.big_kk * nbm); pl.Xs = cols.take(pl.big_kk * nbm); pl.Ys = cols.take(pl.big_kk * nbm);
-    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) {
-        double* T = T_dev + C2 * b.m0;
-        {
-            ProfScope ps(c, "tmat");
-            for (int t = 0; t < pl.nt; ++t) {
-                if (ls->terms[t]->kind == 0) continue;
-                const cplx* sig; size_t st;
-                rgf_sigma_of(ls->terms[t], b.m0, &sig, &st);
-                launch_rgf_gamma(c->stream, pl.K[t], b.nb, sig, st, pl.gdyn + pl.goff[t], pl.dyn);
-            }
-        }
-        for (int pass = 0; pass < (pl.two_pass ? 2 : 1); ++pass)
-            if (int e = rgf_tmat_pass(b, pl, pass == 1, T)) return e;
-        ProfScope ps(c, "tmat");
-        launch_tmat_nan(c->stream, pl.C, b.nb, c->d_info + b.m0, T);
-        return NEGF_OK;
-    });
+    rgf_tmat_layout(r, &pl, &cols);
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) { return rgf_tmat_batch(b, pl, T_dev + C2 * b.m0); });
 }
 
 int negf_layered_transmission_matrix(negf_ctx* c, int h, int n_probes, const int* probe_nk, const int* probe_inds,
@@ -1347,6 +1526,134 @@ int negf_layered_transmission_matrix(negf_ctx* c, int h, int n_probes, const int
     if ((rc = negf_layered_transmission_matrix_dev(c, h, n_probes, probe_nk, probe_inds, probe_sigma, m,
                                                    dev_E(c), c->d_bond_T))) return rc;
     return fetch_pageable(c, m, {{T, c->d_bond_T.p, cnt}}, info);
+}
+
+// ------------------------------------------------- floating probes on layers: response, G^<, G^r
+// The probes of negf_layered_transmission_matrix left floating at every energy, as negf_probe_response,
+// negf_gless_int_probes and negf_gr_int_probes leave the dense system's: nothing crosses to the host.
+int negf_layered_probe_response_dev(negf_ctx* c, int h, int n_probes, const int* probe_nk, const int* probe_inds,
+                                    const double* probe_sigma, int m, const double* E_dev, double* R_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    RgfTmatPlan pl;
+    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
+    if ((rc = rgf_tmat_plan(ls, n_probes, probe_nk, probe_inds, psig, &pl))) return rc;
+    if (m > 0 && (!E_dev || (n_probes > 0 && !R_dev))) return NEGF_EINVAL;
+    if (m == 0) { c->last_m = 0; return NEGF_OK; }
+    // a transmission-matrix call whose matrices stay in a per-batch area, the response kernel behind each batch
+    RgfRun r;
+    if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, true, &r, pl.per_energy))) return rc;
+    const size_t C2 = (size_t)pl.C * pl.C, pc = (size_t)n_probes * pl.nt;
+    ls->work_bytes += 16LL * (long long)pl.stat + 8LL * (long long)C2 * r.nb_max;
+    if ((rc = rgf_tmat_setup(c, ls, psig, &pl)) || (rc = ensure_cap(c, ls->d_deph_T, C2 * r.nb_max))) return rc;
+    RgfCarve cols{ls->d_cols.p};
+    rgf_tmat_layout(r, &pl, &cols);
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) {
+        if (int e = rgf_tmat_batch(b, pl, ls->d_deph_T)) return e;
+        return deph_run_response(c, pl.C, pl.nt, pl.d_porder, b.nb, ls->d_deph_T, R_dev + pc * b.m0);
+    });
+}
+
+int negf_layered_probe_response(negf_ctx* c, int h, int n_probes, const int* probe_nk, const int* probe_inds,
+                                const double* probe_sigma, int m, const double* E, double* R, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    const long Cl = (long)ls->terms.size() + n_probes;
+    if (n_probes < 0 || Cl < 1 || Cl > TMAT_MAX_TERMINALS || (m > 0 && (!E || (n_probes > 0 && !R)))) return NEGF_EINVAL;
+    const size_t cnt = (size_t)m * n_probes * ls->terms.size();
+    if ((rc = stage_grid(c, m, 1, E, nullptr)) || (rc = ensure_cap(c, ls->d_deph_out, cnt + 1))) return rc;
+    if ((rc = negf_layered_probe_response_dev(c, h, n_probes, probe_nk, probe_inds, probe_sigma, m, dev_E(c), ls->d_deph_out))) return rc;
+    if (cnt == 0) return fetch_pageable(c, m, {}, info);
+    return fetch_pageable(c, m, {{R, ls->d_deph_out.p, cnt}}, info);
+}
+
+int negf_layered_gless_int_probes_dev(negf_ctx* c, int h, int ind, int n_probes, const int* probe_nk, const int* probe_inds,
+                                      const double* probe_sigma, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    if (!rgf_less_ind_ok(ls, ind)) return NEGF_EINVAL;
+    RgfTmatPlan pl;
+    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
+    if ((rc = rgf_tmat_plan(ls, n_probes, probe_nk, probe_inds, psig, &pl))) return rc;
+    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
+    RgfDephPlan dp;
+    if ((rc = rgf_deph_plan(ls, pl, ind, &dp))) return rc;
+    RgfRun r;
+    if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, true, &r, dp.per_energy))) return rc;
+    ls->work_bytes += 16LL * (long long)pl.stat;
+    if (dp.floating) ls->work_bytes += 8LL * (long long)((size_t)pl.C * pl.C + (size_t)n_probes * pl.nt) * r.nb_max;
+    if ((rc = rgf_tmat_setup(c, ls, psig, &pl)) || (rc = rgf_deph_setup(c, ls, pl, r, &dp))) return rc;
+    const size_t nbm = (size_t)r.nb_max;
+    RgfCarve cols{ls->d_cols.p};
+    dp.keep = cols.take((size_t)ls->L * pl.cs * nbm); dp.Y = cols.take((size_t)ls->L * pl.cs * nbm);
+    pl.gdyn = cols.take(pl.dyn * nbm);
+    pl.Gab = cols.take(pl.big_kk * nbm); pl.Xs = cols.take(pl.big_kk * nbm); pl.Ys = cols.take(pl.big_kk * nbm);
+    dp.D = cols.take(dp.Dtot * nbm);
+    const RgfSumBlocks sum{reinterpret_cast<const cplx*>(w_dev), reinterpret_cast<cplx*>(out_dev)};
+    NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, (ls->dtot + 2 * ls->utot) * sizeof(cplx), c->stream));
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) { return rgf_deph_batch(b, pl, dp, sum); });
+}
+
+// sum_k w_k G(E_k) on the pattern with the probes in A: negf_layered_gr_int_dev's two sweeps with the probes of each layer
+// taken out of its diagonal before the inverse, as the transmission matrix's factor sweep takes them
+int negf_layered_gr_int_probes_dev(negf_ctx* c, int h, int n_probes, const int* probe_nk, const int* probe_inds,
+                                   const double* probe_sigma, int m, const double* E_dev, const double* w_dev, double* out_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    RgfTmatPlan pl;
+    const cplx* psig = reinterpret_cast<const cplx*>(probe_sigma);
+    if ((rc = rgf_tmat_plan(ls, n_probes, probe_nk, probe_inds, psig, &pl))) return rc;
+    if (!out_dev || (m > 0 && (!E_dev || !w_dev))) return NEGF_EINVAL;
+    RgfRun r;
+    if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, true, &r))) return rc;
+    ls->work_bytes += 16LL * (long long)pl.stat;
+    if ((rc = rgf_tmat_setup(c, ls, psig, &pl))) return rc;
+    const RgfSumBlocks sum{reinterpret_cast<const cplx*>(w_dev), reinterpret_cast<cplx*>(out_dev)};
+    NEGF_HIP_CHECK(hipMemsetAsync(out_dev, 0, (ls->dtot + 2 * ls->utot) * sizeof(cplx), c->stream));
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) {
+        const RgfView v{ls, false};
+        const int e = rgf_factor_sweep(b, v, rgf_sub_probes_step(b, v, pl), rgf_no_step);
+        return e ? e : rgf_solve_sweep(b, v, sum);
+    });
+}
+
+// the host forms of the two sums: grid and weights staged, the block lists and the info back through the pinned buffer
+static int rgf_host_probes_int(negf_ctx* c, int h, const int* ind, int n_probes, const int* probe_nk, const int* probe_inds,
+                               const double* probe_sigma, int m, const double* E, const double* w, double* out, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    const long Cl = (long)ls->terms.size() + n_probes;
+    if (n_probes < 0 || Cl < 1 || Cl > TMAT_MAX_TERMINALS || !out || (m > 0 && (!E || !w))) return NEGF_EINVAL;
+    if (ind && !rgf_less_ind_ok(ls, *ind)) return NEGF_EINVAL;
+    const size_t tot = ls->dtot + 2 * ls->utot;
+    if ((rc = stage_grid(c, m, 1, E, w, tot * sizeof(cplx))) || (rc = ensure_cap(c, ls->d_out, tot))) return rc;
+    double* acc = reinterpret_cast<double*>(ls->d_out.p);
+    rc = ind ? negf_layered_gless_int_probes_dev(c, h, *ind, n_probes, probe_nk, probe_inds, probe_sigma, m, dev_E(c), dev_w(c), acc)
+             : negf_layered_gr_int_probes_dev(c, h, n_probes, probe_nk, probe_inds, probe_sigma, m, dev_E(c), dev_w(c), acc);
+    if (rc) return rc;
+    return fetch_result_and_info(c, m, ls->d_out.p, tot * sizeof(cplx), out, info);
+}
+
+int negf_layered_gless_int_probes(negf_ctx* c, int h, int ind, int n_probes, const int* probe_nk, const int* probe_inds,
+                                  const double* probe_sigma, int m, const double* E, const double* w, double* out, int* info)
+{
+    return rgf_host_probes_int(c, h, &ind, n_probes, probe_nk, probe_inds, probe_sigma, m, E, w, out, info);
+}
+
+int negf_layered_gr_int_probes(negf_ctx* c, int h, int n_probes, const int* probe_nk, const int* probe_inds,
+                               const double* probe_sigma, int m, const double* E, const double* w, double* out, int* info)
+{
+    return rgf_host_probes_int(c, h, nullptr, n_probes, probe_nk, probe_inds, probe_sigma, m, E, w, out, info);
 }
 
 // negf_layered_local_transmission_dev (w null, per-energy tables) and negf_layered_bond_int_dev: negf_local_transmission_dev

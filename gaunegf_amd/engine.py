@@ -1143,6 +1143,78 @@ class Engine:
                                                                     _ptr(sig), int(m), C.c_void_p(E_ptr), C.c_void_p(T_ptr)),
                      "negf_layered_transmission_matrix_dev")
 
+    # ------------------------------------------------ floating dephasing probes on a layered system
+    def layered_probe_response(self, handle, E, probes):
+        """R [m, P, n_t]: the response of the floating ``probes`` (layered_transmission_matrix's lists, any layer) to the
+        system's end terminals (negf_layered_probe_response), as probe_response: probe p's occupation at E_k is
+        sum_c R[k, p, c] f_c(E_k); rows of decoupled probes are exact zeros, the others sum to 1.  Singular energies and
+        energies whose probes reach no end terminal give NaN (with a warning, as probe_response)."""
+        npr, nk, inds, sig = self._probes(probes, sum(self._lsizes(handle)))
+        nt = self.layered_terminal_count(handle)
+        E, _ = self._grid(E)
+        R = np.zeros((E.size, npr, nt), dtype=np.float64)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_probe_response(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig),
+                                                                E.size, _ptr(E), _ptr(R), _ptr(info)),
+                          "negf_layered_probe_response")
+        self._numerical(rc, info[:E.size], "layered_probe_response")
+        lost = np.nonzero(np.isnan(R).any(axis=(1, 2)) & (info[:E.size] == 0))[0] if npr and nt else np.zeros(0, dtype=int)
+        if lost.size:
+            warnings.warn(f"layered_probe_response: probes without a path to any terminal (singular W, undefined occupations) "
+                          f"at energy indices {lost[:8].tolist()}{'...' if lost.size > 8 else ''}", RuntimeWarning)
+        return R
+
+    def layered_probe_response_dev(self, handle, m, E_ptr, R_ptr, probes):
+        """negf_layered_probe_response_dev: grid and the [m, P, n_t] result in HBM; ``probes`` stays a host list."""
+        npr, nk, inds, sig = self._probes(probes, sum(self._lsizes(handle)))
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_probe_response_dev(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig),
+                                                               int(m), C.c_void_p(E_ptr), C.c_void_p(R_ptr)),
+                     "negf_layered_probe_response_dev")
+
+    def layered_gless_int_probes(self, handle, ind, E, w, probes):
+        """sum_k w_k G D_s G^H on the pattern of S with the ``probes`` floating (negf_layered_gless_int_probes): D_s = Gamma_s +
+        sum_p R_ps Gamma_p, G the inverse of the matrix that carries the probes; ``ind`` as layered_gless_int (None: all
+        terminals, no solve).  Returns layered_gless_int's (diagonal, upper, lower) block lists."""
+        npr, nk, inds, sig = self._probes(probes, sum(self._lsizes(handle)))
+        E, w = self._grid(E, w)
+        flat = np.zeros(self.layered_pattern_size(handle), dtype=np.complex128)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_gless_int_probes(self._ctx, int(handle), _ind(ind), npr, _ptr(nk), _ptr(inds),
+                                                                  _ptr(sig), E.size, _ptr(E), _ptr(w), _ptr(flat), _ptr(info)),
+                          "negf_layered_gless_int_probes")
+        self._numerical(rc, info[:E.size], "layered_gless_int_probes")
+        return self._lsplit(handle, flat)
+
+    def layered_gless_int_probes_dev(self, handle, ind, m, E_ptr, w_ptr, out_ptr, probes):
+        """out: layered_pattern_size(handle) complex values, diagonal | upper | lower blocks; ``probes`` stays a host list."""
+        npr, nk, inds, sig = self._probes(probes, sum(self._lsizes(handle)))
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_gless_int_probes_dev(self._ctx, int(handle), _ind(ind), npr, _ptr(nk), _ptr(inds),
+                                                                 _ptr(sig), int(m), C.c_void_p(E_ptr), C.c_void_p(w_ptr),
+                                                                 C.c_void_p(out_ptr)), "negf_layered_gless_int_probes_dev")
+
+    def layered_gr_int_probes(self, handle, E, w, probes):
+        """sum_k w_k G(E_k) on the pattern of S with the ``probes`` in E S - F - Sigma (negf_layered_gr_int_probes):
+        layered_gr_int's (diagonal, upper, lower) block lists."""
+        npr, nk, inds, sig = self._probes(probes, sum(self._lsizes(handle)))
+        E, w = self._grid(E, w)
+        flat = np.zeros(self.layered_pattern_size(handle), dtype=np.complex128)
+        info = np.zeros(max(E.size, 1), dtype=np.int32)
+        rc = self._lcheck(self._lib.negf_layered_gr_int_probes(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig),
+                                                               E.size, _ptr(E), _ptr(w), _ptr(flat), _ptr(info)),
+                          "negf_layered_gr_int_probes")
+        self._numerical(rc, info[:E.size], "layered_gr_int_probes")
+        return self._lsplit(handle, flat)
+
+    def layered_gr_int_probes_dev(self, handle, m, E_ptr, w_ptr, out_ptr, probes):
+        """out: layered_pattern_size(handle) complex values, diagonal | upper | lower blocks; ``probes`` stays a host list."""
+        npr, nk, inds, sig = self._probes(probes, sum(self._lsizes(handle)))
+        self.counters["calls"] += 1; self.counters["points"] += int(m)
+        self._lcheck(self._lib.negf_layered_gr_int_probes_dev(self._ctx, int(handle), npr, _ptr(nk), _ptr(inds), _ptr(sig),
+                                                              int(m), C.c_void_p(E_ptr), C.c_void_p(w_ptr),
+                                                              C.c_void_p(out_ptr)), "negf_layered_gr_int_probes_dev")
+
     def _lgroups(self, handle, groups_per_layer, group_of):
         """(g [L] sizes of the tables, the two host arrays or None) of a bond-table call; only the lengths are checked
         here -- the library must not read past an array -- everything else is the library's NEGF_EINVAL."""

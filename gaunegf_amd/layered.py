@@ -16,6 +16,10 @@ namesakes in transport.py / integrate.py:
     dephasing_probes_layered(system, groups, gamma)                 -> the probes' (indices, block) list
     calculate_effective_transmission_layered(system, leads, energy_list, probes)     -> (T_eff [m], T_coherent [m])
     calculate_effective_current_layered(system, leads, fermi, qV, probes)            -> the current with floating probes
+    calculate_probe_response_layered(system, leads, energy_list, probes)             -> R [m, P, n_leads] of the floating probes
+    calculate_probe_occupations_layered(system, leads, energy_list, probes, f)       -> f_p(E) [m, P]
+    GrLessIntProbesLayered(system, leads, Elist, weights, probes, ind=None)          -> block lists of sum_m w_m G D_s G^H (E_m)
+    GrIntProbesLayered(system, leads, Elist, weights, probes)                        -> block lists of sum_m w_m G(E_m), probes in A
     calculate_bond_transmission_layered(system, leads, energy_list, contact=0, groups=None)
                                                                     -> (diag, up, low, labels): where the transmission flows
     calculate_bond_currents_layered(system, leads, fermi, qV, contact=0, groups=None) -> the same in amperes, integrated
@@ -26,11 +30,12 @@ G Gamma_c G^H is formed on the pattern of S only -- what Tr[P S], a tight-bindin
 read -- from the columns of G on the lead's orbitals, which the two sweeps yield at a few n^2 K products per layer.
 The transmission matrix between all terminals, with Buettiker / D'Amato-Pastawski probes on ANY layer, comes from column
 strips of G on the terminals' orbitals that the backward sweep carries from layer to layer, one pass over the layers
-as they are and one in reverse order; no block of G between distant layers is formed.
+as they are and one in reverse order; no block of G between distant layers is formed.  With the probes FLOATING, their
+response R and G D_s G^H (D_s = Gamma_s + sum_p R_ps Gamma_p, block diagonal over the layers) come from the same two passes
+with the strips of all layers kept until R is known.
 The local (bond) transmission flow[i, j] = 2 Im[K_ij A_ji], K = E S - F, vanishes wherever S and F do: the complete
 orbital-resolved flow map lives on the pattern of S and costs one more pass over the blocks of G Gamma G^H.
-Everything that needs more of G than that raises instead of guessing: eigenchannels, flows with floating probes, the
-floating probes' response and G^<, spin layouts other than 'r', sharding over ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``)
+Everything that needs more of G than that raises instead of guessing: eigenchannels, flows with floating probes, spin layouts other than 'r', sharding over ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``)
 is host-side numpy.
 """
 import numpy as np
@@ -384,6 +389,42 @@ def calculate_effective_transmission_layered(system, leads, energy_list, probes,
     d = drain + n_real if drain < 0 else drain
     s_ = source + n_real if source < 0 else source
     return eff, T[:, d, s_]
+
+
+def calculate_probe_response_layered(system, leads, energy_list, probes, spin=None, checkpoint_file=None, engine=None):
+    """R [m, P, n_leads]: the response of the floating ``probes`` to the leads, solved on the device, as
+    calculate_probe_response: probe p's occupation at E_k is sum_c R[k, p, c] f_c(E_k).  ``probes`` as
+    calculate_transmission_matrix_layered takes them (dephasing_probes_layered makes them)."""
+    _only_restricted(spin); _no_checkpoint(checkpoint_file)
+    with _Bound(system, leads, engine) as b:
+        return b.eng.layered_probe_response(b.h, np.asarray(energy_list), probes)
+
+
+def calculate_probe_occupations_layered(system, leads, energy_list, probes, f, spin=None, checkpoint_file=None, engine=None):
+    """f_p(E_k) [m, P] = sum_c R[k, p, c] f_c(E_k) of the floating probes; ``f``: the leads' occupations, [n_leads] (the
+    same at every energy) or [m, n_leads].  The sum over the leads runs on the host."""
+    R = calculate_probe_response_layered(system, leads, energy_list, probes, spin=spin, checkpoint_file=checkpoint_file,
+                                         engine=engine)
+    f = np.asarray(f, dtype=float)
+    if f.shape not in ((R.shape[2],), (R.shape[0], R.shape[2])):
+        raise ValueError(f"f must be [{R.shape[2]}] or [{R.shape[0]}, {R.shape[2]}], got {f.shape}")
+    return np.einsum('kpc,kc->kp', R, np.broadcast_to(f, (R.shape[0], R.shape[2])))
+
+
+def GrLessIntProbesLayered(system, leads, Elist, weights, probes, ind=None, spin=None, checkpoint_file=None, engine=None):
+    """sum_m w_m G D_s G^H (E_m) on the pattern of S with the ``probes`` floating at every energy, as GrLessIntProbes: D_s =
+    Gamma_s + sum_p R_ps Gamma_p, the non-equilibrium density's integrand with dephasing.  ``ind`` indexes ``leads``, None:
+    Gamma of all terminals.  Returns GrLessIntLayered's (diagonal blocks, upper blocks, lower blocks)."""
+    _only_restricted(spin); _no_checkpoint(checkpoint_file)
+    with _Bound(system, leads, engine) as b:
+        return b.eng.layered_gless_int_probes(b.h, b.term_of(ind), np.asarray(Elist), np.asarray(weights), probes)
+
+
+def GrIntProbesLayered(system, leads, Elist, weights, probes, spin=None, checkpoint_file=None, engine=None):
+    """sum_m w_m G(E_m) on the pattern of S with the ``probes`` in E S - F - Sigma, as GrIntProbes: GrIntLayered's block lists."""
+    _only_restricted(spin); _no_checkpoint(checkpoint_file)
+    with _Bound(system, leads, engine) as b:
+        return b.eng.layered_gr_int_probes(b.h, np.asarray(Elist), np.asarray(weights), probes)
 
 
 def calculate_effective_current_layered(system, leads, fermi, qV, probes, T=None, spin=None, dE=None, engine=None):

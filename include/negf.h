@@ -551,7 +551,7 @@ int negf_gr_int_probes_dev(negf_ctx* ctx, int handle, int n_probes, const int* p
  * A singular layer sets info[k] = the 1-based column of the zero pivot counted over the whole system and returns
  * NEGF_ESINGULAR, as the dense calls do.  negf_set_batch and negf_set_inverse_algo apply.  Every sum has a fixed order:
  * results are bitwise equal from run to run, do not depend on negf_set_batch, and permuting the energies permutes them.
- * Not served: eigenchannels, flows with floating probes, the floating probes' response and G^< on a layered system,
+ * Not served: eigenchannels, flows with floating probes,
  * TERMINALS (leads) on interior layers -- probes, which are arguments of negf_layered_transmission_matrix, may sit on any
  * layer --, spin layouts other than 'r', sharding, checkpoints. */
 int negf_layered_create(negf_ctx* ctx, int n_layers, const int* sizes, const double* F_diag_c128, const double* F_up_c128,
@@ -651,6 +651,44 @@ int negf_layered_transmission_matrix(negf_ctx* ctx, int handle, int n_probes, co
 int negf_layered_transmission_matrix_dev(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk,
                                          const int* probe_inds, const double* probe_sigma_c128, int m, const double* E_dev,
                                          double* T_dev);
+/* The probes of negf_layered_transmission_matrix left FLOATING at every energy -- negf_probe_response,
+ * negf_gless_int_probes and negf_gr_int_probes on a layered system, results on the pattern of S.  Terminals and probe
+ * arguments are negf_layered_transmission_matrix's, with the same NEGF_EINVAL cases before anything is launched; `ind` is
+ * read as negf_layered_gless_int reads it.
+ * negf_layered_probe_response: R [m][n_probes][n_t], probe p's occupation at E_k is sum_c R[k][p][c] f_c(E_k).  With To = T
+ * with zero diagonal: W_pp = sum_{c != p} To[p][c] over ALL terminals, W_pq = -To[p][q], P' = the probes with W_pp > 0,
+ * R[P', :] = W^-1 To[P', 0:n_t], exact zeros outside P' (negf_probe_response's rules with n_c -> n_t).  NaN R: a pivot
+ * that is not positive (probes that reach no end terminal) makes the whole energy NaN with info 0; a singular layer gives
+ * its info and NEGF_ESINGULAR.  With n_probes = 0 nothing is written.
+ * negf_layered_gless_int_probes: sum_k w_k A(E_k), A = G D_s G^H with D_s = scatter(Gamma_s) + sum_p R_ps scatter(Gamma_p)
+ * (ind = NEGF_IND_TOTAL: the sum of all terminals' Gamma, no solve) and G the inverse of the matrix that carries the
+ * probes, in negf_layered_gr_int's block layout with complex weights: diagonal blocks, upper blocks A_{i,i+1}, lower blocks
+ * sum_k w_k conj(A_{i,i+1}(E_k))^T.  Every terminal lives in one layer, so D = (+)_q D_q is block diagonal on the union
+ * lists J_q.  R needs the whole T before D exists: the two strip passes KEEP the strips of all layers, Cfull_i = [G_{i,q}[:,
+ * J_q]]_q (n_i x K_tot; the blocks q >= i from the pass over the layers as they are, the others from the reversed pass),
+ * then Y_i = Cfull_i blockdiag(D_q) for all layers in one launch, A_ii = Y_i Cfull_i^H, A_{i,i+1} = Y_i Cfull_{i+1}^H: one
+ * inverse per layer, pass and energy, nothing recomputed.  Energy k enters every element's sum after k - 1.
+ * negf_layered_gr_int_probes: sum_k w_k G(E_k) on the pattern with the probes in A, negf_layered_gr_int's layout.
+ * The _dev forms follow the stream contract of the device-resident variants: they overwrite out_dev / R_dev, and the
+ * host tables of the probes are uploaded with a wait.  No floating-point atomics; results are bitwise equal from run to
+ * run, independent of negf_set_batch, permuting the probes permutes the rows of R bit for bit and leaves the sums bit
+ * for bit, permuting the energies permutes R.  Profile family of the two new kernels: "deph". */
+int negf_layered_probe_response(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                                const double* probe_sigma_c128, int m, const double* E_c128, double* R, int* info);
+int negf_layered_probe_response_dev(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                                    const double* probe_sigma_c128, int m, const double* E_dev, double* R_dev);
+int negf_layered_gless_int_probes(negf_ctx* ctx, int handle, int ind, int n_probes, const int* probe_nk,
+                                  const int* probe_inds, const double* probe_sigma_c128, int m, const double* E_c128,
+                                  const double* w_c128, double* out_c128, int* info);
+int negf_layered_gless_int_probes_dev(negf_ctx* ctx, int handle, int ind, int n_probes, const int* probe_nk,
+                                      const int* probe_inds, const double* probe_sigma_c128, int m, const double* E_dev,
+                                      const double* w_dev, double* out_dev);
+int negf_layered_gr_int_probes(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                               const double* probe_sigma_c128, int m, const double* E_c128, const double* w_c128,
+                               double* out_c128, int* info);
+int negf_layered_gr_int_probes_dev(negf_ctx* ctx, int handle, int n_probes, const int* probe_nk, const int* probe_inds,
+                                   const double* probe_sigma_c128, int m, const double* E_dev, const double* w_dev,
+                                   double* out_dev);
 /* Where the current injected by the terminals `ind` flows -- negf_local_transmission / negf_bond_int on a layered system:
  *   flow[i][j](E) = 2 Im[K_ij A_ji],  K = E S - F,  A = G Gamma G^H of negf_layered_gless_int for the same `ind`.
  * K is zero wherever S and F are, so the complete orbital-resolved flow lives on the pattern of S, nothing truncated:
@@ -692,7 +730,12 @@ int negf_layered_bond_int_dev(negf_ctx* ctx, int handle, int ind, int m, const d
  * three K_a K_b areas of the largest pair that takes the matrix-core path; once per call: the Gamma blocks of the probes
  * and const terminals (sum K^2).  The result [m][C][C] is the caller's.  A bond call (negf_layered_local_transmission,
  * negf_layered_bond_int) is a G Gamma G^H call plus, with groups, the maps (N + sum (g_i + 1) ints) and, in the host form,
- * the staging of its result (m tables / one table of doubles). */
+ * the staging of its result (m tables / one table of doubles).  The floating-probe calls: negf_layered_probe_response is
+ * a transmission-matrix call plus C^2 doubles per energy in flight (the matrices of the batch); negf_layered_gr_int_probes
+ * the 10 + L matrices and the once-per-call Gamma blocks; negf_layered_gless_int_probes, per energy in flight, the 10 + L
+ * matrices, the KEPT strips and Y of all layers (2 L n_max K_tot elements, in place of the two alternating strips), the
+ * Gamma blocks that depend on E, the three K_a K_b areas, D (sum_q |J_q|^2 elements) and -- for a contact with probes --
+ * C^2 + n_probes n_t doubles (T and R); once per call the Gamma blocks of the probes and const terminals. */
 int negf_layered_workspace_bytes(negf_ctx* ctx, int handle, long long* work);
 
 /* ------------------------------------------------------------- diagnostics */
