@@ -372,7 +372,7 @@ def test_segments_on_the_windowed_inverse_and_on_spin_blocks(engine):
         assert rel_fro(a, GrLessInt(F2, S2, g2, E, w, -1)) < 1e-12
 
 
-@pytest.mark.parametrize("N", [24, 60, 130, 300, 600])       # (600: above 512 orbitals a launch per level instead of one workgroup per integration)
+@pytest.mark.parametrize("N", [24, 60, 130, 300, 600, 730])  # (600: above 512 orbitals a launch per level instead of one workgroup per integration; 730: its 2048 workgroups of 256 cover less than n^2, the grid-stride loop wraps)
 def test_refinement_on_the_device_equals_the_host_refinement(engine, N, capsys):
     """negf_gr_int_refine: the nested-rule update and stopping test of density.py:239-268 run by the library on the level sums
     it has just computed.  Against the host refinement of the same sums (Engine.gr_int_seg + numpy): the same value BITWISE
