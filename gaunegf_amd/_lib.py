@@ -1,5 +1,6 @@
 """
-ctypes binding of libnegf_hip.so -- exactly the symbols declared in include/negf.h.
+ctypes binding of libnegf_hip.so -- exactly the symbols declared in include/negf.h (SIGNATURES) and in its second
+header include/negf_layered_channels.h (SIGNATURES_LAYERED_CHANNELS).
 
 There is no CPU fallback: ``load()`` raises if the library has not been built and
 ``Engine`` (engine.py) raises if no GPU is visible.
@@ -144,6 +145,15 @@ SIGNATURES = {
     "negf_inverse_last": (C.c_int, [_vp, _ip, _ip, _ip]),
 }
 
+# the second header, include/negf_layered_channels.h, one to one; no name sits in both tables
+SIGNATURES_LAYERED_CHANNELS = {
+    "negf_layered_channel_count": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip]),
+    "negf_layered_transmission_channels": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "negf_layered_transmission_channels_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    "negf_eigvalsh_wide_batched": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "negf_set_channel_algo": (C.c_int, [_vp, C.c_int]),
+}
+
 _lib = None
 
 
@@ -164,10 +174,11 @@ def load():
             f"{LIB_PATH} not found: build the HIP library first "
             "(python -m gaunegf_amd.build).  gaunegf_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, SIGNATURES_LAYERED_CHANNELS):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

@@ -26,6 +26,7 @@ def _sources():
 def _deps_mtime():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdrs.append(os.path.join(HERE, "..", "include", "negf.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "negf_layered_channels.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -10,6 +10,7 @@
 #include <map>
 #include <memory>
 #include "../../include/negf.h"
+#include "../../include/negf_layered_channels.h"
 
 // ------------------------------------------------------------------ complex
 // complex128 as an aligned pair: one 16-byte global/LDS access per element.
@@ -332,6 +333,7 @@ struct negf_ctx {
     GjRecord gj_last;              // what the last run_inverse / rgf_inverse launched (negf_inverse_last)
     int chain_rr_quantum = -1, chain_rr_slots = 0;   // negf_set_chain_round_robin
     int small_algo = 0;            // 0: n <= 96 takes the fused single-kernel path, 1: never (negf_set_small_algo)
+    int channel_algo = 0;          // layered channels: 0: K <= 96 takes the LDS kernels, 1: the wide kernels at every K (negf_set_channel_algo)
     // pinned host staging of the host-pointer entry points: [E | w] up, [result | info] down, ONE synchronisation
     // (the layout: PinLayout, negf_api.hip)
     unsigned char* h_pin = nullptr;
@@ -538,6 +540,16 @@ void launch_channel_gauge(hipStream_t st, int n, int nce, int nchan, int nb, con
 // Pivoted Cholesky of the Hermitian PSD K x K matrices G[b]: Lh[b] = L^H (K x K, rows >= rank[b] zero), G ~ L L^H
 bool launch_pivoted_cholesky(hipStream_t st, int K, int nb, const cplx* G, size_t strideG, cplx* Lh, size_t strideL,
                              int* rank);
+// The wide forms (k_eig_wide.hip), K <= eig_wide_kmax() = 512: the same contracts -- launch_pivoted_cholesky_wide writes
+// launch_pivoted_cholesky's L^H and rank, launch_eigvalsh_wide launch_eigvalsh_batched's values (its flag 2 does not
+// occur) -- with the matrix in global memory: `work` holds nb * eig_wide_work_elems(K) values, private to the launch.
+int eig_wide_kmax();
+size_t eig_wide_work_elems(int K);
+bool launch_eigvalsh_wide(hipStream_t st, int K, int nb, const cplx* A, int lda, size_t strideA, const int* rank,
+                          int rank_stride, double* w, int ldw, int nout, bool descending, int* info, bool chk_in, int flag_sign,
+                          cplx* work);
+bool launch_pivoted_cholesky_wide(hipStream_t st, int K, int nb, const cplx* G, size_t strideG, cplx* Lh, size_t strideL,
+                                  int* rank);
 
 // Local (bond) transmission (k_bond.hip): flow[i][j] = 2 Im[(E S - F)_ij conj(A_ij)] from the Hermitian A = G Gamma_c G^H.
 // launch_bond_tables: per-energy tables out [nb][ng][ng]; perm / goff (device, [n] / [ng + 1]) = the orbitals sorted by

@@ -1,5 +1,5 @@
 // Recursive Green's function path for layered (block-tridiagonal) devices: the negf_layered_* entry points of
-// include/negf.h.  Part of negf_api.hip's translation unit (included at its end): it uses that file's allocation,
+// include/negf.h and the eigenchannel entry points of include/negf_layered_channels.h.  Part of negf_api.hip's translation unit (included at its end): it uses that file's allocation,
 // staging and self-energy helpers as they are.
 //
 // A LayeredSystem is an object of its own inside the context: blocks, terminals and workspace are its own, the dense
@@ -60,6 +60,10 @@ struct LayeredSystem {
     DevBuf<cplx> d_pool;                        // [RGF_NBUF][batch][stride] work areas
     DevBuf<cplx> d_gstore;                      // [L][batch][stride] the g_i of a backward sweep
     DevBuf<cplx> d_small;                       // Gamma_a | Gamma_b | G_ab | X | Y of the transmission
+    DevBuf<cplx> d_chan;                        // eigenchannels: Gamma_a | Gamma_b | G_ab | Z | W | H | the wide solver's copy of H
+                                                // per energy in flight, then L^H (once for a const terminal)
+    DevBuf<int> d_chan_rank;                    // ... the rank of every L^H
+    DevBuf<double> d_chan_T;                    // ... [m][nchan] staging of the host-pointer entry point
     DevBuf<cplx> d_cols;                        // column sets of G Gamma G^H: z_i | x | W | Y | Gamma, per energy in flight;
                                                 // of a transmission matrix: strip | strip | Gamma(E) | G_ab | X | Y
     DevBuf<int> d_J;                            // [2][nmax] their union lists, layer 0's then the last layer's
@@ -94,7 +98,9 @@ void free_layered(LayeredSystem* ls)
     for (auto* t : ls->terms) free_terminal(t);
     dev_free(ls->dFd); dev_free(ls->dSd); dev_free(ls->dFu); dev_free(ls->dSu); dev_free(ls->dFl); dev_free(ls->dSl);
     release_bufs(ls->d_pool, ls->d_gstore, ls->d_small, ls->d_out, ls->d_cols);
-    release_bufs(ls->d_site);
+    release_bufs(ls->d_site, ls->d_chan_T);
+    release_bufs(ls->d_chan);
+    release_bufs(ls->d_chan_rank);
     release_bufs(ls->d_J, ls->d_tm_tab, ls->d_bond_map);
     release_bufs(ls->d_bond_out);
     release_bufs(ls->d_tm_sig, ls->d_tm_gam);
@@ -1385,6 +1391,161 @@ int negf_layered_transmission(negf_ctx* c, int h, int term_a, int term_b, int m,
     if ((rc = stage_grid(c, m, 1, E, nullptr, (size_t)m * sizeof(double)))) return rc;
     if ((rc = negf_layered_transmission_dev(c, h, term_a, term_b, m, dev_E(c), c->d_scal))) return rc;
     return fetch_result_and_info(c, m, c->d_scal, (size_t)m * sizeof(double), T, info);
+}
+
+// ------------------------------------------------- transmission eigenchannels (include/negf_layered_channels.h)
+// The dense channel call (negf_api.hip, ChanWork) on the corner block: s = the terminal with the shorter list (a unless
+// K_b < K_a), Gamma_s = L L^H, Z = L^H G_so (the block is gathered as G[I_a, I_b] either way: with s = b it enters Z
+// conjugate-transposed), W = Z Gamma_o, H = W Z^H, then the eigenvalues of H's leading rank x rank block.  Which kernels
+// factor and diagonalise: those of k_channels.hip up to their K = 96, the wide ones (k_eig_wide.hip) above it or where
+// negf_set_channel_algo(1) asks for them.
+struct RgfChanPlan {
+    RgfTerminal *ta, *tb;
+    int Ks, Ko;
+    bool mirror, wide, constant;                // constant: Gamma_s does not depend on E -- factored once per call
+};
+
+static int rgf_chan_plan(negf_ctx* c, int h, int term_a, int term_b, LayeredSystem** lsp, RgfChanPlan* pl)
+{
+    LayeredSystem* ls = get_layered(c, h);
+    if (!ls) return NEGF_EINVAL;
+    const int nt = (int)ls->terms.size();
+    if (term_a < 0 || term_a >= nt || term_b < 0 || term_b >= nt) return NEGF_EINVAL;
+    pl->ta = ls->terms[term_a]; pl->tb = ls->terms[term_b];
+    if (pl->ta->end == pl->tb->end) return NEGF_EINVAL;            // the corner blocks connect opposite end layers only
+    pl->mirror = pl->tb->K < pl->ta->K;
+    const RgfTerminal* s = pl->mirror ? pl->tb : pl->ta;
+    pl->Ks = s->K; pl->Ko = (pl->mirror ? pl->ta : pl->tb)->K;
+    if (pl->Ks > eig_wide_kmax()) return NEGF_EINVAL;
+    pl->wide = c->channel_algo == 1 || pl->Ks > channels_kmax();
+    pl->constant = s->kind == 0;
+    *lsp = ls;
+    return NEGF_OK;
+}
+
+int negf_layered_channel_count(negf_ctx* c, int h, int term_a, int term_b, int* nchan)
+{
+    if (!c || !nchan) return NEGF_EINVAL;
+    LayeredSystem* ls; RgfChanPlan pl;
+    if (int rc = rgf_chan_plan(c, h, term_a, term_b, &ls, &pl)) return rc;
+    *nchan = pl.Ks;
+    return NEGF_OK;
+}
+
+int negf_layered_transmission_channels_dev(negf_ctx* c, int h, int term_a, int term_b, int m, const double* E_dev, int nchan,
+                                           double* T_dev)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    RgfChanPlan pl;
+    if ((rc = rgf_chan_plan(c, h, term_a, term_b, &ls, &pl))) return rc;
+    if (nchan < 1 || !T_dev || (m > 0 && !E_dev)) return NEGF_EINVAL;
+    RgfRun r;
+    if ((rc = ensure_mbuffers(c, m, 1)) || (rc = rgf_workspace(c, ls, m, false, &r))) return rc;
+    RgfTerminal *ta = pl.ta, *tb = pl.tb;
+    const int Ka = ta->K, Kb = tb->K, Ks = pl.Ks, Ko = pl.Ko;
+    const size_t kk = (size_t)Ka * Kb, sa = (size_t)Ka * Ka, sb = (size_t)Kb * Kb, ks2 = (size_t)Ks * Ks, nbm = (size_t)r.nb_max;
+    const size_t wide_per = pl.wide ? eig_wide_work_elems(Ks) : 0;
+    const size_t per = sa + sb + 3 * kk + ks2 + wide_per, nl = pl.constant ? 1 : nbm, lstride = pl.constant ? 0 : ks2;
+    if ((rc = ensure_cap(c, ls->d_chan, per * nbm + ks2 * nl)) || (rc = ensure_cap(c, ls->d_chan_rank, nl))) return rc;
+    ls->work_bytes += 16LL * (long long)(per * nbm + ks2 * nl) + 4LL * (long long)nl;
+    RgfCarve area{ls->d_chan.p};
+    cplx *gamA = area.take(sa * nbm), *gamB = area.take(sb * nbm), *Gab = area.take(kk * nbm), *Z = area.take(kk * nbm);
+    cplx *W = area.take(kk * nbm), *H = area.take(ks2 * nbm), *ework = area.take(wide_per * nbm), *Lh = area.take(ks2 * nl);
+    int* rank = ls->d_chan_rank.p;
+    // a on the last layer: G_ab is cut from G_{L-1,0}; a on layer 0: from G_{0,L-1} (as negf_layered_transmission_dev)
+    const bool lower = ta->end == 1;
+    const int ld = lower ? ls->n[0] : ls->n[ls->L - 1];
+    return rgf_batches(r, m, E_dev, [&](const RgfBatch& b) {
+        cplx* Gc = nullptr;
+        if (int e = rgf_corner_sweep(b, lower, &Gc)) return e;
+        const cplx *sA, *sB; size_t stA, stB;
+        rgf_sigma_of(ta, b.m0, &sA, &stA); rgf_sigma_of(tb, b.m0, &sB, &stB);
+        {
+            ProfScope ps(c, "gamma");
+            launch_rgf_gamma(c->stream, Ka, b.nb, sA, stA, gamA, sa);
+            launch_rgf_gamma(c->stream, Kb, b.nb, sB, stB, gamB, sb);
+        }
+        const cplx *gamS = pl.mirror ? gamB : gamA, *gamO = pl.mirror ? gamA : gamB;
+        const size_t ss = pl.mirror ? sb : sa, so = pl.mirror ? sa : sb;
+        if (!pl.constant || b.m0 == 0) {
+            ProfScope ps(c, "eig");
+            const int nf = pl.constant ? 1 : b.nb;
+            const bool ok = pl.wide ? launch_pivoted_cholesky_wide(c->stream, Ks, nf, gamS, ss, Lh, ks2, rank)
+                                    : launch_pivoted_cholesky(c->stream, Ks, nf, gamS, ss, Lh, ks2, rank);
+            if (!ok) return NEGF_EINVAL;
+        }
+        {
+            ProfScope ps(c, "zgemm");
+            launch_gather_block(c->stream, ld, Ka, Kb, b.nb, Gc, ls->stride, ta->d_idx, tb->d_idx, Gab, kk);
+            launch_zgemm(c->stream, Ks, Ko, Ks, b.nb, Lh, Ks, lstride, Gab, pl.mirror ? Ks : Ko, kk, pl.mirror ? 1 : 0, Z, Ko, kk);
+            launch_zgemm(c->stream, Ks, Ko, Ko, b.nb, Z, Ko, kk, gamO, Ko, so, 0, W, Ko, kk);
+            launch_zgemm(c->stream, Ks, Ks, Ko, b.nb, W, Ko, kk, Z, Ko, kk, 1, H, Ks, ks2);
+        }
+        ProfScope ps(c, "eig");
+        // (all nchan columns are written: values, zeros beyond the rank or K_s, or a whole NaN row for a singular energy)
+        double* Tb = T_dev + (size_t)b.m0 * nchan;
+        const int rs = pl.constant ? 0 : 1;
+        const bool ok = pl.wide ? launch_eigvalsh_wide(c->stream, Ks, b.nb, H, Ks, ks2, rank, rs, Tb, nchan, nchan, true, c->d_info + b.m0, true, -1, ework)
+                                : launch_eigvalsh_batched(c->stream, Ks, b.nb, H, Ks, ks2, rank, rs, Tb, nchan, nchan, true, c->d_info + b.m0, true, -1);
+        return ok ? NEGF_OK : NEGF_EINVAL;
+    });
+}
+
+int negf_layered_transmission_channels(negf_ctx* c, int h, int term_a, int term_b, int m, const double* E, int nchan,
+                                       double* T_chan, int* info)
+{
+    LayeredSystem* ls;
+    int rc = rgf_open(c, h, m, &ls);
+    if (rc) return rc;
+    RgfChanPlan pl;
+    if ((rc = rgf_chan_plan(c, h, term_a, term_b, &ls, &pl))) return rc;
+    if (nchan < 1 || (m > 0 && (!E || !T_chan))) return NEGF_EINVAL;
+    if (m == 0) return NEGF_OK;
+    const size_t cnt = (size_t)m * nchan;
+    if ((rc = stage_grid(c, m, 1, E, nullptr)) || (rc = ensure_cap(c, ls->d_chan_T, cnt))) return rc;
+    if ((rc = negf_layered_transmission_channels_dev(c, h, term_a, term_b, m, dev_E(c), nchan, ls->d_chan_T))) return rc;
+    ls->work_bytes += 8LL * (long long)cnt;
+    return fetch_pageable(c, m, {{T_chan, ls->d_chan_T.p, cnt}}, info);
+}
+
+int negf_eigvalsh_wide_batched(negf_ctx* c, int K, int m, const double* A, double* w, int* info)
+{
+    if (!c) return NEGF_EINVAL;
+    if (K < 1 || K > eig_wide_kmax() || m < 0 || (m > 0 && (!A || !w))) return NEGF_EINVAL;
+    if (m == 0) return NEGF_OK;
+    NEGF_HIP_CHECK(hipSetDevice(c->device));
+    const size_t k2 = (size_t)K * K;
+    cplx *dA = nullptr, *dwork = nullptr; double* dw = nullptr; int* di = nullptr;
+    std::vector<int> hi((size_t)m);
+    // (one way out: whatever fails, everything allocated so far is freed below)
+    int rc = dev_alloc(&dA, k2 * m);
+    if (!rc) rc = dev_alloc(&dwork, eig_wide_work_elems(K) * m);
+    if (!rc) rc = dev_alloc(&dw, (size_t)K * m);
+    if (!rc) rc = dev_alloc(&di, (size_t)m);
+    if (!rc) rc = upload(c, dA, reinterpret_cast<const cplx*>(A), k2 * m);
+    if (!rc) {
+        ProfScope ps(c, "eig");
+        if (!launch_eigvalsh_wide(c->stream, K, m, dA, K, k2, nullptr, 0, dw, K, K, false, di, false, 1, dwork)) rc = NEGF_EINVAL;
+    }
+    if (!rc && hipGetLastError() != hipSuccess) rc = NEGF_EHIP;
+    if (!rc) rc = download(c, w, dw, (size_t)K * m);
+    if (!rc) rc = download(c, hi.data(), di, (size_t)m);
+    dev_free(dA); dev_free(dwork); dev_free(dw); dev_free(di);
+    if (rc) return rc;
+    for (int i = 0; i < m; ++i) {
+        if (info) info[i] = hi[i];
+        if (hi[i] != 0) rc = NEGF_ESINGULAR;
+    }
+    return rc;
+}
+
+int negf_set_channel_algo(negf_ctx* c, int algo)
+{
+    if (!c || (algo != 0 && algo != 1)) return NEGF_EINVAL;
+    c->channel_algo = algo;
+    return NEGF_OK;
 }
 
 // negf_layered_dos_dev (ind null) and negf_layered_contact_dos_dev

@@ -24,6 +24,8 @@ namesakes in transport.py / integrate.py:
                                                                     -> (diag, up, low, labels): where the transmission flows
     calculate_bond_currents_layered(system, leads, fermi, qV, contact=0, groups=None) -> the same in amperes, integrated
     calculate_interlayer_transmission(system, leads, energy_list, contact=0)         -> [m, L - 1] flow across each boundary
+    calculate_eigenchannels_layered(system, leads, energy_list, pair=(0, 1), nchan=None) -> T_n [m, nchan], leads up to 512 wide
+    channel_count_layered(system, leads, pair=(0, 1))               -> min(K_a, K_b)
 
 Per energy the work is L inverses and a handful of products of layer size instead of one N x N inverse.
 G Gamma_c G^H is formed on the pattern of S only -- what Tr[P S], a tight-binding Fock builder and the Mulliken populations
@@ -35,7 +37,10 @@ response R and G D_s G^H (D_s = Gamma_s + sum_p R_ps Gamma_p, block diagonal ove
 with the strips of all layers kept until R is known.
 The local (bond) transmission flow[i, j] = 2 Im[K_ij A_ji], K = E S - F, vanishes wherever S and F do: the complete
 orbital-resolved flow map lives on the pattern of S and costs one more pass over the blocks of G Gamma G^H.
-Everything that needs more of G than that raises instead of guessing: eigenchannels, flows with floating probes, spin layouts other than 'r', sharding over ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``)
+The transmission eigenchannels of a pair of terminals on opposite ends need the corner block of G alone, which the
+transmission already forms: the dense channel call's products on it, and for lists of 97 to 512 orbitals a wide pivoted
+Cholesky and a Householder / bisection eigensolver (values only; scattering states need the leads' columns of G).
+Everything that needs more of G than that raises instead of guessing: channel states, flows with floating probes, spin layouts other than 'r', sharding over ranks and checkpoint files.  The layering itself (``from_dense``, ``partition``)
 is host-side numpy.
 """
 import numpy as np
@@ -577,6 +582,123 @@ def pattern_to_dense(sizes, diag, upper, lower):
     return out
 
 
+# ----------------------------------------------------------------------------- transmission eigenchannels
+# The entry points of include/negf_layered_channels.h (_lib.SIGNATURES_LAYERED_CHANNELS), reached through the engine's
+# own way into the library (Engine._call / _counted / _host): module-level functions, the engine as an argument.
+EIG_WIDE_KMAX = 512
+
+
+def _engine(engine):
+    from .engine import get_engine
+    return engine if engine is not None else get_engine()
+
+
+def set_channel_algo(algo, engine=None):
+    """Which kernels the layered channel call runs: 0 by size (min(K_a, K_b) <= 96 the kernels of the dense channel call,
+    above that the wide ones; default), 1 the wide kernels at every size (tests)."""
+    _engine(engine)._call("negf_set_channel_algo", int(algo))
+
+
+def eigvalsh_wide(A, engine=None):
+    """Ascending eigenvalues [m, K] of the Hermitian matrices A [m, K, K] (or one [K, K] -> [K]), 1 <= K <= 512, read from
+    their lower triangles like numpy.linalg.eigvalsh: the WIDE kernel alone (Householder tridiagonalisation, bisection),
+    a diagnostic (negf_eigvalsh_wide_batched).  A row whose input is not finite is NaN; the engine's ``last_info`` holds
+    the per-matrix flags (1: non-finite)."""
+    import warnings
+    from . import _lib
+    from .engine import _ptr, _first_bad
+    eng = _engine(engine)
+    A = np.ascontiguousarray(A, dtype=np.complex128)
+    single = A.ndim == 2
+    if single:
+        A = A[None]
+    if A.ndim != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError(f"eigvalsh_wide: expected [m, K, K] or [K, K], got {A.shape}")
+    m, K = A.shape[0], A.shape[1]
+    if not 1 <= K <= EIG_WIDE_KMAX:
+        raise ValueError(f"eigvalsh_wide: K = {K} outside 1 .. {EIG_WIDE_KMAX}")
+    w = np.zeros((m, K), dtype=np.float64)
+    info = np.zeros(max(m, 1), dtype=np.int32)
+    rc = eng._call("negf_eigvalsh_wide_batched", K, m, _ptr(A), _ptr(w), _ptr(info))
+    eng.last_info = info[:m]
+    if rc == _lib.NEGF_ESINGULAR:
+        warnings.warn(f"eigvalsh_wide: non-finite input for matrices {_first_bad(np.nonzero(info[:m])[0])}", RuntimeWarning)
+    return w[0] if single else w
+
+
+def layered_channel_count(eng, handle, term_a, term_b):
+    """min(K_a, K_b) of two terminals of an engine-side layered system; ValueError for a pair on the same end layer or
+    more than 512 channels."""
+    import ctypes as C
+    nc = C.c_int(0)
+    eng._call("negf_layered_channel_count", int(handle), int(term_a), int(term_b), C.byref(nc))
+    return nc.value
+
+
+def layered_transmission_channels(eng, handle, term_a, term_b, E, nchan=None):
+    """T_n(E) [m, nchan] of two terminals of an engine-side layered system, descending per energy
+    (negf_layered_transmission_channels); nchan defaults to layered_channel_count().  Rows of singular energies are NaN
+    (with a warning, as layered_transmission); ``eng.last_info`` holds the per-energy info, the eigensolver's flags
+    negative."""
+    import warnings
+    from . import _lib
+    from .engine import _ptr, _first_bad
+    nchan = layered_channel_count(eng, handle, term_a, term_b) if nchan is None else int(nchan)
+    if nchan < 1:
+        raise ValueError("nchan must be at least 1")
+    E, _ = eng._grid(E)
+    T = np.zeros((E.size, nchan), dtype=np.float64)
+    where = "layered_transmission_channels"
+    info = eng._host(where, E.size, int(handle), int(term_a), int(term_b), E.size, _ptr(E), nchan, _ptr(T), raw=True)
+    # info > 0: a singular layer (pivot column in the whole system); < 0: the eigensolver's flags on H -- reported apart
+    eng._numerical(_lib.NEGF_ESINGULAR if np.any(info > 0) else 0, np.where(info > 0, info, 0), where)
+    eng.last_info = info
+    bad = np.nonzero(info < 0)[0]
+    if bad.size:
+        what = {-1: "non-finite H", -2: "Jacobi not converged within its sweep limit"}
+        kinds = sorted({what.get(int(v), str(int(v))) for v in info[bad]})
+        warnings.warn(f"{where}: eigensolver flags ({', '.join(kinds)}) at energy indices {_first_bad(bad)}", RuntimeWarning)
+    return T
+
+
+def layered_transmission_channels_dev(eng, handle, term_a, term_b, m, E_ptr, nchan, T_ptr):
+    """The device-resident form: E_ptr [m] complex128 and T_ptr [m, nchan] float64 are device addresses; the stream
+    contract of Engine.set_stream holds (T is overwritten, nothing waits for the host on a warm call)."""
+    from .engine import _p
+    eng._counted(m)("negf_layered_transmission_channels_dev", int(handle), int(term_a), int(term_b), int(m), _p(E_ptr),
+                    int(nchan), _p(T_ptr))
+
+
+def _opposite_pair(b, pair):
+    """the engine's terminal numbers of ``pair`` = (a, b), indices into the leads; ValueError unless they sit on opposite
+    end layers"""
+    ta, tb = b.term_of(pair[0]), b.term_of(pair[1])
+    if ta is None or tb is None:
+        raise ValueError("pair must name two leads")
+    return ta, tb
+
+
+def channel_count_layered(system, leads, pair=(0, 1), engine=None):
+    """min(K_a, K_b): the number of transmission eigenchannels of ``pair`` = (a, b), indices into ``leads`` on opposite end
+    layers; ValueError for a pair on one end and for more than 512 channels."""
+    with _Bound(system, leads, engine) as b:
+        return layered_channel_count(b.eng, b.h, *_opposite_pair(b, pair))
+
+
+def calculate_eigenchannels_layered(system, leads, energy_list, pair=(0, 1), nchan=None, spin=None, checkpoint_file=None,
+                                    engine=None):
+    """Transmission eigenchannels T_n(E) [m, nchan] of a layered system, descending per energy: the eigenvalues of t^H t,
+    t = Gamma_a^{1/2} G_ab Gamma_b^{1/2}, for ``pair`` = (a, b) read as calculate_transmission_layered reads it (indices into
+    ``leads`` on opposite end layers) -- their sum is calculate_transmission_layered's T(E).  The eigenproblem lives on the
+    shorter of the two orbital lists, at most 512 orbitals (up to 96 the kernels of calculate_transmission_channels, above
+    that a Householder / bisection solver); ``nchan`` defaults to channel_count_layered().  Exact zeros beyond the rank of
+    the factored Gamma; rows of singular energies are NaN, with a warning.  Values only."""
+    _only_restricted(spin); _no_checkpoint(checkpoint_file)
+    with _Bound(system, leads, engine) as b:
+        ta, tb = _opposite_pair(b, pair)
+        return layered_transmission_channels(b.eng, b.h, ta, tb, np.asarray(energy_list), nchan)
+
+
 def _not_served(name, why):
     def fn(*args, **kwargs):
         raise NotImplementedError(f"{name} is not served on layered systems: {why}")
@@ -586,8 +708,9 @@ def _not_served(name, why):
 
 calculate_transmission_channels_layered = _not_served(
     "calculate_transmission_channels_layered",
-    "it needs blocks of G outside the pattern of S, the two corner blocks and the leads' columns (use the dense engine on "
-    "system.to_dense())")
+    "the eigenchannel values of a layered system are calculate_eigenchannels_layered's (pair= instead of two contact "
+    "numbers, leads up to 512 orbitals wide); channel states need the leads' columns of G and stay with the dense engine "
+    "on system.to_dense()")
 calculate_local_transmission_layered = _not_served(
     "calculate_local_transmission_layered",
     "the local transmission of a layered system lives on the pattern of S and is calculate_bond_transmission_layered's "
