@@ -393,6 +393,59 @@ void launch_accumulate(hipStream_t st, int n2, int nb, const cplx* w, const cplx
     hipLaunchKernelGGL(accumulate_final_kernel, dim3(g), dim3(EW_THREADS), 0, st, n2, nchunks, part, acc);
 }
 
+// The same sum over the batch [m0, m0 + nb) of a grid of m energies in an order that does not depend on how the grid was cut
+// into batches (launch_bond_int's order, k_bond.hip): chunk c is the energies [32 c, 32 c + 32) OF THE GRID, ascending and
+// starting from zero, and acc receives the chunk sums in ascending chunk order.  A chunk that a batch boundary cuts is carried:
+// its running sum waits in `carry` [n2] and the next batch continues it.  w and X are indexed from the batch's first energy;
+// `part` holds one record per chunk the batch touches (at most nb).  A grid served in one batch takes launch_accumulate itself:
+// the same chunks, the same order.
+__global__ __launch_bounds__(EW_THREADS) void accumulate_grid_partial_kernel(
+    int n2, int m0, int nb, int c_first, const cplx* __restrict__ w, const cplx* __restrict__ X,
+    const cplx* __restrict__ carry, cplx* __restrict__ part)
+{
+    const int i = blockIdx.x * EW_THREADS + threadIdx.x;
+    const int c = c_first + blockIdx.y;
+    if (i >= n2) return;
+    const int b0 = max(c * ACC_CHUNK, m0) - m0, b1 = min((c + 1) * ACC_CHUNK, m0 + nb) - m0;
+    cplx a = c * ACC_CHUNK < m0 ? carry[i] : cmake(0.0, 0.0);
+    int b = b0;
+    for (; b + 4 <= b1; b += 4) {
+        const cplx x0 = X[(size_t)(b + 0) * n2 + i], x1 = X[(size_t)(b + 1) * n2 + i];
+        const cplx x2 = X[(size_t)(b + 2) * n2 + i], x3 = X[(size_t)(b + 3) * n2 + i];
+        a = cfma(a, w[b + 0], x0); a = cfma(a, w[b + 1], x1);
+        a = cfma(a, w[b + 2], x2); a = cfma(a, w[b + 3], x3);
+    }
+    for (; b < b1; ++b) a = cfma(a, w[b], X[(size_t)b * n2 + i]);
+    part[(size_t)blockIdx.y * n2 + i] = a;
+}
+
+__global__ __launch_bounds__(EW_THREADS) void accumulate_grid_final_kernel(
+    int n2, int nchunks, int last_open, const cplx* __restrict__ part, cplx* __restrict__ carry, cplx* __restrict__ acc)
+{
+    const int i = blockIdx.x * EW_THREADS + threadIdx.x;
+    if (i >= n2) return;
+    const int closed = nchunks - last_open;
+    if (closed > 0) {
+        cplx a = acc[i];
+        for (int c = 0; c < closed; ++c) a = cadd(a, part[(size_t)c * n2 + i]);
+        acc[i] = a;
+    }
+    if (last_open) carry[i] = part[(size_t)(nchunks - 1) * n2 + i];
+}
+
+void launch_accumulate_grid(hipStream_t st, int n2, int m, int m0, int nb, const cplx* w, const cplx* X, cplx* carry, cplx* part, cplx* acc)
+{
+    if (nb <= 0) return;
+    if (m0 == 0 && nb >= m) { launch_accumulate(st, n2, nb, w, X, acc, part); return; }
+    const int c_first = m0 / ACC_CHUNK, c_last = (m0 + nb - 1) / ACC_CHUNK;
+    const int nchunks = c_last - c_first + 1;
+    // the last chunk stays open when the grid goes on behind this batch inside it
+    const int last_open = (m0 + nb < m && (m0 + nb) % ACC_CHUNK != 0) ? 1 : 0;
+    const int g = (n2 + EW_THREADS - 1) / EW_THREADS;
+    hipLaunchKernelGGL(accumulate_grid_partial_kernel, dim3(g, nchunks), dim3(EW_THREADS), 0, st, n2, m0, nb, c_first, w, X, carry, part);
+    hipLaunchKernelGGL(accumulate_grid_final_kernel, dim3(g), dim3(EW_THREADS), 0, st, n2, nchunks, last_open, part, carry, acc);
+}
+
 // ------------------------------------------------------------------ nested refinement (density.py:239-268)
 // One workgroup per integral.  sums [levels][n2]: the weighted sums over the NEW nodes of consecutive levels of the nested rule;
 // the reference's update and stopping test, level by level and in its operation order:

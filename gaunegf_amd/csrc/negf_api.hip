@@ -128,7 +128,7 @@ void free_workspace(negf_ctx* c, bool all = false)
     release_bufs(c->d_blk, c->d_scratch, c->d_gsmall, c->d_small_part);
     if (all) release_bufs(c->d_seg_out, c->d_ref_P, c->d_chan, c->d_chan_rank, c->d_chan_T, c->d_chan_psi, c->d_bond_map, c->d_bond_carry, c->d_bond_T, c->d_pop_W, c->d_pop_Wt,
                           c->d_tmat_H, c->d_tmat_sig, c->d_tmat_gam, c->d_tmat_work, c->d_tmat_tab,
-                          c->d_deph_T, c->d_deph_R, c->d_deph_work, c->d_deph_D, c->d_deph_tab);
+                          c->d_deph_T, c->d_deph_R, c->d_deph_work, c->d_deph_D, c->d_deph_carry, c->d_deph_tab);
 }
 
 void free_mbuffers(negf_ctx* c)
@@ -272,7 +272,10 @@ int ensure_workspace(negf_ctx* c, int m, int blk_stride, int min_batch = 1)
     const int covers = (c->transmission_seen ? 2 : 1) * std::max(m, 1);
     const int want = (c->batch_user == 0 && c->batch >= std::min(covers, 4096) && c->batch >= min_batch)
                          ? c->batch : std::max(auto_batch(c, m), min_batch);
-    if (want > c->batch) {
+    // (a limit set with negf_set_batch holds for a workspace already in place: one larger than the limit -- and than the two
+    //  energies a transmission call needs -- is released and rebuilt at `want`; no dense call sweeps more than the limit)
+    const bool over_limit = c->batch_user > 0 && c->batch > std::max(c->batch_user, min_batch);
+    if (want > c->batch || over_limit) {
         free_workspace(c);
         const size_t n2 = (size_t)c->n * c->n;
         int rc;
@@ -3009,6 +3012,7 @@ int negf_gless_int_probes_dev(negf_ctx* c, int handle, int ind, int n_probes, co
             if ((e = ensure_cap(c, c->d_deph_R, (size_t)n_probes * nc * batch))) return e;
         }
         if (compact && (e = ensure_cap(c, c->d_deph_D, (size_t)KU * KU * batch))) return e;
+        if (batch < m && (e = ensure_cap(c, c->d_deph_carry, n2))) return e;      // (a grid in one batch carries nothing)
         return clear_first(c, out, n2 * sizeof(cplx))(batch);
     };
     return dense_batches(c, p, m, setup, [&](int m0, int nb) {
@@ -3024,7 +3028,8 @@ int negf_gless_int_probes_dev(negf_ctx* c, int handle, int ind, int n_probes, co
         }
         { ProfScope ps(c, "zgemm"); launch_g_d_gh(c, nb, KU, compact ? d_U : nullptr, D, sD); }      // as run_gless_products
         ProfScope ps(c, "accumulate");
-        launch_accumulate(c->stream, (int)n2, nb, w + m0, c->W1, out, c->W2);
+        // (the grid's 32-energy chunks, not the batch's: the bits do not depend on the batch -- launch_bond_int's order)
+        launch_accumulate_grid(c->stream, (int)n2, m, m0, nb, w + m0, c->W1, c->d_deph_carry, c->W2, out);
         return NEGF_OK;
     });
 }

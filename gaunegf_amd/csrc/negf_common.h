@@ -328,6 +328,7 @@ struct negf_ctx {
     DevBuf<double> d_deph_R;       // [batch][P][n_c] responses of the batch (negf_gless_int_probes) / [m][P][n_c] staging of negf_probe_response
     DevBuf<double> d_deph_work;    // [energies in flight][P (P + n_c)] augmented matrices of the response kernel's global class
     DevBuf<cplx> d_deph_D;         // [batch][K_U^2] dephased coupling matrices on the union of the orbitals involved
+    DevBuf<cplx> d_deph_carry;     // [n*n] running sum of the 32-energy chunk a batch boundary cuts (negf_gless_int_probes)
     DevBuf<int> d_deph_tab;        // the union U [K_U] | the terminals' orbital lists as positions in U | the terminals added, in order
     GjSideStreams gj_side;
     GjRecord gj_last;              // what the last run_inverse / rgf_inverse launched (negf_inverse_last)
@@ -395,6 +396,10 @@ void launch_accumulate(hipStream_t st, int n2, int nb, const cplx* w, const cplx
 // the same sum over matrices still in their reduced, un-gathered form: X[b][i][j] = W[b][pivrow_b[i]][colof_b[j]] (piv = [nb][2][n];
 // a matrix with info[b] != 0 counts as NaN, as its gathered form would)
 void launch_accumulate_perm(hipStream_t st, int n, int nb, const cplx* w, const cplx* W, const int* piv, const int* info, cplx* acc, cplx* part);
+// launch_accumulate for the batch [m0, m0 + nb) of a grid of m energies (w, X indexed from the batch's first energy), bitwise
+// independent of the batch cut: the chunks are the grid's; carry [n2] lives across the batches of one grid, part holds one
+// record per chunk the batch touches (at most nb).  A grid in one batch is launch_accumulate itself.
+void launch_accumulate_grid(hipStream_t st, int n2, int m, int m0, int nb, const cplx* w, const cplx* X, cplx* carry, cplx* part, cplx* acc);
 bool launch_accumulate_ranges(hipStream_t st, int n, bool perm, const cplx* w, const cplx* XW, const int* piv, const int* info,
                               int nranges, const int* lo, const int* hi, const int* slot, cplx* out, cplx* part);
 // nested refinement on the device (density.py:239-268): see refine_levels_kernel

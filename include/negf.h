@@ -73,7 +73,24 @@ const char* negf_version(void);
  * of each other, whatever their streams. */
 int         negf_set_stream(negf_ctx* ctx, void* hip_stream);
 /* energies processed per sweep of the workspace (0 = choose from n and free HBM);
- * replaces MAX_VMAP_MEMORY_GB batching, integrate.py:55,100-142 */
+ * replaces MAX_VMAP_MEMORY_GB batching, integrate.py:55,100-142.
+ * batch = b > 0 is a LIMIT, for memory as well (what a caller who shares a device sets it for): from the next call on no
+ * dense call sweeps more than b energies, and the workspace -- three n x n matrices per energy, the bulk of what a
+ * context holds -- holds no more than b of them.  (What shrinks is that workspace with its pivot, site and Sigma-block
+ * staging; the smaller per-sweep areas of single entry points -- channels, transmission matrix, probes, segment sums --
+ * only grow, and keep the size of the largest sweep they have served until the system's dimension changes.)
+ * A workspace in place that is larger than b is released and rebuilt at min(b, m) for the call's m energies; one that is
+ * not larger is kept, or grown to min(b, m) where the grid asks for it.  negf_transmission needs two energies' worth
+ * and sweeps half of what stands: b = 1 gives a workspace of 2 and sweeps of 1, b = 6 sweeps of 3.  batch = 0 lifts the
+ * limit: the workspace then only grows, to the grid (twice the grid once a transmission has run on the context) within
+ * the memory budget.  negf_get_batch and negf_workspace_bytes report the workspace in place.
+ * Per-energy results, and the sums whose comment below says so, do not depend on the limit AS LONG AS the inverse takes the
+ * same kernels for the sweeps compared: "do not depend on negf_set_batch" below is to be read with that condition.  The
+ * inverse chooses its kernels from n and the number of energies in a sweep (negf_inverse_plan reports the choice); two
+ * sweep sizes with different plans give G(E) that differ in rounding, each within the accuracy bound of the inverse, not
+ * the same bits.  The other weighted sums (negf_gr_int, negf_gless_int, their _seg forms, negf_gr_int_probes,
+ * negf_gr_int_refine) add 32 energies of a SWEEP at a time: their bits depend on the sweeps, within the summation bound
+ * of DESIGN.md's accumulate section. */
 int         negf_set_batch(negf_ctx* ctx, int batch);
 int         negf_get_batch(negf_ctx* ctx);
 
@@ -513,7 +530,9 @@ int negf_probe_response_dev(negf_ctx* ctx, int handle, int n_probes, const int* 
  * effective transmission with the probes floating, and probes of zero strength give negf_gless_int's result.  The
  * contacts' matrices are the blocks negf_transmission_matrix uses.  out is n x n, Hermitian for real weights.  A singular
  * energy enters as negf_gless_int's does.  Overlapping probes are added in an order derived from their content: the
- * result does not depend on the caller's probe order, nor on negf_set_batch. */
+ * result does not depend on the caller's probe order, nor on negf_set_batch: the weighted sum adds the energies
+ * [32 c, 32 c + 32) OF THE GRID from zero, then the chunk sums in ascending order, and a chunk that a sweep boundary cuts
+ * waits in a carry buffer for the next sweep (negf_bond_int's order). */
 int negf_gless_int_probes(negf_ctx* ctx, int handle, int ind, int n_probes, const int* probe_nk, const int* probe_inds,
                           const double* probe_sigma_c128, int m, const double* E_c128, const double* w_c128,
                           double* out_c128, int* info);

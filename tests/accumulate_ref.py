@@ -228,3 +228,58 @@ def model_segments(w, X, seg_end, batch, defect=None, perm_seed=1):
             for where, rec in records:
                 out[where] = out[where] + rec
     return out
+
+
+# ------------------------------------------------------------------ float64 model of the grid-chunked sum with carry
+GRID_DEFECTS = ("carry_dropped", "carry_twice", "chunk_from_sweep", "open_chunk_closed_early", "weight_from_sweep_start")
+
+
+def model_grid_sum(w, X, batch, defect=None):
+    """out [n][n] as negf_gless_int_probes forms its weighted sum (launch_accumulate_grid, k_elementwise.hip; the order of
+    launch_bond_int), in float64: the grid is swept `batch` energies at a time, but chunk c is the energies [32 c, 32 c + 32)
+    OF THE GRID, added from zero with cfma in ascending order, and out receives the chunk sums in ascending chunk order.  A
+    chunk that a sweep boundary cuts waits in `carry` and the next sweep continues it.  `defect` plants one of GRID_DEFECTS
+    at every place it can act:
+        carry_dropped            the continued chunk starts from zero
+        carry_twice              the open chunk's running sum goes to the carry AND to out
+        chunk_from_sweep         chunks are counted from the sweep's first energy (launch_accumulate per sweep: no carry)
+        open_chunk_closed_early  the open last chunk is added to out as if finished; the carry keeps what it held
+        weight_from_sweep_start  w[m0 + b] read as w[b]"""
+    w = np.asarray(w, dtype=np.complex128).ravel()
+    m, n = w.size, X[0].shape[0]
+    out = np.zeros((n, n), dtype=np.complex128)
+    carry = np.zeros((n, n), dtype=np.complex128)
+    for m0 in range(0, m, batch):
+        nb = min(batch, m - m0)
+        if defect == "chunk_from_sweep":
+            cuts = [(b0, min(m0 + nb, b0 + ACC_CHUNK), False, False) for b0 in range(m0, m0 + nb, ACC_CHUNK)]
+        else:
+            cuts = []
+            for c in range(m0 // ACC_CHUNK, (m0 + nb - 1) // ACC_CHUNK + 1):
+                g0, g1 = max(c * ACC_CHUNK, m0), min((c + 1) * ACC_CHUNK, m0 + nb)
+                continued = c * ACC_CHUNK < m0
+                is_open = g1 == m0 + nb and g1 < m and g1 % ACC_CHUNK != 0
+                cuts.append((g0, g1, continued, is_open))
+        for g0, g1, continued, is_open in cuts:
+            if continued and defect != "carry_dropped":
+                ar, ai = carry.real.copy(), carry.imag.copy()
+            else:
+                ar = np.zeros((n, n)); ai = np.zeros((n, n))
+            for g in range(g0, g1):
+                wb = w[g - m0] if defect == "weight_from_sweep_start" else w[g]
+                ar, ai = _cfma(ar, ai, wb, np.asarray(X[g], dtype=np.complex128))
+            rec = ar + 1j * ai
+            if is_open and defect == "open_chunk_closed_early":
+                out = out + rec
+            elif is_open:
+                carry = rec
+                if defect == "carry_twice":
+                    out = out + rec
+            else:
+                out = out + rec
+    return out
+
+
+def sweeps_of(m, batch):
+    """[(m0, nb)]: the sweeps of a grid of m energies under a workspace of `batch`."""
+    return [(m0, min(batch, m - m0)) for m0 in range(0, m, batch)]

@@ -30,9 +30,9 @@ class _System:
     def __enter__(self):
         F, S, sig = R.const_system(self.n, 500 + self.n)
         if self.batch:
-            # the workspace only grows while n stands, and a sweep takes all of it: negf_set_batch below a workspace in
-            # place changes nothing.  A system of another size drops the workspace; the next one is built to the limit
-            # (swept() holds the call to it).
+            # a system of another size drops the workspace, so the next one is built to the limit whatever stood before
+            # (a workspace above the limit is rebuilt by the library itself; one below it but above the grid is kept);
+            # swept() holds the call to it.
             self.engine.set_system(np.eye(2), np.eye(2))
         self.engine.set_system(F, S)
         self.h = self.engine.sigma_const(sig)

@@ -25,7 +25,7 @@ import pytest
 import scipy.linalg as sla
 
 import bond_ref as br
-from helpers import chain_lead, random_system
+from helpers import chain_lead, random_system, swept
 
 pytestmark = pytest.mark.gpu
 
@@ -433,6 +433,7 @@ def test_bitwise_run_to_run_and_batch(engine):
             try:
                 cut = [engine.local_transmission(h, 0, E), engine.local_transmission(h, 0, E, groups),
                        engine.bond_int(h, 0, E, w)]
+                swept(engine, batch, E.size)
             finally:
                 engine.set_batch(0)
             for a, b in zip(ref, cut):
@@ -493,7 +494,9 @@ def test_neighbouring_entry_points_unchanged(engine):
             engine.set_batch(7)
             try:
                 engine.bond_int(h, 1, E, np.real(w))
+                swept(engine, 7, E.size)
                 engine.local_transmission(h, 1, E, np.arange(n) % 3)
+                swept(engine, 7, E.size)
             finally:
                 engine.set_batch(0)
             after = (engine.transmission(h, 0, 1, E), engine.gless_int(h, 0, E, w), engine.gless_int(h, None, E, w))

@@ -14,7 +14,7 @@ import textwrap
 import numpy as np
 import pytest
 
-from helpers import chain_lead, random_system
+from helpers import chain_lead, random_system, swept
 
 pytestmark = pytest.mark.gpu
 
@@ -120,7 +120,9 @@ def test_default_rule_chunked(rule, engine, ncL, ncR):
         engine.set_batch(0); engine.set_chain_round_robin(0, 0)
         ref = s.sigma(s.provider(), E)
         engine.set_batch(6); engine.set_chain_round_robin(-1, SLOTS)
-        _same(s.sigma(h, E), ref, f"shift {shift}")
+        got = s.sigma(h, E)
+        swept(engine, 6, M)
+        _same(got, ref, f"shift {shift}")
 
 
 _CHILD = """

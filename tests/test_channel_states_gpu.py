@@ -17,7 +17,7 @@ import pytest
 
 import channel_states_ref as R
 import xprec_channels as X
-from helpers import random_system
+from helpers import random_system, swept
 
 pytestmark = pytest.mark.gpu
 
@@ -283,6 +283,7 @@ def test_batch_streaming_bitwise(engine):
         engine.set_batch(3)
         try:
             T3, p3 = engine.channel_states(h, 0, 1, E)
+            swept(engine, 3, E.size)
         finally:
             engine.set_batch(0)
         T0, p0 = engine.channel_states(h, 0, 1, E)

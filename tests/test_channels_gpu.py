@@ -7,7 +7,7 @@ import warnings
 import numpy as np
 import pytest
 
-from helpers import random_system
+from helpers import random_system, swept
 
 pytestmark = pytest.mark.gpu
 
@@ -272,6 +272,7 @@ def test_batch_streaming_bitwise(engine):
         engine.set_batch(5)
         try:
             streamed = engine.transmission_channels(h, 0, 1, E)
+            swept(engine, 5, E.size)
         finally:
             engine.set_batch(0)
         wide = engine.transmission_channels(h, 0, 1, E, nchan=9)

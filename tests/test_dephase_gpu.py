@@ -28,7 +28,7 @@ import pytest
 
 import dephase_ref as dr
 import tmatrix_ref as tr
-from helpers import random_system
+from helpers import random_system, swept
 
 pytestmark = pytest.mark.gpu
 
@@ -120,6 +120,7 @@ def test_response_in_several_chunks(engine):
             R = engine.probe_response(h, E, c.probes)
             T = engine.transmission_matrix(h, E, c.probes)
             again = engine.probe_response(h, E, c.probes)
+            swept(engine, 220, E.size)
     finally:
         engine.set_batch(0)
     par = np.abs(R - probe_response(T, 2)).max(axis=(1, 2))
@@ -266,6 +267,7 @@ def _bitwise(engine, h, E, probes, n_c):
         engine.set_batch(batch)
         try:
             cut = call(probes)
+            swept(engine, batch, E.size)
         finally:
             engine.set_batch(0)
         for a, b in zip(cut, ref):

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import MockSigma, chain_lead, const_sigma_pair, random_system, rel_fro
+from helpers import MockSigma, chain_lead, const_sigma_pair, random_system, rel_fro, swept
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-8
@@ -262,13 +262,18 @@ def test_api_assertions_and_edges(engine):
     # empty grid (callers pass boolean-masked slices that may be empty, density.py:254)
     out = GrInt(F, S, g_dev, np.array([]), np.array([]))
     assert out.shape == (8, 8) and not np.any(out)
-    # a single point, and a workspace batch smaller than the grid (multi-sweep)
+    # a single point, and a workspace batch smaller than the grid (multi-sweep).  At n = 8 GrInt takes the fused small path,
+    # which has no workspace and is not cut by the limit; GrLessInt's sweeps are, and so are GrInt's at n = 130
     E, w = oracle.real_axis_grid(-3, 0.1, 23, 300.0)
     ref = oracle.GrInt(F, S, g_ref, E, w)
     engine.set_batch(5)
     try:
         assert rel_fro(GrInt(F, S, g_dev, E, w), ref) < TOL
         assert rel_fro(GrLessInt(F, S, g_dev, E, w, -1), oracle.GrLessInt(F, S, g_ref, E, w, -1)) < TOL
+        swept(engine, 5, E.size)
+        F2, S2, g2_dev, g2_ref = _const_provider(130, 3)
+        assert rel_fro(GrInt(F2, S2, g2_dev, E, w), oracle.GrInt(F2, S2, g2_ref, E, w)) < TOL
+        swept(engine, 5, E.size)
     finally:
         engine.set_batch(0)
     assert rel_fro(GrInt(F, S, g_dev, E[:1], w[:1]), oracle.GrInt(F, S, g_ref, E[:1], w[:1])) < TOL
@@ -756,6 +761,7 @@ def test_chain1d_order_prediction_over_batch_chunks(engine):
             sig0, it0, cv0 = g_fresh.sigma_batch(E)
             engine.set_batch(16)                                # 50 energies -> chunks of 16, 16, 16, 2
             sig1, it1, cv1 = g_seq.sigma_batch(E)
+            swept(engine, 16, E.size)
             assert np.array_equal(it0, it1) and np.array_equal(cv0, cv1) and np.array_equal(sig0, sig1), E.size
     finally:
         engine.set_batch(0)

@@ -26,7 +26,7 @@ import scipy.linalg as sla
 import bond_ref as br
 import population_ref as pr
 import xprec
-from helpers import chain_lead, random_system
+from helpers import chain_lead, random_system, swept
 
 pytestmark = pytest.mark.gpu
 
@@ -268,6 +268,7 @@ def test_bitwise_run_to_run_batch_and_relabelling(engine):
             engine.set_batch(batch)
             try:
                 cut = everything()
+                swept(engine, batch, E.size)
             finally:
                 engine.set_batch(0)
             for a, b in zip(ref, cut):

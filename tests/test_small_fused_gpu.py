@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import MockSigma, chain_lead, const_sigma_pair, random_system, rel_fro
+from helpers import MockSigma, chain_lead, const_sigma_pair, random_system, rel_fro, swept
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-8
@@ -319,6 +319,7 @@ def test_segments_across_workspace_chunks(engine):
     engine.set_batch(5)
     try:
         got = GrIntSegments(F, S, g, segs)
+        swept(engine, 5, sum(E.size for E, _ in segs))
     finally:
         engine.set_batch(0)
     for a, b in zip(got, ref):
@@ -340,6 +341,8 @@ def test_segments_on_the_windowed_inverse_and_on_spin_blocks(engine):
         engine.set_batch(batch)
         try:
             got = GrIntSegments(F, S, g, segs)
+            if batch:
+                swept(engine, batch, sum(E.size for E, _ in segs))
         finally:
             engine.set_batch(0)
         for a, b in zip(got, ref):
@@ -490,6 +493,7 @@ def test_segmented_lesser_integrals_and_adaptive_bias_window(engine, N, capsys):
     engine.set_gamma_algo(1); engine.set_batch(7)
     try:
         dense = GrLessIntSegments(F, S, g, segs, -1)
+        swept(engine, 7, sum(E.size for E, _ in segs))
     finally:
         engine.set_gamma_algo(0); engine.set_batch(0)
     for a, (E, w) in zip(dense, segs):

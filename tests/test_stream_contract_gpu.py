@@ -35,7 +35,7 @@ import pytest
 import torch    # at collection, before any engine exists: the library then binds to the HIP runtime torch has loaded (as
                 # under bench.py); loaded after the library, torch brings a second copy of the runtime and sees no GPU
 
-from helpers import chain_lead, random_system
+from helpers import chain_lead, random_system, swept
 from test_small_fused_gpu import _const
 
 pytestmark = pytest.mark.gpu
@@ -245,6 +245,8 @@ class Private:
         if key not in self.refs:
             E, w = _grid(case, k)
             r = _f64(op.host(self.eng, H, E, w)).copy()
+            if SPECS[case].n > 96 and not SPECS[case].layered:          # (below, gr_int and gr_int_seg have no workspace)
+                swept(self.eng, SPECS[case].batch, E.size, transmission=op.name.startswith("transmission"))
             r.setflags(write=False)
             self.refs[key] = r
             self.ref_batch[key] = self.eng.get_batch()                  # how the workspace grouped its sums
@@ -492,7 +494,7 @@ def test_f_info_after_an_asynchronous_call(priv, n):
     eng = priv.eng
     m, at = 12, 5
     _, S = random_system(n, 7)
-    eng.set_batch(16)
+    eng.set_batch(16)                                   # (above the 12 energies: one sweep, nothing is cut)
     eng.set_system(S, S)
     h = eng.sigma_precomputed(np.zeros((m, n, n), dtype=complex))
     try:

@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 import tmatrix_ref as tr
-from helpers import chain_lead, random_system
+from helpers import chain_lead, random_system, swept
 
 pytestmark = pytest.mark.gpu
 
@@ -189,6 +189,7 @@ def test_bitwise_run_to_run_batch_and_probe_order(engine, idx):
             engine.set_batch(batch)
             try:
                 cut = engine.transmission_matrix(h, E, c.probes)
+                swept(engine, batch, E.size)
             finally:
                 engine.set_batch(0)
             assert np.array_equal(cut, ref), batch
