@@ -168,6 +168,16 @@ __device__ __forceinline__ cplx rs_cmul_pinned(cplx a, cplx b)
 #pragma clang fp contract(off)
     return cmake(__builtin_fma(a.x, b.x, -(a.y * b.y)), __builtin_fma(a.y, b.x, a.x * b.y));
 }
+// a b of the deferred pivot-row scaling.  The same value as rs_cmul_pinned; the rounded product of the real part passes through
+// an empty asm so that its sign stays on the addend of the fused operation (v_fma r r -r, the instruction the generic code
+// holds there and scripts/isa_fp64_compare.py counts) instead of moving into a factor of the product
+__device__ __forceinline__ cplx rs_scale_pinned(cplx a, cplx b)
+{
+#pragma clang fp contract(off)
+    double t = a.y * b.y;
+    asm("" : "+v"(t));
+    return cmake(__builtin_fma(a.x, b.x, -t), __builtin_fma(a.y, b.x, a.x * b.y));
+}
 __device__ __forceinline__ cplx rs_cfma_pinned(cplx a, cplx coef, cplx rb)
 {
 #pragma clang fp contract(off)
@@ -213,7 +223,11 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
 {
     const int r = rs_opaque(lane);                      // (see rs_opaque: nothing derived from the lane index is
     cplx a[NBW];                                        //  hoisted out of the fixed-point loop and kept alive)
-    bool avail = r < n && colof[r] < 0;
+    // the rows that may still become pivots, one bit per lane in a scalar register pair: the column steps combine it
+    // with their compare masks by scalar and / and-not, and no lane carries a flag of its own through selects
+    int cr = 0;
+    if (r < n) cr = colof[r];
+    unsigned long long avail = __builtin_amdgcn_ballot_w64(cr < 0);
     cplx myip = cmake(1.0, 0.0);
     cplx* wrow = W + r * P + p0;                        // rows >= n are zero padding
 #pragma unroll
@@ -229,25 +243,24 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             unsigned long long tq0 = 0, tq1 = 0, tq2 = 0, tq3 = 0, tq4 = 0;
             if (stamp_here) tq0 = __builtin_amdgcn_s_memtime();
             const double v = cabs1(a[j]);
-            const unsigned hi = (avail && v == v) ? (unsigned)__double2hiint(v) : 0u;
+            const bool usable = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64(v == v) & avail);
+            const unsigned hi = usable ? (unsigned)__double2hiint(v) : 0u;
             const unsigned m = rs_wave_max_u32(hi);
-            int pphys;
-            if (m != 0) {
-                pphys = (int)__ffsll((unsigned long long)__ballot(hi == m)) - 1;
-            } else {                                    // no usable candidate (zero / NaN column): lowest available row
-                const unsigned long long av = __ballot(avail);
-                pphys = av ? (int)__ffsll(av) - 1 : 0x7fffffff;
-            }
-            pphys = __builtin_amdgcn_readfirstlane(pphys);
+            // the lowest available row whose key equals the maximum.  With no usable candidate (m == 0: a zero / NaN column)
+            // every available row has the key 0, and that is the lowest available row; with none available no lane
+            // equals -1 and the step has no pivot lane.  One straight line, no branch on m.
+            const unsigned long long cand = __builtin_amdgcn_ballot_w64(hi == m) & avail;
+            const int pphys = cand ? __builtin_ctzll(cand) : -1;
             if (stamp_here) tq1 = __builtin_amdgcn_s_memtime();
             const bool is_piv = r == pphys;
+            avail &= ~__builtin_amdgcn_ballot_w64(is_piv);
             cplx rb[NBW];
             // through a 256-byte LDS line: one lane writes its 16 values, all lanes read them back.  The wave-level
             // barriers keep the compiler from ordering the two sides of the divergent branch the other way round
             // (it does, without them), the LDS then executes the wave's instructions in order
             __builtin_amdgcn_wave_barrier();            // the reads of the previous column step are issued
             if (is_piv) {
-                pivrow[p0 + j] = pphys; colof[pphys] = p0 + j;
+                pivrow[p0 + j] = r; colof[r] = p0 + j;
 #pragma unroll
                 for (int s = 0; s < NBW; ++s) rowline[s] = a[s];
             }
@@ -259,7 +272,16 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             if (stamp_here) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tq2 = __builtin_amdgcn_s_memtime(); }
             const cplx ip = rs_factor_recip<PINNED>(rb[j], j == RS_NB - 1);
             const cplx mf = cneg(rs_factor_cmul<PINNED>(a[j], ip));
-            const cplx coef = cmake(is_piv ? 0.0 : mf.x, is_piv ? 0.0 : mf.y);
+            // the pivot lane's own values -- multiplier 0, a one in the pivot column, its reciprocal -- are moves under an exec
+            // mask that holds that lane alone, not selects in every lane (the empty asm keeps the branch from becoming
+            // selects again).  The lane stays in the update below: a + 0 rb, NaN where its row is not finite.  The imaginary
+            // part of the new a[j] is that of the multiplier in every lane.
+            cplx coef = mf;
+            cplx aj = mf;
+            if (is_piv) {
+                coef = cmake(0.0, 0.0); aj = cmake(1.0, 0.0); myip = ip;
+                asm("" : "+v"(aj.x));
+            }
             if (stamp_here) { asm volatile("" :: "v"(coef.x), "v"(coef.y)); tq3 = __builtin_amdgcn_s_memtime(); }
 #pragma unroll
             for (int s = 0; s < NBW; ++s) a[s] = rs_factor_cfma<PINNED>(a[s], coef, rb[s]);
@@ -269,15 +291,16 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
                 tq4 = __builtin_amdgcn_s_memtime();
                 if (lane == 0) { fst[0] = tq0; fst[1] = tq1; fst[2] = tq2; fst[3] = tq3; fst[4] = tq4; }
             }
-            a[j] = is_piv ? cmake(1.0, 0.0) : coef;
-            myip = cmake(is_piv ? ip.x : myip.x, is_piv ? ip.y : myip.y);
-            avail = avail && !is_piv;
+            a[j] = aj;
         }
     }
+    // the deferred pivot-row scaling, pinned in every instantiation: where no test lies between them (the full panels of the
+    // stage schedule) it shares a basic block with the last column step's update, and the compiler's choice of the fused
+    // product in its imaginary part then follows whatever else that block holds
     if (r < n) {
 #pragma unroll
         for (int s = 0; s < NBW; ++s)
-            if (s < pw) wrow[s] = rs_factor_cmul<PINNED>(a[s], myip);     // the deferred pivot-row scaling
+            if (s < pw) wrow[s] = PINNED ? rs_cmul_pinned(a[s], myip) : rs_scale_pinned(a[s], myip);
     }
 }
 
