@@ -217,25 +217,42 @@ __device__ __forceinline__ cplx rs_factor_cfma(cplx a, cplx coef, cplx rb)
 }
 
 // NBW: columns the code is written for (pw <= NBW).  PINNED: the arithmetic in the written-out form above (rs_*_pinned).
-template <int P, int NBW = RS_NB, bool PINNED = false>
+// avail: the rows that may still become pivots, one bit per lane in a scalar register pair: the column steps combine it
+// with their compare masks by scalar and / and-not, and no lane carries a flag of its own through selects.  The mask belongs
+// to the CALLER.  The stage schedule starts every inverse with rs_rows_mask(n) and hands the same mask to every panel
+// (reread = false): only the factoring wave writes colof during an inverse, so the mask IS colof[r] < 0, without the LDS
+// round trip behind the look-ahead barrier.  The generic loop has it read from colof at every panel (reread = true).
+// ROWS: rows of the work matrix (16 T16).  The panel is loaded WITHOUT a test on r < n: the lanes n <= r < 64 read row
+// min(r, ROWS - 1) -- inside W in every class -- and carry whatever lies there through the column steps (zero padding, or,
+// when three workgroups share a CU, the old iterate's slots, Inf / NaN when the iterate is).  Nothing of it is used: such a
+// lane is never in avail, so its key is 0 (usable = finite & avail) and it is never a candidate, never is_piv, never writes
+// the LDS line or a table entry, and its write-back is under r < n.
+__device__ __forceinline__ unsigned long long rs_rows_mask(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }   // ballot(lane < n), scalar
+
+template <int P, int ROWS, int NBW = RS_NB, bool PINNED = false>
 __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colof, cplx* rowline /*[16] LDS*/,
-                                          int p0, int pw, int lane, unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */)
+                                          int p0, int pw, int lane, unsigned long long& avail, bool reread,
+                                          unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */)
 {
     const int r = rs_opaque(lane);                      // (see rs_opaque: nothing derived from the lane index is
     cplx a[NBW];                                        //  hoisted out of the fixed-point loop and kept alive)
-    // the rows that may still become pivots, one bit per lane in a scalar register pair: the column steps combine it
-    // with their compare masks by scalar and / and-not, and no lane carries a flag of its own through selects
-    int cr = 0;
-    if (r < n) cr = colof[r];
-    unsigned long long avail = __builtin_amdgcn_ballot_w64(cr < 0);
+    if (reread) {
+        int cr = 0;
+        if (r < n) cr = colof[r];
+        avail = __builtin_amdgcn_ballot_w64(cr < 0);
+    }
     cplx myip = cmake(1.0, 0.0);
-    cplx* wrow = W + r * P + p0;                        // rows >= n are zero padding
+    cplx* wrow = W + min(r, ROWS - 1) * P + p0;         // (the row itself wherever it is written back: r < n)
 #pragma unroll
     for (int s = 0; s < NBW; ++s) {
         const cplx v = wrow[s];
-        const bool ok = (r < n) & (s < pw);
+        const bool ok = s < pw;                         // (folds where pw is a constant: the full panels of the stage schedule)
         a[s] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
     }
+    // the pivot tables of the panel, stored once behind the last column step (nobody reads them before the barrier that closes
+    // the stage): lane j holds pivrow[p0 + j], the pivot lane of a step the column it took.  -1: nothing to store -- the
+    // lanes j >= pw, the rows that were no pivot here, and a step that found no row available (it leaves both tables alone)
+    int prow = -1, mycol = -1;
 #pragma unroll
     for (int j = 0; j < NBW; ++j) {
         if (j < pw) {
@@ -259,8 +276,8 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             // barriers keep the compiler from ordering the two sides of the divergent branch the other way round
             // (it does, without them), the LDS then executes the wave's instructions in order
             __builtin_amdgcn_wave_barrier();            // the reads of the previous column step are issued
+            asm("v_writelane_b32 %0, %1, %2" : "+v"(prow) : "s"(pphys), "n"(j));
             if (is_piv) {
-                pivrow[p0 + j] = r; colof[r] = p0 + j;
 #pragma unroll
                 for (int s = 0; s < NBW; ++s) rowline[s] = a[s];
             }
@@ -280,6 +297,7 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
             cplx aj = mf;
             if (is_piv) {
                 coef = cmake(0.0, 0.0); aj = cmake(1.0, 0.0); myip = ip;
+                mycol = p0 + j;
                 asm("" : "+v"(aj.x));
             }
             if (stamp_here) { asm volatile("" :: "v"(coef.x), "v"(coef.y)); tq3 = __builtin_amdgcn_s_memtime(); }
@@ -302,6 +320,8 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
         for (int s = 0; s < NBW; ++s)
             if (s < pw) wrow[s] = PINNED ? rs_cmul_pinned(a[s], myip) : rs_scale_pinned(a[s], myip);
     }
+    if (prow >= 0) pivrow[p0 + r] = prow;
+    if (mycol >= 0) colof[r] = mycol;
 }
 
 // ---- trailing update with panel [p0, p0+pw), in place:
@@ -619,7 +639,10 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
             // the factoring wave is its workgroup's critical path (the others wait for it at the barrier):
             // it goes first when it shares its SIMD's issue slots with waves of the other workgroups
             __builtin_amdgcn_s_setprio(3);
-            if (!(RS_ABLATE & 1)) rs_factor<P>(n, W, pivrow, colof, rowline, n0, nw, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
+            // (the generic loop reads the available rows from colof at every panel: the factoring wave changes with the panel
+            // when the roles go by wave number, and a mask carried through this loop costs classes 57 / 65 scratch)
+            unsigned long long avail = 0;
+            if (!(RS_ABLATE & 1)) rs_factor<P, 16 * T16>(n, W, pivrow, colof, rowline, n0, nw, lane, avail, true, (st && sgi + 1 == 1) ? st + 40 : nullptr);
             else if (lane < nw) { pivrow[n0 + lane] = n0 + lane; colof[n0 + lane] = n0 + lane; }
             __builtin_amdgcn_s_setprio(0);
             if (st && lane == 0) st[17 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
@@ -787,6 +810,7 @@ __device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, in
     auto stamp = [&]() __attribute__((always_inline)) { if (st && tid == 0) st[sti] = __builtin_amdgcn_s_memrealtime(); ++sti; };
     // this role's jobs of the full stages (roles 0 .. 2; role 3 factors)
     wave = __builtin_amdgcn_readfirstlane(wave);                // (the same in every lane: the table stays in scalar registers)
+    unsigned long long avail = rs_rows_mask(n);                 // the rows still to become pivots, carried through the panels (rs_factor)
     const unsigned long long jobs = wave == 0 ? rs_sched_word(TR, 0) : wave == 1 ? rs_sched_word(TR, 1) : wave == 2 ? rs_sched_word(TR, 2) : 0ull;
 #pragma unroll 1
     for (int sgi = -1; sgi < 2 * TR; ++sgi) {
@@ -826,8 +850,8 @@ __device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, in
             if (st && lane == 0) st[16 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
             __builtin_amdgcn_s_setprio(3);                      // (see rs_inverse)
             // the narrow last panel in a 4-column instantiation with the arithmetic pinned: bit for bit the generic loop
-            if (!full_next) rs_factor<P, 4, true>(n, W, pivrow, colof, rowline, n0, n - n0, lane);
-            else rs_factor<P>(n, W, pivrow, colof, rowline, n0, RS_NB, lane, (st && sgi + 1 == 1) ? st + 40 : nullptr);
+            if (!full_next) rs_factor<P, 16 * T16, 4, true>(n, W, pivrow, colof, rowline, n0, n - n0, lane, avail, false);
+            else rs_factor<P, 16 * T16>(n, W, pivrow, colof, rowline, n0, RS_NB, lane, avail, false, (st && sgi + 1 == 1) ? st + 40 : nullptr);
             __builtin_amdgcn_s_setprio(0);
             if (st && lane == 0) st[17 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
         }
