@@ -232,7 +232,8 @@ __device__ __forceinline__ unsigned long long rs_rows_mask(int n) { return n >= 
 template <int P, int ROWS, int NBW = RS_NB, bool PINNED = false>
 __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colof, cplx* rowline /*[16] LDS*/,
                                           int p0, int pw, int lane, unsigned long long& avail, bool reread,
-                                          unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */)
+                                          unsigned long long* fst = nullptr /* diagnostic: cycle stamps of column step 4 */,
+                                          int* pivoff = nullptr /* the stage schedule: the pivot rows as byte offsets, see rs_at */)
 {
     const int r = rs_opaque(lane);                      // (see rs_opaque: nothing derived from the lane index is
     cplx a[NBW];                                        //  hoisted out of the fixed-point loop and kept alive)
@@ -320,7 +321,10 @@ __device__ __forceinline__ void rs_factor(int n, cplx* W, int* pivrow, int* colo
         for (int s = 0; s < NBW; ++s)
             if (s < pw) wrow[s] = PINNED ? rs_cmul_pinned(a[s], myip) : rs_scale_pinned(a[s], myip);
     }
-    if (prow >= 0) pivrow[p0 + r] = prow;
+    if (prow >= 0) {
+        pivrow[p0 + r] = prow;
+        if (pivoff) pivoff[p0 + r] = prow * (P * (int)sizeof(cplx));
+    }
     if (mycol >= 0) colof[r] = mycol;
 }
 
@@ -664,15 +668,69 @@ __device__ __forceinline__ void rs_inverse(int n, cplx* W, int* pivrow, int* col
 //  instead of 110 and none, and the two-per-CU ones fall from four waves per SIMD to three)
 constexpr bool rs_stage_sched(int TR) { return TR >= 2 && TR <= 3 && !RS_ABLATE; }     // (an ablation build runs the generic loop, which carries the ablations)
 
+// ---- what a lane of a matrix wave addresses with, made ONCE per inverse (rs_lane at the top of rs_inverse_sched) and handed to
+// every update body of its stages.  Every body used to derive its own copies behind rs_opaque -- a quarter-rate v_mul_lo_u32
+// and two or three adds per base and body, on SIMDs where another workgroup's matrix instruction holds vector issue.  The
+// values pass through rs_opaque here as well, inside the sweep loop: they live from the top of an inverse to its end, while
+// the products' accumulators are dead, and are no invariants of the fixed-point loop (see rs_opaque).
+//   fi, fk: the lane's place in an operand fragment (l & 15, l >> 4);
+//   pb = fi P + fk: the P fragment, element (16 ti + fi, p0 + 4 ks + fk) at W + pb + 16 ti P + p0 + 4 ks;
+//   cb = fk P + fi: the C tile, element (16 ti + fk + 4 r, 16 tj + fi) at W + cb + (16 ti + 4 r) P + 16 tj;
+//   sb = (4 (fi >> 2) + fk) P + (fi & 3): a column strip's C element (16 ti + 4 (fi >> 2) + fk, c0 + (fi & 3)) at W + sb + 16 ti P + c0;
+//   sp = (fi & 3) P + fk: the row strip's P fragment, element (16 TR + (fi & 3), p0 + 4 ks + fk) at W + sp + 16 TR P + p0 + 4 ks.
+struct RsLane { int fi, fk, pb, cb, sb, sp; };
+template <int P>
+__device__ __forceinline__ RsLane rs_lane(int lane)
+{
+    const int l = rs_opaque(lane);
+    RsLane L;
+    L.fi = l & 15; L.fk = l >> 4;
+    L.pb = rs_opaque(L.fi * P + L.fk);
+    L.cb = rs_opaque(L.fk * P + L.fi);
+    L.sb = rs_opaque((4 * (L.fi >> 2) + L.fk) * P + (L.fi & 3));
+    L.sp = rs_opaque((L.fi & 3) * P + L.fk);
+    L.fi = rs_opaque(L.fi); L.fk = rs_opaque(L.fk);
+    return L;
+}
+
+// ---- the pivot table as offsets.  The factoring wave stores pivoff[k] = pivrow[k] P sizeof(cplx), the pivot row's offset in
+// bytes, beside pivrow[k] (rs_factor, once per panel), so the Q fragments and the zeroing of the pivot rows address
+// rs_at(W, pivoff[p0 + k], col) without a multiply or a shift per entry and body.  poff = pivoff + p0.  The stage schedule
+// only: the generic loop and its kernels keep the row table alone.
+__device__ __forceinline__ const cplx* rs_at(const cplx* W, int bytes, int elem) { return reinterpret_cast<const cplx*>(reinterpret_cast<const char*>(W) + bytes) + elem; }
+__device__ __forceinline__ cplx* rs_at(cplx* W, int bytes, int elem) { return reinterpret_cast<cplx*>(reinterpret_cast<char*>(W) + bytes) + elem; }
+// Q fragment of a full panel (FULL) or of the narrow last one (NKS = 1; k >= pw: entry 0 of the panel, the value zeroed)
+template <int NKS, bool FULL>
+__device__ __forceinline__ void rs_load_qf_off(const cplx* W, const int* poff, int pw, int fk, int col, cplx (&qf)[NKS])
+{
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+        const int k = ks * 4 + fk;
+        const bool ok = FULL || k < pw;
+        const cplx v = *rs_at(W, poff[ok ? k : 0], col);
+        qf[ks] = cmake(ok ? v.x : 0.0, ok ? v.y : 0.0);
+    }
+}
+// the two Q fragments of a half tile (columns col and col + second) under a full panel
+template <int NKS>
+__device__ __forceinline__ void rs_load_qh_off(const cplx* W, const int* poff, int fk, int col, int second, cplx (&qh)[2][NKS])
+{
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+        const cplx* q = rs_at(W, poff[ks * 4 + fk], col);
+        qh[0][ks] = q[0]; qh[1][ks] = q[second];
+    }
+}
+
 // row strip of column tile tj < TR (rs_update_tile's strip form with the tile inside the matrix): rows 16 TR + fk < n are
 // stored; RANGE: only the columns [clo, clo + 8) of the tile; MASK: the panel's pivot rows are seeded with 0
 template <int P, int NKS, int TR, bool MASK, bool RANGE>
-__device__ __forceinline__ void rs_rowstrip_tile(int n, cplx* W, const int* colof, int tj, int p0, int fi, int fk,
+__device__ __forceinline__ void rs_rowstrip_tile(int n, cplx* W, const int* colof, const RsLane& L, int tj, int p0,
                                                  const cplx (&qf)[NKS], int clo)
 {
-    const int row = TR * 16 + fk, col = tj * 16 + fi;
-    const cplx* prow = W + (TR * 16 + (fi & 3)) * P + p0 + fk;
-    cplx* cptr = W + row * P + col;
+    const int row = TR * 16 + L.fk, col = tj * 16 + L.fi;
+    const cplx* prow = W + L.sp + TR * 16 * P + p0;
+    cplx* cptr = W + L.cb + TR * 16 * P + tj * 16;
     const int cf = MASK ? colof[row] : -1;
     const cplx cv = *cptr;
     cplx pa[NKS];
@@ -687,39 +745,37 @@ __device__ __forceinline__ void rs_rowstrip_tile(int n, cplx* W, const int* colo
 }
 
 // the pivot rows of a full panel in this lane's column
-template <int P, int NKS>
-__device__ __forceinline__ void rs_zero_pivot_rows_full(cplx* W, const int* pivrow, int p0, int fk, int col)
+template <int NKS>
+__device__ __forceinline__ void rs_zero_pivot_rows_full(cplx* W, const int* poff, int fk, int col)
 {
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) W[pivrow[p0 + ks * 4 + fk] * P + col] = cmake(0.0, 0.0);
+    for (int ks = 0; ks < NKS; ++ks) *rs_at(W, poff[ks * 4 + fk], col) = cmake(0.0, 0.0);
 }
 // ... and of the narrow last panel (one k-step, once a sweep).  Its zero is made here: the 16-byte zero of the full panels
 // stays in registers across the sweep only as long as every store that uses it sits on the hot path
-template <int P>
-__device__ __forceinline__ void rs_zero_pivot_rows_narrow(cplx* W, const int* pivrow, int p0, int pw, int fk, int col)
+__device__ __forceinline__ void rs_zero_pivot_rows_narrow(cplx* W, const int* poff, int pw, int fk, int col)
 {
     double z = 0.0;
     asm volatile("" : "+v"(z));
-    if (fk < pw) W[pivrow[p0 + fk] * P + col] = cmake(z, z);
+    if (fk < pw) *rs_at(W, poff[fk], col) = cmake(z, z);
 }
 
 // job kind WHOLE: full column tile tj under a full panel (FULL, NKS = 2) or under the narrow last one (pw <= 4, NKS = 1) --
 // rs_update_col's whole-tile form without a test on the stores
 template <int P, int TR, int NKS, bool FULL>
-__device__ __forceinline__ void rs_job_whole(int n, cplx* W, const int* pivrow, const int* colof, int tj, int p0, int pw, int lane)
+__device__ __forceinline__ void rs_job_whole(int n, cplx* W, const int* pivoff, const int* colof, const RsLane& L, int tj, int p0, int pw)
 {
-    const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
-    const int col = tj * 16 + fi;
+    const int col = tj * 16 + L.fi;
     cplx qf[NKS];
-    rs_load_qf<P, NKS, -1, FULL>(W, pivrow, tj, p0, pw, fi, fk, qf);
-    if (FULL) rs_zero_pivot_rows_full<P, NKS>(W, pivrow, p0, fk, col);
-    else rs_zero_pivot_rows_narrow<P>(W, pivrow, p0, pw, fk, col);
+    rs_load_qf_off<NKS, FULL>(W, pivoff + p0, pw, L.fk, col, qf);
+    if (FULL) rs_zero_pivot_rows_full<NKS>(W, pivoff + p0, L.fk, col);
+    else rs_zero_pivot_rows_narrow(W, pivoff + p0, pw, L.fk, col);
     constexpr bool M3 = rs_upd_3m(P);
     double qs[NKS];
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) qs[ks] = qf[ks].x + qf[ks].y;
-    cplx* cbase = W + fk * P + col;
-    const cplx* pbase = W + fi * P + p0 + fk;
+    cplx* cbase = W + L.cb + tj * 16;
+    const cplx* pbase = W + L.pb + p0;
     cplx cv[2][4], pa[2][NKS];
     auto fetch = [&](int ti, int s) __attribute__((always_inline)) {
 #pragma unroll
@@ -744,25 +800,23 @@ __device__ __forceinline__ void rs_job_whole(int n, cplx* W, const int* pivrow, 
         for (int r = 0; r < 4; ++r) cbase[(ti * 16 + 4 * r) * P] = M3 ? cmake(ua[r] - ub[r], uc[r] - ua[r] - ub[r]) : cmake(ua[r], uc[r]);
         __builtin_amdgcn_sched_barrier(0);
     }
-    rs_rowstrip_tile<P, NKS, TR, false, false>(n, W, colof, tj, p0, fi, fk, qf, 0);
+    rs_rowstrip_tile<P, NKS, TR, false, false>(n, W, colof, L, tj, p0, qf, 0);
 }
 
 // job kind HALF: columns [clo, clo + 8) of full tile tj under a full panel -- rs_update_col's half-tile form
 template <int P, int TR>
-__device__ __forceinline__ void rs_job_half(int n, cplx* W, const int* pivrow, const int* colof, int tj, int clo, int p0, int lane)
+__device__ __forceinline__ void rs_job_half(int n, cplx* W, const int* pivoff, const int* colof, const RsLane& L, int tj, int clo, int p0)
 {
     constexpr int NKS = RS_NB / 4;
-    const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
     cplx qf[NKS], qh[2][NKS];
     double qs[2][NKS];
-    rs_load_qf<P, NKS, -1, true>(W, pivrow, tj, p0, RS_NB, fi, fk, qf);           // the row strip's 16-column fragment
-    rs_load_qh<P, NKS, true>(W, pivrow, clo, p0, RS_NB, fi, fk, qh);
-    if ((unsigned)(tj * 16 + fi - clo) < 8u) rs_zero_pivot_rows_full<P, NKS>(W, pivrow, p0, fk, tj * 16 + fi);
+    rs_load_qf_off<NKS, true>(W, pivoff + p0, RS_NB, L.fk, tj * 16 + L.fi, qf);   // the row strip's 16-column fragment
+    rs_load_qh_off<NKS>(W, pivoff + p0, L.fk, clo + (L.fi & 3), 4, qh);
+    if ((unsigned)(tj * 16 + L.fi - clo) < 8u) rs_zero_pivot_rows_full<NKS>(W, pivoff + p0, L.fk, tj * 16 + L.fi);
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) { qs[0][ks] = qh[0][ks].x + qh[0][ks].y; qs[1][ks] = qh[1][ks].x + qh[1][ks].y; }
-    const int row = 4 * (fi >> 2) + fk;
-    cplx* cbase = W + row * P + clo + (fi & 3);
-    const cplx* pbase = W + fi * P + p0 + fk;
+    cplx* cbase = W + L.sb + clo;
+    const cplx* pbase = W + L.pb + p0;
     cplx cv[2][2], pa[2][NKS];
     auto fetch = [&](int ti, int s) __attribute__((always_inline)) {
         cv[s][0] = cbase[ti * 16 * P]; cv[s][1] = cbase[ti * 16 * P + 4];
@@ -778,29 +832,69 @@ __device__ __forceinline__ void rs_job_half(int n, cplx* W, const int* pivrow, c
         cbase[ti * 16 * P] = cv[s][0]; cbase[ti * 16 * P + 4] = cv[s][1];
         __builtin_amdgcn_sched_barrier(0);
     }
-    rs_rowstrip_tile<P, NKS, TR, false, true>(n, W, colof, tj, p0, fi, fk, qf, clo);
+    rs_rowstrip_tile<P, NKS, TR, false, true>(n, W, colof, L, tj, p0, qf, clo);
+}
+
+// full row tile ti < TR of the column strip (rs_update_tile's strip form with the rows inside the matrix and nothing masked):
+// columns 16 TR + (fi & 3) < n are stored
+template <int P, int NKS, int TR>
+__device__ __forceinline__ void rs_colstrip_tile(int n, cplx* W, const RsLane& L, int ti, int p0, const cplx (&qf)[NKS])
+{
+    cplx* cptr = W + L.sb + ti * 16 * P + TR * 16;
+    const cplx* prow = W + L.pb + ti * 16 * P + p0;
+    const cplx cv = *cptr;
+    cplx pa[NKS];
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) pa[ks] = prow[ks * 4];
+    double ua = cv.x, ub = 0.0, uc = cv.x + cv.y;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks)
+        mfma3s(ua, ub, uc, pa[ks].x, pa[ks].y, pa[ks].x + pa[ks].y, qf[ks].x, qf[ks].y, qf[ks].x + qf[ks].y);
+    if (TR * 16 + (L.fi & 3) < n) *cptr = cmake(ua - ub, uc - ua - ub);
 }
 
 // job kind STRIP: the column strip (tile TR) under a full panel, every row tile on the 4x4x4 instruction
 template <int T16, int P, int TR>
-__device__ __forceinline__ void rs_job_strip(int n, cplx* W, const int* pivrow, const int* colof, int p0, int lane)
+__device__ __forceinline__ void rs_job_strip(int n, cplx* W, const int* pivoff, const int* colof, const RsLane& L, int p0)
 {
     constexpr int NKS = RS_NB / 4;
-    const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
-    const int col = TR * 16 + (fi & 3);
+    const int col = TR * 16 + (L.fi & 3);
     cplx qf[NKS];
-    rs_load_qf<P, NKS, TR, true>(W, pivrow, TR, p0, RS_NB, fi, fk, qf);
-    if (col < n) rs_zero_pivot_rows_full<P, NKS>(W, pivrow, p0, fk, col);
+    rs_load_qf_off<NKS, true>(W, pivoff + p0, RS_NB, L.fk, col, qf);
+    if (col < n) rs_zero_pivot_rows_full<NKS>(W, pivoff + p0, L.fk, col);
 #pragma unroll
-    for (int ti = 0; ti < T16; ++ti) {
-        rs_update_tile<P, NKS, TR, false>(n, W, colof, ti, TR, p0, RS_NB, fi, fk, qf, TR * 16, TR * 16 + 16);
+    for (int ti = 0; ti < TR; ++ti) {
+        rs_colstrip_tile<P, NKS, TR>(n, W, L, ti, p0, qf);
         __builtin_amdgcn_sched_barrier(0);
     }
+    // the corner block, once a job, in the generic form: its own index arithmetic behind rs_opaque stays inside it and is not
+    // carried through the stages
+    rs_update_tile<P, NKS, TR, false>(n, W, colof, TR, TR, p0, RS_NB, rs_opaque(L.fi), rs_opaque(L.fk), qf, TR * 16, TR * 16 + 16);
+    __builtin_amdgcn_sched_barrier(0);
 }
 
-// rs_inverse for a remainder-strip class with the roles by SIMD (wave = role; role 3 factors every panel)
+// the look-ahead on full row tile ti under a full panel: columns [c0, c0 + 8) inside the matrix, the panel's pivot rows seeded
+// with 0 -- rs_update_half<P, NKS, true, true> on the lane bases
+template <int P, int NKS>
+__device__ __forceinline__ void rs_lookahead_half(cplx* W, const int* colof, const RsLane& L, int ti, int p0,
+                                                  const cplx (&qh)[2][NKS], int c0)
+{
+    cplx* cptr = W + L.sb + ti * 16 * P + c0;
+    const cplx* pbase = W + L.pb + ti * 16 * P + p0;
+    const int cf = colof[ti * 16 + 4 * (L.fi >> 2) + L.fk];
+    cplx cv[2] = {cptr[0], cptr[4]}, pa[NKS];
+    double qs[2][NKS];
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) { pa[ks] = pbase[ks * 4]; qs[0][ks] = qh[0][ks].x + qh[0][ks].y; qs[1][ks] = qh[1][ks].x + qh[1][ks].y; }
+    if (cf >= p0 && cf < p0 + 4 * NKS) { cv[0] = cmake(0.0, 0.0); cv[1] = cmake(0.0, 0.0); }   // a pivot row of the panel (both values: one row)
+    rs_half_mma<P, NKS>(cv, pa, qh, qs);
+    cptr[0] = cv[0]; cptr[4] = cv[1];
+}
+
+// rs_inverse for a remainder-strip class with the roles by SIMD (wave = role; role 3 factors every panel).  pivoff: a second
+// table of 64 entries beside pivrow, the pivot rows as byte offsets (rs_at); written and read here alone
 template <int T16, int P, int TR>
-__device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, int* colof, cplx* rowline, int tid, int wave,
+__device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, int* pivoff, int* colof, cplx* rowline, int tid, int wave,
                                                  unsigned long long* st = nullptr)
 {
     static_assert(TR == T16 - 1 && rs_sched_fits(TR), "a remainder-strip class");
@@ -812,6 +906,7 @@ __device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, in
     wave = __builtin_amdgcn_readfirstlane(wave);                // (the same in every lane: the table stays in scalar registers)
     unsigned long long avail = rs_rows_mask(n);                 // the rows still to become pivots, carried through the panels (rs_factor)
     const unsigned long long jobs = wave == 0 ? rs_sched_word(TR, 0) : wave == 1 ? rs_sched_word(TR, 1) : wave == 2 ? rs_sched_word(TR, 2) : 0ull;
+    const RsLane L = rs_lane<P>(lane);                          // the lane bases of every update body of this inverse
 #pragma unroll 1
     for (int sgi = -1; sgi < 2 * TR; ++sgi) {
         // stage sgi: the full panel [p0, p0 + 8) is applied, panel [n0, n0 + 8) -- the narrow last one after stage 2 TR - 1 -- factored
@@ -820,19 +915,22 @@ __device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, in
         if (sgi >= 0) {
             // look-ahead: the next panel's columns, one row tile per wave.  A full next panel is half of a full tile (two column
             // strips per row tile, the row strip in its own form), the last one the column strip
-            const int fi = rs_opaque(lane & 15), fk = rs_opaque(lane >> 4);
             const int tl = n0 >> 4;
+            // The Q fragments are loaded in ONE straight line whatever the role -- the half tiles' two strips at columns
+            // n0 + (fi & 3) and + 4, the row strip's 16 columns 16 tl + fi, the column strip's 16 TR + (fi & 3) -- with the role
+            // in a scalar column base, a scalar lane mask and a scalar distance of the second fragment (0 where there is none:
+            // two loads of elements the first two read).  Loaded in a branch per role, the fragments met behind the barrier
+            // in sixteen register moves per stage and wave, the factoring wave's included.
             cplx qh[2][NKS];
-            cplx (&qf)[NKS] = qh[0];                            // (one or the other)
-            if (full_next) {
-                if (wave < TR) rs_load_qh<P, NKS, true>(W, pivrow, n0, p0, RS_NB, fi, fk, qh);
-                else if (wave == TR) rs_load_qf<P, NKS, -1, true>(W, pivrow, tl, p0, RS_NB, fi, fk, qf);
-            } else if (wave < T16) rs_load_qf<P, NKS, TR, true>(W, pivrow, TR, p0, RS_NB, fi, fk, qf);
+            cplx (&qf)[NKS] = qh[0];                            // (the roles with one fragment)
+            const bool halves = full_next && wave < TR;
+            const int qcol = (full_next ? (halves ? n0 : tl * 16) : TR * 16) + (L.fi & (full_next && !halves ? 15 : 3));
+            rs_load_qh_off<NKS>(W, pivoff + p0, L.fk, qcol, halves ? 4 : 0, qh);
             __syncthreads();
             if (full_next) {
-                if (wave < TR) rs_update_half<P, NKS, true, true>(n, W, colof, wave, p0, RS_NB, fi, fk, qh, n0);
-                else if (wave == TR) rs_rowstrip_tile<P, NKS, TR, true, true>(n, W, colof, tl, p0, fi, fk, qf, n0);
-            } else if (wave < T16) rs_update_tile<P, NKS, TR, true>(n, W, colof, wave, TR, p0, RS_NB, fi, fk, qf, n0, n0 + RS_NB);
+                if (wave < TR) rs_lookahead_half<P, NKS>(W, colof, L, wave, p0, qh, n0);
+                else if (wave == TR) rs_rowstrip_tile<P, NKS, TR, true, true>(n, W, colof, L, tl, p0, qf, n0);
+            } else if (wave < T16) rs_update_tile<P, NKS, TR, true>(n, W, colof, wave, TR, p0, RS_NB, rs_opaque(L.fi), rs_opaque(L.fk), qf, n0, n0 + RS_NB);   // (once a sweep: generic form)
             __syncthreads();
             // the other columns: this role's jobs of the stage
             unsigned c = (unsigned)(jobs >> (RS_STAGE_BITS * sgi)) & ((1u << RS_STAGE_BITS) - 1u);
@@ -840,9 +938,9 @@ __device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, in
             while (c) {
                 const unsigned kind = c & 3u;
                 const int tj = (int)(c >> 2) & 3;
-                if (kind == RS_JOB_WHOLE) rs_job_whole<P, TR, NKS, true>(n, W, pivrow, colof, tj, p0, RS_NB, lane);
-                else if (kind == RS_JOB_HALF) rs_job_half<P, TR>(n, W, pivrow, colof, tj, tj * 16 + (int)((c >> 4) & 1u) * 8, p0, lane);
-                else rs_job_strip<T16, P, TR>(n, W, pivrow, colof, p0, lane);
+                if (kind == RS_JOB_WHOLE) rs_job_whole<P, TR, NKS, true>(n, W, pivoff, colof, L, tj, p0, RS_NB);
+                else if (kind == RS_JOB_HALF) rs_job_half<P, TR>(n, W, pivoff, colof, L, tj, tj * 16 + (int)((c >> 4) & 1u) * 8, p0);
+                else rs_job_strip<T16, P, TR>(n, W, pivoff, colof, L, p0);
                 c >>= RS_JOB_BITS;
             }
         }
@@ -850,8 +948,8 @@ __device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, in
             if (st && lane == 0) st[16 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
             __builtin_amdgcn_s_setprio(3);                      // (see rs_inverse)
             // the narrow last panel in a 4-column instantiation with the arithmetic pinned: bit for bit the generic loop
-            if (!full_next) rs_factor<P, 16 * T16, 4, true>(n, W, pivrow, colof, rowline, n0, n - n0, lane, avail, false);
-            else rs_factor<P, 16 * T16>(n, W, pivrow, colof, rowline, n0, RS_NB, lane, avail, false, (st && sgi + 1 == 1) ? st + 40 : nullptr);
+            if (!full_next) rs_factor<P, 16 * T16, 4, true>(n, W, pivrow, colof, rowline, n0, n - n0, lane, avail, false, nullptr, pivoff);
+            else rs_factor<P, 16 * T16>(n, W, pivrow, colof, rowline, n0, RS_NB, lane, avail, false, (st && sgi + 1 == 1) ? st + 40 : nullptr, pivoff);
             __builtin_amdgcn_s_setprio(0);
             if (st && lane == 0) st[17 + 2 * (sgi + 1)] = __builtin_amdgcn_s_memrealtime();
         }
@@ -859,7 +957,7 @@ __device__ __forceinline__ void rs_inverse_sched(int n, cplx* W, int* pivrow, in
         __syncthreads();
     }
     // the last stage: the narrow panel [16 TR, n) (one k-step, guarded code) on the full tiles, tile tj by role tj
-    if (wave < TR) rs_job_whole<P, TR, 1, false>(n, W, pivrow, colof, wave, TR * 16, n - TR * 16, lane);
+    if (wave < TR) rs_job_whole<P, TR, 1, false>(n, W, pivoff, colof, L, wave, TR * 16, n - TR * 16);
     stamp();
     __syncthreads();
 }

@@ -183,7 +183,11 @@ __device__ __forceinline__ void chain1d_rs_body(
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ int flags[2 * RS_WAVES];                 // per wave: any(diff > conv), all(diff <= conv)
     __shared__ int pivrow[64], colof[64];
-    __shared__ cplx rowline[RS_NB];                     // pivot row of the column step being factored
+    // the stage schedule's second pivot table, the pivot rows as byte offsets (rs_inverse_sched): 256 bytes more in classes 35 and 51 alone, whose
+    // work matrix leaves them room at three workgroups per CU (class 51: 52 480 + 936 of the 53 760 bytes of 42 granules)
+    constexpr bool SCHED_TABLES = SCHED && REM && rs_stage_sched(REM ? TR : -1);
+    __shared__ int pivoff[SCHED_TABLES ? 64 : 1];
+    __shared__ cplx rowline[RS_NB];                    // pivot row of the column step being factored
 
     // job of this launch slot: in launch order, or -- when the provider has seen this grid before -- in
     // the order of decreasing sweep counts of the previous evaluation (the jobs differ by up to 20x in
@@ -577,7 +581,7 @@ __device__ __forceinline__ void chain1d_rs_body(
         if (!gc_hit && !skip) {
             // a remainder-strip class: the compile-time stage schedule; else, and with the roles by wave number, the generic loop
             // (role 3 factors whether the roles follow the SIMDs or, two waves having reported the same one, the wave numbers)
-            if constexpr (SCHED && REM && rs_stage_sched(REM ? TR : -1)) rs_inverse_sched<T16, P, TR>(n, Ws, pivrow, colof, rowline, tid, wave, st ? st + 8 : nullptr);
+            if constexpr (SCHED_TABLES) rs_inverse_sched<T16, P, TR>(n, Ws, pivrow, pivoff, colof, rowline, tid, wave, st ? st + 8 : nullptr);
             else
             rs_inverse<T16, P, REM ? TR : -1>(n, Ws, pivrow, colof, rowline, tid, wave, chain_roles, st ? st + 8 : nullptr);   // st + 8: stage stamps, st + 24: factor
             if (st && tid == 0) st[1] = __builtin_amdgcn_s_memrealtime();
